@@ -19,10 +19,17 @@ touches the GPU it starts `python -m torch.distributed.run --nproc-per-node N ..
 relays rank 0's JSON line and exits with the child's code.  Under an external launcher (WORLD_SIZE set) --gpus must
 equal WORLD_SIZE or the run fails.  Rank 0 prints ONE JSON line.
 
-Timing: W untimed warm-up steps, then `--repeats` blocks of EXACTLY K steps each, every block bracketed by
-barrier + torch.cuda.synchronize on both sides and reduced with MAX over the ranks; `value` / `ms_per_step` come from
-the MEDIAN block, the minimum and every block's time are reported beside it.  Only the last block carries the
-per-kernel hipEvent pairs the roofline needs (they cost ~3 % of a step), so the median is an event-free block.
+Timing: W untimed warm-up steps, then ONE timed window of exactly K steps, bracketed by barrier + torch.cuda.synchronize
+on both sides and reduced with MAX over the ranks; `ms_per_step` is that window over K and `value` the candidates it
+scored per second.  The per-kernel hipEvent pairs the roofline needs cost ~3 % of a step, so they ride on one more block
+of K steps after the timed window, never in it.
+
+Outputs: --dump-outputs DIR writes the records the timed path returned in its last timed step (the gathered list at
+N > 1) as DIR/<field>.npy, one float32 / float64 array per record field, every value finite: the -inf logdet of a
+singular FIM is written as 0 and flagged in DIR/logdet_singular.npy.  The inputs are a function of the arguments
+alone (synth.py's seeded generators), so two builds run with the same arguments can be compared output for output.
+Between two runs of one build every field is bit-identical except info_ref, which may move by an ulp: a voxel's crowding
+factor goes to its landmarks in the order their atomic slot claims land (fs_fim.hip).
 
 Pipelining: --pipeline P (default 1: one stream, batches strictly back to back) stages the map and the cloud in P scorer
 contexts, each on its own HIP stream, and sends batch k to context k mod P, so that the next batch's ray-march overlaps the
@@ -54,10 +61,9 @@ METRIC = "candidate-goals scored/sec (raycast+FIM) on 512^3 grid; % HBM roofline
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps: ms_per_step = the one timed window over this many steps")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps each; value = the median block")
-    ap.add_argument("--min-timed-seconds", type=float, default=0.5, help="keep adding timed blocks of --steps steps (beyond --repeats) until the timed GPU work adds up to this much: 5 blocks of 20 C3 steps are only 79 ms, too thin for a median (0 = exactly --repeats blocks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the records of the last timed step as DIR/<field>.npy (float32 / float64)")
     ap.add_argument("--pipeline", type=int, default=1, help="scorer contexts (HIP streams) per GPU; successive batches alternate over them (1, the default = one stream, batches strictly back to back; 2 measured +2 %% on C3, but the two FIM kernels then share the CUs and their per-launch durations no longer measure the kernel)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--workload", default="C3", help="C3 (headline) | C5 | REF2D (the reference's own 2-D operating point: 63 rays, L = 40) | C2 | C1")
@@ -72,7 +78,12 @@ def parse(argv=None):
     ap.add_argument("--latency-calls", type=int, default=300, help="calls per latency figure")
     ap.add_argument("--rehearse-multi", action="store_true", help="one rank, but through every code path of the N > 1 run: a one-rank RCCL group, the asynchronous all-gather in every step, the ranking on the gathered list, the multi_gpu keys and the block-sampled parity gate (what a one-GPU box can rehearse of the multi-GPU line; never a scaling figure)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous rehearsal without a GPU: the ranks meet over gloo, all-gather a dummy record block and rank 0 prints a line marked dry_run (no value)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.latency or args.dry_run):
+        ap.error("--dump-outputs writes the throughput line's records: not with --latency or --dry-run")
+    return args
 
 
 # ------------------------------------------------------------------ launcher (never touches the GPU)
@@ -228,6 +239,33 @@ def red_gates(obj, path="") -> list:
                 red.append(here)
             red += red_gates(v, here)
     return red
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rec, seed=0):
+    """--dump-outputs: DIR/<field>.npy for every field of the records `rec` (float32 fields as they are; integer fields as
+    float64, which holds every int32 and uint32 exactly), every value finite.  The record's logdet is -inf for a singular
+    FIM (include/fitslam_frontier.h): logdet.npy holds 0 there and DIR/logdet_singular.npy 1 (0 elsewhere).  Any other
+    non-finite value breaks the record's contract and is an error.  Should the columns exceed 64 MB in all, the same fixed
+    seeded sample of rows is taken from every column and its row numbers go to DIR/sample_index.npy."""
+    cols = {k: rec[k].astype(np.float32 if rec.dtype[k].kind == "f" else np.float64) for k in rec.dtype.names}
+    singular = np.isneginf(cols["logdet"])
+    cols["logdet"][singular] = 0.0
+    cols["logdet_singular"] = singular.astype(np.float32)
+    bad = [k for k, a in cols.items() if not np.all(np.isfinite(a))]
+    if bad:
+        raise ValueError(f"--dump-outputs: non-finite values in {', '.join(bad)} (only logdet may be -inf, for a singular FIM)")
+    row_bytes = sum(a.itemsize for a in cols.values())
+    budget = DUMP_LIMIT_BYTES - (1 << 16)                 # (room for the .npy headers)
+    if rec.shape[0] * row_bytes > budget:
+        keep = np.sort(np.random.default_rng(seed).choice(rec.shape[0], budget // (row_bytes + 8), replace=False))
+        cols = {k: a[keep] for k, a in cols.items()}
+        cols["sample_index"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in cols.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def sample_parity(w, arrival_kw, mx, goals, fsize, black, rec, fim_angle, where):
@@ -770,39 +808,27 @@ def run_rank(args) -> int:
     fence()
     for c in scs:
         c.get_counter(0, reset=True)
-    # Per-kernel hipEvent pairs cost ~0.035 ms per step (measured: 1.06 vs 1.024 ms), so only the LAST timed block carries
-    # them: the roofline's launch durations come from that block, `value` from the median block (an event-free one
-    # whenever --repeats >= 3).  All blocks are listed in "timing".
-    n_rep = max(1, args.repeats)
-    if args.min_timed_seconds > 0:
-        # one untimed calibration block decides the number of blocks — the SAME number on every rank (MAX over the ranks)
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        fence()
-        cal = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev if (multi_path and args.backend == "nccl") else "cpu")
-        if multi_path:
-            dist.all_reduce(cal, op=dist.ReduceOp.MAX)
-        n_rep = int(min(500, max(n_rep, np.ceil(args.min_timed_seconds / max(float(cal[0]), 1e-6)))))
-        for c in scs:
-            c.get_counter(0, reset=True)
-    block_s, local_s = [], []
-    full = None
-    for r in range(n_rep):
-        if r == n_rep - 1:
-            for c in scs:
-                c.enable_kernel_timing(True)
-                for kind in range(5):
-                    c.kernel_time(kind)
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            full = step()
-        t_ready = fence()
-        block_s.append(time.perf_counter() - t0)
-        local_s.append(t_ready - t0)                                 # this rank alone: its steps + its share of the gathers
-    n_steps_all = args.steps * len(block_s)
+    # The timed window: exactly K steps and nothing else.
+    fence()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        full = step()
+    t_ready = fence()
+    dt = time.perf_counter() - t0
+    dt_local = t_ready - t0                                          # this rank alone: its steps + its share of the gathers
+    # what a caller of the timed path received from its last step, copied out before later steps reuse the record buffers
+    timed_rec = shard.records_to_numpy(full) if rank == 0 else None
+    # landmark tests per candidate on this rank, over the timed steps
+    m_tested = sum(c.get_counter(0, reset=True) for c in scs) / (args.steps * n_local)
+    # Per-kernel hipEvent pairs cost ~0.035 ms per step (measured: 1.06 vs 1.024 ms), so the roofline's launch durations come
+    # from one more block of K steps after the timed window
+    for c in scs:
+        c.enable_kernel_timing(True)
+        for kind in range(5):
+            c.kernel_time(kind)
+    for _ in range(args.steps):
+        step()
+    fence()
     n_steps_ev = args.steps                                          # steps of the block that carried the events
 
     def kernel_sum(kind):
@@ -816,8 +842,6 @@ def run_rank(args) -> int:
     fim_ms, fim_n = kernel_sum(1)
     ovf_ms, ovf_n = kernel_sum(2)
     sort_ms, sort_n = kernel_sum(4)
-    # landmark tests per candidate on this rank, over every timed step
-    m_tested = sum(c.get_counter(0, reset=True) for c in scs) / max(1, n_steps_all * n_local)
     multipass, tier3 = sum(c.get_counter(4) for c in scs), sum(c.get_counter(5) for c in scs)
     for c in scs:
         c.enable_kernel_timing(False)
@@ -1056,16 +1080,16 @@ def run_rank(args) -> int:
     multi = None
     if multi_path:
         red_dev = dev if args.backend == "nccl" else "cpu"
-        tmax = torch.tensor(block_s + ([ranked["dt"]] if ranked else []), dtype=torch.float64, device=red_dev)
+        tmax = torch.tensor([dt] + ([ranked["dt"]] if ranked else []), dtype=torch.float64, device=red_dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         vals = [float(x) for x in tmax.tolist()]
-        block_s = vals[:len(block_s)]
+        dt = vals[0]
         if ranked:
             ranked["dt"] = vals[-1]
-        mine = torch.tensor(local_s, dtype=torch.float64, device=red_dev)
+        mine = torch.tensor([dt_local], dtype=torch.float64, device=red_dev)
         everyone = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(everyone, mine)
-        loc = np.array([[float(x) for x in t.tolist()] for t in everyone])        # [rank][block], seconds
+        loc = np.array([float(t[0]) for t in everyone])                           # [rank], seconds
         gather_ms = None
         if args.backend == "nccl":
             with torch.cuda.stream(streams[0]):
@@ -1080,17 +1104,18 @@ def run_rank(args) -> int:
             g = torch.tensor([e0.elapsed_time(e1) / 20], dtype=torch.float64, device=dev)
             dist.all_reduce(g, op=dist.ReduceOp.MAX)
             gather_ms = float(g[0])
-        multi = {"per_rank_ms_per_step": [float(np.median(loc[r]) / args.steps * 1e3) for r in range(world)],
-                 "per_rank_ms_per_step_min": float(np.median(loc, axis=1).min() / args.steps * 1e3),
-                 "per_rank_ms_per_step_max": float(np.median(loc, axis=1).max() / args.steps * 1e3),
-                 "barrier_skew_ms": float(np.median(loc.max(axis=0) - loc.min(axis=0)) * 1e3),
-                 "barrier_skew_note": "per timed block: last rank ready minus first rank ready (each after its own K steps and gathers), median over the blocks",
+        multi = {"per_rank_ms_per_step": [float(loc[r] / args.steps * 1e3) for r in range(world)],
+                 "per_rank_ms_per_step_min": float(loc.min() / args.steps * 1e3),
+                 "per_rank_ms_per_step_max": float(loc.max() / args.steps * 1e3),
+                 "barrier_skew_ms": float((loc.max() - loc.min()) * 1e3),
+                 "barrier_skew_note": "timed window: last rank ready minus first rank ready (each after its own K steps and gathers)",
                  "all_gather_ms": gather_ms,
                  "all_gather_note": f"one blocking all_gather_into_tensor of {n_total} x 32 B between an event pair on the scorer's stream, mean of 20, max over ranks (nccl backend only)"}
 
     exit_code = 0
     if rank == 0:
-        dt = float(np.median(block_s))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, timed_rec)
         value = n_total * args.steps / dt
         R, E = w.n_yaw if w.n_yaw else sc.n_yaw, len(w.elev)
         L = int(w.max_camera_depth / w.resolution)
@@ -1106,7 +1131,7 @@ def run_rank(args) -> int:
         fim_avg_s = (fim_ms / max(fim_n, 1)) * 1e-3
         achieved = (n_local * b_fim / max(launches_per_step, 1e-9)) / fim_avg_s / 1e9 if fim_n else None
         prof = counter_profile(wl_name, args.depth_cells, args.fim_angle)
-        gpu_rec = shard.records_to_numpy(full) if not args.no_parity else None
+        gpu_rec = timed_rec if not args.no_parity else None
         cpu, parity = (None, None)
         if not multi_path and args.cpu_seconds > 0:
             cpu, parity = cpu_baseline(w, arrival_kw, n_total, args.cpu_seconds, gpu_rec, mx, args.fim_angle)
@@ -1162,16 +1187,13 @@ def run_rank(args) -> int:
                        "candidates_per_gpu": per_rank, "total_candidates": n_total,
                        "sharding": f"contiguous blocks over {world} GPU(s), one all-gather of 32-B records ({args.backend})",
                        "pipeline": f"{n_pipe} scorer context(s)/HIP stream(s) per GPU; batch k runs whole on context k mod {n_pipe}"},
-            "timing": {"repeats": len(block_s), "timed_seconds_total": float(sum(block_s)),
-                       "block_ms_per_step": [round(b / args.steps * 1e3, 5) for b in block_s],
-                       "block_ms_per_step_p10_p90": [float(np.percentile(block_s, 10) / args.steps * 1e3), float(np.percentile(block_s, 90) / args.steps * 1e3)],
-                       "median_ms_per_step": dt / args.steps * 1e3, "min_ms_per_step": min(block_s) / args.steps * 1e3,
-                       "value_from": "median block", "kernel_events_in_block": len(block_s) - 1, "value_at_min": n_total * args.steps / min(block_s)},
+            "timing": {"timed_steps": args.steps, "timed_seconds_total": dt,
+                       "value_from": "one window of --steps steps, barrier + synchronize on both sides, max over the ranks; no per-kernel events in it"},
             "roofline": roofline,
             "kernels_ms_per_step": {"fs_raymarch_kernel": ray_ms / n_steps_ev, "fs_fim_kernel": fim_ms / n_steps_ev,
                                     "fs_fim_overflow_kernel": ovf_ms / n_steps_ev, "candidate_sort": sort_ms / n_steps_ev,
                                     "raymarch_algorithmic_GBps": (n_local * b_ray) / ((ray_ms / n_steps_ev) * 1e-3) / 1e9 if ray_n else None,
-                                    "from": "the last timed block (the only one with per-kernel hipEvents); with --pipeline > 1 "
+                                    "from": "one block of K steps with per-kernel hipEvents after the timed window; with --pipeline > 1 "
                                             "a kernel's duration includes the time it shares the chip with the other stream's kernels"},
             "cpu_baseline": cpu, "parity": parity,
             "ranked_step": ({"ms_per_step": ranked["dt"] / args.steps * 1e3, "candidate_goals_per_s": n_total * args.steps / ranked["dt"],

@@ -2,11 +2,15 @@
 a launcher around it must start N ranks itself, relay ONE result line that says n_gpus = N, and refuse a mismatch
 between --gpus and WORLD_SIZE.  The GPU-free part of that is exercised here through --dry-run (gloo rendezvous + the
 all-gather of dummy records; nothing is scored and no value is reported)."""
+import importlib
 import importlib.util
 import json
 import os
 import subprocess
 import sys
+
+import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
@@ -38,10 +42,71 @@ def test_launcher_command_is_one_process_per_gpu_under_torchrun():
 def test_defaults_are_the_headline_configuration():
     b = _bench_module()
     a = b.parse([])
-    assert (a.gpus, a.workload, a.scaling) == (1, "C3", "weak") and a.repeats >= 5
+    assert (a.gpus, a.workload, a.scaling) == (1, "C3", "weak") and a.dump_outputs is None
     # one stream, batches strictly back to back: with more contexts the FIM kernels of two batches share the CUs and the
     # per-launch durations behind `roofline` stop measuring the kernel
     assert a.pipeline == 1 and b.parse(["--pipeline", "2"]).pipeline == 2
+
+
+def test_steps_is_the_number_of_timed_steps():
+    """--steps K is the whole timed window (ms_per_step = window / K): nothing may stretch it to more steps, and it has one."""
+    b = _bench_module()
+    assert b.parse(["--steps", "7"]).steps == 7
+    for argv in (["--steps", "0"], ["--repeats", "5"], ["--min-timed-seconds", "0.5"]):
+        with pytest.raises(SystemExit):
+            b.parse(argv)
+
+
+def test_dump_outputs_writes_every_record_field(tmp_path):
+    b = _bench_module()
+    fs = importlib.import_module("fit-slam_amd")
+    rng = np.random.default_rng(7)
+    rec = np.zeros(1000, dtype=fs.RECORD_DTYPE)
+    for k in fs.RECORD_DTYPE.names:
+        t = rec.dtype[k]
+        rec[k] = rng.standard_normal(1000) if t.kind == "f" else rng.integers(np.iinfo(t).min, np.iinfo(t).max, size=1000, endpoint=True)
+    singular = rng.random(1000) < 0.1
+    rec["logdet"][singular] = -np.inf                                   # a singular FIM (include/fitslam_frontier.h)
+    b.dump_outputs(str(tmp_path / "out"), rec)
+    for k in fs.RECORD_DTYPE.names:
+        a = np.load(tmp_path / "out" / f"{k}.npy")
+        assert a.dtype == (np.float32 if rec.dtype[k].kind == "f" else np.float64) and np.all(np.isfinite(a))
+        if k == "logdet":
+            np.testing.assert_array_equal(a, np.where(singular, 0.0, rec[k]).astype(np.float32))
+        else:
+            np.testing.assert_array_equal(a, rec[k])                  # integer fields exactly, uint32 flags included
+    np.testing.assert_array_equal(np.load(tmp_path / "out" / "logdet_singular.npy"), singular.astype(np.float32))
+    assert not (tmp_path / "out" / "sample_index.npy").exists()
+
+
+def test_dump_outputs_refuses_values_the_record_cannot_hold(tmp_path):
+    """Only logdet may be -inf; a NaN anywhere, or +inf, is a broken record and must not be written as data."""
+    b = _bench_module()
+    fs = importlib.import_module("fit-slam_amd")
+    for k, v in (("info_ref", np.nan), ("trace", np.inf), ("logdet", np.nan), ("logdet", np.inf)):
+        rec = np.zeros(10, dtype=fs.RECORD_DTYPE)
+        rec[k][3] = v
+        with pytest.raises(ValueError, match=k):
+            b.dump_outputs(str(tmp_path / "out"), rec)
+
+
+def test_dump_outputs_samples_past_64_mb(tmp_path, monkeypatch):
+    """Over the limit the same seeded rows of every field, their indices beside them; the same rows on every run."""
+    b = _bench_module()
+    fs = importlib.import_module("fit-slam_amd")
+    rec = np.zeros(5000, dtype=fs.RECORD_DTYPE)
+    rec["arrival"] = np.arange(5000)
+    rec["info_ref"] = np.arange(5000) * 0.5
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", (1 << 16) + 100 * 60)  # room for 100 rows: 4 x 8 B + 4 x 4 B + logdet_singular + the index
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), rec)
+    idx = np.load(tmp_path / "a" / "sample_index.npy")
+    assert idx.shape == (100,) and np.all(np.diff(idx) > 0)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "arrival.npy"), idx)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "info_ref.npy"), (idx * 0.5).astype(np.float32))
+    for k in list(fs.RECORD_DTYPE.names) + ["logdet_singular", "sample_index"]:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy"))
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= b.DUMP_LIMIT_BYTES
 
 
 def test_two_ranks_are_spawned_and_rank0_line_is_relayed():

@@ -67,7 +67,7 @@ def test_scoring_then_rccl_all_gather_on_one_stream(fs):
         dist.destroy_process_group()
 
 
-def test_bench_rehearses_the_multi_gpu_line_on_one_gpu():
+def test_bench_rehearses_the_multi_gpu_line_on_one_gpu(fs, tmp_path):
     """`bench.py --rehearse-multi`: one rank, but a real (one-rank) RCCL group and every code path the N > 1 run takes — the
     asynchronous all-gather behind every step, fs_rank_candidates_dev on the gathered list, the multi_gpu keys (per-rank time,
     barrier skew, the all-gather by itself) and the block-sampled parity gate.  Not a scaling figure; the proof that the first
@@ -78,7 +78,7 @@ def test_bench_rehearses_the_multi_gpu_line_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rehearse-multi", "--workload", "C2", "--steps", "3", "--warmup", "2",
-                        "--repeats", "3"], env=env, capture_output=True, text=True, timeout=600)
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out_lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(out_lines) == 1, out_lines[:5]                          # ONE line on stdout: RCCL's banner went to stderr
@@ -89,3 +89,12 @@ def test_bench_rehearses_the_multi_gpu_line_on_one_gpu():
     assert len(mg["per_rank_ms_per_step"]) == 1 and mg["all_gather_ms"] > 0 and mg["barrier_skew_ms"] == 0.0
     rs = j["ranked_step"]
     assert rs["order_is_a_permutation"] and rs["costs_ascending"] and rs["range_error"] == 0 and rs["ms_per_step"] >= j["ms_per_step"] * 0.9
+    # --dump-outputs: the gathered list of the last timed step, one column per record field
+    dumped = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert sorted(dumped) == sorted(list(fs.RECORD_DTYPE.names) + ["logdet_singular"])
+    assert all(a.shape == (j["config"]["total_candidates"],) and a.dtype in (np.float32, np.float64) and np.all(np.isfinite(a))
+               for a in dumped.values())
+    # singular FIMs (fewer than three visible landmarks) are the flagged rows, and their logdet is written as 0
+    sing = dumped["logdet_singular"] == 1
+    assert np.all(dumped["n_visible"][~sing & (dumped["n_visible"] > 0)] >= 3) and np.all(dumped["logdet"][sing] == 0)
+    assert np.all(dumped["arrival"] == np.round(dumped["arrival"])) and np.any(dumped["n_visible"] > 0)

@@ -237,13 +237,13 @@ def main():
             fim_angle = float(arg.split("=", 1)[1])
     summary = {"source_hash": source_hash(), "workload": args.workload, "depth_cells": args.depth_cells, "fim_angle": fim_angle,
                "collected_with": "tools/pmc_collect.py: rocprofv3 --pmc <one counter set per pass> --kernel-trace --output-format csv -- "
-                                 "python3 bench.py --steps 3 --warmup 2 --repeats 2 --cpu-seconds 0 --no-parity; means over the last 6 dispatches",
+                                 "python3 bench.py --steps 6 --warmup 2 --cpu-seconds 0 --no-parity; means over the last 6 dispatches",
                "counters_missing": []}
 
     if not args.skip_stats:
         d = os.path.join(out, "stats")
         shutil.rmtree(d, ignore_errors=True)
-        run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", *bench, "--steps", "20", "--warmup", "5", "--repeats", "5"],
+        run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", *bench, "--steps", "100", "--warmup", "5"],
             os.path.join(out, "stats.log"), 600)
         for f in glob.glob(os.path.join(d, "**", "*_kernel_stats.csv"), recursive=True):
             shutil.copy(f, os.path.join(out, "kernel_stats.csv"))
@@ -259,7 +259,7 @@ def main():
             continue
         d = os.path.join(out, f"pass_{name}")
         shutil.rmtree(d, ignore_errors=True)
-        rc = run(["rocprofv3", "--pmc", *ctrs, "--kernel-trace", "--output-format", "csv", "-d", d, "--", *bench, "--steps", "3", "--warmup", "2", "--repeats", "2", "--min-timed-seconds", "0"],
+        rc = run(["rocprofv3", "--pmc", *ctrs, "--kernel-trace", "--output-format", "csv", "-d", d, "--", *bench, "--steps", "6", "--warmup", "2"],
                  os.path.join(out, f"pass_{name}.log"), 600)
         if rc != 0:
             summary.setdefault("failed_passes", []).append(name)

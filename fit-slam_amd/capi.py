@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = [
     "fs_multi_set_option", "fs_multi_set_ray_params", "fs_multi_upload_grid", "fs_multi_update_grid_region", "fs_multi_upload_landmarks", "fs_multi_lookup_generate",
     "fs_multi_lookup_load", "fs_multi_set_fim_params", "fs_multi_max_arrival", "fs_multi_score_arrival", "fs_multi_score_candidates",
     "fs_multi_score_fim", "fs_multi_get_frontier_costs", "fs_multi_gather_mode",
+    "fs_plan_paths", "fs_navfn_potential", "fs_get_frontier_costs_planned",
 ]
 
 RECORD_DTYPE = np.dtype([("arrival", "<i4"), ("argmax", "<i4"), ("yaw", "<f4"), ("info_ref", "<f4"),
@@ -150,6 +151,9 @@ def load_library(build: bool = True):
     L.fs_multi_score_fim.argtypes = [vp, i32] + [vp] * 7
     L.fs_multi_get_frontier_costs.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, dbl, dbl, dbl, dbl, C.c_int, vp, vp, vp, vp, vp]
     L.fs_multi_gather_mode.argtypes = [vp]
+    L.fs_plan_paths.argtypes = [vp, C.POINTER(dbl * 7), i32, i32, vp, vp, vp, vp, vp, vp]
+    L.fs_navfn_potential.argtypes = [vp, C.POINTER(dbl * 7), i32, vp]
+    L.fs_get_frontier_costs_planned.argtypes = [vp, C.POINTER(dbl * 7), i32, i32, vp, vp, vp, dbl, dbl, dbl, dbl, C.c_int, vp, vp, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         f = getattr(L, name)
         if name not in ("fs_ctx_destroy", "fs_last_error", "fs_multi_destroy", "fs_multi_last_error", "fs_multi_ctx"):
@@ -190,6 +194,7 @@ class FrontierScorer:
             raise FsError(rc, "fs_ctx_create failed: no gfx950 device / HIP runtime (no CPU fallback exists)")
         self._h = h
         self._elev = (0.0,)
+        self._grid_shape = None          # (nz, ny, nx) of the staged grid: what fs_navfn_potential writes
         self.n_yaw = self.n_elev = self.window = 0
 
     # -- plumbing
@@ -249,7 +254,9 @@ class FrontierScorer:
             c = c[None]
         nz, ny, nx = c.shape
         o = (C.c_double * 3)(*[float(v) for v in origin])
+        self._grid_shape = None
         self._check(self._L.fs_upload_grid(self._h, _p(c), nx, ny, nz, C.byref(o), float(resolution)))
+        self._grid_shape = (nz, ny, nx)
 
     def update_grid_region(self, x0, y0, z0, window, view=False):
         """fs_update_grid_region: `window` [sz][sy][sx] (or [sy][sx]) replaces the cells from (x0, y0, z0) on; view=True passes a
@@ -262,8 +269,10 @@ class FrontierScorer:
         xyz = np.ascontiguousarray(brick_xyz, dtype=np.int32).reshape(-1, 3)
         cells = np.ascontiguousarray(brick_cells, dtype=np.uint8).reshape(-1, 512)
         o = (C.c_double * 3)(*[float(v) for v in origin])
+        self._grid_shape = None
         self._check(self._L.fs_upload_grid_bricks(self._h, nx, ny, nz, C.byref(o), float(resolution), int(default_value),
                                                   xyz.shape[0], _p(xyz), _p(cells)))
+        self._grid_shape = (int(nz), int(ny), int(nx))
 
     def frontier_cells(self, shape_zyx, lethal_threshold=160, want_mask=True):
         mask = np.zeros(shape_zyx, dtype=np.uint8) if want_mask else None
@@ -447,6 +456,47 @@ class FrontierScorer:
         o = lambda p: vp(p) if p else None
         self._check(self._L.fs_rank_candidates_dev(self._h, int(n), vp(d_records), o(d_black), vp(d_path_length), vp(d_path_heading),
                                                    alpha, beta, max_vx, max_wz, vp(d_cost), o(d_au), o(d_du), o(d_order), o(d_err)))
+
+    # -- grid planner (the path columns)
+    def plan_paths(self, robot_pose7, goal_xyz, achievable_in=None, allow_unknown=False):
+        """setPlanForFrontier ("A*PlannerDistance") for every goal: one potential field from the robot, a descent per goal."""
+        pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
+        goal = np.ascontiguousarray(goal_xyz, dtype=np.float64).reshape(-1, 3)
+        n = goal.shape[0]
+        ai = None if achievable_in is None else np.ascontiguousarray(achievable_in, dtype=np.uint8).reshape(-1)
+        if ai is not None and ai.shape[0] != n:
+            raise ValueError(f"achievable_in has {ai.shape[0]} entries for {n} goals")
+        pl, plm, ph = np.zeros(n), np.zeros(n), np.zeros(n)
+        ach = np.zeros(n, dtype=np.uint8)
+        self._check(self._L.fs_plan_paths(self._h, C.byref(pose), 1 if allow_unknown else 0, n, _p(goal), _p(ai), _p(pl), _p(plm), _p(ph), _p(ach)))
+        return dict(path_length=pl, path_length_m=plm, path_heading=ph, achievable=ach)
+
+    def navfn_potential(self, robot_pose7, allow_unknown=False) -> np.ndarray:
+        """The potential field plan_paths descends, float32 [ny][nx] of the grid this scorer staged."""
+        pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
+        if self._grid_shape is None:
+            raise FsError(FS_E_STATE, "no grid staged through this scorer (upload_grid / upload_grid_bricks)")
+        nz, ny, nx = self._grid_shape
+        if nz != 1:
+            raise FsError(FS_E_INVALID, "the grid planner is defined on a 2-D costmap (nz == 1)")
+        pot = np.zeros((ny, nx), dtype=np.float32)
+        self._check(self._L.fs_navfn_potential(self._h, C.byref(pose), 1 if allow_unknown else 0, _p(pot)))
+        return pot
+
+    def get_frontier_costs_planned(self, robot_pose7, goal_xyz, frontier_size=None, blacklisted=None, allow_unknown=False,
+                                   with_fim=False, alpha=0.25, beta=1.0, max_vx=0.5, max_wz=0.5):
+        """get_frontier_costs with the path columns planned on the device in the same call (plan -> score -> rank)."""
+        pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
+        goal = np.ascontiguousarray(goal_xyz, dtype=np.float64).reshape(-1, 3)
+        n = goal.shape[0]
+        fs = None if frontier_size is None else np.ascontiguousarray(frontier_size, dtype=np.int32)
+        bl = None if blacklisted is None else np.ascontiguousarray(blacklisted, dtype=np.uint8)
+        rec = np.zeros(n, dtype=RECORD_DTYPE)
+        cost = np.zeros(n); au = np.zeros(n); du = np.zeros(n); order = np.zeros(n, dtype=np.int32); plm = np.zeros(n)
+        self._check(self._L.fs_get_frontier_costs_planned(self._h, C.byref(pose), 1 if allow_unknown else 0, n, _p(goal), _p(fs), _p(bl),
+                                                          alpha, beta, max_vx, max_wz, 1 if with_fim else 0, _p(rec), _p(cost), _p(au), _p(du),
+                                                          _p(order), _p(plm)))
+        return dict(records=rec, weighted_cost=cost, arrival_utility=au, distance_utility=du, order=order, path_length_m=plm)
 
     def selftest_fp64(self, max_abs=256) -> int:
         bad = C.c_int64()

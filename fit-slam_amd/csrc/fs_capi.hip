@@ -286,6 +286,21 @@ struct fs_ctx {
     std::map<uint64_t, GraphEntry> graphs;
     DevBuf<char> d_out;            // packed results of fs_get_frontier_costs (records | cost | utilities | order | error flag)
 
+    // batched grid planner (fs_navfn.hip): the potential field is kept per (grid generation, robot cell, allow_unknown); every
+    // staging call that writes the grid bumps grid_gen
+    uint64_t grid_gen = 1;
+    bool nav_valid = false;
+    uint64_t nav_gen = 0;
+    int32_t nav_rx = -1, nav_ry = -1, nav_allow = -1, nav_buf = 0;
+    int64_t nav_builds = 0, nav_rounds = 0, nav_launches = 0;
+    DevBuf<uint8_t> d_nav_cost;
+    DevBuf<float> d_nav_pot;          // [2][ny][nx]: the round buffers
+    DevBuf<uint32_t> d_nav_flags;     // [2][tiles]
+    DevBuf<int32_t> d_nav_any;        // one word per round of a batch
+    DevBuf<float> d_nav_path;         // [n][2][4 * max(nx, ny)] path points
+    DevBuf<char> d_nav_in, d_nav_out; // goal cells | headings;  path length | length in m | heading | achievable
+    PinnedBuf h_nav_in, h_nav_out;
+
     // timing
     bool timing = false;
     std::vector<TimedLaunch> launches;
@@ -853,6 +868,8 @@ void fs_ctx_destroy(fs_ctx *c)
     c->d_seg_all.release(); c->d_brick_xyz.release(); c->d_bad.release(); c->d_count.release();
     c->d_fc_parent_t.release(); c->d_fc_parent_f.release(); c->d_fc_aux.release(); c->d_fc_state.release(); c->d_fc_labels.release();
     c->d_fc_queue.release(); c->d_fc_visited.release(); c->d_fc_clusters.release(); c->d_fc_sums.release();
+    c->d_nav_cost.release(); c->d_nav_pot.release(); c->d_nav_flags.release(); c->d_nav_any.release(); c->d_nav_path.release();
+    c->d_nav_in.release(); c->d_nav_out.release(); c->h_nav_in.release(); c->h_nav_out.release();
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -992,6 +1009,7 @@ int fs_upload_grid(fs_ctx *c, const uint8_t *cells, int32_t nx, int32_t ny, int3
     const uint64_t total = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
     // (cell offsets are 32-bit unsigned in the walks, one z step is a signed 32-bit stride; everything else indexes in 64 bits)
     if (total >= (1ull << 32) || (uint64_t)nx * (uint64_t)ny >= (1ull << 31)) return fail(c, FS_E_INVALID, "dense grids are limited to 2^32 cells (and 2^31 per z slice)");
+    ++c->grid_gen;
     FS_HIP(c, c->d_cells.ensure((size_t)total));
     FS_HIP(c, hipMemcpyAsync(c->d_cells.p, cells, (size_t)total, hipMemcpyHostToDevice, c->stream));
     {
@@ -1027,6 +1045,7 @@ int fs_update_grid_region(fs_ctx *c, int32_t x0, int32_t y0, int32_t z0, int32_t
     if (slice_stride == 0) slice_stride = row_stride * (int64_t)sy;
     if (row_stride < sx || slice_stride < row_stride * (int64_t)(sy - 1) + sx) return fail(c, FS_E_INVALID, "window strides smaller than the window");
     const size_t total = (size_t)sx * (size_t)sy * (size_t)sz;
+    ++c->grid_gen;
     FS_HIP(c, c->h_win.ensure(total));
     FS_HIP(c, c->d_win.ensure(total));
     for (int32_t z = 0; z < sz; ++z)
@@ -1059,6 +1078,7 @@ int fs_upload_grid_bricks(fs_ctx *c, int32_t nx, int32_t ny, int32_t nz, const d
     const uint64_t total = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
     // (cell offsets are 32-bit unsigned in the walks, one z step is a signed 32-bit stride; everything else indexes in 64 bits)
     if (total >= (1ull << 32) || (uint64_t)nx * (uint64_t)ny >= (1ull << 31)) return fail(c, FS_E_INVALID, "dense grids are limited to 2^32 cells (and 2^31 per z slice)");
+    ++c->grid_gen;
     FS_HIP(c, c->d_cells.ensure((size_t)total));
     FS_HIP(c, hipMemsetAsync(c->d_cells.p, default_value, (size_t)total, c->stream));
     if (n_bricks > 0) {
@@ -1652,6 +1672,12 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
 {
     // host-side figures of the sparse class image ("ray.layout" 3): 1000 bricks of the grid, 1001 bricks its pool holds
     if (c && value && (which == 1000 || which == 1001)) { *value = (int64_t)(which == 1000 ? c->sparse_bricks : c->sparse_pool_bricks); return FS_OK; }
+    // ... of the grid planner (fs_plan_paths): 1002 potential fields built, 1003 rounds of the last one, 1004 round launches in all
+    if (c && value && which >= 1002 && which <= 1004) {
+        *value = which == 1002 ? c->nav_builds : which == 1003 ? c->nav_rounds : c->nav_launches;
+        if (reset) { if (which == 1002) c->nav_builds = 0; else if (which == 1004) c->nav_launches = 0; }
+        return FS_OK;
+    }
     if (!c || !value || which < 0 || which >= FS_N_COUNTERS) return FS_E_INVALID;
     FS_HIP(c, hipSetDevice(c->device));
     *value = 0;
@@ -2249,16 +2275,24 @@ int arrival_records_dev(fs_ctx *c, int32_t n, const double *d_goal, const int32_
 // candidates the device-side sequence is a captured launch graph per power-of-two bucket (run_maybe_graphed): the list is
 // padded to the bucket with blacklisted dummies, which no kernel spends work on and which a stable ascending sort leaves behind
 // every real candidate.
+// `planned`: the achievability and path columns already lie in device memory (fs_get_frontier_costs_planned: the planner wrote
+// them on this stream) — they are read there, never staged through the host, and the call is not graphed.
+struct PlannedCols {
+    const uint8_t *achievable;
+    const double *path_length, *path_heading;
+};
+
 int frontier_costs_core(fs_ctx *c, int32_t n, const double *goal_xyz, const int32_t *frontier_size, const uint8_t *blacklisted,
                         const uint8_t *achievable_in, const double *path_length, const double *path_heading,
                         double alpha, double beta, double max_vx, double max_wz, bool with_fim,
-                        fs_record *records, double *weighted_cost, double *arrival_utility, double *distance_utility, int32_t *order)
+                        fs_record *records, double *weighted_cost, double *arrival_utility, double *distance_utility, int32_t *order,
+                        const PlannedCols *planned = nullptr)
 {
     FS_HIP(c, hipSetDevice(c->device));
     int rc = check_scoring_state(c, true, with_fim);
     if (rc) return rc;
-    const bool rank = path_length != nullptr;
-    const bool graphed = c->opt_graph && !c->timing && n <= FS_GRAPH_MAX_N;
+    const bool rank = path_length != nullptr || planned != nullptr;
+    const bool graphed = c->opt_graph && !c->timing && n <= FS_GRAPH_MAX_N && !planned;
     const int32_t cap = graphed ? graph_bucket(n) : n;
     const size_t nn = (size_t)n, cc = (size_t)cap, pad = (cc + 15) & ~(size_t)15;
     // input block: goal | path length | path heading | frontier size | blacklist | achievable
@@ -2271,7 +2305,7 @@ int frontier_costs_core(fs_ctx *c, int32_t n, const double *goal_xyz, const int3
     FS_HIP(c, c->h_out.ensure(total_out)); FS_HIP(c, c->d_out.ensure(total_out));
     char *h = c->h_in.p;
     std::memcpy(h + i_goal, goal_xyz, 24 * nn);
-    if (rank) { std::memcpy(h + i_len, path_length, 8 * nn); std::memcpy(h + i_head, path_heading, 8 * nn); }
+    if (rank && !planned) { std::memcpy(h + i_len, path_length, 8 * nn); std::memcpy(h + i_head, path_heading, 8 * nn); }
     if (frontier_size) std::memcpy(h + i_fsize, frontier_size, 4 * nn); else std::memset(h + i_fsize, 0, 4 * nn);
     if (blacklisted) std::memcpy(h + i_black, blacklisted, nn); else std::memset(h + i_black, 0, nn);
     if (achievable_in) std::memcpy(h + i_achin, achievable_in, nn); else std::memset(h + i_achin, 1, nn);
@@ -2290,12 +2324,14 @@ int frontier_costs_core(fs_ctx *c, int32_t n, const double *goal_xyz, const int3
         const double *d_goal = reinterpret_cast<const double *>(din + i_goal);
         const int32_t *d_fsize = reinterpret_cast<const int32_t *>(din + i_fsize);
         const uint8_t *d_black = reinterpret_cast<const uint8_t *>(din + i_black), *d_achin = reinterpret_cast<const uint8_t *>(din + i_achin);
+        const double *d_len = reinterpret_cast<const double *>(din + i_len), *d_head = reinterpret_cast<const double *>(din + i_head);
+        if (planned) { d_achin = planned->achievable; d_len = planned->path_length; d_head = planned->path_heading; }
         fs_record *d_rec = reinterpret_cast<fs_record *>(dout + o_rec);
         int r = with_fim ? fs_score_candidates_dev(c, cap, d_goal, d_fsize, d_black, d_achin, d_rec)
                          : arrival_records_dev(c, cap, d_goal, d_fsize, d_black, d_achin, d_rec);
         if (r) return r;
         if (rank) {
-            r = fs_rank_candidates_dev(c, cap, d_rec, d_black, reinterpret_cast<const double *>(din + i_len), reinterpret_cast<const double *>(din + i_head),
+            r = fs_rank_candidates_dev(c, cap, d_rec, d_black, d_len, d_head,
                                        alpha, beta, max_vx, max_wz, reinterpret_cast<double *>(dout + o_cost), reinterpret_cast<double *>(dout + o_au),
                                        reinterpret_cast<double *>(dout + o_du), reinterpret_cast<int32_t *>(dout + o_order), reinterpret_cast<int32_t *>(dout + o_err));
             if (r) return r;
@@ -2578,6 +2614,231 @@ int fs_selftest_fp64(fs_ctx *c, int32_t max_abs, int64_t *mismatches)
             if (std::memcmp(&q, &hd[t], 8) != 0) ++bad;
         }
     *mismatches = bad;
+    return FS_OK;
+}
+
+}  // extern "C"
+
+// ================================================================== batched grid planner (fs_navfn.hip)
+// FrontierCostCalculator::setPlanForFrontier ("A*PlannerDistance", DEP/src/CostCalculator.cpp:193-393) for a whole frontier list:
+// every frontier plans back to the same robot cell (setStart(map_goal); setGoal(map_start), :269-271), so ONE potential field
+// from the robot serves the list and only the descents are per frontier.
+
+namespace {
+
+// Rounds are launched in batches without a host synchronisation in between; after a batch the host reads the batch's
+// "a tile changed" words.  A round after a quiet round is quiet too (no tile active, nothing to copy), so a batch that overshoots
+// the last round costs launches, never a different field.
+#define NAVFN_BATCH_FIRST 8
+#define NAVFN_BATCH 16
+#define NAVFN_MAX_ROUNDS (1 << 22)
+
+// Costmap2D::worldToMap on the staged grid
+bool nav_world_to_map(const fs_ctx *c, double wx, double wy, int32_t &mx, int32_t &my)
+{
+    if (wx < c->origin[0] || wy < c->origin[1]) return false;
+    const double qx = (wx - c->origin[0]) / c->res, qy = (wy - c->origin[1]) / c->res;
+    if (!(qx < 4294967296.0) || !(qy < 4294967296.0)) return false;
+    const unsigned ux = static_cast<unsigned>(qx), uy = static_cast<unsigned>(qy);
+    if (ux >= (unsigned)c->nx || uy >= (unsigned)c->ny) return false;
+    mx = (int32_t)ux; my = (int32_t)uy;
+    return true;
+}
+
+// CostCalculator.cpp:209-217: quatToEuler's yaw of the robot and the bearing of the goal, both in [0, 2 pi), the smaller way round
+double nav_heading(const double pose7[7], double gx, double gy)
+{
+    const double qx = pose7[3], qy = pose7[4], qz = pose7[5], qw = pose7[6];
+    double robot_yaw = std::atan2(2.0 * (qw * qz + qx * qy), 1.0 - 2.0 * (qy * qy + qz * qz));
+    if (robot_yaw < 0) robot_yaw = robot_yaw + (M_PI * 2);
+    double goal_yaw = std::atan2(gy - pose7[1], gx - pose7[0]);
+    if (goal_yaw < 0) goal_yaw = goal_yaw + (M_PI * 2);
+    double h = std::abs(robot_yaw - goal_yaw);
+    if (h > M_PI) h = (2 * M_PI) - h;
+    return h;
+}
+
+int nav_check(fs_ctx *c, const double robot_pose7[7])
+{
+    if (!robot_pose7) return fail(c, FS_E_INVALID, "null robot pose");
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (c->nz != 1) return fail(c, FS_E_INVALID, "the grid planner is defined on a 2-D costmap (nz == 1)");
+    return FS_OK;
+}
+
+// The field for (robot cell, allow_unknown) on the staged grid: the cached one, or built now (synchronises the stream).
+int navfn_field(fs_ctx *c, int32_t rx, int32_t ry, int32_t allow, const float **field)
+{
+    const int nx = c->nx, ny = c->ny;
+    const size_t ns = (size_t)nx * (size_t)ny;
+    allow = allow ? 1 : 0;
+    if (!(c->nav_valid && c->nav_gen == c->grid_gen && c->nav_rx == rx && c->nav_ry == ry && c->nav_allow == allow)) {
+        c->nav_valid = false;
+        const size_t tiles = (size_t)((nx + NAVFN_TILE - 1) / NAVFN_TILE) * (size_t)((ny + NAVFN_TILE - 1) / NAVFN_TILE);
+        FS_HIP(c, c->d_nav_cost.ensure(ns));
+        FS_HIP(c, c->d_nav_pot.ensure(2 * ns));
+        FS_HIP(c, c->d_nav_flags.ensure(2 * tiles));
+        FS_HIP(c, c->d_nav_any.ensure(NAVFN_BATCH));
+        float *buf[2] = {c->d_nav_pot.p, c->d_nav_pot.p + ns};
+        uint32_t *flags[2] = {c->d_nav_flags.p, c->d_nav_flags.p + tiles};
+        {
+            ScopedTimer t(c, 6);
+            FS_HIP(c, fs_launch_navfn_costs(c->d_cells.p, nx, ny, allow, c->d_nav_cost.p, c->stream));
+            FS_HIP(c, fs_launch_navfn_init(buf[0], buf[1], nx, ny, rx, ry, flags[0], c->stream));
+        }
+        int64_t r = 0, rounds = 0;
+        for (int batch = NAVFN_BATCH_FIRST;; batch = NAVFN_BATCH) {
+            FS_HIP(c, hipMemsetAsync(c->d_nav_any.p, 0, sizeof(int32_t) * batch, c->stream));
+            {
+                ScopedTimer t(c, 7);
+                for (int k = 0; k < batch; ++k, ++r)
+                    FS_HIP(c, fs_launch_navfn_round(buf[r & 1], buf[(r + 1) & 1], c->d_nav_cost.p, flags[r & 1], flags[(r + 1) & 1], nx, ny,
+                                                    c->d_nav_any.p + k, c->stream));
+            }
+            c->nav_launches += batch;
+            int32_t any[NAVFN_BATCH] = {0};
+            FS_HIP(c, hipMemcpyAsync(any, c->d_nav_any.p, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, c->stream));
+            FS_HIP(c, hipStreamSynchronize(c->stream));
+            if (!any[batch - 1]) {
+                int k = 0;
+                while (any[k]) ++k;                  // the first quiet round of the batch: the field's last round
+                rounds = r - batch + k + 1;
+                break;
+            }
+            if (r >= NAVFN_MAX_ROUNDS) return fail(c, FS_E_HIP, "potential field did not settle in %d rounds", NAVFN_MAX_ROUNDS);
+        }
+        c->nav_buf = (int32_t)(r & 1);               // (after a quiet round both buffers hold the field)
+        c->nav_valid = true;
+        c->nav_gen = c->grid_gen; c->nav_rx = rx; c->nav_ry = ry; c->nav_allow = allow;
+        c->nav_rounds = rounds;
+        ++c->nav_builds;
+    }
+    *field = c->d_nav_pot.p + (size_t)c->nav_buf * ns;
+    return FS_OK;
+}
+
+// Output block of the path kernel in d_nav_out: path length | length in m | heading | achievable.
+struct NavOutLayout {
+    size_t len, len_m, head, ach, total;
+    explicit NavOutLayout(size_t n) : len(0), len_m(8 * n), head(16 * n), ach(24 * n), total(24 * n + ((n + 15) & ~(size_t)15)) {}
+};
+
+// Goal cells and headings staged, the field (cached or built), the path kernel: the four columns land in d_nav_out on the
+// context's stream.  Not synchronised.
+int navfn_plan_enqueue(fs_ctx *c, const double robot7[7], int32_t allow, int32_t n, const double *goal_xyz, const uint8_t *achievable_in)
+{
+    const size_t nn = (size_t)n;
+    const int32_t max_cycles = 4 * std::max(c->nx, c->ny);      // CostCalculator.cpp:284
+    const size_t i_cell = 0, i_head = (4 * nn + 7) & ~(size_t)7, total_in = i_head + 8 * nn;
+    const NavOutLayout O(nn);
+    // every buffer this call uses is sized before a pointer into any of them is taken
+    FS_HIP(c, c->h_nav_in.ensure(total_in)); FS_HIP(c, c->d_nav_in.ensure(total_in));
+    FS_HIP(c, c->d_nav_out.ensure(O.total));
+    FS_HIP(c, c->d_nav_path.ensure(nn * 2 * (size_t)max_cycles));
+    int32_t rx = 0, ry = 0;
+    const bool robot_on = nav_world_to_map(c, robot7[0], robot7[1], rx, ry);
+    int32_t *cell = reinterpret_cast<int32_t *>(c->h_nav_in.p + i_cell);
+    double *head = reinterpret_cast<double *>(c->h_nav_in.p + i_head);
+    bool need_field = false;
+    for (size_t i = 0; i < nn; ++i) {
+        int32_t gx = 0, gy = 0;
+        const bool planned = (!achievable_in || achievable_in[i]) && robot_on && nav_world_to_map(c, goal_xyz[3 * i], goal_xyz[3 * i + 1], gx, gy);
+        cell[i] = planned ? gy * c->nx + gx : -1;
+        head[i] = planned ? nav_heading(robot7, goal_xyz[3 * i], goal_xyz[3 * i + 1]) : 0.0;
+        need_field |= planned;
+    }
+    const float *field = nullptr;
+    if (need_field) { const int rc = navfn_field(c, rx, ry, allow, &field); if (rc) return rc; }
+    FS_HIP(c, hipMemcpyAsync(c->d_nav_in.p, c->h_nav_in.p, total_in, hipMemcpyHostToDevice, c->stream));
+    FsNavfnPathArgs a{};
+    a.pot = field; a.nx = c->nx; a.ny = c->ny; a.n = n;
+    a.goal_cell = reinterpret_cast<const int32_t *>(c->d_nav_in.p + i_cell);
+    a.heading_in = reinterpret_cast<const double *>(c->d_nav_in.p + i_head);
+    a.robot_x = rx; a.robot_y = ry; a.max_cycles = max_cycles;
+    a.scratch = c->d_nav_path.p;
+    a.ox = c->origin[0]; a.oy = c->origin[1]; a.res = c->res;
+    a.path_length = reinterpret_cast<double *>(c->d_nav_out.p + O.len);
+    a.path_length_m = reinterpret_cast<double *>(c->d_nav_out.p + O.len_m);
+    a.path_heading = reinterpret_cast<double *>(c->d_nav_out.p + O.head);
+    a.achievable = reinterpret_cast<uint8_t *>(c->d_nav_out.p + O.ach);
+    ScopedTimer t(c, 8);
+    FS_HIP(c, fs_launch_navfn_paths(a, c->stream));
+    return FS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fs_navfn_potential(fs_ctx *c, const double robot_pose7[7], int32_t allow_unknown, float *potential)
+{
+    if (!c) return FS_E_INVALID;
+    if (!potential) return fail(c, FS_E_INVALID, "null pointer");
+    int rc = nav_check(c, robot_pose7);
+    if (rc) return rc;
+    int32_t rx = 0, ry = 0;
+    if (!nav_world_to_map(c, robot_pose7[0], robot_pose7[1], rx, ry)) return fail(c, FS_E_INVALID, "the robot is off the costmap: no potential field");
+    const float *field = nullptr;
+    rc = navfn_field(c, rx, ry, allow_unknown, &field);
+    if (rc) return rc;
+    FS_HIP(c, hipMemcpyAsync(potential, field, sizeof(float) * (size_t)c->nx * (size_t)c->ny, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    return FS_OK;
+}
+
+int fs_plan_paths(fs_ctx *c, const double robot_pose7[7], int32_t allow_unknown, int32_t n, const double *goal_xyz,
+                  const uint8_t *achievable_in, double *path_length, double *path_length_m, double *path_heading, uint8_t *achievable)
+{
+    if (!c) return FS_E_INVALID;
+    if (n < 0 || (n > 0 && (!goal_xyz || !path_length || !path_length_m || !path_heading || !achievable))) return fail(c, FS_E_INVALID, "null pointer");
+    int rc = nav_check(c, robot_pose7);
+    if (rc) return rc;
+    if (n == 0) return FS_OK;
+    rc = navfn_plan_enqueue(c, robot_pose7, allow_unknown, n, goal_xyz, achievable_in);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    const size_t nn = (size_t)n;
+    const NavOutLayout O(nn);
+    FS_HIP(c, c->h_nav_out.ensure(O.total));
+    FS_HIP(c, hipMemcpyAsync(c->h_nav_out.p, c->d_nav_out.p, O.total, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    std::memcpy(path_length, c->h_nav_out.p + O.len, 8 * nn);
+    std::memcpy(path_length_m, c->h_nav_out.p + O.len_m, 8 * nn);
+    std::memcpy(path_heading, c->h_nav_out.p + O.head, 8 * nn);
+    std::memcpy(achievable, c->h_nav_out.p + O.ach, nn);
+    return FS_OK;
+}
+
+int fs_get_frontier_costs_planned(fs_ctx *c, const double robot_pose7[7], int32_t allow_unknown, int32_t n, const double *goal_xyz,
+                                  const int32_t *frontier_size, const uint8_t *blacklisted, double alpha, double beta, double max_vx, double max_wz,
+                                  int with_fisher_information, fs_record *records, double *weighted_cost, double *arrival_utility,
+                                  double *distance_utility, int32_t *order, double *path_length_m)
+{
+    if (!c) return FS_E_INVALID;
+    if (n < 0 || (n > 0 && (!goal_xyz || !records || !weighted_cost))) return fail(c, FS_E_INVALID, "null pointer");
+    int rc = nav_check(c, robot_pose7);
+    if (rc) return rc;
+    if (n == 0) return FS_OK;
+    rc = check_scoring_state(c, true, with_fisher_information != 0);
+    if (rc) return rc;
+    const size_t nn = (size_t)n;
+    const NavOutLayout O(nn);
+    FS_HIP(c, c->h_nav_out.ensure(O.total));
+    rc = navfn_plan_enqueue(c, robot_pose7, allow_unknown, n, goal_xyz, nullptr);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (path_length_m) FS_HIP(c, hipMemcpyAsync(c->h_nav_out.p + O.len_m, c->d_nav_out.p + O.len_m, 8 * nn, hipMemcpyDeviceToHost, c->stream));
+    // the planner's columns stay where the path kernel wrote them: scoring reads its achievability, ranking its path columns
+    const PlannedCols cols{reinterpret_cast<const uint8_t *>(c->d_nav_out.p + O.ach), reinterpret_cast<const double *>(c->d_nav_out.p + O.len),
+                           reinterpret_cast<const double *>(c->d_nav_out.p + O.head)};
+    rc = frontier_costs_core(c, n, goal_xyz, frontier_size, blacklisted, nullptr, nullptr, nullptr, alpha, beta, max_vx, max_wz,
+                             with_fisher_information != 0, records, weighted_cost, arrival_utility, distance_utility, order, &cols);
+    if (rc) {
+        // (frontier_costs_core can fail before its own synchronisation: the copy into h_nav_out above must have landed before a
+        // later call may grow that buffer)
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    if (path_length_m) std::memcpy(path_length_m, c->h_nav_out.p + O.len_m, 8 * nn);
     return FS_OK;
 }
 

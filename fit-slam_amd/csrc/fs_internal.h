@@ -110,6 +110,28 @@ hipError_t fs_launch_frontier_clusters(const uint8_t *d_map, int nx, int ny, dou
                                        int32_t *d_aux, uint32_t *d_queue, uint8_t *d_visited, int32_t *d_state, int32_t *d_labels,
                                        int32_t max_clusters, fs_frontier_cluster *d_clusters, long long *d_sums, hipStream_t s);
 
+// ---- batched grid planner (fs_navfn.hip): one NavFn potential field per (grid, robot cell, allow_unknown) by a
+// tiled Jacobi schedule, then NavFn::calcPath from every frontier.  The tile size is part of the field's definition.
+#define NAVFN_TILE 32
+struct FsNavfnPathArgs {
+    const float *pot;          // [ny][nx] converged field
+    int32_t nx, ny;
+    int32_t n;
+    const int32_t *goal_cell;  // [n] y * nx + x of the frontier cell, -1: not planned (achievable_in 0, off the map, robot off the map)
+    const double *heading_in;  // [n] setPlanForFrontier's heading (host, libm), used where the plan succeeds
+    int32_t robot_x, robot_y;
+    int32_t max_cycles;        // 4 * max(nx, ny)
+    float *scratch;            // [n][2][max_cycles] path points x then y
+    double ox, oy, res;
+    double *path_length, *path_length_m, *path_heading;   // path_length_m may be nullptr
+    uint8_t *achievable;
+};
+hipError_t fs_launch_navfn_costs(const uint8_t *d_cells, int nx, int ny, int allow_unknown, uint8_t *d_cost, hipStream_t s);
+hipError_t fs_launch_navfn_init(float *d_a, float *d_b, int nx, int ny, int rx, int ry, uint32_t *d_flags_prev, hipStream_t s);
+hipError_t fs_launch_navfn_round(const float *d_a, float *d_b, const uint8_t *d_cost, const uint32_t *d_prev, uint32_t *d_cur, int nx, int ny,
+                                 int32_t *d_any, hipStream_t s);
+hipError_t fs_launch_navfn_paths(const FsNavfnPathArgs &a, hipStream_t s);
+
 // ---- key-frame pose information (computeInformationForPose)
 struct FsKfArgs {
     int32_t n;                 // poses

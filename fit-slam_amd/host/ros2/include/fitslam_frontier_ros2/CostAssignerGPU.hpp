@@ -54,7 +54,10 @@ public:
     void setFrontierBlacklist(std::vector<FrontierPtr> &blacklist);
 
     // which planner fills path length / heading: "RoadmapPlannerDistance" (the reference's choice,
-    // DEP/src/CostAssigner.cpp:38), "A*PlannerDistance" or "EuclideanDistance"
+    // DEP/src/CostAssigner.cpp:38), "A*PlannerDistance" or "EuclideanDistance" — the reference's planners, one frontier at a
+    // time on the host — or "NavFnGPU": the grid planner of "A*PlannerDistance" for the whole list in ONE fs_plan_paths call on
+    // the first device (one NavFn potential per tick, every descent batched; the field is the converged one of DESIGN.md 4.9,
+    // not the reference's per-frontier partial A* wave), in both routes
     void setPlannerMethod(const std::string &method) { planner_method_ = method; }
 
     // true: the whole cost assignment as ONE device call, fs_multi_get_frontier_costs — the planner runs first (on every live
@@ -70,6 +73,9 @@ private:
     bool assignCostsFused(std::vector<FrontierPtr> &frontier_list, geometry_msgs::msg::Pose start_pose_w);   // the same through ONE call
     bool prepareTick(std::vector<FrontierPtr> &frontier_list);   // what both routes do first (:51-72): snapshot, limits, list checks
     void plan(geometry_msgs::msg::Pose start_pose_w, FrontierPtr &frontier);   // the reference's planner named by planner_method_ (:98-109)
+    // "NavFnGPU": fs_plan_paths over the list (plan_in = its achievable_in); the columns onto every frontier with apply[i]
+    void planAllOnDevice(const geometry_msgs::msg::Pose &start_pose_w, std::vector<FrontierPtr> &frontier_list, const std::vector<double> &goal,
+                         const std::vector<uint8_t> &plan_in, const std::vector<uint8_t> &apply, std::vector<double> &heading);
     void snapshotCostmap();                                  // fs_upload_grid under the costmap mutex
     void pushRayParams();                                    // fs_set_ray_params (+ cached arrival limits)
     void restoreArrivalLimits();                             // hands the cached limits back to every device

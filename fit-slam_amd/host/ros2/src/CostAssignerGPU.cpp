@@ -178,6 +178,35 @@ void CostAssignerGPU::plan(geometry_msgs::msg::Pose start_pose_w, FrontierPtr &f
         planner_->setPlanForFrontierEuclidean(start_pose_w, frontier, map_data, false, planner_allow_unknown_);
 }
 
+// "NavFnGPU": FrontierCostCalculator::setPlanForFrontier ("A*PlannerDistance", CostCalculator.cpp:193-393) for the whole list in
+// ONE call — fs_plan_paths on the first device (the grid is already staged there by snapshotCostmap): one NavFn potential from the
+// robot cell, every frontier's descent batched.  plan_in[i] = 0: not planned (the reference returns at once for
+// an unachievable frontier, :196-204: DBL_MAX columns, achievable false).  Every frontier with apply[i] gets the columns the
+// reference's planner would have set; the headings come back in `heading` (the ranking's column).
+void CostAssignerGPU::planAllOnDevice(const geometry_msgs::msg::Pose &start_pose_w, std::vector<FrontierPtr> &frontier_list,
+                                      const std::vector<double> &goal, const std::vector<uint8_t> &plan_in, const std::vector<uint8_t> &apply,
+                                      std::vector<double> &heading)
+{
+    const int32_t n = static_cast<int32_t>(frontier_list.size());
+    const double pose7[7] = {start_pose_w.position.x, start_pose_w.position.y, start_pose_w.position.z, start_pose_w.orientation.x,
+                             start_pose_w.orientation.y, start_pose_w.orientation.z, start_pose_w.orientation.w};
+    std::vector<double> plen(n), plen_m(n);
+    std::vector<uint8_t> ach(n);
+    heading.assign(n, 0.0);
+    fs_ctx *ctx = fs_multi_ctx(scorer_, 0);
+    const int rc = fs_plan_paths(ctx, pose7, planner_allow_unknown_ ? 1 : 0, n, goal.data(), plan_in.data(), plen.data(), plen_m.data(),
+                                 heading.data(), ach.data());
+    if (rc != FS_OK) throw std::runtime_error(std::string("fs_plan_paths: ") + fs_last_error(ctx));
+    for (int32_t i = 0; i < n; ++i) {
+        if (!apply[i]) continue;
+        auto &f = frontier_list[i];
+        f->setAchievability(ach[i] != 0);                                        // :196-204, :257-300
+        f->setPathLength(plen[i]);                                               // :330
+        f->setPathLengthInM(plen_m[i]);                                          // :331
+        if (!ach[i]) f->setFisherInformation(0);
+    }
+}
+
 // assignCosts through ONE device call (fs_multi_get_frontier_costs).  The planner runs FIRST, on every frontier that is not
 // blacklisted and as if achievable; what it decides (a frontier it cannot reach: achievable = false) enters the call as
 // achievable_in, which the arrival step can only clear further — the final flag is the AND of the same conditions in either
@@ -196,15 +225,27 @@ bool CostAssignerGPU::assignCostsFused(std::vector<FrontierPtr> &frontier_list, 
         std::lock_guard<std::mutex> lock(blacklist_mutex_);
         for (int32_t i = 0; i < n; ++i) black[i] = frontier_blacklist_.count(frontier_list[i]) > 0 ? 1 : 0;   // :77
     }
+    const bool on_device = planner_method_ == "NavFnGPU";
+    std::vector<uint8_t> live(n);
     for (int32_t i = 0; i < n; ++i) {
         auto &f = frontier_list[i];
         const geometry_msgs::msg::Point &g = f->getGoalPoint();
         goal[3 * i] = g.x; goal[3 * i + 1] = g.y; goal[3 * i + 2] = 0.0;
         fsize[i] = f->getSize();
-        if (black[i]) continue;
+        live[i] = black[i] ? 0 : 1;
+        if (black[i] || on_device) continue;
         plan(start_pose_w, f);                                                   // (the reference's planners return at once for a frontier that is already unachievable)
         ach_in[i] = f->isAchievable() ? 1 : 0;
         if (ach_in[i]) { plen[i] = f->getPathLength(); phead[i] = f->getPathHeading(); }
+    }
+    if (on_device) {                                                             // every live frontier planned in one call
+        std::vector<double> heading;
+        planAllOnDevice(start_pose_w, frontier_list, goal, live, live, heading);
+        for (int32_t i = 0; i < n; ++i) {
+            if (black[i]) continue;
+            ach_in[i] = frontier_list[i]->isAchievable() ? 1 : 0;
+            if (ach_in[i]) { plen[i] = frontier_list[i]->getPathLength(); phead[i] = heading[i]; }
+        }
     }
     std::vector<fs_record> rec(n);
     const int rc = fs_multi_get_frontier_costs(scorer_, n, goal.data(), fsize.data(), black.data(), ach_in.data(), plen.data(), phead.data(),
@@ -257,6 +298,13 @@ bool CostAssignerGPU::assignCosts(std::vector<FrontierPtr> &frontier_list, geome
     check(fs_multi_score_arrival(scorer_, n, goal.data(), fsize.data(), black.data(), ach_in.data(), nullptr, arrival.data(),
                                  argmax.data(), yaw.data(), ach.data(), status.data()), "fs_multi_score_arrival");
 
+    const bool on_device = planner_method_ == "NavFnGPU";
+    std::vector<double> heading;
+    if (on_device) {                                                             // the plans of :98-109, one call for the list
+        std::vector<uint8_t> plan_in(n), apply(n);
+        for (int32_t i = 0; i < n; ++i) { apply[i] = black[i] ? 0 : 1; plan_in[i] = (!black[i] && ach[i]) ? 1 : 0; }
+        planAllOnDevice(start_pose_w, frontier_list, goal, plan_in, apply, heading);
+    }
     for (int32_t i = 0; i < n; ++i) {
         auto &frontier = frontier_list[i];
         if (black[i]) {                                                          // :77-86
@@ -270,9 +318,11 @@ bool CostAssignerGPU::assignCosts(std::vector<FrontierPtr> &frontier_list, geome
         }
         frontier->setArrivalInformation(static_cast<double>(arrival[i]));        // CostCalculator.cpp:52 / :112
         frontier->setGoalOrientation(yaw[i]);                                    // :53 / :119
-        frontier->setAchievability(ach[i] != 0);                                 // :78-82, :114-118
-        // planning stays with the reference (:98-109); it skips frontiers that are not achievable
-        plan(start_pose_w, frontier);
+        if (!on_device) {                                                        // ("NavFnGPU" planned above: achievability is the planner's)
+            frontier->setAchievability(ach[i] != 0);                             // :78-82, :114-118
+            // planning stays with the reference (:98-109); it skips frontiers that are not achievable
+            plan(start_pose_w, frontier);
+        }
         planner_->recomputeNormalizationFactors(frontier);                       // :118
     }
 
@@ -285,7 +335,7 @@ bool CostAssignerGPU::assignCosts(std::vector<FrontierPtr> &frontier_list, geome
         rec[i].arrival = black[i] ? 0 : arrival[i];
         rec[i].flags = (!black[i] && f->isAchievable()) ? FS_FLAG_ACHIEVABLE : 0u;
         plen[i] = f->getPathLength();
-        phead[i] = (black[i] || !f->isAchievable()) ? 0.0 : f->getPathHeading();
+        phead[i] = (black[i] || !f->isAchievable()) ? 0.0 : (on_device ? heading[i] : f->getPathHeading());
     }
     fs_ctx *rank_ctx = fs_multi_ctx(scorer_, 0);                                  // the gathered list is ranked on the first device
     const int rc = fs_rank_candidates(rank_ctx, n, rec.data(), black.data(), plen.data(), phead.data(), alpha_, beta_, max_vx_, max_wx_,

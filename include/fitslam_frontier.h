@@ -401,6 +401,29 @@ int fs_rank_candidates_dev(fs_ctx *ctx, int32_t n, const fs_record *d_records, c
                            double *d_weighted_cost, double *d_arrival_utility, double *d_distance_utility,
                            int32_t *d_order, int32_t *d_range_error);
 
+/* ---------------------------------------------------------------- grid planner (the path columns) */
+
+/* FrontierCostCalculator::setPlanForFrontier ("A*PlannerDistance", DEP/src/CostCalculator.cpp:193-393) for n frontiers at once:
+ * one NavFn potential from the robot cell over the staged 2-D grid, then NavFn::calcPath from every goal.  robot_pose7 = xyz + quat xyzw.
+ * achievable_in [n] or NULL (= all).  Outputs [n]: path_length (points), path_length_m, path_heading, achievable.
+ * The field is the fixed point of NavFn's cell update under the tiled schedule of DESIGN.md 4.9 (the reference's A* stops its wave
+ * at the goal and drops pushes beyond 10 000 per buffer: per frontier, a partial field); it is kept per context for (grid,
+ * robot cell, allow_unknown) — fs_upload_grid, fs_upload_grid_bricks and fs_update_grid_region drop it.  A frontier that is not
+ * planned (achievable_in 0, robot or goal off the map, goal cell unreached, calcPath failed): achievable 0 and DBL_MAX in the
+ * three columns.  nz > 1: FS_E_INVALID. */
+int fs_plan_paths(fs_ctx *ctx, const double robot_pose7[7], int32_t allow_unknown, int32_t n, const double *goal_xyz,
+                  const uint8_t *achievable_in, double *path_length, double *path_length_m, double *path_heading, uint8_t *achievable);
+/* the potential field fs_plan_paths descends, [ny][nx] float (NavFn::getPotArray): for tests and visualisation.  Robot off the
+ * map: FS_E_INVALID */
+int fs_navfn_potential(fs_ctx *ctx, const double robot_pose7[7], int32_t allow_unknown, float *potential);
+/* fs_get_frontier_costs with the path columns planned on the device: plan -> arrival (+ Fisher) -> U1 -> order, one call; the
+ * planner's achievability feeds achievable_in; path_length_m [n] or NULL.  Same results, bit for bit, as fs_plan_paths followed by
+ * fs_get_frontier_costs on its columns; the path columns never visit the host in between. */
+int fs_get_frontier_costs_planned(fs_ctx *ctx, const double robot_pose7[7], int32_t allow_unknown, int32_t n, const double *goal_xyz,
+                  const int32_t *frontier_size, const uint8_t *blacklisted, double alpha, double beta, double max_vx, double max_wz,
+                  int with_fisher_information, fs_record *records, double *weighted_cost, double *arrival_utility,
+                  double *distance_utility, int32_t *order, double *path_length_m);
+
 #ifdef __cplusplus
 }
 #endif

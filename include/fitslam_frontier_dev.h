@@ -19,7 +19,8 @@ extern "C" {
 /* Per-kernel device time.  With timing enabled every kernel launch is bracketed by hipEvents on
  * the context's stream; fs_kernel_time returns and resets the accumulated (ms, launches) of
  * kernel kind: 0 ray-march, 1 FIM accumulate, 2 FIM HBM-table tier, 3 utility/rank, 4 candidate sort,
- * 5 frontier-cell stencil. */
+ * 5 frontier-cell stencil, 6 planner cost conversion + field set-up, 7 planner field rounds (one bracket per batch of rounds),
+ * 8 planner path descent. */
 int  fs_enable_kernel_timing(fs_ctx *ctx, int enable);
 int  fs_kernel_time(fs_ctx *ctx, int kind, double *total_ms, int64_t *launches);
 
@@ -70,7 +71,9 @@ int  fs_set_option(fs_ctx *ctx, const char *key, double value);
  * showed (the pass prediction's input; reset with the cloud, the table and the visibility volume) — 12 per landmark of the
  * chunks in range and cone (the cone workers), 13 per landmark of the chunks that can also meet the lookup table's box (the
  * cone-off and info-only workers); 10 / 11 = landmark tests / candidates since the last spatially sorted call (the sort's own
- * accumulators: CLEARED by every call of 2048 candidates or more — not running totals).  Host-side: 1000 / 1001 = bricks of the grid / bricks in the pool of "ray.layout" 3. */
+ * accumulators: CLEARED by every call of 2048 candidates or more — not running totals).  Host-side: 1000 / 1001 = bricks of the grid / bricks in the pool of "ray.layout" 3;
+ * 1002 = potential fields the grid planner built (fs_plan_paths: a call that reuses the cached field adds nothing), 1003 = rounds
+ * of the last field built, 1004 = field rounds launched in all (1002 and 1004 are reset by `reset`). */
 int  fs_get_counter(fs_ctx *ctx, int which, int64_t *value, int reset);
 
 /* ---------------------------------------------------------------- self test */

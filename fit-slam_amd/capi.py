@@ -32,6 +32,8 @@ EXPORTED_SYMBOLS = [
     "fs_multi_lookup_load", "fs_multi_set_fim_params", "fs_multi_max_arrival", "fs_multi_score_arrival", "fs_multi_score_candidates",
     "fs_multi_score_fim", "fs_multi_get_frontier_costs", "fs_multi_gather_mode",
     "fs_plan_paths", "fs_navfn_potential", "fs_get_frontier_costs_planned",
+    "fs_set_roadmap_params", "fs_roadmap_add_nodes", "fs_roadmap_rebuild", "fs_roadmap_connect", "fs_roadmap_get_graph", "fs_roadmap_plan",
+    "fs_get_frontier_costs_roadmap",
 ]
 
 RECORD_DTYPE = np.dtype([("arrival", "<i4"), ("argmax", "<i4"), ("yaw", "<f4"), ("info_ref", "<f4"),
@@ -154,6 +156,13 @@ def load_library(build: bool = True):
     L.fs_plan_paths.argtypes = [vp, C.POINTER(dbl * 7), i32, i32, vp, vp, vp, vp, vp, vp]
     L.fs_navfn_potential.argtypes = [vp, C.POINTER(dbl * 7), i32, vp]
     L.fs_get_frontier_costs_planned.argtypes = [vp, C.POINTER(dbl * 7), i32, i32, vp, vp, vp, dbl, dbl, dbl, dbl, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.fs_set_roadmap_params.argtypes = [vp, dbl, dbl, dbl, dbl]
+    L.fs_roadmap_add_nodes.argtypes = [vp, i32, vp, i32]
+    L.fs_roadmap_rebuild.argtypes = [vp]
+    L.fs_roadmap_connect.argtypes = [vp, i32, vp]
+    L.fs_roadmap_get_graph.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), vp, vp, vp, vp]
+    L.fs_roadmap_plan.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, vp, vp, vp, vp]
+    L.fs_get_frontier_costs_roadmap.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, vp, dbl, dbl, dbl, dbl, C.c_int, vp, vp, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         f = getattr(L, name)
         if name not in ("fs_ctx_destroy", "fs_last_error", "fs_multi_destroy", "fs_multi_last_error", "fs_multi_ctx"):
@@ -496,6 +505,63 @@ class FrontierScorer:
         self._check(self._L.fs_get_frontier_costs_planned(self._h, C.byref(pose), 1 if allow_unknown else 0, n, _p(goal), _p(fs), _p(bl),
                                                           alpha, beta, max_vx, max_wz, 1 if with_fim else 0, _p(rec), _p(cost), _p(au), _p(du),
                                                           _p(order), _p(plm)))
+        return dict(records=rec, weighted_cost=cost, arrival_utility=au, distance_utility=du, order=order, path_length_m=plm)
+
+    # -- frontier roadmap (the reference's default planner, "RoadmapPlannerDistance")
+    def set_roadmap_params(self, grid_cell_size=1.0, radius_to_decide_edges=6.1, min_distance_between_two_frontier_nodes=0.25,
+                           min_distance_between_robot_pose_and_node=0.25):
+        """FrontierRoadMap's parameters; a new set starts an empty roadmap."""
+        self._check(self._L.fs_set_roadmap_params(self._h, float(grid_cell_size), float(radius_to_decide_edges),
+                                                  float(min_distance_between_two_frontier_nodes), float(min_distance_between_robot_pose_and_node)))
+
+    def roadmap_add_nodes(self, xy, is_robot_pose=False):
+        """populateNodes: addNodes (frontier goal points) or addRobotPoseAsNode.  xy [n][2] (extra columns ignored)."""
+        p = np.ascontiguousarray(np.asarray(xy, dtype=np.float64).reshape(-1, np.asarray(xy).shape[-1])[:, :2])
+        self._check(self._L.fs_roadmap_add_nodes(self._h, p.shape[0], _p(p), 1 if is_robot_pose else 0))
+
+    def roadmap_rebuild(self):
+        """reConstructGraph(entireGraph = true) on the staged 2-D grid, on the device."""
+        self._check(self._L.fs_roadmap_rebuild(self._h))
+
+    def roadmap_connect(self, xy):
+        """constructNewEdges for the points xy [n][2] (append the robot pose for constructNewEdgeRobotPose)."""
+        p = np.ascontiguousarray(np.asarray(xy, dtype=np.float64).reshape(-1, np.asarray(xy).shape[-1])[:, :2])
+        self._check(self._L.fs_roadmap_connect(self._h, p.shape[0], _p(p)))
+
+    def roadmap_graph(self):
+        """dict(xy [n][2], key [n], row_ptr [n + 1], col [n_edges]) of the roadmap as the context holds it."""
+        n, e = C.c_int32(), C.c_int64()
+        self._check(self._L.fs_roadmap_get_graph(self._h, C.byref(n), C.byref(e), None, None, None, None))
+        xy = np.zeros((n.value, 2)); key = np.zeros(n.value, np.uint8)
+        row = np.zeros(n.value + 1, np.int32); col = np.zeros(e.value, np.int32)
+        self._check(self._L.fs_roadmap_get_graph(self._h, C.byref(n), C.byref(e), _p(xy), _p(key), _p(row), _p(col)))
+        return dict(xy=xy, key=key, row_ptr=row, col=col)
+
+    def roadmap_plan(self, robot_pose7, goal_xyz, achievable_in=None):
+        """setPlanForFrontierRoadmap for every goal: one shortest-path tree from the robot's closest key node."""
+        pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
+        goal = np.ascontiguousarray(goal_xyz, dtype=np.float64).reshape(-1, 3)
+        n = goal.shape[0]
+        ai = None if achievable_in is None else np.ascontiguousarray(achievable_in, dtype=np.uint8).reshape(-1)
+        if ai is not None and ai.shape[0] != n:
+            raise ValueError(f"achievable_in has {ai.shape[0]} entries for {n} goals")
+        pl, plm, ph = np.zeros(n), np.zeros(n), np.zeros(n)
+        ach = np.zeros(n, dtype=np.uint8)
+        self._check(self._L.fs_roadmap_plan(self._h, C.byref(pose), n, _p(goal), _p(ai), _p(pl), _p(plm), _p(ph), _p(ach)))
+        return dict(path_length=pl, path_length_m=plm, path_heading=ph, achievable=ach)
+
+    def get_frontier_costs_roadmap(self, robot_pose7, goal_xyz, frontier_size=None, blacklisted=None, with_fim=False,
+                                   alpha=0.25, beta=1.0, max_vx=0.5, max_wz=0.5):
+        """get_frontier_costs with the path columns planned on the roadmap in the same call (plan -> score -> rank)."""
+        pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
+        goal = np.ascontiguousarray(goal_xyz, dtype=np.float64).reshape(-1, 3)
+        n = goal.shape[0]
+        fs = None if frontier_size is None else np.ascontiguousarray(frontier_size, dtype=np.int32)
+        bl = None if blacklisted is None else np.ascontiguousarray(blacklisted, dtype=np.uint8)
+        rec = np.zeros(n, dtype=RECORD_DTYPE)
+        cost = np.zeros(n); au = np.zeros(n); du = np.zeros(n); order = np.zeros(n, dtype=np.int32); plm = np.zeros(n)
+        self._check(self._L.fs_get_frontier_costs_roadmap(self._h, C.byref(pose), n, _p(goal), _p(fs), _p(bl), alpha, beta, max_vx, max_wz,
+                                                          1 if with_fim else 0, _p(rec), _p(cost), _p(au), _p(du), _p(order), _p(plm)))
         return dict(records=rec, weighted_cost=cost, arrival_utility=au, distance_utility=du, order=order, path_length_m=plm)
 
     def selftest_fp64(self, max_abs=256) -> int:

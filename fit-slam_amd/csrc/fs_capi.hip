@@ -301,6 +301,26 @@ struct fs_ctx {
     DevBuf<char> d_nav_in, d_nav_out; // goal cells | headings;  path length | length in m | heading | achievable
     PinnedBuf h_nav_in, h_nav_out;
 
+    // frontier roadmap (fs_roadmap.hip).  The host keeps FrontierRoadMap's two containers — the spatial hash (cell ->
+    // node ids in insertion order) and roadmap_ (a key flag and an adjacency list in append order per node) — and the device a copy
+    // of them as CSR.  Every mutation bumps rm_gen; the device copy, its transpose and the shortest-path tree (kept per root node)
+    // are valid for the generation they were made for.
+    double rm_cell = 1.0, rm_radius = 6.1, rm_min_frontier = 0.25, rm_min_robot = 0.25;
+    std::vector<double> rm_xy;
+    std::map<std::pair<int, int>, std::vector<int32_t>> rm_hash;
+    std::vector<uint8_t> rm_key;
+    std::vector<std::vector<int32_t>> rm_adj;
+    uint64_t rm_gen = 1, rm_dev_gen = 0, rm_t_gen = 0, rm_tree_gen = 0;
+    int32_t rm_tree_root = -1, rm_tree_buf = 0;
+    int64_t rm_tree_builds = 0, rm_tree_rounds = 0, rm_traced = 0;
+    DevBuf<double> d_rm_xy, d_rm_d;
+    DevBuf<uint8_t> d_rm_key;
+    DevBuf<uint64_t> d_rm_cell_key;
+    DevBuf<int32_t> d_rm_row, d_rm_col, d_rm_trow, d_rm_tcol, d_rm_tmp, d_rm_cell_start, d_rm_cell_nodes, d_rm_cand_off, d_rm_cand;
+    DevBuf<int32_t> d_rm_hops, d_rm_pred, d_rm_word;
+    DevBuf<char> d_rm_in, d_rm_out;   // goals | headings | modes;  path length | length in m | heading | achievable
+    PinnedBuf h_rm_in, h_rm_out;
+
     // timing
     bool timing = false;
     std::vector<TimedLaunch> launches;
@@ -870,6 +890,10 @@ void fs_ctx_destroy(fs_ctx *c)
     c->d_fc_queue.release(); c->d_fc_visited.release(); c->d_fc_clusters.release(); c->d_fc_sums.release();
     c->d_nav_cost.release(); c->d_nav_pot.release(); c->d_nav_flags.release(); c->d_nav_any.release(); c->d_nav_path.release();
     c->d_nav_in.release(); c->d_nav_out.release(); c->h_nav_in.release(); c->h_nav_out.release();
+    c->d_rm_xy.release(); c->d_rm_d.release(); c->d_rm_key.release(); c->d_rm_cell_key.release(); c->d_rm_row.release(); c->d_rm_col.release();
+    c->d_rm_trow.release(); c->d_rm_tcol.release(); c->d_rm_tmp.release(); c->d_rm_cell_start.release(); c->d_rm_cell_nodes.release();
+    c->d_rm_cand_off.release(); c->d_rm_cand.release(); c->d_rm_hops.release(); c->d_rm_pred.release(); c->d_rm_word.release();
+    c->d_rm_in.release(); c->d_rm_out.release(); c->h_rm_in.release(); c->h_rm_out.release();
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1676,6 +1700,14 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
     if (c && value && which >= 1002 && which <= 1004) {
         *value = which == 1002 ? c->nav_builds : which == 1003 ? c->nav_rounds : c->nav_launches;
         if (reset) { if (which == 1002) c->nav_builds = 0; else if (which == 1004) c->nav_launches = 0; }
+        return FS_OK;
+    }
+    // ... of the roadmap planner (fs_roadmap_plan): 1005 shortest-path trees built, 1006 rounds of the last one; 1007 segments the
+    // roadmap calls have walked (fs_roadmap_rebuild, fs_roadmap_connect)
+    if (c && value && which >= 1005 && which <= 1007) {
+        int64_t &v = which == 1005 ? c->rm_tree_builds : which == 1006 ? c->rm_tree_rounds : c->rm_traced;
+        *value = v;
+        if (reset && which != 1006) v = 0;
         return FS_OK;
     }
     if (!c || !value || which < 0 || which >= FS_N_COUNTERS) return FS_E_INVALID;
@@ -2839,6 +2871,460 @@ int fs_get_frontier_costs_planned(fs_ctx *c, const double robot_pose7[7], int32_
         return rc;
     }
     if (path_length_m) std::memcpy(path_length_m, c->h_nav_out.p + O.len_m, 8 * nn);
+    return FS_OK;
+}
+
+}  // extern "C"
+
+// ================================================================== frontier roadmap (fs_roadmap.hip)
+// FrontierRoadMap's node and edge bookkeeping (populateNodes, constructNewEdges) stays on the host, where its order-dependent
+// insertions are cheap; every isConnectable of a call is walked on the device in one batch, the whole-graph rebuild and the
+// planner run there.
+
+namespace {
+
+#define RM_MAX_PER_CELL 20          // populateNodes throws once a cell holds more (FrontierRoadmap.cpp:244-248)
+#define RM_TREE_BATCH 16
+
+int rm_check_grid(fs_ctx *c)
+{
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (c->nz != 1) return fail(c, FS_E_INVALID, "the roadmap is defined on a 2-D costmap (nz == 1)");
+    return FS_OK;
+}
+
+int32_t rm_nodes(const fs_ctx *c) { return (int32_t)(c->rm_xy.size() / 2); }
+
+// getNodesWithinRadius(node p, radius_to_decide_edges) in the reference's order (p itself included: callers skip it)
+void rm_within_radius(const fs_ctx *c, int32_t p, std::vector<int32_t> &out)
+{
+    out.clear();
+    const double px = c->rm_xy[2 * (size_t)p], py = c->rm_xy[2 * (size_t)p + 1];
+    const int cx = fs_rm_cell(px, c->rm_cell), cy = fs_rm_cell(py, c->rm_cell);
+    const int cr = (int)std::ceil(c->rm_radius / c->rm_cell);
+    for (int dx = -cr; dx <= cr; ++dx)
+        for (int dy = -cr; dy <= cr; ++dy) {
+            const auto it = c->rm_hash.find({cx + dx, cy + dy});
+            if (it == c->rm_hash.end()) continue;
+            for (const int32_t q : it->second) {
+                const double ex = px - c->rm_xy[2 * (size_t)q], ey = py - c->rm_xy[2 * (size_t)q + 1];
+                if (std::sqrt(ex * ex + ey * ey) < c->rm_radius) out.push_back(q);
+            }
+        }
+}
+
+// isConnectable (FrontierRoadmap.cpp:716-737): visitor (253, 254, 0, 255), max_length = (unsigned)(max_connection_length / res)
+// handed on as a double, max_connection_length = 1.5 * radius (:20); rejected above radius / res * 0.3 unknown cells
+FsSegArgs rm_seg_args(fs_ctx *c, int32_t n)
+{
+    FsSegArgs a{};
+    a.grid = grid_dev(c);
+    a.n = n; a.start = c->d_seg_start.p; a.end = c->d_seg_end.p;
+    a.max_length = (double)(unsigned)(c->rm_radius * 1.5 / c->res);
+    a.obst_min = 253; a.obst_max = 254; a.trace_min = 0; a.trace_max = 255;
+    a.ok = c->d_seg_ok.p; a.hit = c->d_seg_hit.p; a.traced = c->d_seg_traced.p; a.unknown = c->d_seg_unknown.p; a.all = c->d_seg_all.p;
+    return a;
+}
+double rm_unknown_limit(const fs_ctx *c) { return c->rm_radius / c->res * 0.3; }
+
+int rm_seg_ensure(fs_ctx *c, size_t n)
+{
+    FS_HIP(c, c->d_seg_start.ensure(3 * n)); FS_HIP(c, c->d_seg_end.ensure(3 * n));
+    FS_HIP(c, c->d_seg_ok.ensure(n)); FS_HIP(c, c->d_seg_hit.ensure(n));
+    FS_HIP(c, c->d_seg_traced.ensure(n)); FS_HIP(c, c->d_seg_unknown.ensure(n)); FS_HIP(c, c->d_seg_all.ensure(n));
+    return FS_OK;
+}
+
+// node positions and the spatial hash (occupied cells in ascending key order) on the device; synchronised by the caller before
+// the host vectors go out of scope
+int rm_upload_nodes(fs_ctx *c, FsRoadmapDev &g, std::vector<uint64_t> &keys, std::vector<int32_t> &start, std::vector<int32_t> &nodes)
+{
+    const int32_t n = rm_nodes(c);
+    std::vector<std::pair<uint64_t, const std::vector<int32_t> *>> cells;
+    for (const auto &kv : c->rm_hash)
+        if (!kv.second.empty()) cells.push_back({((uint64_t)(uint32_t)kv.first.first << 32) | (uint32_t)kv.first.second, &kv.second});
+    std::sort(cells.begin(), cells.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+    keys.clear(); start.assign(1, 0); nodes.clear();
+    for (const auto &e : cells) {
+        keys.push_back(e.first);
+        nodes.insert(nodes.end(), e.second->begin(), e.second->end());
+        start.push_back((int32_t)nodes.size());
+    }
+    FS_HIP(c, c->d_rm_xy.ensure(2 * (size_t)n)); FS_HIP(c, c->d_rm_cell_key.ensure(keys.size()));
+    FS_HIP(c, c->d_rm_cell_start.ensure(start.size())); FS_HIP(c, c->d_rm_cell_nodes.ensure(nodes.size()));
+    FS_HIP(c, hipMemcpyAsync(c->d_rm_xy.p, c->rm_xy.data(), sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, hipMemcpyAsync(c->d_rm_cell_key.p, keys.data(), sizeof(uint64_t) * keys.size(), hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, hipMemcpyAsync(c->d_rm_cell_start.p, start.data(), sizeof(int32_t) * start.size(), hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, hipMemcpyAsync(c->d_rm_cell_nodes.p, nodes.data(), sizeof(int32_t) * nodes.size(), hipMemcpyHostToDevice, c->stream));
+    g = FsRoadmapDev{n, c->d_rm_xy.p, c->rm_cell, c->rm_radius, (int32_t)keys.size(), c->d_rm_cell_key.p, c->d_rm_cell_start.p,
+                     c->d_rm_cell_nodes.p};
+    return FS_OK;
+}
+
+// the device's nodes, key flags and CSR for the current generation (uploaded from the host lists after a host-side mutation),
+// then its transpose
+int rm_device_graph(fs_ctx *c)
+{
+    const int32_t n = rm_nodes(c);
+    if (c->rm_dev_gen != c->rm_gen) {
+        std::vector<int32_t> row(1, 0), col;
+        for (const auto &l : c->rm_adj) { col.insert(col.end(), l.begin(), l.end()); row.push_back((int32_t)col.size()); }
+        FS_HIP(c, c->d_rm_xy.ensure(2 * (size_t)n)); FS_HIP(c, c->d_rm_key.ensure(n));
+        FS_HIP(c, c->d_rm_row.ensure(row.size())); FS_HIP(c, c->d_rm_col.ensure(col.size()));
+        FS_HIP(c, hipMemcpyAsync(c->d_rm_xy.p, c->rm_xy.data(), sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        FS_HIP(c, hipMemcpyAsync(c->d_rm_key.p, c->rm_key.data(), (size_t)n, hipMemcpyHostToDevice, c->stream));
+        FS_HIP(c, hipMemcpyAsync(c->d_rm_row.p, row.data(), sizeof(int32_t) * row.size(), hipMemcpyHostToDevice, c->stream));
+        FS_HIP(c, hipMemcpyAsync(c->d_rm_col.p, col.data(), sizeof(int32_t) * col.size(), hipMemcpyHostToDevice, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        c->rm_dev_gen = c->rm_gen;
+    }
+    if (c->rm_t_gen != c->rm_gen) {
+        size_t e = 0;
+        for (const auto &l : c->rm_adj) e += l.size();
+        FS_HIP(c, c->d_rm_tmp.ensure(2 * (size_t)n + 1)); FS_HIP(c, c->d_rm_trow.ensure((size_t)n + 1)); FS_HIP(c, c->d_rm_tcol.ensure(e));
+        int32_t *indeg = c->d_rm_tmp.p, *cursor = c->d_rm_tmp.p + n;
+        FS_HIP(c, hipMemsetAsync(c->d_rm_tmp.p, 0, sizeof(int32_t) * 2 * (size_t)n, c->stream));
+        FS_HIP(c, fs_launch_rm_transpose(n, c->d_rm_row.p, c->d_rm_col.p, indeg, nullptr, nullptr, nullptr, c->stream, 0));
+        FS_HIP(c, fs_launch_rm_scan(indeg, n, c->d_rm_trow.p, c->stream));
+        FS_HIP(c, fs_launch_rm_transpose(n, c->d_rm_row.p, c->d_rm_col.p, nullptr, c->d_rm_trow.p, cursor, c->d_rm_tcol.p, c->stream, 1));
+        c->rm_t_gen = c->rm_gen;
+    }
+    return FS_OK;
+}
+
+// The shortest-path tree from `root` for the current generation: the cached one, or built now (synchronises the stream).
+int rm_tree(fs_ctx *c, int32_t root, const double **d, const int32_t **pred)
+{
+    const int32_t n = rm_nodes(c);
+    const size_t nn = (size_t)n;
+    if (!(c->rm_tree_gen == c->rm_gen && c->rm_tree_root == root)) {
+        c->rm_tree_gen = 0;
+        int rc = rm_device_graph(c);
+        if (rc) return rc;
+        FS_HIP(c, c->d_rm_d.ensure(2 * nn)); FS_HIP(c, c->d_rm_hops.ensure(2 * nn)); FS_HIP(c, c->d_rm_pred.ensure(2 * nn));
+        FS_HIP(c, c->d_rm_word.ensure(RM_TREE_BATCH));
+        FsRmTree t{n, root, c->d_rm_xy.p, c->d_rm_trow.p, c->d_rm_tcol.p, {c->d_rm_d.p, c->d_rm_d.p + nn}, {c->d_rm_hops.p, c->d_rm_hops.p + nn},
+                   {c->d_rm_pred.p, c->d_rm_pred.p + nn}};
+        FS_HIP(c, fs_launch_rm_tree_init(t, c->stream));
+        // d settles within n - 1 rounds (a minimum over walks is reached on a simple path), hops / predecessor within n more
+        const int64_t max_rounds = 2 * (int64_t)n + 2;
+        int64_t rounds = 0;
+        if (n <= RM_TREE_ONE_WG) {
+            FS_HIP(c, fs_launch_rm_tree_block(t, (int32_t)max_rounds, c->d_rm_word.p, c->stream));
+            int32_t r = 0;
+            FS_HIP(c, hipMemcpyAsync(&r, c->d_rm_word.p, sizeof r, hipMemcpyDeviceToHost, c->stream));
+            FS_HIP(c, hipStreamSynchronize(c->stream));
+            if (r < 0) return fail(c, FS_E_HIP, "the roadmap tree did not settle in %lld rounds", (long long)max_rounds);
+            rounds = r;
+        } else {
+            for (int64_t r = 0;;) {
+                FS_HIP(c, hipMemsetAsync(c->d_rm_word.p, 0, sizeof(int32_t) * RM_TREE_BATCH, c->stream));
+                for (int k = 0; k < RM_TREE_BATCH; ++k, ++r) FS_HIP(c, fs_launch_rm_tree_round(t, (int32_t)(r & 1), c->d_rm_word.p + k, c->stream));
+                int32_t any[RM_TREE_BATCH] = {0};
+                FS_HIP(c, hipMemcpyAsync(any, c->d_rm_word.p, sizeof any, hipMemcpyDeviceToHost, c->stream));
+                FS_HIP(c, hipStreamSynchronize(c->stream));
+                if (!any[RM_TREE_BATCH - 1]) {
+                    int k = 0;
+                    while (any[k]) ++k;                 // the first quiet round of the batch
+                    rounds = r - RM_TREE_BATCH + k + 1;
+                    break;
+                }
+                if (r >= max_rounds) return fail(c, FS_E_HIP, "the roadmap tree did not settle in %lld rounds", (long long)max_rounds);
+            }
+        }
+        c->rm_tree_buf = (int32_t)(rounds & 1);        // (after the quiet round both buffers hold the tree)
+        c->rm_tree_gen = c->rm_gen; c->rm_tree_root = root;
+        c->rm_tree_rounds = rounds;
+        ++c->rm_tree_builds;
+    }
+    *d = c->d_rm_d.p + (size_t)c->rm_tree_buf * nn;
+    *pred = c->d_rm_pred.p + (size_t)c->rm_tree_buf * nn;
+    return FS_OK;
+}
+
+// Output block of the plan kernel in d_rm_out: path length | length in m | heading | achievable.
+struct RmOutLayout {
+    size_t len, len_m, head, ach, total;
+    explicit RmOutLayout(size_t n) : len(0), len_m(8 * n), head(16 * n), ach(24 * n), total(24 * n + ((n + 15) & ~(size_t)15)) {}
+};
+
+// Start node, tree (cached or built), goals staged, the plan kernel: the four columns land in d_rm_out on the context's stream.
+int roadmap_plan_enqueue(fs_ctx *c, const double robot7[7], int32_t n, const double *goal_xyz, const uint8_t *achievable_in)
+{
+    const size_t nn = (size_t)n;
+    const size_t i_goal = 0, i_head = 16 * nn, i_mode = 24 * nn, total_in = 24 * nn + nn;
+    const RmOutLayout O(nn);
+    FS_HIP(c, c->h_rm_in.ensure(total_in)); FS_HIP(c, c->d_rm_in.ensure(total_in));
+    FS_HIP(c, c->d_rm_out.ensure(O.total));
+    double *goal = reinterpret_cast<double *>(c->h_rm_in.p + i_goal), *head = reinterpret_cast<double *>(c->h_rm_in.p + i_head);
+    uint8_t *mode = reinterpret_cast<uint8_t *>(c->h_rm_in.p + i_mode);
+    bool need_tree = false;
+    for (size_t i = 0; i < nn; ++i) {
+        const double gx = goal_xyz[3 * i], gy = goal_xyz[3 * i + 1];
+        goal[2 * i] = gx; goal[2 * i + 1] = gy;
+        // getPlan's early return (FrontierRoadmap.cpp:548-554) comes before any search
+        mode[i] = (achievable_in && !achievable_in[i]) ? 0 : (robot7[0] == gx && robot7[1] == gy) ? 1 : 2;
+        head[i] = mode[i] ? nav_heading(robot7, gx, gy) : 0.0;
+        need_tree |= mode[i] == 2;
+    }
+    const int32_t nodes = rm_nodes(c);
+    const int32_t root = fs_rm_closest(c->rm_xy.data(), c->rm_key.data(), nodes, c->rm_cell, robot7[0], robot7[1]);
+    const double *d = nullptr;
+    const int32_t *pred = nullptr;
+    if (need_tree && root >= 0) { const int rc = rm_tree(c, root, &d, &pred); if (rc) return rc; }
+    FS_HIP(c, hipMemcpyAsync(c->d_rm_in.p, c->h_rm_in.p, total_in, hipMemcpyHostToDevice, c->stream));
+    FsRmPlanArgs a{};
+    a.n_nodes = nodes; a.xy = c->d_rm_xy.p; a.key = c->d_rm_key.p; a.cell = c->rm_cell;
+    a.d = d; a.pred = pred; a.root = root;
+    a.n = n;
+    a.goal = reinterpret_cast<const double *>(c->d_rm_in.p + i_goal);
+    a.heading_in = reinterpret_cast<const double *>(c->d_rm_in.p + i_head);
+    a.mode = reinterpret_cast<const uint8_t *>(c->d_rm_in.p + i_mode);
+    a.path_length = reinterpret_cast<double *>(c->d_rm_out.p + O.len);
+    a.path_length_m = reinterpret_cast<double *>(c->d_rm_out.p + O.len_m);
+    a.path_heading = reinterpret_cast<double *>(c->d_rm_out.p + O.head);
+    a.achievable = reinterpret_cast<uint8_t *>(c->d_rm_out.p + O.ach);
+    FS_HIP(c, fs_launch_rm_plan(a, c->stream));
+    return FS_OK;
+}
+
+bool rm_finite_xy(const double *xy, int32_t n, int stride)
+{
+    for (int32_t i = 0; i < n; ++i)
+        if (!std::isfinite(xy[(size_t)stride * i]) || !std::isfinite(xy[(size_t)stride * i + 1])) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fs_set_roadmap_params(fs_ctx *c, double grid_cell_size, double radius_to_decide_edges, double min_distance_between_two_frontier_nodes,
+                          double min_distance_between_robot_pose_and_node)
+{
+    if (!c) return FS_E_INVALID;
+    if (!(grid_cell_size > 0 && std::isfinite(grid_cell_size)) || !(radius_to_decide_edges > 0 && std::isfinite(radius_to_decide_edges)) ||
+        !(min_distance_between_two_frontier_nodes >= 0 && std::isfinite(min_distance_between_two_frontier_nodes)) ||
+        !(min_distance_between_robot_pose_and_node >= 0 && std::isfinite(min_distance_between_robot_pose_and_node)))
+        return fail(c, FS_E_INVALID, "roadmap parameters: cell and radius > 0, distances >= 0, all finite");
+    c->rm_cell = grid_cell_size; c->rm_radius = radius_to_decide_edges;
+    c->rm_min_frontier = min_distance_between_two_frontier_nodes; c->rm_min_robot = min_distance_between_robot_pose_and_node;
+    // the hash is cut by the cell size: a new parameter set starts an empty roadmap, as a new FrontierRoadMap does
+    c->rm_xy.clear(); c->rm_hash.clear(); c->rm_key.clear(); c->rm_adj.clear();
+    ++c->rm_gen;
+    return FS_OK;
+}
+
+int fs_roadmap_add_nodes(fs_ctx *c, int32_t n, const double *xy, int32_t is_robot_pose)
+{
+    if (!c) return FS_E_INVALID;
+    if (n < 0 || (n > 0 && !xy)) return fail(c, FS_E_INVALID, "null pointer");
+    if (!rm_finite_xy(xy, n, 2)) return fail(c, FS_E_INVALID, "non-finite node position");
+    if (n == 0) return FS_OK;
+    ++c->rm_gen;
+    const double min_d = is_robot_pose ? c->rm_min_robot : c->rm_min_frontier;
+    for (int32_t i = 0; i < n; ++i) {
+        const double x = xy[2 * (size_t)i], y = xy[2 * (size_t)i + 1];
+        const int cx = fs_rm_cell(x, c->rm_cell), cy = fs_rm_cell(y, c->rm_cell);
+        bool fresh = true;
+        for (int dx = -1; dx <= 1 && fresh; ++dx)
+            for (int dy = -1; dy <= 1 && fresh; ++dy) {
+                const auto it = c->rm_hash.find({cx + dx, cy + dy});
+                if (it == c->rm_hash.end()) continue;
+                for (const int32_t q : it->second) {
+                    const double ex = x - c->rm_xy[2 * (size_t)q], ey = y - c->rm_xy[2 * (size_t)q + 1];
+                    if (std::sqrt(ex * ex + ey * ey) < min_d) { fresh = false; break; }
+                }
+            }
+        if (!fresh) continue;
+        std::vector<int32_t> &cell = c->rm_hash[{cx, cy}];
+        cell.push_back(rm_nodes(c));
+        c->rm_xy.push_back(x); c->rm_xy.push_back(y);
+        c->rm_key.push_back(0);
+        c->rm_adj.emplace_back();
+        if (cell.size() > RM_MAX_PER_CELL)
+            return fail(c, FS_E_RANGE, "hash cell (%d, %d) holds more than %d nodes (the reference throws; the node stays added, the rest of the list is not)",
+                        cx, cy, RM_MAX_PER_CELL);
+    }
+    return FS_OK;
+}
+
+int fs_roadmap_rebuild(fs_ctx *c)
+{
+    if (!c) return FS_E_INVALID;
+    int rc = rm_check_grid(c);
+    if (rc) return rc;
+    const int32_t n = rm_nodes(c);
+    ++c->rm_gen;
+    std::fill(c->rm_key.begin(), c->rm_key.end(), (uint8_t)1);     // roadmap_.clear(), then roadmap_[point] = {} for every node
+    for (auto &l : c->rm_adj) l.clear();
+    if (n == 0) return FS_OK;
+    const size_t nn = (size_t)n;
+    FsRoadmapDev g{};
+    std::vector<uint64_t> keys;
+    std::vector<int32_t> cstart, cnodes;
+    rc = rm_upload_nodes(c, g, keys, cstart, cnodes);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    FS_HIP(c, c->d_rm_tmp.ensure(nn + 1)); FS_HIP(c, c->d_rm_cand_off.ensure(nn + 1)); FS_HIP(c, c->d_rm_row.ensure(nn + 1));
+    FS_HIP(c, c->d_rm_key.ensure(nn));
+    FS_HIP(c, hipMemcpyAsync(c->d_rm_key.p, c->rm_key.data(), nn, hipMemcpyHostToDevice, c->stream));
+    // candidates: count, scan, fill
+    FS_HIP(c, fs_launch_rm_candidates(g, nullptr, c->d_rm_tmp.p, c->origin[2], nullptr, nullptr, nullptr, c->stream));
+    FS_HIP(c, fs_launch_rm_scan(c->d_rm_tmp.p, n, c->d_rm_cand_off.p, c->stream));
+    int32_t total = 0;
+    FS_HIP(c, hipMemcpyAsync(&total, c->d_rm_cand_off.p + n, sizeof total, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    rc = rm_seg_ensure(c, (size_t)total);
+    if (rc) return rc;
+    FS_HIP(c, c->d_rm_cand.ensure((size_t)total));
+    FS_HIP(c, fs_launch_rm_candidates(g, c->d_rm_cand_off.p, nullptr, c->origin[2], c->d_seg_start.p, c->d_seg_end.p, c->d_rm_cand.p, c->stream));
+    // every isConnectable of the rebuild: one batch of segment walks
+    FS_HIP(c, fs_launch_segments(rm_seg_args(c, total), c->stream));
+    // accepted edges: count, scan, compact in order
+    const double limit = rm_unknown_limit(c);
+    FS_HIP(c, fs_launch_rm_edges(n, c->d_rm_cand_off.p, c->d_rm_cand.p, c->d_seg_ok.p, c->d_seg_hit.p, c->d_seg_unknown.p, limit, nullptr,
+                                 c->d_rm_tmp.p, nullptr, c->stream));
+    FS_HIP(c, fs_launch_rm_scan(c->d_rm_tmp.p, n, c->d_rm_row.p, c->stream));
+    std::vector<int32_t> row(nn + 1);
+    FS_HIP(c, hipMemcpyAsync(row.data(), c->d_rm_row.p, sizeof(int32_t) * (nn + 1), hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    const int32_t e = row[nn];
+    FS_HIP(c, c->d_rm_col.ensure((size_t)e));
+    FS_HIP(c, fs_launch_rm_edges(n, c->d_rm_cand_off.p, c->d_rm_cand.p, c->d_seg_ok.p, c->d_seg_hit.p, c->d_seg_unknown.p, limit, c->d_rm_row.p,
+                                 nullptr, c->d_rm_col.p, c->stream));
+    std::vector<int32_t> col((size_t)e);
+    FS_HIP(c, hipMemcpyAsync(col.data(), c->d_rm_col.p, sizeof(int32_t) * (size_t)e, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    for (int32_t p = 0; p < n; ++p) c->rm_adj[(size_t)p].assign(col.begin() + row[(size_t)p], col.begin() + row[(size_t)p + 1]);
+    c->rm_dev_gen = c->rm_gen;
+    c->rm_traced += total;
+    return FS_OK;
+}
+
+int fs_roadmap_connect(fs_ctx *c, int32_t n, const double *xy)
+{
+    if (!c) return FS_E_INVALID;
+    if (n < 0 || (n > 0 && !xy)) return fail(c, FS_E_INVALID, "null pointer");
+    if (!rm_finite_xy(xy, n, 2)) return fail(c, FS_E_INVALID, "non-finite point");
+    int rc = rm_check_grid(c);
+    if (rc) return rc;
+    const int32_t nodes = rm_nodes(c);
+    if (n == 0 || nodes == 0) return FS_OK;      // (an empty hash: the reference's closest-node search would not return)
+    // every point's closest hash node and its neighbours within the radius; the walks neighbour -> closest node in one batch
+    std::vector<int32_t> closest((size_t)n), nb_off(1, 0), nb, tmp;
+    for (int32_t i = 0; i < n; ++i) {
+        closest[(size_t)i] = fs_rm_closest(c->rm_xy.data(), nullptr, nodes, c->rm_cell, xy[2 * (size_t)i], xy[2 * (size_t)i + 1]);
+        rm_within_radius(c, closest[(size_t)i], tmp);
+        for (const int32_t q : tmp) if (q != closest[(size_t)i]) nb.push_back(q);
+        nb_off.push_back((int32_t)nb.size());
+    }
+    const size_t total = nb.size();
+    std::vector<uint8_t> ok(total), hit(total);
+    std::vector<int32_t> unknown(total);
+    if (total) {
+        std::vector<double> s(3 * total), e(3 * total);
+        for (int32_t i = 0; i < n; ++i)
+            for (int32_t k = nb_off[(size_t)i]; k < nb_off[(size_t)i + 1]; ++k) {
+                const int32_t q = nb[(size_t)k], p = closest[(size_t)i];
+                s[3 * (size_t)k] = c->rm_xy[2 * (size_t)q]; s[3 * (size_t)k + 1] = c->rm_xy[2 * (size_t)q + 1]; s[3 * (size_t)k + 2] = c->origin[2];
+                e[3 * (size_t)k] = c->rm_xy[2 * (size_t)p]; e[3 * (size_t)k + 1] = c->rm_xy[2 * (size_t)p + 1]; e[3 * (size_t)k + 2] = c->origin[2];
+            }
+        rc = rm_seg_ensure(c, total);
+        if (rc) return rc;
+        FS_HIP(c, hipMemcpyAsync(c->d_seg_start.p, s.data(), sizeof(double) * 3 * total, hipMemcpyHostToDevice, c->stream));
+        FS_HIP(c, hipMemcpyAsync(c->d_seg_end.p, e.data(), sizeof(double) * 3 * total, hipMemcpyHostToDevice, c->stream));
+        FS_HIP(c, fs_launch_segments(rm_seg_args(c, (int32_t)total), c->stream));
+        FS_HIP(c, hipMemcpyAsync(ok.data(), c->d_seg_ok.p, total, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipMemcpyAsync(hit.data(), c->d_seg_hit.p, total, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipMemcpyAsync(unknown.data(), c->d_seg_unknown.p, sizeof(int32_t) * total, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        c->rm_traced += (int64_t)total;
+    }
+    // constructNewEdges' insertions, in order (FrontierRoadmap.cpp:279-334)
+    ++c->rm_gen;
+    const double limit = rm_unknown_limit(c);
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t p = closest[(size_t)i];
+        c->rm_key[(size_t)p] = 1;
+        for (int32_t k = nb_off[(size_t)i]; k < nb_off[(size_t)i + 1]; ++k) {
+            const int32_t q = nb[(size_t)k];
+            c->rm_key[(size_t)q] = 1;
+            std::vector<int32_t> &a = c->rm_adj[(size_t)p], &b = c->rm_adj[(size_t)q];
+            if (std::find(a.begin(), a.end(), q) != a.end() || std::find(b.begin(), b.end(), p) != b.end()) continue;
+            if (ok[(size_t)k] && !hit[(size_t)k] && !((double)unknown[(size_t)k] > limit)) { a.push_back(q); b.push_back(p); }
+        }
+    }
+    return FS_OK;
+}
+
+int fs_roadmap_get_graph(fs_ctx *c, int32_t *n_nodes, int64_t *n_edges, double *xy, uint8_t *key, int32_t *row_ptr, int32_t *col)
+{
+    if (!c) return FS_E_INVALID;
+    const int32_t n = rm_nodes(c);
+    int64_t e = 0;
+    for (const auto &l : c->rm_adj) e += (int64_t)l.size();
+    if (n_nodes) *n_nodes = n;
+    if (n_edges) *n_edges = e;
+    if (xy) std::memcpy(xy, c->rm_xy.data(), sizeof(double) * 2 * (size_t)n);
+    if (key) std::memcpy(key, c->rm_key.data(), (size_t)n);
+    if (row_ptr || col) {
+        int64_t k = 0;
+        for (int32_t p = 0; p < n; ++p) {
+            if (row_ptr) row_ptr[p] = (int32_t)k;
+            for (const int32_t q : c->rm_adj[(size_t)p]) { if (col) col[k] = q; ++k; }
+        }
+        if (row_ptr) row_ptr[n] = (int32_t)k;
+    }
+    return FS_OK;
+}
+
+int fs_roadmap_plan(fs_ctx *c, const double robot_pose7[7], int32_t n, const double *goal_xyz, const uint8_t *achievable_in,
+                    double *path_length, double *path_length_m, double *path_heading, uint8_t *achievable)
+{
+    if (!c) return FS_E_INVALID;
+    if (!robot_pose7 || n < 0 || (n > 0 && (!goal_xyz || !path_length || !path_length_m || !path_heading || !achievable)))
+        return fail(c, FS_E_INVALID, "null pointer");
+    FS_HIP(c, hipSetDevice(c->device));
+    if (n == 0) return FS_OK;
+    int rc = roadmap_plan_enqueue(c, robot_pose7, n, goal_xyz, achievable_in);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    const size_t nn = (size_t)n;
+    const RmOutLayout O(nn);
+    FS_HIP(c, c->h_rm_out.ensure(O.total));
+    FS_HIP(c, hipMemcpyAsync(c->h_rm_out.p, c->d_rm_out.p, O.total, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    std::memcpy(path_length, c->h_rm_out.p + O.len, 8 * nn);
+    std::memcpy(path_length_m, c->h_rm_out.p + O.len_m, 8 * nn);
+    std::memcpy(path_heading, c->h_rm_out.p + O.head, 8 * nn);
+    std::memcpy(achievable, c->h_rm_out.p + O.ach, nn);
+    return FS_OK;
+}
+
+int fs_get_frontier_costs_roadmap(fs_ctx *c, const double robot_pose7[7], int32_t n, const double *goal_xyz, const int32_t *frontier_size,
+                                  const uint8_t *blacklisted, double alpha, double beta, double max_vx, double max_wz, int with_fisher_information,
+                                  fs_record *records, double *weighted_cost, double *arrival_utility, double *distance_utility, int32_t *order,
+                                  double *path_length_m)
+{
+    if (!c) return FS_E_INVALID;
+    if (!robot_pose7 || n < 0 || (n > 0 && (!goal_xyz || !records || !weighted_cost))) return fail(c, FS_E_INVALID, "null pointer");
+    FS_HIP(c, hipSetDevice(c->device));
+    if (n == 0) return FS_OK;
+    int rc = check_scoring_state(c, true, with_fisher_information != 0);
+    if (rc) return rc;
+    const size_t nn = (size_t)n;
+    const RmOutLayout O(nn);
+    FS_HIP(c, c->h_rm_out.ensure(O.total));
+    rc = roadmap_plan_enqueue(c, robot_pose7, n, goal_xyz, nullptr);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (path_length_m) FS_HIP(c, hipMemcpyAsync(c->h_rm_out.p + O.len_m, c->d_rm_out.p + O.len_m, 8 * nn, hipMemcpyDeviceToHost, c->stream));
+    // the planner's columns stay where the plan kernel wrote them: scoring reads its achievability, ranking its path columns
+    const PlannedCols cols{reinterpret_cast<const uint8_t *>(c->d_rm_out.p + O.ach), reinterpret_cast<const double *>(c->d_rm_out.p + O.len),
+                           reinterpret_cast<const double *>(c->d_rm_out.p + O.head)};
+    rc = frontier_costs_core(c, n, goal_xyz, frontier_size, blacklisted, nullptr, nullptr, nullptr, alpha, beta, max_vx, max_wz,
+                             with_fisher_information != 0, records, weighted_cost, arrival_utility, distance_utility, order, &cols);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (path_length_m) std::memcpy(path_length_m, c->h_rm_out.p + O.len_m, 8 * nn);
     return FS_OK;
 }
 

@@ -132,6 +132,98 @@ hipError_t fs_launch_navfn_round(const float *d_a, float *d_b, const uint8_t *d_
                                  int32_t *d_any, hipStream_t s);
 hipError_t fs_launch_navfn_paths(const FsNavfnPathArgs &a, hipStream_t s);
 
+// ---- frontier roadmap (fs_roadmap.hip): FrontierRoadMap's spatial hash and roadmap_ on the device
+// FrontierRoadMap::getGridCell: floor(x / grid_cell_size), truncated to int
+__host__ __device__ inline int fs_rm_cell(double v, double cell) { return (int)floor(v / cell); }
+
+// getClosestNodeInRoadMap (key != nullptr: nodes that are keys of roadmap_ only) / getClosestNodeInHashmap (key == nullptr) of the
+// query (qx, qy), DEP/src/planners/FrontierRoadmap.cpp:464-543, as a scan over the node list: the reference grows a square of
+// (int)(cell * m) hash cells, m = 1, 2, ..., until one holds a candidate, and keeps the first strict minimum of the distance in
+// its scan order (dx outer, dy inner, insertion order).  That square is the first (int)(cell * m) >= the Chebyshev cell distance
+// of the nearest candidate, so two passes over the nodes give the same node: the radius, then the minimum distance with ties to the
+// smallest (dx, dy, index).  -1: no candidate (the reference searches forever).
+__host__ __device__ inline int32_t fs_rm_closest(const double *xy, const uint8_t *key, int32_t n, double cell, double qx, double qy)
+{
+    const int64_t cx = fs_rm_cell(qx, cell), cy = fs_rm_cell(qy, cell);
+    int64_t cmin = INT64_MAX;
+    for (int32_t k = 0; k < n; ++k) {
+        if (key && !key[k]) continue;
+        const int64_t ax = fs_rm_cell(xy[2 * k], cell) - cx, ay = fs_rm_cell(xy[2 * k + 1], cell) - cy;
+        const int64_t c = (ax < 0 ? -ax : ax) > (ay < 0 ? -ay : ay) ? (ax < 0 ? -ax : ax) : (ay < 0 ? -ay : ay);
+        if (c < cmin) cmin = c;
+    }
+    if (cmin == INT64_MAX) return -1;
+    int64_t m = (int64_t)floor((double)cmin / cell);
+    if (m < 1) m = 1;
+    while (m > 1 && (int64_t)(cell * (double)(m - 1)) >= cmin) --m;
+    while ((int64_t)(cell * (double)m) < cmin) ++m;
+    const int64_t R = (int64_t)(cell * (double)m);
+    int32_t best = -1;
+    double bd = 0.0;
+    int64_t bdx = 0, bdy = 0;
+    for (int32_t k = 0; k < n; ++k) {
+        if (key && !key[k]) continue;
+        const int64_t ax = fs_rm_cell(xy[2 * k], cell) - cx, ay = fs_rm_cell(xy[2 * k + 1], cell) - cy;
+        if (ax < -R || ax > R || ay < -R || ay > R) continue;
+        const double ex = qx - xy[2 * k], ey = qy - xy[2 * k + 1];
+        const double d = sqrt(ex * ex + ey * ey);                   // distanceBetweenFrontiers (pow(e, 2) == e * e)
+        if (best < 0 || d < bd || (d == bd && (ax < bdx || (ax == bdx && ay < bdy)))) {
+            best = k; bd = d; bdx = ax; bdy = ay;
+        }
+    }
+    return best;
+}
+
+struct FsRoadmapDev {
+    int32_t n;                 // nodes, insertion order
+    const double *xy;          // [n][2]
+    double cell, radius;       // grid_cell_size, radius_to_decide_edges
+    int32_t n_cells;           // occupied hash cells
+    const uint64_t *cell_key;  // [n_cells] ascending: (uint32)cx << 32 | (uint32)cy
+    const int32_t *cell_start; // [n_cells + 1] into cell_nodes
+    const int32_t *cell_nodes; // node ids cell by cell, insertion order inside a cell
+};
+// reConstructGraph(entireGraph = true): candidates of every node in getNodesWithinRadius order (count, then fill the segments
+// candidate -> node after an exclusive scan of the counts), the segment walk (fs_launch_segments), then the accepted edges
+// compacted in order (count, scan, fill)
+hipError_t fs_launch_rm_candidates(const FsRoadmapDev &g, const int32_t *d_off, int32_t *d_count, double oz, double *d_start,
+                                   double *d_end, int32_t *d_cand, hipStream_t s);
+hipError_t fs_launch_rm_edges(int32_t n, const int32_t *d_cand_off, const int32_t *d_cand, const uint8_t *d_ok, const uint8_t *d_hit,
+                              const int32_t *d_unknown, double unknown_limit, const int32_t *d_row, int32_t *d_count, int32_t *d_col,
+                              hipStream_t s);
+// exclusive scan of n counts by one workgroup: out[0..n], out[n] = the total
+hipError_t fs_launch_rm_scan(const int32_t *d_in, int32_t n, int32_t *d_out, hipStream_t s);
+// the transposed CSR (in-edges), the shortest-path tree from node `root` and the path columns
+hipError_t fs_launch_rm_transpose(int32_t n, const int32_t *d_row, const int32_t *d_col, int32_t *d_indeg, int32_t *d_trow,
+                                  int32_t *d_cursor, int32_t *d_tcol, hipStream_t s, int phase);
+struct FsRmTree {
+    int32_t n, root;
+    const double *xy;
+    const int32_t *trow, *tcol;      // in-edges of every node
+    double *d[2];                    // the two round buffers of the key (distance, hops, predecessor)
+    int32_t *hops[2], *pred[2];
+};
+#define RM_TREE_ONE_WG 16384         // up to this many nodes the whole relaxation is one workgroup's loop
+hipError_t fs_launch_rm_tree_init(const FsRmTree &t, hipStream_t s);
+hipError_t fs_launch_rm_tree_block(const FsRmTree &t, int32_t max_rounds, int32_t *d_rounds, hipStream_t s);
+hipError_t fs_launch_rm_tree_round(const FsRmTree &t, int32_t src, int32_t *d_any, hipStream_t s);
+struct FsRmPlanArgs {
+    int32_t n_nodes;
+    const double *xy;
+    const uint8_t *key;
+    double cell;
+    const double *d;                 // converged tree (nullptr: no start node)
+    const int32_t *pred;
+    int32_t root;
+    int32_t n;
+    const double *goal;              // [n][2]
+    const uint8_t *mode;             // [n] 0 not planned, 1 goal == robot xy, 2 plan
+    const double *heading_in;        // [n]
+    double *path_length, *path_length_m, *path_heading;
+    uint8_t *achievable;
+};
+hipError_t fs_launch_rm_plan(const FsRmPlanArgs &a, hipStream_t s);
+
 // ---- key-frame pose information (computeInformationForPose)
 struct FsKfArgs {
     int32_t n;                 // poses

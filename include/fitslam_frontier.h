@@ -424,6 +424,44 @@ int fs_get_frontier_costs_planned(fs_ctx *ctx, const double robot_pose7[7], int3
                   int with_fisher_information, fs_record *records, double *weighted_cost, double *arrival_utility,
                   double *distance_utility, int32_t *order, double *path_length_m);
 
+/* ---------------------------------------------------------------- frontier roadmap (the reference's default planner) */
+
+/* FrontierRoadMap's parameters (DEP/params/exploration.yaml:23-27; defaults 1.0, 6.1, 0.25, 0.25); max_connection_length is
+ * 1.5 * radius (DEP/src/planners/FrontierRoadmap.cpp:20).  A new parameter set starts an empty roadmap. */
+int fs_set_roadmap_params(fs_ctx *ctx, double grid_cell_size, double radius_to_decide_edges, double min_distance_between_two_frontier_nodes,
+                          double min_distance_between_robot_pose_and_node);
+/* FrontierRoadMap::populateNodes(populateClosest = true) (FrontierRoadmap.cpp:185-252) — addNodes (is_robot_pose 0) or
+ * addRobotPoseAsNode (1): a point closer than the minimum distance to a node of the 3 x 3 hash cells around it is dropped.  xy [n][2].
+ * A cell that comes to hold more than 20 nodes: FS_E_RANGE, that node added, the rest of the list not (the reference throws). */
+int fs_roadmap_add_nodes(fs_ctx *ctx, int32_t n, const double *xy, int32_t is_robot_pose);
+/* FrontierRoadMap::reConstructGraph(entireGraph = true, optimizeRoadmap = false) (FrontierRoadmap.cpp:347-408) on the device: every
+ * node becomes a key of the roadmap, its list the nodes within the radius that pass isConnectable (:716-737) on the staged 2-D grid,
+ * in getNodesWithinRadius's order.  nz > 1: FS_E_INVALID. */
+int fs_roadmap_rebuild(fs_ctx *ctx);
+/* FrontierRoadMap::constructNewEdges (FrontierRoadmap.cpp:279-334; with the robot pose in xy also constructNewEdgeRobotPose): each
+ * point's closest hash node linked both ways to the nodes within the radius it can connect to.  Every isConnectable of the call is
+ * walked on the device in one batch, the insertions follow on the host in the reference's order.  xy [n][2].  No node: a no-op. */
+int fs_roadmap_connect(fs_ctx *ctx, int32_t n, const double *xy);
+/* The roadmap, for tests and visualisation: node positions xy [n][2] in insertion order, key [n] (1: a key of roadmap_, what
+ * getClosestNodeInRoadMap considers), the adjacency as CSR row_ptr [n + 1], col [n_edges] in append order.  Any pointer may be NULL
+ * (call first with NULL arrays for the sizes). */
+int fs_roadmap_get_graph(fs_ctx *ctx, int32_t *n_nodes, int64_t *n_edges, double *xy, uint8_t *key, int32_t *row_ptr, int32_t *col);
+/* FrontierCostCalculator::setPlanForFrontierRoadmap ("RoadmapPlannerDistance", DEP/src/CostCalculator.cpp:395-438) for n frontiers:
+ * the start is the key node closest to the robot, each goal's end node the key node closest to it (getClosestNodeInRoadMap,
+ * FrontierRoadmap.cpp:506-543), the route the shortest-path tree from the start under squared segment lengths — ONE tree per
+ * (roadmap, start node), kept until the roadmap changes — where the reference runs an A* per frontier (astar.cpp:42-93; DESIGN.md
+ * 4.10 records where the two differ).  Outputs [n]: path_length = path_length_m (metres, summed from the goal end), path_heading,
+ * achievable.  achievable_in 0, no key node or goal node not reached: achievable 0 and DBL_MAX in the three columns; a goal at the
+ * robot's exact position: length 0. */
+int fs_roadmap_plan(fs_ctx *ctx, const double robot_pose7[7], int32_t n, const double *goal_xyz, const uint8_t *achievable_in,
+                    double *path_length, double *path_length_m, double *path_heading, uint8_t *achievable);
+/* fs_get_frontier_costs with the path columns planned on the roadmap in the same call: plan -> arrival (+ Fisher) -> U1 -> order.
+ * Same results, bit for bit, as fs_roadmap_plan followed by fs_get_frontier_costs on its columns; the path columns never visit the host. */
+int fs_get_frontier_costs_roadmap(fs_ctx *ctx, const double robot_pose7[7], int32_t n, const double *goal_xyz, const int32_t *frontier_size,
+                  const uint8_t *blacklisted, double alpha, double beta, double max_vx, double max_wz, int with_fisher_information,
+                  fs_record *records, double *weighted_cost, double *arrival_utility, double *distance_utility, int32_t *order,
+                  double *path_length_m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "fs_multi_score_fim", "fs_multi_get_frontier_costs", "fs_multi_gather_mode",
     "fs_plan_paths", "fs_navfn_potential", "fs_get_frontier_costs_planned",
     "fs_set_roadmap_params", "fs_roadmap_add_nodes", "fs_roadmap_rebuild", "fs_roadmap_connect", "fs_roadmap_get_graph", "fs_roadmap_plan",
-    "fs_get_frontier_costs_roadmap",
+    "fs_get_frontier_costs_roadmap", "fs_roadmap_next_goal",
 ]
 
 RECORD_DTYPE = np.dtype([("arrival", "<i4"), ("argmax", "<i4"), ("yaw", "<f4"), ("info_ref", "<f4"),
@@ -163,6 +163,8 @@ def load_library(build: bool = True):
     L.fs_roadmap_get_graph.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), vp, vp, vp, vp]
     L.fs_roadmap_plan.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, vp, vp, vp, vp]
     L.fs_get_frontier_costs_roadmap.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, vp, dbl, dbl, dbl, dbl, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.fs_roadmap_next_goal.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, vp, vp, i32, vp, i32, dbl, vp, dbl,
+                                       C.POINTER(i32), C.POINTER(i32), vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(i64), vp, vp]
     for name in EXPORTED_SYMBOLS:
         f = getattr(L, name)
         if name not in ("fs_ctx_destroy", "fs_last_error", "fs_multi_destroy", "fs_multi_last_error", "fs_multi_ctx"):
@@ -563,6 +565,44 @@ class FrontierScorer:
         self._check(self._L.fs_get_frontier_costs_roadmap(self._h, C.byref(pose), n, _p(goal), _p(fs), _p(bl), alpha, beta, max_vx, max_wz,
                                                           1 if with_fim else 0, _p(rec), _p(cost), _p(au), _p(du), _p(order), _p(plm)))
         return dict(records=rec, weighted_cost=cost, arrival_utility=au, distance_utility=du, order=order, path_length_m=plm)
+
+    def roadmap_next_goal(self, robot_pose7, goal_xyz, path_length_m, achievable, blacklisted=None, blacklist_xy=None,
+                          n_local=5, local_radius=12.0, fi_pose7=None, fi_threshold=550.0, want_matrix=False, want_selection=False):
+        """FullPathOptimizer::getNextGoal on the staged roadmap: the selection, the pair matrix over [robot, locals, closest global]
+        and the exhaustive tour search over the locals.  dict(next_index (-1: the zero frontier), status (0 SAFE, 1 UNSAFE,
+        2 UNDETERMINED), tour (input indices: the locals in visiting order, then the closest global), tour_length, n_tied, n_locals),
+        plus selection [n] (1 local, 2 global, | 4 closest global) with want_selection and pair_length_m [(k + 2)][(k + 2)] (None
+        without locals) with want_matrix.  fi_pose7 None: no Fisher-information check."""
+        pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
+        goal = np.ascontiguousarray(goal_xyz, dtype=np.float64).reshape(-1, 3)
+        n = goal.shape[0]
+        plm = np.ascontiguousarray(path_length_m, dtype=np.float64).reshape(-1)
+        ach = np.ascontiguousarray(achievable, dtype=np.uint8).reshape(-1)
+        bl = None if blacklisted is None else np.ascontiguousarray(blacklisted, dtype=np.uint8).reshape(-1)
+        for name, a in (("path_length_m", plm), ("achievable", ach), ("blacklisted", bl)):
+            if a is not None and a.shape[0] != n:
+                raise ValueError(f"{name} has {a.shape[0]} entries for {n} goals")
+        circ = np.zeros((0, 2)) if blacklist_xy is None else np.ascontiguousarray(np.asarray(blacklist_xy, dtype=np.float64).reshape(-1, 2))
+        fi = None if fi_pose7 is None else np.ascontiguousarray(fi_pose7, dtype=np.float64).reshape(7)
+        nl = int(n_local)
+        room = max(nl, 0) + 2
+        nxt, st, tsz = C.c_int32(), C.c_int32(), C.c_int32()
+        tl, nt = C.c_double(), C.c_int64()
+        tour = np.zeros(max(nl, 0) + 1, dtype=np.int32)
+        sel = np.zeros(n, dtype=np.uint8)
+        mat = np.zeros(room * room) if want_matrix else None
+        self._check(self._L.fs_roadmap_next_goal(self._h, C.byref(pose), n, _p(goal), _p(plm), _p(ach), _p(bl), circ.shape[0],
+                                                 _p(circ) if circ.shape[0] else None, nl, float(local_radius), _p(fi),
+                                                 float(fi_threshold), C.byref(nxt), C.byref(st), _p(tour), C.byref(tsz), C.byref(tl),
+                                                 C.byref(nt), _p(sel), _p(mat)))
+        k = int(np.count_nonzero((sel & 3) == 1))
+        out = dict(next_index=nxt.value, status=st.value, tour=tour[:tsz.value].copy(), tour_length=tl.value, n_tied=nt.value,
+                   n_locals=k)
+        if want_selection:
+            out["selection"] = sel
+        if want_matrix:
+            out["pair_length_m"] = mat[:(k + 2) * (k + 2)].reshape(k + 2, k + 2).copy() if k else None
+        return out
 
     def selftest_fp64(self, max_abs=256) -> int:
         bad = C.c_int64()

@@ -320,6 +320,14 @@ struct fs_ctx {
     DevBuf<int32_t> d_rm_hops, d_rm_pred, d_rm_word;
     DevBuf<char> d_rm_in, d_rm_out;   // goals | headings | modes;  path length | length in m | heading | achievable
     PinnedBuf h_rm_in, h_rm_out;
+    // next goal (fs_roadmap_next_goal): a batch of trees with buffers of its own (the single tree above stays
+    // cached), the pair matrix, the tour search's winners
+    int32_t tour_one_wg = RM_TREE_ONE_WG;     // "roadmap.tour_one_wg": above this many nodes the batch runs a round per launch
+    int64_t tour_tree_builds = 0, tour_tree_rounds = 0, tour_evaluated = 0;
+    DevBuf<double> d_tour_d;
+    DevBuf<int32_t> d_tour_hops, d_tour_pred, d_tour_word;
+    DevBuf<char> d_tour_work;                 // matrix | result | block winners
+    PinnedBuf h_tour_out;                     // matrix | result | rounds of each tree
 
     // timing
     bool timing = false;
@@ -894,6 +902,8 @@ void fs_ctx_destroy(fs_ctx *c)
     c->d_rm_trow.release(); c->d_rm_tcol.release(); c->d_rm_tmp.release(); c->d_rm_cell_start.release(); c->d_rm_cell_nodes.release();
     c->d_rm_cand_off.release(); c->d_rm_cand.release(); c->d_rm_hops.release(); c->d_rm_pred.release(); c->d_rm_word.release();
     c->d_rm_in.release(); c->d_rm_out.release(); c->h_rm_in.release(); c->h_rm_out.release();
+    c->d_tour_d.release(); c->d_tour_hops.release(); c->d_tour_pred.release(); c->d_tour_word.release(); c->d_tour_work.release();
+    c->h_tour_out.release();
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1689,6 +1699,7 @@ int fs_set_option(fs_ctx *c, const char *key, double value)
     if (std::strcmp(key, "fim.bits1") == 0 && value >= 10 && value <= 14) { c->opt_bits1 = (int)value; return FS_OK; }
     if (std::strcmp(key, "fim.skip32") == 0 && value >= 1 && value <= 32) { c->opt_skip32 = (int)value; return FS_OK; }
     if (std::strcmp(key, "fim.headroom") == 0 && value >= 8 && value <= 64) { c->opt_headroom = (int)value; return FS_OK; }
+    if (std::strcmp(key, "roadmap.tour_one_wg") == 0 && value >= 0 && value <= RM_TREE_ONE_WG) { c->tour_one_wg = (int32_t)value; return FS_OK; }
     return fail(c, FS_E_INVALID, "unknown option %s", key);
 }
 
@@ -1708,6 +1719,14 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
         int64_t &v = which == 1005 ? c->rm_tree_builds : which == 1006 ? c->rm_tree_rounds : c->rm_traced;
         *value = v;
         if (reset && which != 1006) v = 0;
+        return FS_OK;
+    }
+    // ... of the next-goal search (fs_roadmap_next_goal): 1008 trees built, 1009 rounds of the last call's batch (its slowest tree),
+    // 1010 tours evaluated
+    if (c && value && which >= 1008 && which <= 1010) {
+        int64_t &v = which == 1008 ? c->tour_tree_builds : which == 1009 ? c->tour_tree_rounds : c->tour_evaluated;
+        *value = v;
+        if (reset && which != 1009) v = 0;
         return FS_OK;
     }
     if (!c || !value || which < 0 || which >= FS_N_COUNTERS) return FS_E_INVALID;
@@ -3326,6 +3345,243 @@ int fs_get_frontier_costs_roadmap(fs_ctx *c, const double robot_pose7[7], int32_
     if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
     if (path_length_m) std::memcpy(path_length_m, c->h_rm_out.p + O.len_m, 8 * nn);
     return FS_OK;
+}
+
+}  // extern "C"
+
+// ================================================================== next goal (FullPathOptimizer::getNextGoal)
+// The selection is sequential and small and stays on the host; the pair matrix (one tree per source, all in one launch) and the
+// exhaustive tour search run on the device.
+
+namespace {
+
+#define FS_SAFE 0
+#define FS_UNSAFE 1
+#define FS_UNDETERMINED 2
+#define TOUR_SEL_LOCAL 1
+#define TOUR_SEL_GLOBAL 2
+#define TOUR_SEL_CLOSEST 4
+
+// work buffer on the device: matrix | result (length, robot leg, rank, count) | block winners (length, leg, rank, count columns)
+constexpr size_t kTourOffRes = 2048, kTourOffBlk = 2048 + 64, kTourMaxBlk = 1024;
+constexpr size_t kTourWork = kTourOffBlk + 4 * 8 * kTourMaxBlk;
+// pinned host block: matrix | result | rounds of each tree
+constexpr size_t kTourOffRounds = kTourOffRes + 64, kTourOut = kTourOffRounds + 4 * RM_TOUR_MAX_TREES;
+
+// getFilteredFrontiersN (FullPathOptimizer.cpp:157-227) with all its quirks; ties in path length go to the lower input index (the
+// reference's std::sort is not stable).  cg = closest_global_frontier, -1 while unset.
+void tour_select(int32_t n, const double *plm, const std::vector<uint8_t> &eligible, int32_t n_local, double radius,
+                 std::vector<int32_t> &loc, std::vector<int32_t> &glob, int32_t &cg)
+{
+    std::vector<int32_t> all;
+    for (int32_t i = 0; i < n; ++i) if (eligible[(size_t)i]) all.push_back(i);
+    std::stable_sort(all.begin(), all.end(), [plm](int32_t a, int32_t b) { return plm[a] < plm[b]; });
+    loc.clear(); glob.clear(); cg = -1;
+    if (all.empty()) return;
+    bool global_assigned = false, need_to_pop = false;
+    int64_t counter = 1;
+    for (const int32_t f : all) {
+        const double L = plm[f];
+        if (L <= radius && counter <= n_local) { loc.push_back(f); cg = f; need_to_pop = true; }
+        else if (L <= radius && counter > n_local) { cg = f; need_to_pop = false; }
+        else if (L > radius) {
+            if (!global_assigned) { cg = f; global_assigned = true; }
+            need_to_pop = false;
+            glob.push_back(f);
+        }
+        ++counter;
+    }
+    if (need_to_pop) loc.pop_back();
+    if (glob.empty() && loc.empty()) glob.push_back(cg);
+}
+
+// isRobotPoseSafe (FullPathOptimizer.cpp:342-352) through the one-pose info-only scorer: safe when info_ref > threshold
+int tour_pose_safe(fs_ctx *c, const double *pose7, double threshold, int32_t *status)
+{
+    float info = 0.0f;
+    int32_t nvox = 0;
+    const int rc = fs_score_fim(c, 1, pose7, &info, nullptr, nullptr, nullptr, nullptr, &nvox);
+    if (rc) return rc;
+    *status = (double)info > threshold ? FS_SAFE : FS_UNSAFE;
+    return FS_OK;
+}
+
+// rank -> the lexicographic permutation of 0..k-1 of that rank (factorial number system)
+void tour_unrank(int64_t rank, int k, int32_t *perm)
+{
+    int64_t f = 1;
+    for (int t = 2; t < k; ++t) f *= t;
+    std::vector<int32_t> left;
+    for (int t = 0; t < k; ++t) left.push_back(t);
+    for (int t = 0; t < k; ++t) {
+        const int64_t d = rank / f;
+        rank -= d * f;
+        if (t < k - 1) f /= (k - 1 - t);
+        perm[t] = left[(size_t)d];
+        left.erase(left.begin() + d);
+    }
+}
+
+// The trees of the batch (one per distinct source root), then the pair kernel and the tour search, all on the stream; the
+// one-workgroup route leaves everything to the caller's single synchronisation, the round-per-launch route polls its rounds.
+// Result, matrix and (one-workgroup route) the trees' rounds are copied to h_tour_out.
+int tour_enqueue(fs_ctx *c, const FsRmPairArgs &pa_in, int32_t K, const int32_t *roots, int32_t k, bool *polled, int64_t *rounds_out)
+{
+    const int32_t n = rm_nodes(c);
+    const size_t nn = (size_t)n;
+    FsRmPairArgs pa = pa_in;
+    FS_HIP(c, c->d_tour_work.ensure(kTourWork)); FS_HIP(c, c->h_tour_out.ensure(kTourOut));
+    FS_HIP(c, c->d_tour_word.ensure(std::max(RM_TREE_BATCH, RM_TOUR_MAX_TREES)));
+    *polled = false;
+    *rounds_out = 0;
+    if (K > 0) {
+        int rc = rm_device_graph(c);
+        if (rc) return rc;
+        FS_HIP(c, c->d_tour_d.ensure(2 * nn * K)); FS_HIP(c, c->d_tour_hops.ensure(2 * nn * K)); FS_HIP(c, c->d_tour_pred.ensure(2 * nn * K));
+        FsRmTreeBatch B{};
+        B.t = FsRmTree{n, -1, c->d_rm_xy.p, c->d_rm_trow.p, c->d_rm_tcol.p, {c->d_tour_d.p, nullptr}, {c->d_tour_hops.p, nullptr},
+                       {c->d_tour_pred.p, nullptr}};
+        B.k = K;
+        for (int32_t b = 0; b < K; ++b) B.root[b] = roots[b];
+        FS_HIP(c, fs_launch_rm_batch_init(B, c->stream));
+        const int64_t max_rounds = 2 * (int64_t)n + 2;        // as rm_tree
+        if (n <= c->tour_one_wg) {
+            FS_HIP(c, fs_launch_rm_batch_block(B, (int32_t)max_rounds, c->d_tour_word.p, c->stream));
+            FS_HIP(c, hipMemcpyAsync(c->h_tour_out.p + kTourOffRounds, c->d_tour_word.p, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost,
+                                     c->stream));
+        } else {
+            *polled = true;
+            for (int64_t r = 0;;) {
+                FS_HIP(c, hipMemsetAsync(c->d_tour_word.p, 0, sizeof(int32_t) * RM_TREE_BATCH, c->stream));
+                for (int q = 0; q < RM_TREE_BATCH; ++q, ++r) FS_HIP(c, fs_launch_rm_batch_round(B, (int32_t)(r & 1), c->d_tour_word.p + q, c->stream));
+                int32_t any[RM_TREE_BATCH] = {0};
+                FS_HIP(c, hipMemcpyAsync(any, c->d_tour_word.p, sizeof any, hipMemcpyDeviceToHost, c->stream));
+                FS_HIP(c, hipStreamSynchronize(c->stream));
+                if (!any[RM_TREE_BATCH - 1]) {
+                    int q = 0;
+                    while (any[q]) ++q;
+                    *rounds_out = r - RM_TREE_BATCH + q + 1;
+                    break;
+                }
+                if (r >= max_rounds) return fail(c, FS_E_HIP, "the tour trees did not settle in %lld rounds", (long long)max_rounds);
+            }
+        }
+        // (after its quiet round both buffers of a tree hold it: buffer 0 is read)
+        pa.d = c->d_tour_d.p; pa.pred = c->d_tour_pred.p;
+    }
+    pa.n_nodes = n; pa.xy = c->d_rm_xy.p;
+    pa.M = reinterpret_cast<double *>(c->d_tour_work.p);
+    FS_HIP(c, fs_launch_rm_pairs(pa, c->stream));
+    int64_t total = 1;
+    for (int t = 2; t <= k; ++t) total *= t;
+    FsRmTourArgs ta{};
+    ta.k = k; ta.M = pa.M; ta.total = total;
+    const int32_t blocks = fs_rm_tour_blocks(total, &ta.chunk);
+    char *blk = c->d_tour_work.p + kTourOffBlk;
+    ta.blen = reinterpret_cast<double *>(blk); ta.bleg = ta.blen + kTourMaxBlk;
+    ta.brank = reinterpret_cast<int64_t *>(ta.bleg + kTourMaxBlk); ta.bcnt = ta.brank + kTourMaxBlk;
+    FS_HIP(c, fs_launch_rm_tour(ta, blocks, reinterpret_cast<double *>(c->d_tour_work.p + kTourOffRes), c->stream));
+    FS_HIP(c, hipMemcpyAsync(c->h_tour_out.p, c->d_tour_work.p, kTourOffRes + 32, hipMemcpyDeviceToHost, c->stream));
+    c->tour_evaluated += total;
+    return FS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fs_roadmap_next_goal(fs_ctx *c, const double robot_pose7[7], int32_t n, const double *goal_xyz, const double *path_length_m,
+                         const uint8_t *achievable, const uint8_t *blacklisted, int32_t n_blacklist_circles, const double *blacklist_xy,
+                         int32_t n_local, double local_radius, const double *fi_pose7, double fi_threshold, int32_t *next_index,
+                         int32_t *status, int32_t *tour, int32_t *tour_size, double *tour_length, int64_t *n_tied, uint8_t *selection,
+                         double *pair_length_m)
+{
+    if (!c) return FS_E_INVALID;
+    if (!robot_pose7 || n < 0 || (n > 0 && (!goal_xyz || !path_length_m || !achievable)) || n_blacklist_circles < 0 ||
+        (n_blacklist_circles > 0 && !blacklist_xy) || !next_index || !status || !tour || !tour_size || !tour_length || !n_tied)
+        return fail(c, FS_E_INVALID, "null pointer");
+    if (n_local < 1 || n_local > RM_TOUR_MAX_LOCAL) return fail(c, FS_E_INVALID, "n_local must be 1..%d", RM_TOUR_MAX_LOCAL);
+    if (!(local_radius >= 0 && std::isfinite(local_radius))) return fail(c, FS_E_INVALID, "local_radius must be finite and >= 0");
+    if (!std::isfinite(robot_pose7[0]) || !std::isfinite(robot_pose7[1])) return fail(c, FS_E_INVALID, "non-finite robot pose");
+    FS_HIP(c, hipSetDevice(c->device));
+    if (rm_nodes(c) == 0) return fail(c, FS_E_STATE, "no roadmap: fs_roadmap_add_nodes has not given it a node");
+    // eligibility: achievable, not blacklisted, outside every blacklist circle (isInBlacklistedRegion: distance < 1.7)
+    std::vector<uint8_t> eligible((size_t)n);
+    for (int32_t i = 0; i < n; ++i) {
+        bool ok = achievable[i] && !(blacklisted && blacklisted[i]);
+        for (int32_t b = 0; ok && b < n_blacklist_circles; ++b) {
+            const double ex = goal_xyz[3 * (size_t)i] - blacklist_xy[2 * (size_t)b], ey = goal_xyz[3 * (size_t)i + 1] - blacklist_xy[2 * (size_t)b + 1];
+            if (std::sqrt(ex * ex + ey * ey) < 1.7) ok = false;
+        }
+        if (ok && (std::isnan(path_length_m[i]) || !std::isfinite(goal_xyz[3 * (size_t)i]) || !std::isfinite(goal_xyz[3 * (size_t)i + 1])))
+            return fail(c, FS_E_INVALID, "eligible frontier %d has a NaN path length or a non-finite goal", (int)i);
+        eligible[(size_t)i] = ok;
+    }
+    std::vector<int32_t> loc, glob;
+    int32_t cg = -1;
+    tour_select(n, path_length_m, eligible, n_local, local_radius, loc, glob, cg);
+    if (selection) {
+        for (int32_t i = 0; i < n; ++i) selection[i] = 0;
+        for (const int32_t f : loc) selection[f] = TOUR_SEL_LOCAL;
+        for (const int32_t f : glob) selection[f] = TOUR_SEL_GLOBAL;
+        if (cg >= 0) selection[cg] |= TOUR_SEL_CLOSEST;
+    }
+    *next_index = -1; *status = FS_UNDETERMINED; *tour_size = 0; *tour_length = 0.0; *n_tied = 0;
+    const int32_t k = (int32_t)loc.size();
+    if (k == 0) {
+        if (glob.empty()) return FS_OK;                                 // the zero frontier
+        *next_index = cg; tour[0] = cg; *tour_size = 1; *status = FS_SAFE;
+        return fi_pose7 ? tour_pose_safe(c, fi_pose7, fi_threshold, status) : FS_OK;
+    }
+    // the nodes [robot, locals in selection order, closest global], their closest key nodes, one tree per distinct source root
+    const int32_t m = k + 2, nodes = rm_nodes(c);
+    FsRmPairArgs pa{};
+    pa.m = m; pa.charge = local_radius * 100000.0;
+    for (int32_t i = 0; i < m; ++i) {
+        const double *g = i == 0 ? robot_pose7 : goal_xyz + 3 * (size_t)(i <= k ? loc[(size_t)i - 1] : cg);
+        pa.pxy[2 * i] = g[0]; pa.pxy[2 * i + 1] = g[1];
+        pa.start[i] = fs_rm_closest(c->rm_xy.data(), c->rm_key.data(), nodes, c->rm_cell, g[0], g[1]);
+    }
+    int32_t roots[RM_TOUR_MAX_TREES], K = 0;
+    for (int32_t i = 0; i < m - 1; ++i) {
+        pa.tree[i] = 0;
+        if (pa.start[i] < 0) continue;
+        int32_t b = 0;
+        while (b < K && roots[b] != pa.start[i]) ++b;
+        if (b == K) roots[K++] = pa.start[i];
+        pa.tree[i] = b;
+    }
+    bool polled = false;
+    int64_t rounds = 0;
+    int rc = tour_enqueue(c, pa, K, roots, k, &polled, &rounds);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    if (!polled) {
+        for (int32_t b = 0; b < K; ++b) {
+            int32_t r = 0;
+            std::memcpy(&r, c->h_tour_out.p + kTourOffRounds + 4 * (size_t)b, sizeof r);
+            if (r < 0) return fail(c, FS_E_HIP, "a tour tree did not settle in %lld rounds", (long long)(2 * (int64_t)nodes + 2));
+            rounds = std::max<int64_t>(rounds, r);
+        }
+    }
+    c->tour_tree_builds += K;
+    c->tour_tree_rounds = rounds;
+    if (pair_length_m) std::memcpy(pair_length_m, c->h_tour_out.p, sizeof(double) * (size_t)m * (size_t)m);
+    double res[2];
+    int64_t ri[2];
+    std::memcpy(res, c->h_tour_out.p + kTourOffRes, sizeof res);
+    std::memcpy(ri, c->h_tour_out.p + kTourOffRes + 16, sizeof ri);
+    *tour_length = res[0];
+    *n_tied = ri[1];
+    if (!(res[0] < pa.charge)) return FS_OK;                            // getBestFullPath false: the zero frontier
+    int32_t perm[RM_TOUR_MAX_LOCAL];
+    tour_unrank(ri[0], k, perm);
+    for (int32_t t = 0; t < k; ++t) tour[t] = loc[(size_t)perm[t]];
+    tour[k] = cg;
+    *tour_size = k + 1;
+    *next_index = tour[0];
+    *status = FS_SAFE;
+    return fi_pose7 ? tour_pose_safe(c, fi_pose7, fi_threshold, status) : FS_OK;
 }
 
 }  // extern "C"

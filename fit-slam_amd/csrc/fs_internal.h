@@ -224,6 +224,49 @@ struct FsRmPlanArgs {
 };
 hipError_t fs_launch_rm_plan(const FsRmPlanArgs &a, hipStream_t s);
 
+// ---- next goal (FullPathOptimizer::getNextGoal): the pair matrix over [robot, locals, closest global] and the
+// exhaustive tour search over the locals' orders
+#define RM_TOUR_MAX_LOCAL 12                          // 12! < 2^31
+#define RM_TOUR_MAX_NODES (RM_TOUR_MAX_LOCAL + 2)
+#define RM_TOUR_MAX_TREES (RM_TOUR_MAX_LOCAL + 1)     // a tree per distinct source root: the robot and the locals
+// K trees in one set of buffers: tree b's two round buffers at + 2 * n * b of t.d[0] / t.hops[0] / t.pred[0] (t.root and the
+// second buffer pointers are ignored); every tree is relax()'s, so each equals the single tree from its root
+struct FsRmTreeBatch {
+    FsRmTree t;
+    int32_t k;
+    int32_t root[RM_TOUR_MAX_TREES];
+};
+hipError_t fs_launch_rm_batch_init(const FsRmTreeBatch &b, hipStream_t s);
+// one workgroup per tree (n <= the one-workgroup limit): rounds[b] as rm_tree_block's rounds[0]
+hipError_t fs_launch_rm_batch_block(const FsRmTreeBatch &b, int32_t max_rounds, int32_t *d_rounds, hipStream_t s);
+// one round of every tree per launch, blockIdx.y = tree: any[0] = 1 when a key of any tree changed
+hipError_t fs_launch_rm_batch_round(const FsRmTreeBatch &b, int32_t src, int32_t *d_any, hipStream_t s);
+struct FsRmPairArgs {
+    int32_t m;                              // nodes of the matrix
+    int32_t n_nodes;                        // roadmap nodes
+    const double *xy;                       // [n_nodes][2]
+    const double *d;                        // tree b's converged distances at d + 2 * n_nodes * b
+    const int32_t *pred;                    // ... and predecessors
+    double charge;                          // an unreachable pair's length
+    double pxy[2 * RM_TOUR_MAX_NODES];      // the nodes' goal points
+    int32_t start[RM_TOUR_MAX_NODES];       // closest key node of each point (-1: none)
+    int32_t tree[RM_TOUR_MAX_NODES];        // the tree rooted at start[i] (sources 0..m-2)
+    double *M;                              // [m][m], symmetric, 0 on the diagonal
+};
+hipError_t fs_launch_rm_pairs(const FsRmPairArgs &a, hipStream_t s);
+// the tour search: lane chunks of lexicographic ranks, one (length, robot leg, rank, count) per block, then one workgroup over the
+// blocks; out = {length, robot leg} doubles then {rank, count} int64 at out + 2
+struct FsRmTourArgs {
+    int32_t k;                              // locals; the matrix is (k + 2)^2
+    const double *M;
+    int64_t total;                          // k!
+    int64_t chunk;                          // ranks per lane
+    double *blen, *bleg;                    // [blocks]
+    int64_t *brank, *bcnt;
+};
+int32_t fs_rm_tour_blocks(int64_t total, int64_t *chunk);
+hipError_t fs_launch_rm_tour(const FsRmTourArgs &a, int32_t blocks, double *d_out, hipStream_t s);
+
 // ---- key-frame pose information (computeInformationForPose)
 struct FsKfArgs {
     int32_t n;                 // poses

@@ -173,7 +173,7 @@ __device__ __forceinline__ bool relax(const FsRmTree &t, int src, int32_t v)
 
 // The whole relaxation in one workgroup (n <= RM_TREE_ONE_WG): rounds separated by the workgroup barrier.  rounds[0] = rounds run
 // (the last one quiet), or -1 if max_rounds passed without a quiet round.  The converged tree is in buffer rounds[0] & 1.
-__global__ __launch_bounds__(1024) void rm_tree_block_kernel(FsRmTree t, int32_t max_rounds, int32_t *__restrict__ rounds)
+__device__ __forceinline__ void tree_block(const FsRmTree &t, int32_t max_rounds, int32_t *__restrict__ rounds)
 {
     int src = 0;
     for (int32_t r = 1; r <= max_rounds; ++r) {
@@ -186,6 +186,11 @@ __global__ __launch_bounds__(1024) void rm_tree_block_kernel(FsRmTree t, int32_t
         }
     }
     if (threadIdx.x == 0) rounds[0] = -1;
+}
+
+__global__ __launch_bounds__(1024) void rm_tree_block_kernel(FsRmTree t, int32_t max_rounds, int32_t *__restrict__ rounds)
+{
+    tree_block(t, max_rounds, rounds);
 }
 
 // ... or one round per launch (larger graphs): any[0] = 1 (plain store) when a key changed
@@ -224,6 +229,198 @@ __global__ void rm_plan_kernel(const FsRmPlanArgs a)
     a.path_length_m[f] = len;
     a.path_heading[f] = head;
     a.achievable[f] = ok;
+}
+
+
+// ---- next goal
+
+// tree b of a batch: the graph of B.t, its own root and round buffers
+__device__ __forceinline__ FsRmTree batch_tree(const FsRmTreeBatch &B, int b)
+{
+    FsRmTree t = B.t;
+    const size_t o = 2 * (size_t)t.n * (size_t)b;
+    t.root = B.root[b];
+    t.d[0] = B.t.d[0] + o; t.d[1] = t.d[0] + t.n;
+    t.hops[0] = B.t.hops[0] + o; t.hops[1] = t.hops[0] + t.n;
+    t.pred[0] = B.t.pred[0] + o; t.pred[1] = t.pred[0] + t.n;
+    return t;
+}
+
+__global__ void rm_batch_init_kernel(FsRmTreeBatch B)
+{
+    const FsRmTree t = batch_tree(B, blockIdx.y);
+    const int32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= t.n) return;
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        t.d[b][v] = v == t.root ? 0.0 : INFINITY;
+        t.hops[b][v] = v == t.root ? 0 : INT32_MAX;
+        t.pred[b][v] = -1;
+    }
+}
+
+// every tree of the batch in a workgroup of its own, the loop of rm_tree_block_kernel.  The tree's descriptor sits in LDS: relax()
+// picks its buffers by the round's parity, and a descriptor in registers would be indexed through scratch.
+__global__ __launch_bounds__(1024) void rm_batch_block_kernel(FsRmTreeBatch B, int32_t max_rounds, int32_t *__restrict__ rounds)
+{
+    __shared__ FsRmTree t;
+    if (threadIdx.x == 0) t = batch_tree(B, blockIdx.x);
+    __syncthreads();
+    tree_block(t, max_rounds, rounds + blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void rm_batch_round_kernel(FsRmTreeBatch B, int32_t src, int32_t *__restrict__ any)
+{
+    __shared__ FsRmTree t;
+    if (threadIdx.x == 0) t = batch_tree(B, blockIdx.y);
+    __syncthreads();
+    const int32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    const int ch = (v < t.n && relax(t, src, v)) ? 1 : 0;
+    if (__syncthreads_or(ch) && threadIdx.x == 0) any[0] = 1;
+}
+
+// getPlan(point i, true, point j, true) for every pair i < j, one lane each: the tree from i's closest key node, the segment
+// lengths summed from j's end back along the predecessors as rm_plan_kernel does.  The lower index is the direction (DESIGN.md
+// 4.11); M[j][i] = M[i][j].
+__global__ __launch_bounds__(256) void rm_pairs_kernel(const FsRmPairArgs a)
+{
+    const int32_t l = threadIdx.x, m = a.m;
+    if (l >= m * m) return;
+    const int32_t i = l / m, j = l % m;
+    if (i == j) { a.M[l] = 0.0; return; }
+    if (i > j) return;
+    double len = a.charge;
+    if (a.pxy[2 * i] == a.pxy[2 * j] && a.pxy[2 * i + 1] == a.pxy[2 * j + 1]) {
+        len = 0.0;
+    } else {
+        const int32_t root = a.start[i];
+        int32_t v = a.start[j];
+        if (root >= 0 && v >= 0) {
+            const size_t o = 2 * (size_t)a.n_nodes * (size_t)a.tree[i];
+            const double *d = a.d + o;
+            const int32_t *pred = a.pred + o;
+            if (d[v] < INFINITY) {
+                double s = 0.0;
+                for (int32_t k = 0; v != root && k < a.n_nodes; ++k) {
+                    const int32_t u = pred[v];
+                    const double ex = a.xy[2 * v] - a.xy[2 * u], ey = a.xy[2 * v + 1] - a.xy[2 * u + 1];
+                    s += sqrt(ex * ex + ey * ey);
+                    v = u;
+                }
+                len = s;
+            }
+        }
+    }
+    a.M[i * m + j] = len;
+    a.M[j * m + i] = len;
+}
+
+constexpr int kTourThreads = 256;
+constexpr int kTourMinChunk = 64;       // ranks per lane at least (the unranking is paid once per lane)
+constexpr int kTourMaxBlocks = 1024;
+
+// a lane's or a block's best tour: the lexicographic minimum of (length, robot leg, rank), and how many tours have that length
+struct TourBest {
+    double len, leg;
+    int64_t rank, cnt;
+};
+
+__device__ __forceinline__ void tour_merge(TourBest &a, const TourBest &b)
+{
+    if (b.len < a.len) {
+        a = b;
+    } else if (b.len == a.len) {
+        a.cnt += b.cnt;
+        if (b.leg < a.leg || (b.leg == a.leg && b.rank < a.rank)) { a.leg = b.leg; a.rank = b.rank; }
+    }
+}
+
+// the workgroup's minimum in thread 0: across the wave by shuffles, then across the waves in LDS
+__device__ TourBest tour_block_reduce(TourBest x)
+{
+    __shared__ TourBest part[kTourThreads / 64];
+    for (int o = 32; o > 0; o >>= 1) {
+        TourBest y;
+        y.len = __shfl_xor(x.len, o); y.leg = __shfl_xor(x.leg, o);
+        y.rank = __shfl_xor(x.rank, o); y.cnt = __shfl_xor(x.cnt, o);
+        tour_merge(x, y);
+    }
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = x;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) tour_merge(x, part[w]);
+    return x;
+}
+
+// The exhaustive tour search.  Lane g takes the ranks [g * chunk, (g + 1) * chunk) of the lexicographic order of the locals'
+// positions 0..k-1: it unranks the first (factorial number system), then steps with next_permutation.  Tour length = the legs
+// robot -> p0 -> ... -> p(k-1) -> global added left to right in fp64 from 0.0, the reference's order; the prefix sums of the legs are
+// kept, so a step re-adds only the legs from the first changed position on, and every length is bit-equal to a full recomputation.
+// The permutation and the prefix sums live in LDS, [position][lane].
+__global__ __launch_bounds__(kTourThreads) void rm_tour_kernel(const FsRmTourArgs a)
+{
+    __shared__ double Ms[RM_TOUR_MAX_NODES * RM_TOUR_MAX_NODES];
+    __shared__ double P[RM_TOUR_MAX_LOCAL + 1][kTourThreads];
+    __shared__ uint8_t perm[RM_TOUR_MAX_LOCAL][kTourThreads];
+    const int k = a.k, m = k + 2, L = threadIdx.x;
+    for (int i = L; i < m * m; i += blockDim.x) Ms[i] = a.M[i];
+    __syncthreads();
+    TourBest best{INFINITY, INFINITY, INT64_MAX, 0};
+    const int64_t r0 = ((int64_t)blockIdx.x * blockDim.x + L) * a.chunk;
+    const int64_t r1 = r0 + a.chunk < a.total ? r0 + a.chunk : a.total;
+    if (r0 < a.total) {
+        // unrank r0: digit t (base k - t) picks the digit-th unused position
+        int64_t f = 1;
+        for (int t = 2; t < k; ++t) f *= t;                      // (k - 1)!
+        uint32_t used = 0;
+        int64_t r = r0;
+        for (int t = 0; t < k; ++t) {
+            const int64_t dgt = r / f;
+            r -= dgt * f;
+            if (t < k - 1) f /= (k - 1 - t);
+            int c = -1;
+            for (int64_t s = 0; s <= dgt;) { ++c; if (!(used >> c & 1u)) ++s; }
+            used |= 1u << c;
+            perm[t][L] = (uint8_t)c;
+        }
+        int first = 0;                                          // legs from position `first` on are (re)added
+        for (int64_t rank = r0;; ++rank) {
+            int prev = first == 0 ? 0 : perm[first - 1][L] + 1;
+            double acc = first == 0 ? 0.0 : P[first][L];
+            for (int t = first; t < k; ++t) {
+                const int cur = perm[t][L] + 1;
+                acc += Ms[prev * m + cur];
+                P[t + 1][L] = acc;
+                prev = cur;
+            }
+            acc += Ms[prev * m + (k + 1)];
+            tour_merge(best, TourBest{acc, Ms[perm[0][L] + 1], rank, 1});
+            if (rank + 1 >= r1) break;
+            // next_permutation: i = the last ascent, j = the last element above p[i]; swap, reverse the suffix
+            int i = k - 2;
+            while (perm[i][L] >= perm[i + 1][L]) --i;           // an ascent exists: rank + 1 < k!
+            int j = k - 1;
+            while (perm[j][L] <= perm[i][L]) --j;
+            uint8_t x = perm[i][L]; perm[i][L] = perm[j][L]; perm[j][L] = x;
+            for (int lo = i + 1, hi = k - 1; lo < hi; ++lo, --hi) { x = perm[lo][L]; perm[lo][L] = perm[hi][L]; perm[hi][L] = x; }
+            first = i;
+        }
+    }
+    best = tour_block_reduce(best);
+    if (L == 0) { a.blen[blockIdx.x] = best.len; a.bleg[blockIdx.x] = best.leg; a.brank[blockIdx.x] = best.rank; a.bcnt[blockIdx.x] = best.cnt; }
+}
+
+// one workgroup over the blocks' winners (the same total order, so the result does not depend on the blocks' order)
+__global__ __launch_bounds__(kTourThreads) void rm_tour_reduce_kernel(const FsRmTourArgs a, int32_t blocks, double *__restrict__ out)
+{
+    TourBest best{INFINITY, INFINITY, INT64_MAX, 0};
+    for (int32_t b = threadIdx.x; b < blocks; b += blockDim.x) tour_merge(best, TourBest{a.blen[b], a.bleg[b], a.brank[b], a.bcnt[b]});
+    best = tour_block_reduce(best);
+    if (threadIdx.x == 0) {
+        out[0] = best.len; out[1] = best.leg;
+        int64_t *o = reinterpret_cast<int64_t *>(out + 2);
+        o[0] = best.rank; o[1] = best.cnt;
+    }
 }
 
 }  // namespace
@@ -285,5 +482,53 @@ hipError_t fs_launch_rm_plan(const FsRmPlanArgs &a, hipStream_t s)
 {
     if (a.n <= 0) return hipSuccess;
     hipLaunchKernelGGL(rm_plan_kernel, dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_rm_batch_init(const FsRmTreeBatch &b, hipStream_t s)
+{
+    if (b.t.n <= 0 || b.k <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rm_batch_init_kernel, dim3((unsigned)((b.t.n + 255) / 256), (unsigned)b.k), dim3(256), 0, s, b);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_rm_batch_block(const FsRmTreeBatch &b, int32_t max_rounds, int32_t *d_rounds, hipStream_t s)
+{
+    if (b.k <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rm_batch_block_kernel, dim3((unsigned)b.k), dim3(1024), 0, s, b, max_rounds, d_rounds);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_rm_batch_round(const FsRmTreeBatch &b, int32_t src, int32_t *d_any, hipStream_t s)
+{
+    if (b.t.n <= 0 || b.k <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rm_batch_round_kernel, dim3((unsigned)((b.t.n + 255) / 256), (unsigned)b.k), dim3(256), 0, s, b, src, d_any);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_rm_pairs(const FsRmPairArgs &a, hipStream_t s)
+{
+    if (a.m < 2 || a.m > RM_TOUR_MAX_NODES) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rm_pairs_kernel, dim3(1), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// blocks of the tour search for k! tours and the ranks per lane
+int32_t fs_rm_tour_blocks(int64_t total, int64_t *chunk)
+{
+    int64_t blocks = (total + (int64_t)kTourThreads * kTourMinChunk - 1) / ((int64_t)kTourThreads * kTourMinChunk);
+    blocks = blocks < 1 ? 1 : blocks > kTourMaxBlocks ? kTourMaxBlocks : blocks;
+    const int64_t lanes = blocks * kTourThreads;
+    *chunk = (total + lanes - 1) / lanes;
+    return (int32_t)blocks;
+}
+
+hipError_t fs_launch_rm_tour(const FsRmTourArgs &a, int32_t blocks, double *d_out, hipStream_t s)
+{
+    if (a.k < 1 || a.k > RM_TOUR_MAX_LOCAL || blocks < 1 || blocks > kTourMaxBlocks) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rm_tour_kernel, dim3((unsigned)blocks), dim3(kTourThreads), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rm_tour_reduce_kernel, dim3(1), dim3(kTourThreads), 0, s, a, blocks, d_out);
     return hipGetLastError();
 }

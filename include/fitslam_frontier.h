@@ -462,6 +462,31 @@ int fs_get_frontier_costs_roadmap(fs_ctx *ctx, const double robot_pose7[7], int3
                   fs_record *records, double *weighted_cost, double *arrival_utility, double *distance_utility, int32_t *order,
                   double *path_length_m);
 
+/* ---------------------------------------------------------------- next goal (FullPathOptimizer::getNextGoal) */
+/* FullPathOptimizer::getNextGoal (DEP/src/FullPathOptimizer.cpp:548-661) on the roadmap the context holds.
+ * Inputs: the frontier list as fs_roadmap_plan left it — goal_xyz [n][3], path_length_m [n], achievable [n], blacklisted [n] (may be
+ * NULL) — and blacklist_xy [n_blacklist_circles][2], the circle centres isInBlacklistedRegion tests (distance < 1.7 m).
+ * getFilteredFrontiersN (:157-227) splits the eligible frontiers into at most n_local (1..12; the reference's 5) locals of path length
+ * <= local_radius (the reference's 12.0) and globals, with every quirk of the reference; ties in path length go to the lower index.
+ * The pair lengths over the nodes [robot, locals in selection order, closest global] are getPlan(i, true, j, true) for i < j — one
+ * shortest-path tree per source, all in one launch —, local_radius * 100000 where there is no path; the tour search tries every
+ * order of the locals (robot -> locals -> closest global) and keeps the shortest, ties to the shortest robot leg, then the first
+ * order in lexicographic order of the selection positions.  fi_pose7 NULL: use_fi false; otherwise isRobotPoseSafe on it through the
+ * info-only scorer (unsafe unless info_ref > fi_threshold) on the reference's two branches.
+ * Outputs: next_index (-1: the reference's zero frontier), status (0 SAFE, 1 UNSAFE, 2 UNDETERMINED), tour [<= n_local + 1] and
+ * tour_size (the locals in visiting order, then the closest global; without locals only the closest global; 0 with the zero
+ * frontier), tour_length (the winning length; 0 when no tour was searched), n_tied (tours of that length; 0 when none was searched).
+ * selection [n] (may be NULL): 1 local, 2 global, 0 in neither list (not eligible, or a local the reference drops), | 4 on the
+ * closest global.  pair_length_m (may be NULL): room for (n_local + 2)^2; with k >= 1 locals the (k + 2)^2 symmetric matrix is
+ * written row-major (row 0: the robot's lengths, calculateLengthRobotToGoal).  No roadmap node: FS_E_STATE; n_local outside 1..12:
+ * FS_E_INVALID.  One synchronisation (plus the scorer's own when the FI check runs, and the round polling of roadmaps too large
+ * for one workgroup per tree). */
+int fs_roadmap_next_goal(fs_ctx *ctx, const double robot_pose7[7], int32_t n, const double *goal_xyz, const double *path_length_m,
+                         const uint8_t *achievable, const uint8_t *blacklisted, int32_t n_blacklist_circles, const double *blacklist_xy,
+                         int32_t n_local, double local_radius, const double *fi_pose7, double fi_threshold, int32_t *next_index,
+                         int32_t *status, int32_t *tour, int32_t *tour_size, double *tour_length, int64_t *n_tied, uint8_t *selection,
+                         double *pair_length_m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "fs_multi_score_fim", "fs_multi_get_frontier_costs", "fs_multi_gather_mode",
     "fs_plan_paths", "fs_navfn_potential", "fs_get_frontier_costs_planned",
     "fs_set_roadmap_params", "fs_roadmap_add_nodes", "fs_roadmap_rebuild", "fs_roadmap_connect", "fs_roadmap_get_graph", "fs_roadmap_plan",
-    "fs_get_frontier_costs_roadmap", "fs_roadmap_next_goal",
+    "fs_get_frontier_costs_roadmap", "fs_roadmap_next_goal", "fs_refine_paths", "fs_refine_field",
 ]
 
 RECORD_DTYPE = np.dtype([("arrival", "<i4"), ("argmax", "<i4"), ("yaw", "<f4"), ("info_ref", "<f4"),
@@ -165,6 +165,8 @@ def load_library(build: bool = True):
     L.fs_get_frontier_costs_roadmap.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, vp, dbl, dbl, dbl, dbl, C.c_int, vp, vp, vp, vp, vp, vp]
     L.fs_roadmap_next_goal.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, vp, vp, i32, vp, i32, dbl, vp, dbl,
                                        C.POINTER(i32), C.POINTER(i32), vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(i64), vp, vp]
+    L.fs_refine_paths.argtypes = [vp, i32, vp, vp, i32, dbl, dbl, i32, vp, vp, vp, vp, vp, vp]
+    L.fs_refine_field.argtypes = [vp, C.POINTER(dbl * 2), i32, dbl, dbl, i32, vp]
     for name in EXPORTED_SYMBOLS:
         f = getattr(L, name)
         if name not in ("fs_ctx_destroy", "fs_last_error", "fs_multi_destroy", "fs_multi_last_error", "fs_multi_ctx"):
@@ -602,6 +604,61 @@ class FrontierScorer:
             out["selection"] = sel
         if want_matrix:
             out["pair_length_m"] = mat[:(k + 2) * (k + 2)].reshape(k + 2, k + 2).copy() if k else None
+        return out
+
+    # -- leg refinement (computePathBetweenPointsThetaStar: the path the robot drives)
+    def refine_paths(self, starts, goals, allow_unknown=True, w_euc=1.0, w_traversal=2.0, corners=8):
+        """computePathBetweenPointsThetaStar for every leg starts[i] -> goals[i] ([n][2] world; extra columns ignored): one cost
+        field per distinct start cell, a descent and Theta*'s parent rule per leg.  dict(status [n] (0 path, 1 start off the map,
+        2 goal off the map, 3 start unsafe, 4 goal unsafe, 5 no path), cost [n], vertices (a [V][2] array per leg, start first),
+        poses (a [N][2] array per leg: the interpolated path the reference publishes))."""
+        def pts(a):
+            a = np.asarray(a, dtype=np.float64)
+            a = a.reshape(-1, a.shape[-1]) if a.ndim else a.reshape(-1, 2)
+            return np.ascontiguousarray(a[:, :2])
+        s, g = pts(starts), pts(goals)
+        n = s.shape[0]
+        if g.shape[0] != n:
+            raise ValueError(f"{g.shape[0]} goals for {n} starts")
+        st = np.zeros(n, dtype=np.int32); cost = np.zeros(n)
+        nv = np.zeros(n, dtype=np.int32); npz = np.zeros(n, dtype=np.int32)
+        args = (1 if allow_unknown else 0, float(w_euc), float(w_traversal), int(corners))
+        # size first (the fields are cached, so the second call only repeats the legs)
+        self._check(self._L.fs_refine_paths(self._h, n, _p(s), _p(g), *args, _p(st), _p(cost), _p(nv), None, _p(npz), None))
+        vert = np.zeros((int(nv.sum()), 2)); pose = np.zeros((int(npz.sum()), 2))
+        self._check(self._L.fs_refine_paths(self._h, n, _p(s), _p(g), *args, _p(st), _p(cost), _p(nv), _p(vert), _p(npz), _p(pose)))
+        vo, po = np.concatenate([[0], np.cumsum(nv)]), np.concatenate([[0], np.cumsum(npz)])
+        return dict(status=st, cost=cost, n_vertices=nv, n_poses=npz,
+                    vertices=[vert[vo[i]:vo[i + 1]] for i in range(n)], poses=[pose[po[i]:po[i + 1]] for i in range(n)])
+
+    def refine_field(self, start_xy, allow_unknown=True, w_euc=1.0, w_traversal=2.0, corners=8) -> np.ndarray:
+        """The cost field refine_paths descends from start_xy, float64 [ny][nx] of the grid this scorer staged (DBL_MAX: not reached)."""
+        if self._grid_shape is None:
+            raise FsError(FS_E_STATE, "no grid staged through this scorer (upload_grid / upload_grid_bricks)")
+        nz, ny, nx = self._grid_shape
+        if nz != 1:
+            raise FsError(FS_E_INVALID, "the leg refinement is defined on a 2-D costmap (nz == 1)")
+        xy = np.asarray(start_xy, dtype=np.float64).reshape(-1)
+        start = (C.c_double * 2)(float(xy[0]), float(xy[1]))
+        out = np.zeros((ny, nx))
+        self._check(self._L.fs_refine_field(self._h, C.byref(start), 1 if allow_unknown else 0, float(w_euc), float(w_traversal),
+                                            int(corners), _p(out)))
+        return out
+
+    def refine_tour(self, robot_pose7, goal_xyz, tour):
+        """getNextGoal's published plan for a roadmap_next_goal result: the legs robot -> goal[tour[0]] -> goal[tour[1]] -> ...,
+        planned as computePathBetweenPointsThetaStar(..., true) does.  refine_paths' dict plus `path`: the poses of the legs that
+        found a path, back to back (what FullPathOptimizer accumulates into its plan)."""
+        robot = np.asarray(robot_pose7, dtype=np.float64).reshape(7)[:2]
+        goal = np.asarray(goal_xyz, dtype=np.float64).reshape(-1, 3)[:, :2]
+        idx = np.asarray(tour["tour"] if isinstance(tour, dict) else tour, dtype=np.int64).reshape(-1)
+        if idx.size == 0:
+            return dict(status=np.zeros(0, np.int32), cost=np.zeros(0), n_vertices=np.zeros(0, np.int32), n_poses=np.zeros(0, np.int32),
+                        vertices=[], poses=[], path=np.zeros((0, 2)))
+        pts = np.vstack([robot[None], goal[idx]])
+        out = self.refine_paths(pts[:-1], pts[1:])
+        ok = [p for p, s in zip(out["poses"], out["status"]) if s == 0]
+        out["path"] = np.vstack(ok) if ok else np.zeros((0, 2))
         return out
 
     def selftest_fp64(self, max_abs=256) -> int:

@@ -329,6 +329,26 @@ struct fs_ctx {
     DevBuf<char> d_tour_work;                 // matrix | result | block winners
     PinnedBuf h_tour_out;                     // matrix | result | rounds of each tree
 
+    // any-angle leg refinement (fs_refine.hip): a slab of rf_max_fields fp64 fields; slot s holds the field of
+    // rf_key[s] for grid generation rf_gen[s] (0: empty).  Every staging call that writes the grid bumps grid_gen, which drops them.
+    struct RfKey {
+        int32_t src = -1, allow = 0, corners = 0;
+        double w_euc = 0.0, w_trav = 0.0;
+        bool operator==(const RfKey &o) const { return src == o.src && allow == o.allow && corners == o.corners && w_euc == o.w_euc && w_trav == o.w_trav; }
+    };
+    int32_t rf_max_fields = 16;               // "refine.max_fields": fields relaxed together / kept
+    std::vector<RfKey> rf_key;
+    std::vector<uint64_t> rf_gen;
+    size_t rf_slab_cells = 0;                 // nx * ny the slab was laid out for
+    int64_t rf_builds = 0, rf_rounds = 0, rf_walks = 0;
+    int64_t rf_chain_cap = 0;
+    int32_t rf_vert_cap = 0, rf_pose_cap = 0;
+    DevBuf<double> d_rf_g;
+    DevBuf<uint32_t> d_rf_flags;              // [2][fields][tiles]
+    DevBuf<int32_t> d_rf_any, d_rf_in, d_rf_scratch;   // rounds x fields words | legs' inputs | chain, parents, vertex cells
+    DevBuf<char> d_rf_out, d_rf_pts;          // per-leg columns | vertex and pose slots (when the page-locked buffer is not mapped)
+    PinnedBuf h_rf_in, h_rf_out, h_rf_pts;
+
     // timing
     bool timing = false;
     std::vector<TimedLaunch> launches;
@@ -904,6 +924,8 @@ void fs_ctx_destroy(fs_ctx *c)
     c->d_rm_in.release(); c->d_rm_out.release(); c->h_rm_in.release(); c->h_rm_out.release();
     c->d_tour_d.release(); c->d_tour_hops.release(); c->d_tour_pred.release(); c->d_tour_word.release(); c->d_tour_work.release();
     c->h_tour_out.release();
+    c->d_rf_g.release(); c->d_rf_flags.release(); c->d_rf_any.release(); c->d_rf_in.release(); c->d_rf_scratch.release();
+    c->d_rf_out.release(); c->d_rf_pts.release(); c->h_rf_in.release(); c->h_rf_out.release(); c->h_rf_pts.release();
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1700,6 +1722,10 @@ int fs_set_option(fs_ctx *c, const char *key, double value)
     if (std::strcmp(key, "fim.skip32") == 0 && value >= 1 && value <= 32) { c->opt_skip32 = (int)value; return FS_OK; }
     if (std::strcmp(key, "fim.headroom") == 0 && value >= 8 && value <= 64) { c->opt_headroom = (int)value; return FS_OK; }
     if (std::strcmp(key, "roadmap.tour_one_wg") == 0 && value >= 0 && value <= RM_TREE_ONE_WG) { c->tour_one_wg = (int32_t)value; return FS_OK; }
+    if (std::strcmp(key, "refine.max_fields") == 0 && value >= 1 && value <= RF_MAX_FIELDS) {
+        if ((int32_t)value != c->rf_max_fields) { c->rf_max_fields = (int32_t)value; c->rf_key.clear(); c->rf_gen.clear(); }
+        return FS_OK;
+    }
     return fail(c, FS_E_INVALID, "unknown option %s", key);
 }
 
@@ -1727,6 +1753,14 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
         int64_t &v = which == 1008 ? c->tour_tree_builds : which == 1009 ? c->tour_tree_rounds : c->tour_evaluated;
         *value = v;
         if (reset && which != 1009) v = 0;
+        return FS_OK;
+    }
+    // ... of the leg refinement (fs_refine_paths / fs_refine_field): 1011 fields built, 1012 rounds of the last field built, 1013
+    // line-of-sight walks
+    if (c && value && which >= 1011 && which <= 1013) {
+        int64_t &v = which == 1011 ? c->rf_builds : which == 1012 ? c->rf_rounds : c->rf_walks;
+        *value = v;
+        if (reset && which != 1012) v = 0;
         return FS_OK;
     }
     if (!c || !value || which < 0 || which >= FS_N_COUNTERS) return FS_E_INVALID;
@@ -3582,6 +3616,258 @@ int fs_roadmap_next_goal(fs_ctx *c, const double robot_pose7[7], int32_t n, cons
     *next_index = tour[0];
     *status = FS_SAFE;
     return fi_pose7 ? tour_pose_safe(c, fi_pose7, fi_threshold, status) : FS_OK;
+}
+
+}  // extern "C"
+
+// ================================================================== any-angle leg refinement (fs_refine.hip)
+// computePathBetweenPointsThetaStar (DEP/src/Helpers.cpp:540-588) for a batch of legs: one converged cost field per distinct start
+// cell — relaxed together, kept per context —, then one wave per leg for the descent, Theta*'s parent rule and the interpolation.
+
+namespace {
+
+// Rounds are launched in batches and polled as the grid planner's are (a round after a quiet round is quiet too).
+#define RF_BATCH_FIRST 8
+#define RF_BATCH 16
+#define RF_MAX_ROUNDS (1 << 22)
+
+int rf_check(fs_ctx *c, double w_euc, double w_trav, int32_t corners)
+{
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (c->nz != 1) return fail(c, FS_E_INVALID, "the leg refinement is defined on a 2-D costmap (nz == 1)");
+    if (corners != 4 && corners != 8) return fail(c, FS_E_INVALID, "corners must be 4 or 8");
+    // (w_euc > 0 makes the field's fixed point unique; the bounds keep DBL_MAX an absorbing "not reached")
+    if (!(w_euc > 0.0 && w_euc <= 1e6) || !(w_trav >= 0.0 && w_trav <= 1e6)) return fail(c, FS_E_INVALID, "weights outside 0 < w_euc <= 1e6, 0 <= w_traversal <= 1e6");
+    return FS_OK;
+}
+
+void rf_moves(double w_euc, double e[8])
+{
+    static const int m[8][2] = {{0, 1}, {0, -1}, {1, 0}, {-1, 0}, {1, -1}, {-1, 1}, {1, 1}, {-1, -1}};
+    for (int i = 0; i < 8; ++i) e[i] = w_euc * std::sqrt((double)(m[i][0] * m[i][0] + m[i][1] * m[i][1]));
+}
+
+// The fields of `srcs` (at most rf_max_fields distinct start cells) in the slab: cached ones found, the others built now in one
+// batch (polls the stream).  slot[i] = the slab block of srcs[i].
+int rf_fields(fs_ctx *c, const fs_ctx::RfKey &base, const std::vector<int32_t> &srcs, std::vector<int32_t> &slot)
+{
+    const int M = c->rf_max_fields;
+    const size_t ns = (size_t)c->nx * (size_t)c->ny;
+    const double *before = c->d_rf_g.p;
+    FS_HIP(c, c->d_rf_g.ensure((size_t)M * ns));
+    if (c->rf_slab_cells != ns || (int)c->rf_key.size() != M || c->d_rf_g.p != before) {
+        c->rf_key.assign(M, fs_ctx::RfKey{});
+        c->rf_gen.assign(M, 0);
+        c->rf_slab_cells = ns;
+    }
+    slot.assign(srcs.size(), -1);
+    std::vector<char> used(M, 0);
+    for (size_t i = 0; i < srcs.size(); ++i) {
+        fs_ctx::RfKey k = base;
+        k.src = srcs[i];
+        for (int s = 0; s < M; ++s)
+            if (!used[s] && c->rf_gen[s] == c->grid_gen && c->rf_key[s] == k) { slot[i] = s; used[s] = 1; break; }
+    }
+    FsRefineFieldArgs a{};
+    a.n = 0;
+    for (size_t i = 0; i < srcs.size(); ++i) {
+        if (slot[i] >= 0) continue;
+        int pick = -1;
+        for (int s = 0; s < M && pick < 0; ++s) if (!used[s] && c->rf_gen[s] != c->grid_gen) pick = s;   // empty or stale first
+        for (int s = 0; s < M && pick < 0; ++s) if (!used[s]) pick = s;
+        if (pick < 0) return fail(c, FS_E_INVALID, "more fields than refine.max_fields in one group");
+        used[pick] = 1;
+        slot[i] = pick;
+        a.f[a.n++] = FsRefineFieldDesc{pick, srcs[i]};
+    }
+    if (a.n == 0) return FS_OK;
+    const int nx = c->nx, ny = c->ny;
+    a.cells = c->d_cells.p; a.g = c->d_rf_g.p;
+    a.nx = nx; a.ny = ny; a.tx = (nx + RF_TILE - 1) / RF_TILE; a.ty = (ny + RF_TILE - 1) / RF_TILE;
+    a.allow = base.allow; a.corners = base.corners; a.w_trav = base.w_trav;
+    rf_moves(base.w_euc, a.e);
+    const size_t tiles = (size_t)a.tx * (size_t)a.ty;
+    FS_HIP(c, c->d_rf_flags.ensure(2 * (size_t)a.n * tiles));
+    FS_HIP(c, c->d_rf_any.ensure((size_t)RF_BATCH * a.n));
+    uint32_t *flags[2] = {c->d_rf_flags.p, c->d_rf_flags.p + (size_t)a.n * tiles};
+    for (int i = 0; i < a.n; ++i) c->rf_gen[a.f[i].slot] = 0;      // (until the build has finished)
+    FS_HIP(c, fs_launch_refine_init(a, flags[0], c->stream));
+    std::vector<int64_t> rounds((size_t)a.n, -1);
+    std::vector<int32_t> any((size_t)RF_BATCH * a.n);
+    int64_t r = 0;
+    for (int batch = RF_BATCH_FIRST;; batch = RF_BATCH) {
+        FS_HIP(c, hipMemsetAsync(c->d_rf_any.p, 0, sizeof(int32_t) * batch * a.n, c->stream));
+        for (int k = 0; k < batch; ++k, ++r)
+            FS_HIP(c, fs_launch_refine_round(a, flags[r & 1], flags[(r + 1) & 1], c->d_rf_any.p + (size_t)k * a.n, c->stream));
+        FS_HIP(c, hipMemcpyAsync(any.data(), c->d_rf_any.p, sizeof(int32_t) * batch * a.n, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        bool done = true;
+        for (int f = 0; f < a.n; ++f) {
+            if (rounds[f] >= 0) continue;
+            int k = 0;
+            while (k < batch && any[(size_t)k * a.n + f]) ++k;
+            if (k < batch) rounds[f] = r - batch + k + 1;           // the first quiet round of the batch: the field's last round
+            else done = false;
+        }
+        if (done) break;
+        if (r >= RF_MAX_ROUNDS) return fail(c, FS_E_HIP, "cost field did not settle in %d rounds", RF_MAX_ROUNDS);
+    }
+    for (int i = 0; i < a.n; ++i) {
+        fs_ctx::RfKey k = base;
+        k.src = a.f[i].src;
+        c->rf_key[a.f[i].slot] = k;
+        c->rf_gen[a.f[i].slot] = c->grid_gen;
+    }
+    c->rf_builds += a.n;
+    c->rf_rounds = rounds[(size_t)a.n - 1];
+    return FS_OK;
+}
+
+// Per-leg output columns in d_rf_out / h_rf_out: status | n_vertices | n_poses (int32) | cost (f64) | chain length | LOS walks (i64).
+struct RfOutLayout {
+    size_t st, nv, np, cost, chain, walks, total;
+    explicit RfOutLayout(size_t n) : st(0), nv(4 * n), np(8 * n), cost((12 * n + 7) & ~(size_t)7), chain(cost + 8 * n), walks(chain + 8 * n),
+                                     total(walks + 8 * n) {}
+};
+
+}  // namespace
+
+extern "C" {
+
+int fs_refine_field(fs_ctx *c, const double start_xy[2], int32_t allow_unknown, double w_euc, double w_traversal, int32_t corners, double *g)
+{
+    if (!c) return FS_E_INVALID;
+    if (!start_xy || !g) return fail(c, FS_E_INVALID, "null pointer");
+    int rc = rf_check(c, w_euc, w_traversal, corners);
+    if (rc) return rc;
+    int32_t sx = 0, sy = 0;
+    if (!nav_world_to_map(c, start_xy[0], start_xy[1], sx, sy)) return fail(c, FS_E_INVALID, "the start is off the costmap: no field");
+    fs_ctx::RfKey base;
+    base.allow = allow_unknown ? 1 : 0; base.corners = corners; base.w_euc = w_euc; base.w_trav = w_traversal;
+    std::vector<int32_t> slot;
+    rc = rf_fields(c, base, std::vector<int32_t>{sy * c->nx + sx}, slot);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    const size_t ns = (size_t)c->nx * (size_t)c->ny;
+    FS_HIP(c, hipMemcpyAsync(g, c->d_rf_g.p + (size_t)slot[0] * ns, sizeof(double) * ns, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    return FS_OK;
+}
+
+int fs_refine_paths(fs_ctx *c, int32_t n, const double *start_xy, const double *goal_xy, int32_t allow_unknown, double w_euc,
+                    double w_traversal, int32_t corners, int32_t *status, double *cost, int32_t *n_vertices, double *vertex_xy,
+                    int32_t *n_poses, double *pose_xy)
+{
+    if (!c) return FS_E_INVALID;
+    if (n < 0 || (n > 0 && (!start_xy || !goal_xy || !status || !cost || !n_vertices || !n_poses))) return fail(c, FS_E_INVALID, "null pointer");
+    int rc = rf_check(c, w_euc, w_traversal, corners);
+    if (rc) return rc;
+    if (n == 0) return FS_OK;
+    const size_t nn = (size_t)n;
+    const int nx = c->nx, ny = c->ny, M = c->rf_max_fields;
+    fs_ctx::RfKey base;
+    base.allow = allow_unknown ? 1 : 0; base.corners = corners; base.w_euc = w_euc; base.w_trav = w_traversal;
+    // refusals before any field (worldToMap of start, then goal), the distinct start cells in order of first appearance
+    std::vector<int32_t> pre(nn, 0), scell(nn, -1), gcell(nn, -1), fld(nn, -1), srcs;
+    std::map<int32_t, int32_t> seen;
+    for (size_t i = 0; i < nn; ++i) {
+        int32_t sx = 0, sy = 0, gx = 0, gy = 0;
+        if (!nav_world_to_map(c, start_xy[2 * i], start_xy[2 * i + 1], sx, sy)) { pre[i] = FS_REFINE_START_OFF_MAP; continue; }
+        if (!nav_world_to_map(c, goal_xy[2 * i], goal_xy[2 * i + 1], gx, gy)) { pre[i] = FS_REFINE_GOAL_OFF_MAP; continue; }
+        scell[i] = sy * nx + sx; gcell[i] = gy * nx + gx;
+        auto it = seen.find(scell[i]);
+        if (it == seen.end()) { it = seen.emplace(scell[i], (int32_t)srcs.size()).first; srcs.push_back(scell[i]); }
+        fld[i] = it->second;
+    }
+    const int n_groups = (int)((srcs.size() + M - 1) / M);
+    const RfOutLayout O(nn);
+    if (c->rf_chain_cap == 0) {
+        c->rf_chain_cap = std::max<int64_t>(4096, 4 * ((int64_t)nx + ny));
+        c->rf_vert_cap = 256;
+        c->rf_pose_cap = std::max<int32_t>(1024, 2 * (nx + ny));
+    }
+    int64_t walks = 0;
+    for (int attempt = 0; n_groups > 0; ++attempt) {
+        const int64_t ccap = c->rf_chain_cap;
+        const int32_t vcap = c->rf_vert_cap, pcap = c->rf_pose_cap;
+        const size_t pts_bytes = 16 * nn * ((size_t)vcap + (size_t)pcap);
+        // every buffer this attempt uses is sized before a pointer into any of them is taken
+        FS_HIP(c, c->h_rf_in.ensure(16 * nn)); FS_HIP(c, c->d_rf_in.ensure(4 * nn));
+        FS_HIP(c, c->d_rf_scratch.ensure(3 * nn * (size_t)ccap));
+        FS_HIP(c, c->d_rf_out.ensure(O.total)); FS_HIP(c, c->h_rf_out.ensure(O.total));
+        FS_HIP(c, c->h_rf_pts.ensure(pts_bytes));
+        const bool mapped = c->h_rf_pts.dev != nullptr;
+        if (!mapped) FS_HIP(c, c->d_rf_pts.ensure(pts_bytes));
+        double *pts = reinterpret_cast<double *>(mapped ? c->h_rf_pts.dev : c->d_rf_pts.p);
+        int32_t *in = reinterpret_cast<int32_t *>(c->h_rf_in.p);
+        FsRefineLegArgs a{};
+        a.cells = c->d_cells.p; a.nx = nx; a.ny = ny;
+        a.ox = c->origin[0]; a.oy = c->origin[1]; a.res = c->res;
+        a.allow = base.allow; a.corners = corners; a.w_euc = w_euc; a.w_trav = w_traversal;
+        rf_moves(w_euc, a.e);
+        a.chain = c->d_rf_scratch.p; a.par = a.chain + nn * (size_t)ccap; a.vtx = a.par + nn * (size_t)ccap; a.chain_cap = ccap;
+        a.vert = pts; a.vert_cap = vcap; a.pose = pts + 2 * nn * (size_t)vcap; a.pose_cap = pcap;
+        char *o = c->d_rf_out.p;
+        a.status = reinterpret_cast<int32_t *>(o + O.st); a.n_vertices = reinterpret_cast<int32_t *>(o + O.nv);
+        a.n_poses = reinterpret_cast<int32_t *>(o + O.np); a.cost = reinterpret_cast<double *>(o + O.cost);
+        a.chain_len = reinterpret_cast<int64_t *>(o + O.chain); a.walks = reinterpret_cast<int64_t *>(o + O.walks);
+        size_t nk = 0;
+        for (int grp = 0; grp < n_groups; ++grp) {
+            const size_t f0 = (size_t)grp * M, f1 = std::min(srcs.size(), f0 + M);
+            std::vector<int32_t> slot;
+            rc = rf_fields(c, base, std::vector<int32_t>(srcs.begin() + f0, srcs.begin() + f1), slot);
+            if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+            a.g = c->d_rf_g.p;                                // (the slab exists only after rf_fields: the first call allocates it)
+            const size_t k0 = nk;
+            for (size_t i = 0; i < nn; ++i) {
+                if (pre[i] || (size_t)fld[i] < f0 || (size_t)fld[i] >= f1) continue;
+                in[4 * nk] = scell[i]; in[4 * nk + 1] = gcell[i]; in[4 * nk + 2] = slot[fld[i] - f0]; in[4 * nk + 3] = (int32_t)i;
+                ++nk;
+            }
+            FS_HIP(c, hipMemcpyAsync(c->d_rf_in.p + 4 * k0, in + 4 * k0, 16 * (nk - k0), hipMemcpyHostToDevice, c->stream));
+            a.leg_in = c->d_rf_in.p + 4 * k0;
+            FS_HIP(c, fs_launch_refine_legs(a, (int32_t)(nk - k0), c->stream));
+        }
+        FS_HIP(c, hipMemcpyAsync(c->h_rf_out.p, c->d_rf_out.p, O.total, hipMemcpyDeviceToHost, c->stream));
+        if (!mapped) FS_HIP(c, hipMemcpyAsync(c->h_rf_pts.p, c->d_rf_pts.p, pts_bytes, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        const char *h = c->h_rf_out.p;
+        const int32_t *st = reinterpret_cast<const int32_t *>(h + O.st), *nv = reinterpret_cast<const int32_t *>(h + O.nv),
+                      *np = reinterpret_cast<const int32_t *>(h + O.np);
+        const int64_t *cl = reinterpret_cast<const int64_t *>(h + O.chain), *wk = reinterpret_cast<const int64_t *>(h + O.walks);
+        bool again = false;
+        walks = 0;
+        for (size_t i = 0; i < nn; ++i) {
+            if (pre[i]) continue;
+            if (st[i] == FS_REFINE_BROKEN) return fail(c, FS_E_HIP, "leg %zu: the descent left the cost field", i);
+            if (st[i] == FS_REFINE_OVERFLOW) {
+                again = true;
+                c->rf_chain_cap = std::max<int64_t>(c->rf_chain_cap, cl[i]);
+                c->rf_vert_cap = std::max(c->rf_vert_cap, nv[i]);
+                c->rf_pose_cap = std::max(c->rf_pose_cap, np[i]);
+            }
+            walks += wk[i];
+        }
+        if (!again) break;
+        if (attempt >= 3) return fail(c, FS_E_HIP, "leg scratch did not settle");
+    }
+    c->rf_walks += walks;
+    const char *h = c->h_rf_out.p;
+    const double *pts = reinterpret_cast<const double *>(c->h_rf_pts.p);
+    const size_t vcap = (size_t)c->rf_vert_cap, pcap = (size_t)c->rf_pose_cap;
+    size_t vo = 0, po = 0;
+    for (size_t i = 0; i < nn; ++i) {
+        if (pre[i]) { status[i] = pre[i]; cost[i] = std::numeric_limits<double>::max(); n_vertices[i] = 0; n_poses[i] = 0; continue; }
+        status[i] = reinterpret_cast<const int32_t *>(h + O.st)[i];
+        cost[i] = reinterpret_cast<const double *>(h + O.cost)[i];
+        n_vertices[i] = reinterpret_cast<const int32_t *>(h + O.nv)[i];
+        n_poses[i] = reinterpret_cast<const int32_t *>(h + O.np)[i];
+        if (vertex_xy && n_vertices[i]) std::memcpy(vertex_xy + 2 * vo, pts + 2 * i * vcap, 16 * (size_t)n_vertices[i]);
+        if (pose_xy && n_poses[i]) std::memcpy(pose_xy + 2 * po, pts + 2 * nn * vcap + 2 * i * pcap, 16 * (size_t)n_poses[i]);
+        vo += (size_t)n_vertices[i];
+        po += (size_t)n_poses[i];
+    }
+    return FS_OK;
 }
 
 }  // extern "C"

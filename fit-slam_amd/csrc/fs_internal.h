@@ -132,6 +132,52 @@ hipError_t fs_launch_navfn_round(const float *d_a, float *d_b, const uint8_t *d_
                                  int32_t *d_any, hipStream_t s);
 hipError_t fs_launch_navfn_paths(const FsNavfnPathArgs &a, hipStream_t s);
 
+// ---- any-angle leg refinement (fs_refine.hip): one converged fp64 cost field per start cell (all fields of a
+// call relaxed in the same launches, blockIdx.y = field), then one wave per leg: descent, Theta*'s parent rule, interpolation.
+#define RF_TILE 32
+#define RF_MAX_FIELDS 32           // the most fields one build relaxes together ("refine.max_fields" is 1..RF_MAX_FIELDS)
+// per-leg status of fs_refine_paths (include/fitslam_frontier.h); OVERFLOW / BROKEN never leave the library
+enum : int32_t {
+    FS_REFINE_OK = 0, FS_REFINE_START_OFF_MAP = 1, FS_REFINE_GOAL_OFF_MAP = 2, FS_REFINE_START_UNSAFE = 3, FS_REFINE_GOAL_UNSAFE = 4,
+    FS_REFINE_NO_PATH = 5, FS_REFINE_OVERFLOW = 100, FS_REFINE_BROKEN = 101
+};
+struct FsRefineFieldDesc {
+    int32_t slot;              // which [ny][nx] block of the field slab
+    int32_t src;               // y * nx + x of the start cell
+};
+struct FsRefineFieldArgs {
+    const uint8_t *cells;      // the staged 2-D grid
+    double *g;                 // the field slab [slots][ny][nx]
+    int32_t nx, ny, tx, ty;
+    int32_t allow, corners;
+    double w_trav;
+    double e[8];               // w_euc * sqrt(dx^2 + dy^2) of moves[]
+    int32_t n;                 // fields in this build (gridDim.y)
+    FsRefineFieldDesc f[RF_MAX_FIELDS];
+};
+struct FsRefineLegArgs {
+    const uint8_t *cells;
+    const double *g;           // the field slab
+    int32_t nx, ny;
+    double ox, oy, res;
+    int32_t allow, corners;
+    double w_euc, w_trav;
+    double e[8];
+    const int32_t *leg_in;     // [blocks][4]: start cell, goal cell, field slot, output index
+    int32_t *chain, *par, *vtx;   // [legs][chain_cap] scratch: the descent (goal first), the chain's parents, the vertex cells
+    int64_t chain_cap;
+    double *vert;              // [legs][vert_cap][2] vertex world points
+    int32_t vert_cap;
+    double *pose;              // [legs][pose_cap][2] interpolated poses
+    int32_t pose_cap;
+    int32_t *status, *n_vertices, *n_poses;   // [legs]
+    double *cost;
+    int64_t *chain_len, *walks;
+};
+hipError_t fs_launch_refine_init(const FsRefineFieldArgs &a, uint32_t *d_flags_prev, hipStream_t s);
+hipError_t fs_launch_refine_round(const FsRefineFieldArgs &a, const uint32_t *d_prev, uint32_t *d_cur, int32_t *d_any, hipStream_t s);
+hipError_t fs_launch_refine_legs(const FsRefineLegArgs &a, int32_t n_blocks, hipStream_t s);
+
 // ---- frontier roadmap (fs_roadmap.hip): FrontierRoadMap's spatial hash and roadmap_ on the device
 // FrontierRoadMap::getGridCell: floor(x / grid_cell_size), truncated to int
 __host__ __device__ inline int fs_rm_cell(double v, double cell) { return (int)floor(v / cell); }

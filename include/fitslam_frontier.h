@@ -487,6 +487,26 @@ int fs_roadmap_next_goal(fs_ctx *ctx, const double robot_pose7[7], int32_t n, co
                          int32_t *status, int32_t *tour, int32_t *tour_size, double *tour_length, int64_t *n_tied, uint8_t *selection,
                          double *pair_length_m);
 
+/* ---------------------------------------------------------------- leg refinement (computePathBetweenPointsThetaStar) */
+/* The path the robot drives: computePathBetweenPointsThetaStar (DEP/src/Helpers.cpp:540-588; FullPathOptimizer::refineAndPublishPath
+ * and getNextGoal's per-leg plans) for n legs on the staged 2-D grid.  start_xy, goal_xy [n][2] world.  Parameters as the reference's
+ * ThetaStar: allow_unknown, w_euc (> 0; the reference's 1), w_traversal (>= 0; 2), corners (4 or 8: a prefix of moves[]; 8).
+ * Restated as data-parallel work: one converged fp64 cost field per distinct start cell — kept per context for
+ * (grid, start cell, allow_unknown, weights, corners) until fs_upload_grid, fs_upload_grid_bricks or fs_update_grid_region —, the
+ * descent from the goal in moves[] order, Theta*'s resetParent rule along the descent with line-of-sight sums taken as exact integers.
+ * Outputs [n]: status (0 path, 1 start off the map, 2 goal off the map, 3 start unsafe, 4 goal unsafe, 5 no path), cost (the goal's
+ * g; DBL_MAX without a path), n_vertices, n_poses (0 without a path).  vertex_xy [sum n_vertices][2]: the any-angle vertices of each
+ * leg, start first, goal last, at cell centres; pose_xy [sum n_poses][2]: ThetaStar::backtrace + linearInterpolation at the costmap
+ * resolution, the published poses; legs back to back in input order.  Either may be NULL: call first with both NULL for the counts.
+ * A bad leg does not fail the call; nz > 1: FS_E_INVALID.  One synchronisation, plus the round polling of fields not cached. */
+int fs_refine_paths(fs_ctx *ctx, int32_t n, const double *start_xy, const double *goal_xy, int32_t allow_unknown, double w_euc,
+                    double w_traversal, int32_t corners, int32_t *status, double *cost, int32_t *n_vertices, double *vertex_xy,
+                    int32_t *n_poses, double *pose_xy);
+/* the cost field fs_refine_paths descends from start_xy, [ny][nx] double (DBL_MAX where not reached; everywhere for an unsafe start):
+ * for tests and visualisation.  Start off the map: FS_E_INVALID */
+int fs_refine_field(fs_ctx *ctx, const double start_xy[2], int32_t allow_unknown, double w_euc, double w_traversal, int32_t corners,
+                    double *g);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,7 +63,9 @@ int  fs_kernel_time(fs_ctx *ctx, int kind, double *total_ms, int64_t *launches);
  * cloud takes 0.06 ms on the host, 0.18 ms on the device).  Same split rule; tied coordinates may land in different leaves, so the
  * last bits of the float columns differ between the two (the order of summation); integers never do.  Set before the upload.
  * "fim.specialise" (default 1): 0 = always the general FIM worker (no INFO_ONLY / YAW_ONLY instantiation; identical integers,
- * float sums to the last bits) — the A/B switch of tests/test_gpu_reference_visibility.py. */
+ * float sums to the last bits) — the A/B switch of tests/test_gpu_reference_visibility.py.
+ * "refine.max_fields" (default 16, 1..32): how many cost fields fs_refine_paths relaxes together and keeps cached (8 B per cell per
+ * field); a call with more distinct starts runs its legs group by group (identical results). */
 int  fs_set_option(fs_ctx *ctx, const char *key, double value);
 /* Device-side counters: 0 = landmark visibility tests performed (M_tested summed over candidates),
  * 4 = candidates scored in several voxel-partitioned passes, 5 = candidates re-scored with the table in HBM,
@@ -73,7 +75,9 @@ int  fs_set_option(fs_ctx *ctx, const char *key, double value);
  * cone-off and info-only workers); 10 / 11 = landmark tests / candidates since the last spatially sorted call (the sort's own
  * accumulators: CLEARED by every call of 2048 candidates or more — not running totals).  Host-side: 1000 / 1001 = bricks of the grid / bricks in the pool of "ray.layout" 3;
  * 1002 = potential fields the grid planner built (fs_plan_paths: a call that reuses the cached field adds nothing), 1003 = rounds
- * of the last field built, 1004 = field rounds launched in all (1002 and 1004 are reset by `reset`). */
+ * of the last field built, 1004 = field rounds launched in all (1002 and 1004 are reset by `reset`); 1011 = cost fields the leg
+ * refinement built (fs_refine_paths / fs_refine_field: a cached field adds nothing), 1012 = rounds of the last field built,
+ * 1013 = line-of-sight walks of the legs (1011 and 1013 are reset by `reset`). */
 int  fs_get_counter(fs_ctx *ctx, int which, int64_t *value, int reset);
 
 /* ---------------------------------------------------------------- self test */

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "fs_plan_paths", "fs_navfn_potential", "fs_get_frontier_costs_planned",
     "fs_set_roadmap_params", "fs_roadmap_add_nodes", "fs_roadmap_rebuild", "fs_roadmap_connect", "fs_roadmap_get_graph", "fs_roadmap_plan",
     "fs_get_frontier_costs_roadmap", "fs_roadmap_next_goal", "fs_refine_paths", "fs_refine_field",
+    "fs_search_frontiers", "fs_get_frontier_costs_searched",
 ]
 
 RECORD_DTYPE = np.dtype([("arrival", "<i4"), ("argmax", "<i4"), ("yaw", "<f4"), ("info_ref", "<f4"),
@@ -54,6 +55,12 @@ class FrontierClusterC(C.Structure):
 CLUSTER_DTYPE = np.dtype([("label", "<i4"), ("size", "<i4"), ("centroid_x", "<f8"), ("centroid_y", "<f8"),
                           ("min_x", "<i4"), ("min_y", "<i4"), ("max_x", "<i4"), ("max_y", "<i4")])
 assert CLUSTER_DTYPE.itemsize == C.sizeof(FrontierClusterC) == 40
+
+
+# fs_frontier_record: one Frontier record of fs_search_frontiers
+FRONTIER_RECORD_DTYPE = np.dtype([("goal_x", "<f8"), ("goal_y", "<f8"), ("size", "<i4"), ("label", "<i4"),
+                                  ("goal_cell", "<i4"), ("seed_cell", "<i4")])
+assert FRONTIER_RECORD_DTYPE.itemsize == 32
 
 
 class RayParamsC(C.Structure):
@@ -167,6 +174,9 @@ def load_library(build: bool = True):
                                        C.POINTER(i32), C.POINTER(i32), vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(i64), vp, vp]
     L.fs_refine_paths.argtypes = [vp, i32, vp, vp, i32, dbl, dbl, i32, vp, vp, vp, vp, vp, vp]
     L.fs_refine_field.argtypes = [vp, C.POINTER(dbl * 2), i32, dbl, dbl, i32, vp]
+    L.fs_search_frontiers.argtypes = [vp, C.POINTER(dbl * 2), i32, dbl, i32, i32, i32, vp, i32, vp, C.POINTER(i32), i64, vp, C.POINTER(i64)]
+    L.fs_get_frontier_costs_searched.argtypes = [vp, C.POINTER(dbl * 7), i32, dbl, i32, i32, i32, i32, vp, dbl, dbl, dbl, dbl, C.c_int,
+                                                 i32, vp, C.POINTER(i32), vp, vp, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         f = getattr(L, name)
         if name not in ("fs_ctx_destroy", "fs_last_error", "fs_multi_destroy", "fs_multi_last_error", "fs_multi_ctx"):
@@ -306,6 +316,73 @@ class FrontierScorer:
                                                  int(max_frontier_cluster_size), _p(labels), int(max_clusters), _p(cl),
                                                  C.byref(n), C.byref(cells)))
         return labels, cl[:min(n.value, max_clusters)].copy(), n.value, cells.value
+
+    # first-round output capacity of the search calls when the caller gives none: frontier lists are far shorter than the grid, so
+    # a longer one costs a second call with exact sizes instead of nx * ny zeroed records every time
+    SEARCH_FIRST_RECORDS, SEARCH_FIRST_CELLS = 4096, 65536
+
+    def search_frontiers(self, robot_xy, lethal_threshold=160, max_frontier_distance=50.0, min_frontier_cluster_size=1,
+                         max_frontier_cluster_size=20, seeds=None, max_records=None, want_every=True):
+        """FrontierSearch::searchFrom on the device, pieces and goal points included (fs_search_frontiers): returns (frontiers
+        (FRONTIER_RECORD_DTYPE, output order), every_xy [n_cells][2] or None).  seeds None: Nearest seeds; else the cells
+        (y * nx + x) that start one buildNewFrontier each, in order.  max_records None: every record (the buffers grow to what
+        the search reports, at most the grid's cell count); else at most that many (last_search_counts has the full counts)."""
+        _, ny, nx = self._staged_shape()
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
+        xy = (C.c_double * 2)(float(robot_xy[0]), float(robot_xy[1]))
+        cap = min(nx * ny, self.SEARCH_FIRST_RECORDS) if max_records is None else int(max_records)
+        ecap = min(nx * ny, self.SEARCH_FIRST_CELLS) if want_every else 0
+        while True:
+            rec = np.zeros(max(cap, 0), dtype=FRONTIER_RECORD_DTYPE)
+            every = np.zeros((ecap, 2)) if want_every else None
+            n, cells = C.c_int32(), C.c_int64()
+            self._check(self._L.fs_search_frontiers(self._h, C.byref(xy), int(lethal_threshold), float(max_frontier_distance),
+                                                    int(min_frontier_cluster_size), int(max_frontier_cluster_size),
+                                                    0 if sd is None else sd.shape[0], _p(sd), cap, _p(rec), C.byref(n),
+                                                    ecap, _p(every), C.byref(cells)))
+            grow = (max_records is None and n.value > cap) or (want_every and cells.value > ecap)
+            if not grow:
+                break
+            cap = max(cap, n.value) if max_records is None else cap
+            ecap = max(ecap, cells.value) if want_every else 0
+        self.last_search_counts = (n.value, cells.value)
+        return rec[:min(n.value, cap)].copy(), None if every is None else every[:cells.value].copy()
+
+    def get_frontier_costs_searched(self, robot_pose7, lethal_threshold=160, max_frontier_distance=50.0, min_frontier_cluster_size=1,
+                                    max_frontier_cluster_size=20, blacklist_xy=None, allow_unknown=False, with_fim=False, alpha=0.25,
+                                    beta=1.0, max_vx=0.5, max_wz=0.5, max_records=None):
+        """searchFrom -> plan -> score -> rank in one call (fs_get_frontier_costs_searched): returns (frontiers, the dict
+        get_frontier_costs_planned returns).  blacklist_xy [k][2]: goal points to mark blacklisted (exact equality).
+        max_records None: as many as the search finds (a longer list than the first round holds is searched again with exact
+        sizes); else more records than that raise FsError."""
+        _, ny, nx = self._staged_shape()
+        cap = min(nx * ny, self.SEARCH_FIRST_RECORDS) if max_records is None else int(max_records)
+        pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
+        bl = None if blacklist_xy is None else np.ascontiguousarray(np.asarray(blacklist_xy, dtype=np.float64).reshape(-1, 2))
+        while True:
+            fr = np.zeros(max(cap, 0), dtype=FRONTIER_RECORD_DTYPE)
+            rec = np.zeros(max(cap, 0), dtype=RECORD_DTYPE)
+            cost = np.zeros(max(cap, 0)); au = np.zeros(max(cap, 0)); du = np.zeros(max(cap, 0))
+            order = np.zeros(max(cap, 0), dtype=np.int32); plm = np.zeros(max(cap, 0))
+            n = C.c_int32()
+            rc = self._L.fs_get_frontier_costs_searched(self._h, C.byref(pose), int(lethal_threshold), float(max_frontier_distance),
+                                                        int(min_frontier_cluster_size), int(max_frontier_cluster_size), 1 if allow_unknown else 0,
+                                                        0 if bl is None else bl.shape[0], _p(bl), alpha, beta, max_vx, max_wz,
+                                                        1 if with_fim else 0, cap, _p(fr), C.byref(n), _p(rec), _p(cost), _p(au), _p(du),
+                                                        _p(order), _p(plm))
+            if rc == FS_E_INVALID and max_records is None and n.value > cap:
+                cap = n.value
+                continue
+            self._check(rc)
+            break
+        k = n.value
+        return fr[:k].copy(), dict(records=rec[:k].copy(), weighted_cost=cost[:k].copy(), arrival_utility=au[:k].copy(),
+                                   distance_utility=du[:k].copy(), order=order[:k].copy(), path_length_m=plm[:k].copy())
+
+    def _staged_shape(self):
+        if self._grid_shape is None:
+            raise FsError(FS_E_STATE, "no grid staged (upload_grid)")
+        return self._grid_shape
 
     def max_arrival(self):
         a, b, c = C.c_double(), C.c_double(), C.c_double()

@@ -3,6 +3,7 @@
 // table) and the launch sequences.  No CPU compute fallback exists: every scoring entry point
 // launches the HIP kernels of fs_raymarch.hip / fs_fim.hip / fs_rank.hip or fails.
 #include "fs_internal.h"
+#include "fs_median_sort.h"
 
 #include <algorithm>
 #include <atomic>
@@ -261,6 +262,15 @@ struct fs_ctx {
     DevBuf<uint8_t> d_fc_visited;
     DevBuf<fs_frontier_cluster> d_fc_clusters;
     DevBuf<long long> d_fc_sums;
+    // fs_search_frontiers (fs_search.hip)
+    DevBuf<int32_t> d_fs_bcount, d_fs_cidx, d_fs_root, d_fs_best_idx, d_fs_csize, d_fs_owner, d_fs_key, d_fs_pos, d_fs_q, d_fs_state, d_fs_seeds;
+    DevBuf<int32_t> d_fs_emit_comp, d_fs_emit_seed, d_fs_emit_base, d_fs_rec_base, d_fs_fsize;
+    DevBuf<unsigned long long> d_fs_best_d2;
+    DevBuf<fs_msort_elem> d_fs_sort;
+    DevBuf<fs_frontier_record> d_fs_rec;
+    DevBuf<double> d_fs_every, d_fs_goal, d_fs_black_xy;
+    DevBuf<uint8_t> d_fs_black;
+    int64_t fs_levels = 0, fs_guarded = 0;      // counters 1014 / 1015 of the last search
     // "cloud.order": where the landmark cloud is put into its k-d leaf order — 0 on the host, 2 on the device (fs_cloud.hip), 1 (default)
     // on the device from FS_CLOUD_DEVICE_FROM landmarks on: fs_upload_landmarks 1.2 ms at C3's 100 k landmarks, 4.4 ms at 500 k on the
     // device (the host form: 4.4 / 20.2 ms with its top levels on threads of their own, 13.3 / 78.9 ms on one thread —
@@ -916,6 +926,11 @@ void fs_ctx_destroy(fs_ctx *c)
     c->d_seg_all.release(); c->d_brick_xyz.release(); c->d_bad.release(); c->d_count.release();
     c->d_fc_parent_t.release(); c->d_fc_parent_f.release(); c->d_fc_aux.release(); c->d_fc_state.release(); c->d_fc_labels.release();
     c->d_fc_queue.release(); c->d_fc_visited.release(); c->d_fc_clusters.release(); c->d_fc_sums.release();
+    c->d_fs_bcount.release(); c->d_fs_cidx.release(); c->d_fs_root.release(); c->d_fs_best_idx.release(); c->d_fs_csize.release();
+    c->d_fs_owner.release(); c->d_fs_key.release(); c->d_fs_pos.release(); c->d_fs_q.release(); c->d_fs_state.release(); c->d_fs_seeds.release();
+    c->d_fs_emit_comp.release(); c->d_fs_emit_seed.release(); c->d_fs_emit_base.release(); c->d_fs_rec_base.release(); c->d_fs_fsize.release();
+    c->d_fs_best_d2.release(); c->d_fs_sort.release(); c->d_fs_rec.release(); c->d_fs_every.release();
+    c->d_fs_goal.release(); c->d_fs_black_xy.release(); c->d_fs_black.release();
     c->d_nav_cost.release(); c->d_nav_pot.release(); c->d_nav_flags.release(); c->d_nav_any.release(); c->d_nav_path.release();
     c->d_nav_in.release(); c->d_nav_out.release(); c->h_nav_in.release(); c->h_nav_out.release();
     c->d_rm_xy.release(); c->d_rm_d.release(); c->d_rm_key.release(); c->d_rm_cell_key.release(); c->d_rm_row.release(); c->d_rm_col.release();
@@ -1255,6 +1270,142 @@ int fs_frontier_clusters(fs_ctx *c, const double robot_xy[2], int32_t lethal_thr
     if (n_cells) *n_cells = state[6];
     if (c->d_fc_labels.cap * sizeof(int32_t) > ((size_t)64 << 20)) c->d_fc_labels.release();   // (same rule as the stencil mask and the brick list)
     return FS_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// fs_search_frontiers up to its results: fs_frontier_clusters' kernels (no cluster records, no labels), then fs_search.hip's stage.
+// Not synchronised.  *on_map = false: the robot is off the map and nothing was enqueued.  want_cols: the scoring calls' goal
+// [records][3] and size [records] columns are written too (d_fs_goal, d_fs_fsize); *args_out: the stage's arguments.
+int search_enqueue(fs_ctx *c, const double robot_xy[2], int32_t lethal_threshold, double max_frontier_distance, int32_t min_size,
+                   int32_t max_size, int32_t n_seeds, const int32_t *seeds, bool want_every, bool *on_map_out,
+                   bool want_cols = false, FsSearchArgs *args_out = nullptr)
+{
+    *on_map_out = false;
+    if (!robot_xy) return fail(c, FS_E_INVALID, "null robot position");
+    if (min_size < 0 || max_size < 1) return fail(c, FS_E_INVALID, "min_frontier_cluster_size >= 0 and max_frontier_cluster_size >= 1");
+    if (seeds && n_seeds < 0) return fail(c, FS_E_INVALID, "n_seeds < 0");
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (c->nz != 1) return fail(c, FS_E_INVALID, "the frontier search is defined on a 2-D costmap (nz == 1)");
+    const size_t cells = (size_t)c->nx * c->ny;
+    if (seeds) {
+        if ((size_t)n_seeds > cells) return fail(c, FS_E_INVALID, "more seeds than cells");
+        for (int32_t k = 0; k < n_seeds; ++k)
+            if (seeds[k] < 0 || (size_t)seeds[k] >= cells) return fail(c, FS_E_INVALID, "seed %d: cell %d is off the map", k, seeds[k]);
+    }
+    // :26-33 — worldToMap of the robot position (as fs_frontier_clusters)
+    const double px = robot_xy[0], py = robot_xy[1];
+    bool on_map = !(px < c->origin[0] || py < c->origin[1]);
+    unsigned int mx = 0, my = 0;
+    if (on_map) {
+        const double qx = (px - c->origin[0]) / c->res, qy = (py - c->origin[1]) / c->res;
+        on_map = qx < 4294967296.0 && qy < 4294967296.0;
+        if (on_map) {
+            mx = static_cast<unsigned int>(qx); my = static_cast<unsigned int>(qy);
+            on_map = mx < (unsigned int)c->nx && my < (unsigned int)c->ny;
+        }
+    }
+    if (!on_map) return FS_OK;
+    const size_t nb = (cells + 1023) / 1024, ne = std::max(cells, (size_t)(seeds ? n_seeds : 0)) + 1;
+    FS_HIP(c, c->d_fc_parent_t.ensure(cells)); FS_HIP(c, c->d_fc_parent_f.ensure(cells)); FS_HIP(c, c->d_fc_aux.ensure(cells));
+    FS_HIP(c, c->d_fc_queue.ensure(cells)); FS_HIP(c, c->d_fc_visited.ensure(cells)); FS_HIP(c, c->d_fc_state.ensure(8));
+    FS_HIP(c, c->d_fc_clusters.ensure(1)); FS_HIP(c, c->d_fc_sums.ensure(2));
+    FS_HIP(c, c->d_fs_bcount.ensure(nb + 1)); FS_HIP(c, c->d_fs_cidx.ensure(cells)); FS_HIP(c, c->d_fs_root.ensure(cells));
+    FS_HIP(c, c->d_fs_best_idx.ensure(cells)); FS_HIP(c, c->d_fs_csize.ensure(cells)); FS_HIP(c, c->d_fs_owner.ensure(cells));
+    FS_HIP(c, c->d_fs_key.ensure(cells)); FS_HIP(c, c->d_fs_pos.ensure(cells)); FS_HIP(c, c->d_fs_q.ensure(cells));
+    FS_HIP(c, c->d_fs_state.ensure(16)); FS_HIP(c, c->d_fs_best_d2.ensure(cells));
+    FS_HIP(c, c->d_fs_emit_comp.ensure(ne)); FS_HIP(c, c->d_fs_emit_seed.ensure(ne)); FS_HIP(c, c->d_fs_emit_base.ensure(ne));
+    FS_HIP(c, c->d_fs_rec_base.ensure(ne)); FS_HIP(c, c->d_fs_sort.ensure(cells)); FS_HIP(c, c->d_fs_rec.ensure(cells));
+    if (want_every) FS_HIP(c, c->d_fs_every.ensure(2 * cells));
+    if (want_cols) { FS_HIP(c, c->d_fs_goal.ensure(3 * cells)); FS_HIP(c, c->d_fs_fsize.ensure(cells)); }
+    if (seeds && n_seeds > 0) {
+        FS_HIP(c, c->d_fs_seeds.ensure((size_t)n_seeds));
+        FS_HIP(c, hipMemcpyAsync(c->d_fs_seeds.p, seeds, sizeof(int32_t) * (size_t)n_seeds, hipMemcpyHostToDevice, c->stream));
+    }
+    FS_HIP(c, hipMemsetAsync(c->d_fs_state.p, 0, 16 * sizeof(int32_t), c->stream));
+    const double reach = max_frontier_distance + (max_size * c->res * 1.414);      // :67
+    {
+        ScopedTimer t(c, 5);
+        FS_HIP(c, fs_launch_frontier_clusters(c->d_cells.p, c->nx, c->ny, c->origin[0], c->origin[1], c->res, px, py,
+                                              (int32_t)(my * (unsigned int)c->nx + mx), reach, lethal_threshold,
+                                              c->d_fc_parent_t.p, c->d_fc_parent_f.p, c->d_fc_aux.p, c->d_fc_queue.p, c->d_fc_visited.p,
+                                              c->d_fc_state.p, nullptr, 0, c->d_fc_clusters.p, c->d_fc_sums.p, c->stream));
+    }
+    FsSearchArgs a{};
+    a.parent_f = c->d_fc_parent_f.p; a.aux = c->d_fc_aux.p;
+    a.nx = c->nx; a.ny = c->ny; a.ox = c->origin[0]; a.oy = c->origin[1]; a.res = c->res;
+    a.robot_cell = (int32_t)(my * (unsigned int)c->nx + mx);
+    // a component has at most nx * ny cells, so every max_size >= nx * ny cuts exactly as nx * ny does (and max + 1 cannot wrap)
+    a.min_size = min_size; a.max_size = (int32_t)std::min<int64_t>(max_size, (int64_t)cells);
+    a.n_seeds = seeds ? n_seeds : -1; a.seeds = c->d_fs_seeds.p;
+    a.bcount = c->d_fs_bcount.p; a.cidx = c->d_fs_cidx.p; a.comp_root = c->d_fs_root.p; a.best_idx = c->d_fs_best_idx.p;
+    a.csize = c->d_fs_csize.p; a.owner = c->d_fs_owner.p; a.best_d2 = c->d_fs_best_d2.p;
+    a.emit_comp = c->d_fs_emit_comp.p; a.emit_seed = c->d_fs_emit_seed.p; a.emit_base = c->d_fs_emit_base.p; a.rec_base = c->d_fs_rec_base.p;
+    a.key = c->d_fs_key.p; a.pos = c->d_fs_pos.p; a.q = c->d_fs_q.p; a.sortbuf = c->d_fs_sort.p; a.rec = c->d_fs_rec.p;
+    a.goal_xyz = want_cols ? c->d_fs_goal.p : nullptr; a.fsize = want_cols ? c->d_fs_fsize.p : nullptr;
+    a.every = want_every ? c->d_fs_every.p : nullptr;
+    a.state = c->d_fs_state.p;
+    {
+        ScopedTimer t(c, 9);
+        FS_HIP(c, fs_launch_frontier_search(a, c->stream));
+    }
+    if (args_out) *args_out = a;
+    *on_map_out = true;
+    return FS_OK;
+}
+
+// the search's results: the counts and the first records in one round trip; more records than the first round holds, and the
+// every list, in a second.  *n_records / *n_cells are what was found.
+int search_results(fs_ctx *c, int32_t max_records, fs_frontier_record *records, int32_t *n_records, int64_t max_every, double *every_xy,
+                   int64_t *n_cells)
+{
+    const size_t first = (size_t)std::min<int32_t>(max_records, 1024);
+    const size_t o_rec = 64;
+    FS_HIP(c, c->h_out.ensure(o_rec + first * sizeof(fs_frontier_record)));
+    FS_HIP(c, hipMemcpyAsync(c->h_out.p, c->d_fs_state.p, 16 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (first) FS_HIP(c, hipMemcpyAsync(c->h_out.p + o_rec, c->d_fs_rec.p, first * sizeof(fs_frontier_record), hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    int32_t state[16];
+    std::memcpy(state, c->h_out.p, sizeof state);
+    c->fs_levels = state[FSS_LEVELS];
+    c->fs_guarded = state[FSS_GUARDED];
+    if (state[FSS_ERROR]) return fail(c, FS_E_INVALID, "a seed is not a frontier cell the search found, or two seeds share a component");
+    const int32_t n = state[FSS_RECORDS], stored = std::min(n, max_records);
+    if (stored > 0) {
+        std::memcpy(records, c->h_out.p + o_rec, sizeof(fs_frontier_record) * std::min<size_t>((size_t)stored, first));
+        if ((size_t)stored > first)
+            FS_HIP(c, hipMemcpyAsync(records + first, c->d_fs_rec.p + first, sizeof(fs_frontier_record) * ((size_t)stored - first), hipMemcpyDeviceToHost, c->stream));
+    }
+    const int64_t every = std::min<int64_t>(state[FSS_CELLS], max_every);
+    if (every_xy && every > 0) FS_HIP(c, hipMemcpyAsync(every_xy, c->d_fs_every.p, 2 * sizeof(double) * (size_t)every, hipMemcpyDeviceToHost, c->stream));
+    if ((size_t)stored > first || (every_xy && every > 0)) FS_HIP(c, hipStreamSynchronize(c->stream));
+    *n_records = n;
+    if (n_cells) *n_cells = state[FSS_CELLS];
+    return FS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fs_search_frontiers(fs_ctx *c, const double robot_xy[2], int32_t lethal_threshold, double max_frontier_distance,
+                        int32_t min_frontier_cluster_size, int32_t max_frontier_cluster_size, int32_t n_seeds, const int32_t *seeds,
+                        int32_t max_records, fs_frontier_record *records, int32_t *n_records,
+                        int64_t max_every, double *every_xy, int64_t *n_cells)
+{
+    if (!c) return FS_E_INVALID;
+    if (!n_records || max_records < 0 || (max_records > 0 && !records) || max_every < 0) return fail(c, FS_E_INVALID, "null pointer or negative capacity");
+    *n_records = 0;
+    if (n_cells) *n_cells = 0;
+    bool on_map = false;
+    const int rc = search_enqueue(c, robot_xy, lethal_threshold, max_frontier_distance, min_frontier_cluster_size, max_frontier_cluster_size,
+                                  n_seeds, seeds, every_xy != nullptr && max_every > 0, &on_map);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (!on_map) return FS_OK;
+    return search_results(c, max_records, records, n_records, max_every, every_xy, n_cells);
 }
 
 int fs_set_arrival_limits(fs_ctx *c, double max_gt, double min_gt)
@@ -1763,6 +1914,9 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
         if (reset && which != 1012) v = 0;
         return FS_OK;
     }
+    // ... of the frontier search (fs_search_frontiers): 1014 breadth-first levels of the last search's deepest component, 1015 its
+    // pieces whose median sort the guard stopped
+    if (c && value && (which == 1014 || which == 1015)) { *value = which == 1014 ? c->fs_levels : c->fs_guarded; return FS_OK; }
     if (!c || !value || which < 0 || which >= FS_N_COUNTERS) return FS_E_INVALID;
     FS_HIP(c, hipSetDevice(c->device));
     *value = 0;
@@ -2366,13 +2520,21 @@ struct PlannedCols {
     const uint8_t *achievable;
     const double *path_length, *path_heading;
 };
+// `dev`: the goal, size and blacklist columns lie in device memory as well (fs_get_frontier_costs_searched: the search wrote them);
+// goal_xyz / frontier_size / blacklisted are then ignored and nothing is staged through the host.  Only with `planned`.
+struct DevCols {
+    const double *goal_xyz;
+    const int32_t *frontier_size;
+    const uint8_t *blacklisted;
+};
 
 int frontier_costs_core(fs_ctx *c, int32_t n, const double *goal_xyz, const int32_t *frontier_size, const uint8_t *blacklisted,
                         const uint8_t *achievable_in, const double *path_length, const double *path_heading,
                         double alpha, double beta, double max_vx, double max_wz, bool with_fim,
                         fs_record *records, double *weighted_cost, double *arrival_utility, double *distance_utility, int32_t *order,
-                        const PlannedCols *planned = nullptr)
+                        const PlannedCols *planned = nullptr, const DevCols *dev = nullptr)
 {
+    if (dev && !planned) return fail(c, FS_E_INVALID, "device-resident candidate columns need the planner's columns");
     FS_HIP(c, hipSetDevice(c->device));
     int rc = check_scoring_state(c, true, with_fim);
     if (rc) return rc;
@@ -2389,11 +2551,13 @@ int frontier_costs_core(fs_ctx *c, int32_t n, const double *goal_xyz, const int3
     FS_HIP(c, c->h_in.ensure(total_in)); FS_HIP(c, c->d_in.ensure(total_in));
     FS_HIP(c, c->h_out.ensure(total_out)); FS_HIP(c, c->d_out.ensure(total_out));
     char *h = c->h_in.p;
-    std::memcpy(h + i_goal, goal_xyz, 24 * nn);
-    if (rank && !planned) { std::memcpy(h + i_len, path_length, 8 * nn); std::memcpy(h + i_head, path_heading, 8 * nn); }
-    if (frontier_size) std::memcpy(h + i_fsize, frontier_size, 4 * nn); else std::memset(h + i_fsize, 0, 4 * nn);
-    if (blacklisted) std::memcpy(h + i_black, blacklisted, nn); else std::memset(h + i_black, 0, nn);
-    if (achievable_in) std::memcpy(h + i_achin, achievable_in, nn); else std::memset(h + i_achin, 1, nn);
+    if (!dev) {                                                 // (with dev the columns never visit the host)
+        std::memcpy(h + i_goal, goal_xyz, 24 * nn);
+        if (rank && !planned) { std::memcpy(h + i_len, path_length, 8 * nn); std::memcpy(h + i_head, path_heading, 8 * nn); }
+        if (frontier_size) std::memcpy(h + i_fsize, frontier_size, 4 * nn); else std::memset(h + i_fsize, 0, 4 * nn);
+        if (blacklisted) std::memcpy(h + i_black, blacklisted, nn); else std::memset(h + i_black, 0, nn);
+        if (achievable_in) std::memcpy(h + i_achin, achievable_in, nn); else std::memset(h + i_achin, 1, nn);
+    }
     if (cap > n) {                                              // the dummies: blacklisted, at the origin, nothing else
         std::memset(h + i_goal + 24 * nn, 0, 24 * (cc - nn));
         if (rank) { std::memset(h + i_len + 8 * nn, 0, 8 * (cc - nn)); std::memset(h + i_head + 8 * nn, 0, 8 * (cc - nn)); }
@@ -2405,12 +2569,13 @@ int frontier_costs_core(fs_ctx *c, int32_t n, const double *goal_xyz, const int3
     const bool in_place = c->opt_zero_copy && cap <= FS_ZERO_COPY_MAX_N && c->h_in.dev && c->h_out.dev;
     char *din = in_place ? c->h_in.dev : c->d_in.p, *dout = in_place ? c->h_out.dev : c->d_out.p;
     auto enqueue = [&]() -> int {
-        if (!in_place) FS_HIP(c, hipMemcpyAsync(din, c->h_in.p, total_in, hipMemcpyHostToDevice, c->stream));
+        if (!in_place && !dev) FS_HIP(c, hipMemcpyAsync(din, c->h_in.p, total_in, hipMemcpyHostToDevice, c->stream));
         const double *d_goal = reinterpret_cast<const double *>(din + i_goal);
         const int32_t *d_fsize = reinterpret_cast<const int32_t *>(din + i_fsize);
         const uint8_t *d_black = reinterpret_cast<const uint8_t *>(din + i_black), *d_achin = reinterpret_cast<const uint8_t *>(din + i_achin);
         const double *d_len = reinterpret_cast<const double *>(din + i_len), *d_head = reinterpret_cast<const double *>(din + i_head);
         if (planned) { d_achin = planned->achievable; d_len = planned->path_length; d_head = planned->path_heading; }
+        if (dev) { d_goal = dev->goal_xyz; d_fsize = dev->frontier_size; d_black = dev->blacklisted; }
         fs_record *d_rec = reinterpret_cast<fs_record *>(dout + o_rec);
         int r = with_fim ? fs_score_candidates_dev(c, cap, d_goal, d_fsize, d_black, d_achin, d_rec)
                          : arrival_records_dev(c, cap, d_goal, d_fsize, d_black, d_achin, d_rec);
@@ -2852,6 +3017,42 @@ int navfn_plan_enqueue(fs_ctx *c, const double robot7[7], int32_t allow, int32_t
     return FS_OK;
 }
 
+// navfn_plan_enqueue for goal points that lie in device memory (fs_get_frontier_costs_searched: the search wrote them): the goal
+// cells are computed on the device; only the headings come from the host, where setPlanForFrontier's heading is defined with the
+// host's libm (h_heading [n], used where a plan succeeds).  Every goal is planned (no achievable_in).  Not synchronised.
+int navfn_plan_enqueue_dev(fs_ctx *c, const double robot7[7], int32_t allow, int32_t n, const double *d_goal_xyz, const double *h_heading)
+{
+    const size_t nn = (size_t)n;
+    const int32_t max_cycles = 4 * std::max(c->nx, c->ny);      // CostCalculator.cpp:284
+    const size_t i_cell = 0, i_head = (4 * nn + 7) & ~(size_t)7, total_in = i_head + 8 * nn;
+    const NavOutLayout O(nn);
+    FS_HIP(c, c->h_nav_in.ensure(total_in)); FS_HIP(c, c->d_nav_in.ensure(total_in));
+    FS_HIP(c, c->d_nav_out.ensure(O.total));
+    FS_HIP(c, c->d_nav_path.ensure(nn * 2 * (size_t)max_cycles));
+    int32_t rx = 0, ry = 0;
+    const bool robot_on = nav_world_to_map(c, robot7[0], robot7[1], rx, ry);
+    const float *field = nullptr;
+    if (robot_on && n > 0) { const int rc = navfn_field(c, rx, ry, allow, &field); if (rc) return rc; }
+    std::memcpy(c->h_nav_in.p + i_head, h_heading, 8 * nn);
+    FS_HIP(c, hipMemcpyAsync(c->d_nav_in.p + i_head, c->h_nav_in.p + i_head, 8 * nn, hipMemcpyHostToDevice, c->stream));
+    int32_t *d_cell = reinterpret_cast<int32_t *>(c->d_nav_in.p + i_cell);
+    FS_HIP(c, fs_launch_goal_cells(d_goal_xyz, n, c->nx, c->ny, c->origin[0], c->origin[1], c->res, robot_on ? 1 : 0, d_cell, c->stream));
+    FsNavfnPathArgs a{};
+    a.pot = field; a.nx = c->nx; a.ny = c->ny; a.n = n;
+    a.goal_cell = d_cell;
+    a.heading_in = reinterpret_cast<const double *>(c->d_nav_in.p + i_head);
+    a.robot_x = rx; a.robot_y = ry; a.max_cycles = max_cycles;
+    a.scratch = c->d_nav_path.p;
+    a.ox = c->origin[0]; a.oy = c->origin[1]; a.res = c->res;
+    a.path_length = reinterpret_cast<double *>(c->d_nav_out.p + O.len);
+    a.path_length_m = reinterpret_cast<double *>(c->d_nav_out.p + O.len_m);
+    a.path_heading = reinterpret_cast<double *>(c->d_nav_out.p + O.head);
+    a.achievable = reinterpret_cast<uint8_t *>(c->d_nav_out.p + O.ach);
+    ScopedTimer t(c, 8);
+    FS_HIP(c, fs_launch_navfn_paths(a, c->stream));
+    return FS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2924,6 +3125,72 @@ int fs_get_frontier_costs_planned(fs_ctx *c, const double robot_pose7[7], int32_
         return rc;
     }
     if (path_length_m) std::memcpy(path_length_m, c->h_nav_out.p + O.len_m, 8 * nn);
+    return FS_OK;
+}
+
+int fs_get_frontier_costs_searched(fs_ctx *c, const double robot_pose7[7], int32_t lethal_threshold, double max_frontier_distance,
+                                   int32_t min_frontier_cluster_size, int32_t max_frontier_cluster_size, int32_t allow_unknown,
+                                   int32_t n_blacklist, const double *blacklist_xy, double alpha, double beta, double max_vx, double max_wz,
+                                   int with_fisher_information, int32_t max_records, fs_frontier_record *frontiers, int32_t *n_frontiers,
+                                   fs_record *records, double *weighted_cost, double *arrival_utility, double *distance_utility,
+                                   int32_t *order, double *path_length_m)
+{
+    if (!c) return FS_E_INVALID;
+    if (!robot_pose7 || !n_frontiers || max_records < 0 || (max_records > 0 && (!frontiers || !records || !weighted_cost)) ||
+        n_blacklist < 0 || (n_blacklist > 0 && !blacklist_xy))
+        return fail(c, FS_E_INVALID, "null pointer or negative count");
+    *n_frontiers = 0;
+    int rc = nav_check(c, robot_pose7);
+    if (rc) return rc;
+    rc = check_scoring_state(c, true, with_fisher_information != 0);
+    if (rc) return rc;
+    // the search writes the goal and size columns where the planner and the scorer read them; the blacklist is matched there too
+    bool on_map = false;
+    FsSearchArgs sa{};
+    rc = search_enqueue(c, robot_pose7, lethal_threshold, max_frontier_distance, min_frontier_cluster_size, max_frontier_cluster_size,
+                        0, nullptr, false, &on_map, true, &sa);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (!on_map) return FS_OK;
+    const size_t cells = (size_t)c->nx * c->ny;
+    FS_HIP(c, c->d_fs_black.ensure(cells));
+    if (n_blacklist > 0) {
+        FS_HIP(c, c->d_fs_black_xy.ensure(2 * (size_t)n_blacklist));
+        FS_HIP(c, hipMemcpyAsync(c->d_fs_black_xy.p, blacklist_xy, 16 * (size_t)n_blacklist, hipMemcpyHostToDevice, c->stream));
+    }
+    FS_HIP(c, fs_launch_search_blacklist(sa, c->d_fs_black_xy.p, n_blacklist, c->d_fs_black.p, c->stream));
+    // the count (which sizes every launch below) and the records the caller receives; a list longer than the first round holds
+    // costs a second one
+    std::vector<fs_frontier_record> found((size_t)std::min<int32_t>(max_records, 1024));
+    int32_t n = 0;
+    rc = search_results(c, (int32_t)found.size(), found.data(), &n, 0, nullptr, nullptr);
+    if (rc) return rc;
+    *n_frontiers = n;
+    if (n > max_records) return fail(c, FS_E_INVALID, "%d frontiers found, room for %d: no partial ranking", n, max_records);
+    if (n == 0) return FS_OK;
+    if ((size_t)n > found.size()) {
+        const size_t have = found.size();
+        found.resize((size_t)n);
+        FS_HIP(c, hipMemcpyAsync(found.data() + have, c->d_fs_rec.p + have, sizeof(fs_frontier_record) * ((size_t)n - have), hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    // setPlanForFrontier's heading is the host's libm by the planner's definition: computed from the records the
+    // caller receives, the only column that goes up
+    std::vector<double> heading((size_t)n);
+    for (int32_t k = 0; k < n; ++k) heading[k] = nav_heading(robot_pose7, found[k].goal_x, found[k].goal_y);
+    const size_t nn = (size_t)n;
+    const NavOutLayout O(nn);
+    FS_HIP(c, c->h_nav_out.ensure(O.total));
+    rc = navfn_plan_enqueue_dev(c, robot_pose7, allow_unknown, n, c->d_fs_goal.p, heading.data());
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (path_length_m) FS_HIP(c, hipMemcpyAsync(c->h_nav_out.p + O.len_m, c->d_nav_out.p + O.len_m, 8 * nn, hipMemcpyDeviceToHost, c->stream));
+    const PlannedCols cols{reinterpret_cast<const uint8_t *>(c->d_nav_out.p + O.ach), reinterpret_cast<const double *>(c->d_nav_out.p + O.len),
+                           reinterpret_cast<const double *>(c->d_nav_out.p + O.head)};
+    const DevCols dev{c->d_fs_goal.p, c->d_fs_fsize.p, c->d_fs_black.p};
+    rc = frontier_costs_core(c, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, alpha, beta, max_vx, max_wz,
+                             with_fisher_information != 0, records, weighted_cost, arrival_utility, distance_utility, order, &cols, &dev);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (path_length_m) std::memcpy(path_length_m, c->h_nav_out.p + O.len_m, 8 * nn);
+    std::memcpy(frontiers, found.data(), sizeof(fs_frontier_record) * nn);
     return FS_OK;
 }
 

@@ -110,6 +110,37 @@ hipError_t fs_launch_frontier_clusters(const uint8_t *d_map, int nx, int ny, dou
                                        int32_t *d_aux, uint32_t *d_queue, uint8_t *d_visited, int32_t *d_state, int32_t *d_labels,
                                        int32_t max_clusters, fs_frontier_cluster *d_clusters, long long *d_sums, hipStream_t s);
 
+// ---- frontier search tail (fs_search.hip): pieces and goal points of the components fs_launch_frontier_clusters
+// found (launched with max_clusters = 0, so that aux[root] == -2 marks a found component).  Every scratch array holds nx * ny
+// entries (emit_* / rec_base: max(nx * ny, n_seeds) + 1); state [16] zeroed before the launch.
+struct fs_msort_elem;                     // fs_median_sort.h
+enum { FSS_COMPONENTS = 0, FSS_EMITTED = 1, FSS_CELLS = 2, FSS_RECORDS = 3, FSS_ERROR = 4, FSS_LEVELS = 5, FSS_GUARDED = 6 };
+struct FsSearchArgs {
+    const int32_t *parent_f, *aux;
+    int32_t nx, ny;
+    double ox, oy, res;
+    int32_t robot_cell;
+    int32_t min_size, max_size;
+    int32_t n_seeds;                      // < 0: Nearest seeds
+    const int32_t *seeds;                 // [n_seeds] (device)
+    int32_t *bcount, *cidx, *comp_root, *best_idx, *csize, *owner;
+    unsigned long long *best_d2;
+    int32_t *emit_comp, *emit_seed, *emit_base, *rec_base;
+    int32_t *key, *pos, *q;
+    fs_msort_elem *sortbuf;
+    fs_frontier_record *rec;              // [nx * ny]
+    double *goal_xyz;                     // [nx * ny][3] or NULL: the goal column of the scoring calls
+    int32_t *fsize;                       // [nx * ny] or NULL: the frontier-size column
+    double *every;                        // [nx * ny][2] or NULL
+    int32_t *state;
+};
+hipError_t fs_launch_frontier_search(const FsSearchArgs &a, hipStream_t s);
+// after the search, on the same stream: blacklisted [records] = the goal point equals one of black_xy [n_black][2] bit for bit
+hipError_t fs_launch_search_blacklist(const FsSearchArgs &a, const double *d_black_xy, int32_t n_black, uint8_t *d_blacklisted, hipStream_t s);
+// the grid planner's goal cells (y * nx + x, -1 off the map) of device-resident goal points [n][3]
+hipError_t fs_launch_goal_cells(const double *d_goal_xyz, int32_t n, int32_t nx, int32_t ny, double ox, double oy, double res, int32_t robot_on,
+                                int32_t *d_cell, hipStream_t s);
+
 // ---- batched grid planner (fs_navfn.hip): one NavFn potential field per (grid, robot cell, allow_unknown) by a
 // tiled Jacobi schedule, then NavFn::calcPath from every frontier.  The tile size is part of the field's definition.
 #define NAVFN_TILE 32

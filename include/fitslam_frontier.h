@@ -171,6 +171,33 @@ int fs_frontier_clusters(fs_ctx *ctx, const double robot_xy[2], int32_t lethal_t
                          int32_t max_frontier_cluster_size, int32_t *labels, int32_t max_clusters,
                          fs_frontier_cluster *clusters, int32_t *n_clusters, int64_t *n_cells);
 
+/* The whole of FrontierSearch::searchFrom on the device: fs_frontier_clusters' components, then what
+ * buildNewFrontier (:98-216) does with each — a breadth-first walk from a seed cell in nhood8 order, pieces of
+ * max_frontier_cluster_size + 1 cells in the order of that queue, the remainder if it exceeds min_frontier_cluster_size, per piece
+ * the angular-median goal point (getCentroidOfCells, SortByMedianFunctor, libstdc++'s std::sort, the middle element) — and
+ * searchFrom's size filter.  The label image never leaves the device.
+ *   seeds     NULL (n_seeds ignored): per component (ascending label) its cell nearest the robot's cell, squared cell distance,
+ *             ties to the smaller index.  Otherwise n_seeds cells (y * nx + x), each starting one buildNewFrontier, records in list
+ *             order: the reference's own order when the seeds are the cells its outer search met first.  A seed that is not a
+ *             frontier cell the search found, or a second seed in one component: FS_E_INVALID, nothing written.
+ *   records   [max_records]; *n_records = records found (may exceed max_records: the first ones are stored)
+ *   every_xy  [max_every][2] or NULL: every_frontier_list, the world coordinates of every collected cell in emission order (cells of
+ *             dropped pieces included); *n_cells = its length (may exceed max_every)
+ * min_frontier_cluster_size >= 0 and max_frontier_cluster_size >= 1 (any value up to INT32_MAX: one at or above nx * ny cuts no
+ * component).  A robot position off the map gives no records.  The call
+ * synchronises once when every_xy is NULL and at most 1024 records are stored; the goal's UID (generateUID) is the caller's. */
+typedef struct {
+    double  goal_x, goal_y;      /* the goal point (mapToWorld of the median cell) */
+    int32_t size;                /* Frontier::getSize(): cells of the piece */
+    int32_t label;               /* the component's label (as fs_frontier_clusters) */
+    int32_t goal_cell;           /* y * nx + x of the goal point */
+    int32_t seed_cell;           /* the seed of the buildNewFrontier call that made the piece */
+} fs_frontier_record;
+int fs_search_frontiers(fs_ctx *ctx, const double robot_xy[2], int32_t lethal_threshold, double max_frontier_distance,
+                        int32_t min_frontier_cluster_size, int32_t max_frontier_cluster_size, int32_t n_seeds, const int32_t *seeds,
+                        int32_t max_records, fs_frontier_record *records, int32_t *n_records,
+                        int64_t max_every, double *every_xy, int64_t *n_cells);
+
 /* Replaces double FrontierCostCalculator::setMaxArrivalInformation() (DEP/include/.../CostCalculator.hpp:58,
  * DEP/src/CostCalculator.cpp:123-191): geometric maximum of the FOV window on an obstacle-free fan from
  * world (0,0).  max_value = the window maximum (0 if (0,0) is off-map: limits stay unset, as the
@@ -423,6 +450,20 @@ int fs_get_frontier_costs_planned(fs_ctx *ctx, const double robot_pose7[7], int3
                   const int32_t *frontier_size, const uint8_t *blacklisted, double alpha, double beta, double max_vx, double max_wz,
                   int with_fisher_information, fs_record *records, double *weighted_cost, double *arrival_utility,
                   double *distance_utility, int32_t *order, double *path_length_m);
+/* searchFrom -> plan -> score -> rank in one call: fs_search_frontiers with Nearest seeds from the pose's xy, then
+ * fs_get_frontier_costs_planned on its records (goal_xyz = (goal_x, goal_y, 0), frontier_size = size, blacklisted = the goal point
+ * equals one of blacklist_xy [n_blacklist][2] bit for bit: FrontierGoalPointEquality, the key of frontier_blacklist_).  Every
+ * column after frontiers [max_records] has *n_frontiers entries.  More records than max_records: FS_E_INVALID with *n_frontiers
+ * set and nothing else written (a ranking over part of the list would be wrong).  The goal, size and blacklist columns stay in
+ * device memory between the search and the scoring (only the planner's host-libm heading goes up).  Same results, bit for bit,
+ * as the two calls, except the Fisher float sums (info_ref, trace, logdet), which are not run-to-run bit-stable in the scorer
+ * itself; the ranking's columns read only its integers. */
+int fs_get_frontier_costs_searched(fs_ctx *ctx, const double robot_pose7[7], int32_t lethal_threshold, double max_frontier_distance,
+                  int32_t min_frontier_cluster_size, int32_t max_frontier_cluster_size, int32_t allow_unknown,
+                  int32_t n_blacklist, const double *blacklist_xy, double alpha, double beta, double max_vx, double max_wz,
+                  int with_fisher_information, int32_t max_records, fs_frontier_record *frontiers, int32_t *n_frontiers,
+                  fs_record *records, double *weighted_cost, double *arrival_utility, double *distance_utility, int32_t *order,
+                  double *path_length_m);
 
 /* ---------------------------------------------------------------- frontier roadmap (the reference's default planner) */
 

@@ -20,7 +20,7 @@ extern "C" {
  * the context's stream; fs_kernel_time returns and resets the accumulated (ms, launches) of
  * kernel kind: 0 ray-march, 1 FIM accumulate, 2 FIM HBM-table tier, 3 utility/rank, 4 candidate sort,
  * 5 frontier-cell stencil, 6 planner cost conversion + field set-up, 7 planner field rounds (one bracket per batch of rounds),
- * 8 planner path descent. */
+ * 8 planner path descent, 9 frontier search: pieces and goal points (fs_search_frontiers; its clustering kernels count as 5). */
 int  fs_enable_kernel_timing(fs_ctx *ctx, int enable);
 int  fs_kernel_time(fs_ctx *ctx, int kind, double *total_ms, int64_t *launches);
 
@@ -77,7 +77,9 @@ int  fs_set_option(fs_ctx *ctx, const char *key, double value);
  * 1002 = potential fields the grid planner built (fs_plan_paths: a call that reuses the cached field adds nothing), 1003 = rounds
  * of the last field built, 1004 = field rounds launched in all (1002 and 1004 are reset by `reset`); 1011 = cost fields the leg
  * refinement built (fs_refine_paths / fs_refine_field: a cached field adds nothing), 1012 = rounds of the last field built,
- * 1013 = line-of-sight walks of the legs (1011 and 1013 are reset by `reset`). */
+ * 1013 = line-of-sight walks of the legs (1011 and 1013 are reset by `reset`); 1014 = breadth-first levels of the deepest
+ * component of the last fs_search_frontiers, 1015 = pieces of the last search whose median sort stopped a scan at either end of
+ * the array (fs_median_sort.h's guard: a cyclic order on which the reference's std::sort leaves the array). */
 int  fs_get_counter(fs_ctx *ctx, int which, int64_t *value, int reset);
 
 /* ---------------------------------------------------------------- self test */

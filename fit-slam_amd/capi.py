@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "fs_plan_paths", "fs_navfn_potential", "fs_get_frontier_costs_planned",
     "fs_set_roadmap_params", "fs_roadmap_add_nodes", "fs_roadmap_rebuild", "fs_roadmap_connect", "fs_roadmap_get_graph", "fs_roadmap_plan",
     "fs_get_frontier_costs_roadmap", "fs_roadmap_next_goal", "fs_refine_paths", "fs_refine_field",
+    "fs_roadmap_set_keyframes", "fs_roadmap_optimize", "fs_roadmap_get_anchors",
     "fs_search_frontiers", "fs_get_frontier_costs_searched",
 ]
 
@@ -172,6 +173,9 @@ def load_library(build: bool = True):
     L.fs_get_frontier_costs_roadmap.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, vp, dbl, dbl, dbl, dbl, C.c_int, vp, vp, vp, vp, vp, vp]
     L.fs_roadmap_next_goal.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, vp, vp, i32, vp, i32, dbl, vp, dbl,
                                        C.POINTER(i32), C.POINTER(i32), vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(i64), vp, vp]
+    L.fs_roadmap_set_keyframes.argtypes = [vp, i32, vp, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.fs_roadmap_optimize.argtypes = [vp]
+    L.fs_roadmap_get_anchors.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), vp, vp]
     L.fs_refine_paths.argtypes = [vp, i32, vp, vp, i32, dbl, dbl, i32, vp, vp, vp, vp, vp, vp]
     L.fs_refine_field.argtypes = [vp, C.POINTER(dbl * 2), i32, dbl, dbl, i32, vp]
     L.fs_search_frontiers.argtypes = [vp, C.POINTER(dbl * 2), i32, dbl, i32, i32, i32, vp, i32, vp, C.POINTER(i32), i64, vp, C.POINTER(i64)]
@@ -617,6 +621,30 @@ class FrontierScorer:
         row = np.zeros(n.value + 1, np.int32); col = np.zeros(e.value, np.int32)
         self._check(self._L.fs_roadmap_get_graph(self._h, C.byref(n), C.byref(e), _p(xy), _p(key), _p(row), _p(col)))
         return dict(xy=xy, key=key, row_ptr=row, col=col)
+
+    def roadmap_set_keyframes(self, kf_id, pose7):
+        """mapDataCallback for one map message: kf_id [n], pose7 [n][7] (x y z qx qy qz qw).  Anchors every pending node; returns
+        (n_anchored, n_orphaned)."""
+        ids = np.ascontiguousarray(np.asarray(kf_id, dtype=np.int32).reshape(-1))
+        poses = np.ascontiguousarray(np.asarray(pose7, dtype=np.float64).reshape(-1, 7))
+        if poses.shape[0] != ids.shape[0]:
+            raise ValueError("one pose per key-frame id")
+        a, o = C.c_int32(), C.c_int32()
+        self._check(self._L.fs_roadmap_set_keyframes(self._h, ids.shape[0], _p(ids), _p(poses), C.byref(a), C.byref(o)))
+        return a.value, o.value
+
+    def roadmap_optimize(self):
+        """reConstructGraph(entireGraph = true, optimizeRoadmap = true): re-place every anchor, de-duplicate, rebuild the edges."""
+        self._check(self._L.fs_roadmap_optimize(self._h))
+
+    def roadmap_anchors(self):
+        """dict(n_pending, kf_id [n_records], point_c [n_records][3] float32): keyframe_mapping_ in the order roadmap_optimize
+        consumes it."""
+        k, r = C.c_int32(), C.c_int64()
+        self._check(self._L.fs_roadmap_get_anchors(self._h, C.byref(k), C.byref(r), None, None))
+        ids = np.zeros(r.value, np.int32); pts = np.zeros((r.value, 3), np.float32)
+        self._check(self._L.fs_roadmap_get_anchors(self._h, C.byref(k), C.byref(r), _p(ids), _p(pts)))
+        return dict(n_pending=k.value, kf_id=ids, point_c=pts)
 
     def roadmap_plan(self, robot_pose7, goal_xyz, achievable_in=None):
         """setPlanForFrontierRoadmap for every goal: one shortest-path tree from the robot's closest key node."""

@@ -17,6 +17,7 @@
 #include <map>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
@@ -338,6 +339,24 @@ struct fs_ctx {
     DevBuf<int32_t> d_tour_hops, d_tour_pred, d_tour_word;
     DevBuf<char> d_tour_work;                 // matrix | result | block winners
     PinnedBuf h_tour_out;                     // matrix | result | rounds of each tree
+    // key-frame anchors of the roadmap (fs_roadmap_kf.hip).  kf_order is keyframe_mapping_'s shadow: its keys are
+    // inserted in the sequence the reference inserts them, so iterating it is iterating keyframe_mapping_.  Records live on the
+    // device: (handle, p_c float3, ordinal in its key frame's vector), appended in time order.
+    std::vector<double> kf_queue;                       // no_kf_parent_queue_: pending node positions [k][2], FIFO
+    std::unordered_map<int32_t, int32_t> kf_handle;     // id -> handle (every id a message has named)
+    std::vector<int32_t> kf_handle_id;                  // handle -> id
+    std::vector<int64_t> kf_handle_count;               // handle -> records (the length of keyframe_mapping_[id])
+    std::unordered_map<int32_t, int32_t> kf_order;      // id -> handle, in keyframe_mapping_'s insertion sequence
+    std::vector<int32_t> kf_slot;                       // handle -> slot of the latest message (-1: not in it)
+    int64_t kf_records = 0;
+    int32_t kf_one_wg = FS_KF_DEDUP_ONE_WG;             // "roadmap.dedup_one_wg": above this many points a round per launch
+    int64_t kf_rounds = 0, kf_points = 0;               // counters 1017 / 1018 (1016: kf_records)
+    DevBuf<float> d_kf_rt, d_kf_rec_p, d_kf_pts, d_kf_out;
+    DevBuf<double> d_kf_queue;
+    DevBuf<int32_t> d_kf_rec_h, d_kf_rec_ord, d_kf_tab, d_kf_work, d_kf_cand, d_kf_word;
+    DevBuf<uint64_t> d_kf_cell_key, d_kf_hkey;
+    DevBuf<uint8_t> d_kf_state;
+    PinnedBuf h_kf;
 
     // any-angle leg refinement (fs_refine.hip): a slab of rf_max_fields fp64 fields; slot s holds the field of
     // rf_key[s] for grid generation rf_gen[s] (0: empty).  Every staging call that writes the grid bumps grid_gen, which drops them.
@@ -939,6 +958,9 @@ void fs_ctx_destroy(fs_ctx *c)
     c->d_rm_in.release(); c->d_rm_out.release(); c->h_rm_in.release(); c->h_rm_out.release();
     c->d_tour_d.release(); c->d_tour_hops.release(); c->d_tour_pred.release(); c->d_tour_word.release(); c->d_tour_work.release();
     c->h_tour_out.release();
+    c->d_kf_rt.release(); c->d_kf_rec_p.release(); c->d_kf_pts.release(); c->d_kf_out.release(); c->d_kf_queue.release();
+    c->d_kf_rec_h.release(); c->d_kf_rec_ord.release(); c->d_kf_tab.release(); c->d_kf_work.release(); c->d_kf_cand.release();
+    c->d_kf_word.release(); c->d_kf_cell_key.release(); c->d_kf_hkey.release(); c->d_kf_state.release(); c->h_kf.release();
     c->d_rf_g.release(); c->d_rf_flags.release(); c->d_rf_any.release(); c->d_rf_in.release(); c->d_rf_scratch.release();
     c->d_rf_out.release(); c->d_rf_pts.release(); c->h_rf_in.release(); c->h_rf_out.release(); c->h_rf_pts.release();
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
@@ -1873,6 +1895,7 @@ int fs_set_option(fs_ctx *c, const char *key, double value)
     if (std::strcmp(key, "fim.skip32") == 0 && value >= 1 && value <= 32) { c->opt_skip32 = (int)value; return FS_OK; }
     if (std::strcmp(key, "fim.headroom") == 0 && value >= 8 && value <= 64) { c->opt_headroom = (int)value; return FS_OK; }
     if (std::strcmp(key, "roadmap.tour_one_wg") == 0 && value >= 0 && value <= RM_TREE_ONE_WG) { c->tour_one_wg = (int32_t)value; return FS_OK; }
+    if (std::strcmp(key, "roadmap.dedup_one_wg") == 0 && value >= 0 && value <= FS_KF_DEDUP_ONE_WG) { c->kf_one_wg = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "refine.max_fields") == 0 && value >= 1 && value <= RF_MAX_FIELDS) {
         if ((int32_t)value != c->rf_max_fields) { c->rf_max_fields = (int32_t)value; c->rf_key.clear(); c->rf_gen.clear(); }
         return FS_OK;
@@ -1896,6 +1919,12 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
         int64_t &v = which == 1005 ? c->rm_tree_builds : which == 1006 ? c->rm_tree_rounds : c->rm_traced;
         *value = v;
         if (reset && which != 1006) v = 0;
+        return FS_OK;
+    }
+    // ... of the key-frame anchors (fs_roadmap_set_keyframes / fs_roadmap_optimize): 1016 anchor records stored (never reset: the
+    // store is keyframe_mapping_), 1017 de-duplication rounds of the last optimise, 1018 points it de-duplicated
+    if (c && value && which >= 1016 && which <= 1018) {
+        *value = which == 1016 ? c->kf_records : which == 1017 ? c->kf_rounds : c->kf_points;
         return FS_OK;
     }
     // ... of the next-goal search (fs_roadmap_next_goal): 1008 trees built, 1009 rounds of the last call's batch (its slowest tree),
@@ -3416,6 +3445,62 @@ bool rm_finite_xy(const double *xy, int32_t n, int stride)
     return true;
 }
 
+// the record store grows without losing what it holds (DevBuf::ensure does not keep contents)
+template <class T>
+int kf_grow(fs_ctx *c, DevBuf<T> &b, size_t used, size_t need)
+{
+    if (need <= b.cap) return FS_OK;
+    DevBuf<T> nb;
+    FS_HIP(c, nb.ensure(std::max(need, 2 * b.cap)));
+    if (used) FS_HIP(c, hipMemcpyAsync(nb.p, b.p, sizeof(T) * used, hipMemcpyDeviceToDevice, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    b.release();
+    b.p = nb.p; b.cap = nb.cap;
+    nb.p = nullptr; nb.cap = 0;
+    return FS_OK;
+}
+
+// base[h] of every handle in keyframe_mapping_'s iteration order: the prefix of the record counts of the handles before it (only
+// the key frames of the latest message when `present_only`, the others -1).  Returns the total.
+int64_t kf_bases(const fs_ctx *c, bool present_only, std::vector<int32_t> &base)
+{
+    base.assign(c->kf_handle_id.size(), -1);
+    int64_t m = 0;
+    for (const auto &kv : c->kf_order) {
+        const int32_t h = kv.second;
+        if (present_only && c->kf_slot[(size_t)h] < 0) continue;
+        base[(size_t)h] = (int32_t)m;
+        m += c->kf_handle_count[(size_t)h];
+    }
+    return m;
+}
+
+// the de-duplication rounds (fs_roadmap_kf.hip): one workgroup's loop up to kf_one_wg points, a round per launch above it, polled in
+// batches of RM_TREE_BATCH.  Returns the rounds run (the last one quiet) through *rounds.
+int kf_dedup_rounds(fs_ctx *c, const FsKfDedup &d, int64_t *rounds)
+{
+    const int64_t max_rounds = (int64_t)d.m + 1;
+    if (d.m <= c->kf_one_wg) {
+        FS_HIP(c, fs_launch_kf_dedup_block(d, (int32_t)max_rounds, c->stream));
+        *rounds = -2;                   // read from hdr[2] with the results
+        return FS_OK;
+    }
+    FS_HIP(c, c->d_kf_word.ensure(RM_TREE_BATCH));
+    int64_t r = 0;
+    int src = 0;
+    for (;;) {
+        FS_HIP(c, hipMemsetAsync(c->d_kf_word.p, 0, sizeof(int32_t) * RM_TREE_BATCH, c->stream));
+        for (int k = 0; k < RM_TREE_BATCH; ++k, src ^= 1) FS_HIP(c, fs_launch_kf_dedup_round(d, src, c->d_kf_word.p + k, c->stream));
+        int32_t any[RM_TREE_BATCH];
+        FS_HIP(c, hipMemcpyAsync(any, c->d_kf_word.p, sizeof any, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        for (int k = 0; k < RM_TREE_BATCH; ++k)
+            if (!any[k]) { *rounds = r + k + 1; return FS_OK; }
+        r += RM_TREE_BATCH;
+        if (r > max_rounds) return fail(c, FS_E_HIP, "the de-duplication did not settle in %lld rounds", (long long)max_rounds);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -3433,6 +3518,13 @@ int fs_set_roadmap_params(fs_ctx *c, double grid_cell_size, double radius_to_dec
     // the hash is cut by the cell size: a new parameter set starts an empty roadmap, as a new FrontierRoadMap does
     c->rm_xy.clear(); c->rm_hash.clear(); c->rm_key.clear(); c->rm_adj.clear();
     ++c->rm_gen;
+    // ... and no pending node, key frame or anchor.  Fresh maps, not clear(): a cleared unordered_map keeps its buckets, and the
+    // bucket count decides the iteration order of what is inserted next.
+    c->kf_queue.clear();
+    std::unordered_map<int32_t, int32_t>().swap(c->kf_handle);
+    std::unordered_map<int32_t, int32_t>().swap(c->kf_order);
+    c->kf_handle_id.clear(); c->kf_handle_count.clear(); c->kf_slot.clear();
+    c->kf_records = 0;
     return FS_OK;
 }
 
@@ -3463,6 +3555,7 @@ int fs_roadmap_add_nodes(fs_ctx *c, int32_t n, const double *xy, int32_t is_robo
         c->rm_xy.push_back(x); c->rm_xy.push_back(y);
         c->rm_key.push_back(0);
         c->rm_adj.emplace_back();
+        c->kf_queue.push_back(x); c->kf_queue.push_back(y);     // populateNodes(addNewToQueue = true) queues before its throw
         if (cell.size() > RM_MAX_PER_CELL)
             return fail(c, FS_E_RANGE, "hash cell (%d, %d) holds more than %d nodes (the reference throws; the node stays added, the rest of the list is not)",
                         cx, cy, RM_MAX_PER_CELL);
@@ -3574,6 +3667,200 @@ int fs_roadmap_connect(fs_ctx *c, int32_t n, const double *xy)
             if (std::find(a.begin(), a.end(), q) != a.end() || std::find(b.begin(), b.end(), p) != b.end()) continue;
             if (ok[(size_t)k] && !hit[(size_t)k] && !((double)unknown[(size_t)k] > limit)) { a.push_back(q); b.push_back(p); }
         }
+    }
+    return FS_OK;
+}
+
+int fs_roadmap_set_keyframes(fs_ctx *c, int32_t n, const int32_t *kf_id, const double *pose7, int32_t *n_anchored, int32_t *n_orphaned)
+{
+    if (!c) return FS_E_INVALID;
+    if (n < 0 || (n > 0 && (!kf_id || !pose7))) return fail(c, FS_E_INVALID, "null pointer");
+    FS_HIP(c, hipSetDevice(c->device));
+    // the message's table: one slot per distinct id holding its last pose (latest_keyframe_poses_), every occurrence's id in the
+    // cell of its own position (spatial_kf_map_) — checked whole before anything changes
+    std::unordered_map<int32_t, int32_t> slot_of;
+    std::vector<int32_t> slot_id, occ_slot((size_t)n);
+    std::vector<float> rt;
+    for (int32_t i = 0; i < n; ++i) {
+        const double *q = pose7 + 7 * (size_t)i;
+        for (int k = 0; k < 7; ++k)
+            if (!std::isfinite(q[k])) return fail(c, FS_E_INVALID, "key frame %d: non-finite pose", (int)i);
+        float T[FS_KF_RT];
+        const float det = fs_kf_pose_table(q, T);
+        bool finite = std::isfinite(det) && det != 0.0f;
+        for (int k = 0; k < FS_KF_RT; ++k) finite = finite && std::isfinite(T[k]);
+        if (!finite) return fail(c, FS_E_INVALID, "key frame %d: the float rotation has no inverse", (int)i);
+        const auto it = slot_of.emplace(kf_id[i], (int32_t)slot_id.size());
+        if (it.second) { slot_id.push_back(kf_id[i]); rt.resize(rt.size() + FS_KF_RT); }
+        occ_slot[(size_t)i] = it.first->second;
+        std::copy(T, T + FS_KF_RT, rt.begin() + (size_t)FS_KF_RT * it.first->second);
+    }
+    const int32_t slots = (int32_t)slot_id.size();
+    std::vector<int32_t> ints((size_t)slots);                  // handle [slots] | cell_start [cells + 1] | cell_slots [n]
+    for (int32_t s = 0; s < slots; ++s) {
+        const auto it = c->kf_handle.emplace(slot_id[(size_t)s], (int32_t)c->kf_handle_id.size());
+        if (it.second) { c->kf_handle_id.push_back(slot_id[(size_t)s]); c->kf_handle_count.push_back(0); }
+        ints[(size_t)s] = it.first->second;
+    }
+    c->kf_slot.assign(c->kf_handle_id.size(), -1);
+    for (int32_t s = 0; s < slots; ++s) c->kf_slot[(size_t)ints[(size_t)s]] = s;
+    std::map<uint64_t, std::vector<int32_t>> cells;
+    for (int32_t i = 0; i < n; ++i) {
+        const int cx = fs_rm_cell(pose7[7 * (size_t)i], c->rm_cell), cy = fs_rm_cell(pose7[7 * (size_t)i + 1], c->rm_cell);
+        cells[((uint64_t)(uint32_t)cx << 32) | (uint32_t)cy].push_back(occ_slot[(size_t)i]);
+    }
+    std::vector<uint64_t> keys;
+    const size_t o_start = ints.size();
+    ints.push_back(0);
+    for (const auto &kv : cells) { keys.push_back(kv.first); ints.push_back(ints.back() + (int32_t)kv.second.size()); }
+    const size_t o_slots = ints.size();
+    for (const auto &kv : cells) ints.insert(ints.end(), kv.second.begin(), kv.second.end());
+    FS_HIP(c, c->d_kf_rt.ensure(rt.size())); FS_HIP(c, c->d_kf_tab.ensure(ints.size())); FS_HIP(c, c->d_kf_cell_key.ensure(keys.size()));
+    if (!rt.empty()) FS_HIP(c, hipMemcpyAsync(c->d_kf_rt.p, rt.data(), sizeof(float) * rt.size(), hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, hipMemcpyAsync(c->d_kf_tab.p, ints.data(), sizeof(int32_t) * ints.size(), hipMemcpyHostToDevice, c->stream));
+    if (!keys.empty()) FS_HIP(c, hipMemcpyAsync(c->d_kf_cell_key.p, keys.data(), sizeof(uint64_t) * keys.size(), hipMemcpyHostToDevice, c->stream));
+    // the queue, drained: parents counted, scanned, the records appended in (queue order, list order)
+    const int32_t k = (int32_t)(c->kf_queue.size() / 2);
+    int32_t anchored = 0, orphaned = 0;
+    if (k > 0) {
+        const size_t nk = (size_t)k;
+        FS_HIP(c, c->d_kf_queue.ensure(2 * nk)); FS_HIP(c, c->d_kf_work.ensure(2 * nk + 1));
+        FS_HIP(c, hipMemcpyAsync(c->d_kf_queue.p, c->kf_queue.data(), sizeof(double) * 2 * nk, hipMemcpyHostToDevice, c->stream));
+        const FsKfTable t{c->rm_cell, c->d_kf_rt.p, c->d_kf_tab.p, (int32_t)keys.size(), c->d_kf_cell_key.p, c->d_kf_tab.p + o_start,
+                          c->d_kf_tab.p + o_slots};
+        int32_t *count = c->d_kf_work.p, *off = c->d_kf_work.p + nk;
+        FS_HIP(c, fs_launch_kf_anchor(t, k, c->d_kf_queue.p, nullptr, count, nullptr, nullptr, c->stream));
+        FS_HIP(c, fs_launch_rm_scan(count, k, off, c->stream));
+        FS_HIP(c, c->h_kf.ensure(sizeof(int32_t) * (nk + 1)));
+        int32_t *h = reinterpret_cast<int32_t *>(c->h_kf.p);
+        FS_HIP(c, hipMemcpyAsync(h, count, sizeof(int32_t) * nk, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipMemcpyAsync(h + nk, off + nk, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < nk; ++i) orphaned += h[i] == 0 ? 1 : 0;
+        anchored = k - orphaned;
+        const int64_t total = h[nk], used = c->kf_records;
+        if (used + total > (int64_t)INT32_MAX) return fail(c, FS_E_RANGE, "more than 2^31 - 1 anchor records");
+        int rc = kf_grow(c, c->d_kf_rec_h, (size_t)used, (size_t)(used + total));
+        if (!rc) rc = kf_grow(c, c->d_kf_rec_ord, (size_t)used, (size_t)(used + total));
+        if (!rc) rc = kf_grow(c, c->d_kf_rec_p, 3 * (size_t)used, 3 * (size_t)(used + total));
+        if (rc) return rc;
+        if (total > 0) {
+            FS_HIP(c, fs_launch_kf_anchor(t, k, c->d_kf_queue.p, off, nullptr, c->d_kf_rec_h.p + used, c->d_kf_rec_p.p + 3 * used, c->stream));
+            // keyframe_mapping_[id].push_back in record order: the shadow map's insertions and each record's ordinal in its vector
+            FS_HIP(c, c->h_kf.ensure(sizeof(int32_t) * 2 * (size_t)total));
+            h = reinterpret_cast<int32_t *>(c->h_kf.p);
+            FS_HIP(c, hipMemcpyAsync(h, c->d_kf_rec_h.p + used, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+            FS_HIP(c, hipStreamSynchronize(c->stream));
+            int32_t *ord = h + total;
+            for (int64_t r = 0; r < total; ++r) {
+                const int32_t hd = h[r];
+                const int32_t id = c->kf_handle_id[(size_t)hd];
+                if (c->kf_order.count(id) == 0) c->kf_order[id] = hd;
+                ord[r] = (int32_t)c->kf_handle_count[(size_t)hd]++;
+            }
+            FS_HIP(c, hipMemcpyAsync(c->d_kf_rec_ord.p + used, ord, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, c->stream));
+            FS_HIP(c, hipStreamSynchronize(c->stream));
+            c->kf_records += total;
+        }
+        c->kf_queue.clear();
+    }
+    if (n_anchored) *n_anchored = anchored;
+    if (n_orphaned) *n_orphaned = orphaned;
+    return FS_OK;
+}
+
+int fs_roadmap_optimize(fs_ctx *c)
+{
+    if (!c) return FS_E_INVALID;
+    int rc = rm_check_grid(c);
+    if (rc) return rc;
+    // optimizeSHM's sequence: the records of the latest message's key frames in keyframe_mapping_'s order, re-placed
+    std::vector<int32_t> tab;
+    const int64_t m64 = kf_bases(c, true, tab);
+    if (m64 > (int64_t)INT32_MAX / 2) return fail(c, FS_E_RANGE, "too many anchor points");
+    const int32_t m = (int32_t)m64;
+    const size_t H = tab.size(), mm = (size_t)m;
+    tab.insert(tab.end(), c->kf_slot.begin(), c->kf_slot.end());        // base [H] | slot [H]
+    std::vector<float> out;
+    int32_t kept = 0, cut = INT32_MAX;
+    int64_t rounds = 0;
+    if (m > 0) {
+        uint32_t cap = 64;
+        while (cap < 2 * (uint32_t)m) cap <<= 1;
+        FS_HIP(c, c->d_kf_tab.ensure(2 * H)); FS_HIP(c, c->d_kf_pts.ensure(2 * mm)); FS_HIP(c, c->d_kf_out.ensure(4 + 2 * mm));
+        FS_HIP(c, c->d_kf_hkey.ensure(cap)); FS_HIP(c, c->d_kf_state.ensure(2 * mm));
+        // ints: hcount [cap] | hcursor [cap] | hstart [cap + 1] | hpts [m] | pslot [m] | count [m] | cand_off [m + 1] | keep_off [m + 1]
+        const size_t o_cursor = cap, o_start = 2 * (size_t)cap, o_pts = o_start + cap + 1, o_slot = o_pts + mm, o_count = o_slot + mm,
+                     o_cand = o_count + mm, o_keep = o_cand + mm + 1, n_ints = o_keep + mm + 1;
+        FS_HIP(c, c->d_kf_work.ensure(n_ints));
+        int32_t *w = c->d_kf_work.p;
+        FS_HIP(c, hipMemcpyAsync(c->d_kf_tab.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, c->stream));
+        FS_HIP(c, fs_launch_kf_place((int32_t)c->kf_records, c->d_kf_rec_h.p, c->d_kf_rec_ord.p, c->d_kf_rec_p.p, c->d_kf_tab.p + H, c->d_kf_tab.p,
+                                     c->d_kf_rt.p, c->d_kf_pts.p, c->stream));
+        FS_HIP(c, hipMemsetAsync(c->d_kf_state.p, 0, 2 * mm, c->stream));
+        FsKfDedup d{};
+        d.m = m; d.xy = c->d_kf_pts.p; d.cell = c->rm_cell; d.min_d = c->rm_min_frontier; d.mask = cap - 1;
+        d.hkey = c->d_kf_hkey.p; d.hcount = w; d.hcursor = w + o_cursor; d.hstart = w + o_start; d.hpts = w + o_pts; d.pslot = w + o_slot;
+        d.cand_off = w + o_cand; d.state[0] = c->d_kf_state.p; d.state[1] = c->d_kf_state.p + mm;
+        d.hdr = reinterpret_cast<int32_t *>(c->d_kf_out.p);
+        FS_HIP(c, fs_launch_kf_dedup_cells(d, c->stream));
+        FS_HIP(c, fs_launch_kf_dedup_conflicts(d, nullptr, w + o_count, nullptr, c->stream));
+        FS_HIP(c, fs_launch_rm_scan(w + o_count, m, w + o_cand, c->stream));
+        int32_t total = 0;
+        FS_HIP(c, hipMemcpyAsync(&total, w + o_cand + mm, sizeof total, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        FS_HIP(c, c->d_kf_cand.ensure((size_t)total));
+        d.cand = c->d_kf_cand.p;
+        FS_HIP(c, fs_launch_kf_dedup_conflicts(d, w + o_cand, nullptr, c->d_kf_cand.p, c->stream));
+        rc = kf_dedup_rounds(c, d, &rounds);
+        if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+        FS_HIP(c, fs_launch_kf_dedup_finish(d, 0, w + o_count, w + o_keep, c->d_kf_out.p + 4, c->stream));
+        FS_HIP(c, c->h_kf.ensure(sizeof(float) * (4 + 2 * mm)));
+        FS_HIP(c, hipMemcpyAsync(c->h_kf.p, c->d_kf_out.p, sizeof(float) * (4 + 2 * mm), hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        const int32_t *hdr = reinterpret_cast<const int32_t *>(c->h_kf.p);
+        kept = hdr[0]; cut = hdr[1];
+        if (rounds == -2) rounds = hdr[2];
+        if (rounds < 0) return fail(c, FS_E_HIP, "the de-duplication did not settle in %lld rounds", (long long)m + 1);
+        if (kept < 0 || kept > m) return fail(c, FS_E_HIP, "de-duplication: %d points kept of %d", (int)kept, (int)m);
+        const float *xy = reinterpret_cast<const float *>(c->h_kf.p) + 4;
+        out.assign(xy, xy + 2 * (size_t)kept);
+    }
+    c->kf_rounds = rounds; c->kf_points = m;
+    // the hash populateNodes leaves: the kept points in sequence order, no key and no edge until the rebuild
+    ++c->rm_gen;
+    c->rm_xy.assign(out.begin(), out.end());
+    c->rm_hash.clear();
+    for (int32_t i = 0; i < kept; ++i)
+        c->rm_hash[{fs_rm_cell(c->rm_xy[2 * (size_t)i], c->rm_cell), fs_rm_cell(c->rm_xy[2 * (size_t)i + 1], c->rm_cell)}].push_back(i);
+    c->rm_key.assign((size_t)kept, 0);
+    c->rm_adj.assign((size_t)kept, {});
+    if (cut != INT32_MAX)
+        return fail(c, FS_E_RANGE, "optimise: a hash cell holds more than %d nodes (the reference throws out of optimizeSHM; %d nodes kept, "
+                    "no key node, no edge)", FS_KF_MAX_PER_CELL, (int)kept);
+    return fs_roadmap_rebuild(c);
+}
+
+int fs_roadmap_get_anchors(fs_ctx *c, int32_t *n_pending, int64_t *n_records, int32_t *kf_id, float *point_c)
+{
+    if (!c) return FS_E_INVALID;
+    if (n_pending) *n_pending = (int32_t)(c->kf_queue.size() / 2);
+    if (n_records) *n_records = c->kf_records;
+    if ((!kf_id && !point_c) || c->kf_records == 0) return FS_OK;
+    FS_HIP(c, hipSetDevice(c->device));
+    const size_t R = (size_t)c->kf_records;
+    std::vector<int32_t> h(2 * R);
+    std::vector<float> p(3 * R);
+    FS_HIP(c, hipMemcpyAsync(h.data(), c->d_kf_rec_h.p, sizeof(int32_t) * R, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipMemcpyAsync(h.data() + R, c->d_kf_rec_ord.p, sizeof(int32_t) * R, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipMemcpyAsync(p.data(), c->d_kf_rec_p.p, sizeof(float) * 3 * R, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<int32_t> base;
+    kf_bases(c, false, base);
+    for (size_t r = 0; r < R; ++r) {
+        const size_t o = (size_t)base[(size_t)h[r]] + (size_t)h[R + r];
+        if (kf_id) kf_id[o] = c->kf_handle_id[(size_t)h[r]];
+        if (point_c) std::copy(&p[3 * r], &p[3 * r] + 3, point_c + 3 * o);
     }
     return FS_OK;
 }

@@ -344,6 +344,48 @@ struct FsRmTourArgs {
 int32_t fs_rm_tour_blocks(int64_t total, int64_t *chunk);
 hipError_t fs_launch_rm_tour(const FsRmTourArgs &a, int32_t blocks, double *d_out, hipStream_t s);
 
+// ---- key-frame anchors of the roadmap (fs_roadmap_kf.hip): mapDataCallback's anchoring, optimizeSHM's re-placement
+// and de-duplication
+#define FS_KF_RT 24                   // a key-frame slot: R [9] row-major, t [3], R^-1 [9], -R^-1 t [3] (float)
+#define FS_KF_MAX_PER_CELL 20         // populateNodes throws once a cell holds more (FrontierRoadmap.cpp:244-248)
+#define FS_KF_DEDUP_ONE_WG 16384      // up to this many points the de-duplication rounds are one workgroup's loop
+float fs_kf_pose_table(const double pose7[7], float T[FS_KF_RT]);
+struct FsKfTable {                    // one map message
+    double cell;                      // grid_cell_size (getGridCell)
+    const float *rt;                  // [slots][FS_KF_RT]: one slot per distinct id (its last pose in the message)
+    const int32_t *handle;            // [slots] the id's handle in the record store
+    int32_t n_cells;                  // occupied key-frame cells
+    const uint64_t *cell_key;         // [n_cells] ascending: (uint32)cx << 32 | (uint32)cy
+    const int32_t *cell_start;        // [n_cells + 1]
+    const int32_t *cell_slots;        // slots cell by cell, in message order (duplicates kept)
+};
+// pending nodes xy [n][2] (queue order): parents counted (d_off == nullptr) or the records (handle, p_c) written from d_off[i] on
+hipError_t fs_launch_kf_anchor(const FsKfTable &t, int32_t n, const double *d_xy, const int32_t *d_off, int32_t *d_count, int32_t *d_rec_h,
+                               float *d_rec_p, hipStream_t s);
+// record i -> out_xy[h_base[h] + rec_ord[i]] = (T_kf * p_c).xy, T_kf the slot h_slot[h] of d_rt; h_base[h] < 0: skipped
+hipError_t fs_launch_kf_place(int32_t n_rec, const int32_t *d_rec_h, const int32_t *d_rec_ord, const float *d_rec_p, const int32_t *d_h_slot,
+                              const int32_t *d_h_base, const float *d_rt, float *d_out_xy, hipStream_t s);
+struct FsKfDedup {
+    int32_t m;                        // points, sequence order
+    const float *xy;                  // [m][2]
+    double cell, min_d;
+    uint32_t mask;                    // hash capacity - 1 (capacity a power of two >= 2m)
+    uint64_t *hkey;                   // [capacity] cell key of each hash slot
+    int32_t *hcount, *hcursor;        // [capacity]
+    int32_t *hstart;                  // [capacity + 1]
+    int32_t *hpts;                    // [m] points slot by slot
+    int32_t *pslot;                   // [m] each point's hash slot
+    const int32_t *cand_off, *cand;   // conflicts: [m + 1], [total]
+    uint8_t *state[2];                // round buffers: 0 undecided, 1 accepted, 2 rejected
+    int32_t *hdr;                     // [4]: kept points, cut (the point that is a cell's 21st node; INT32_MAX none), rounds, 0
+};
+hipError_t fs_launch_kf_dedup_cells(const FsKfDedup &d, hipStream_t s);
+hipError_t fs_launch_kf_dedup_conflicts(const FsKfDedup &d, const int32_t *d_off, int32_t *d_count, int32_t *d_out, hipStream_t s);
+hipError_t fs_launch_kf_dedup_block(const FsKfDedup &d, int32_t max_rounds, hipStream_t s);
+hipError_t fs_launch_kf_dedup_round(const FsKfDedup &d, int32_t src, int32_t *d_any, hipStream_t s);
+// the cut, then the kept points compacted in order into d_out_xy (hdr[0] = how many); reads the verdicts from buffer src
+hipError_t fs_launch_kf_dedup_finish(const FsKfDedup &d, int32_t src, int32_t *d_keep, int32_t *d_keep_off, float *d_out_xy, hipStream_t s);
+
 // ---- key-frame pose information (computeInformationForPose)
 struct FsKfArgs {
     int32_t n;                 // poses

@@ -503,6 +503,33 @@ int fs_get_frontier_costs_roadmap(fs_ctx *ctx, const double robot_pose7[7], int3
                   fs_record *records, double *weighted_cost, double *arrival_utility, double *distance_utility, int32_t *order,
                   double *path_length_m);
 
+/* Key-frame anchors (FrontierRoadMap's loop-closure correction).  Every node fs_roadmap_add_nodes accepts — the one
+ * that trips its FS_E_RANGE included — is queued as pending (no_kf_parent_queue_); fs_set_roadmap_params clears the queue, the key
+ * frames and the anchors, as a new FrontierRoadMap starts empty.
+ * fs_roadmap_set_keyframes: mapDataCallback (DEP/src/planners/FrontierRoadmap.cpp:42-130) for one map message of n key frames, kf_id [n]
+ * and pose7 [n][7] = x y z qx qy qz qw.  The message replaces the key-frame table (an id named twice keeps its last pose) and the
+ * key-frame cell hash (getGridCell with the roadmap's grid_cell_size: each cell lists its ids in message order, duplicates kept).
+ * Then every pending node is taken in FIFO order: the parents are every id of its own cell; else the first occupied cell of the
+ * square of radius (int)(grid_cell_size * m), m = 1, 2, ..., scanned dx outer / dy inner, given up once the radius passes 7 (not
+ * necessarily the nearest cell).  For each parent, T_kf^-1 * (float x, float y, 0) is appended to the anchors of that id, in float32:
+ * T_kf = Translation3f * Quaternionf with the quaternion NOT normalised and the general 3 x 3 inverse, not the transpose.  A node
+ * without parents is dropped.  The queue ends empty; anchors are never removed.  n_anchored / n_orphaned (may be NULL): pending
+ * nodes that got parents / were dropped.  An empty message (n = 0) drops every pending node.  A non-finite pose, or one whose float
+ * rotation has determinant 0: FS_E_INVALID and nothing changes.
+ * fs_roadmap_optimize: reConstructGraph(entireGraph = true, optimizeRoadmap = true) (:347-408) — optimizeSHM (:132-155), then the
+ * rebuild of fs_roadmap_rebuild.  Every anchor of an id the latest message holds becomes the point (T_kf * p_c).xy (float), in the
+ * order of the reference's std::unordered_map<int, std::vector<Eigen::Vector3f>> keyframe_mapping_ under libstdc++ (its iteration
+ * order, then append order); anchors of other ids are skipped and kept.  populateNodes(populateClosest = true) on an empty hash turns
+ * the points into the new node list (a point closer than min_distance_between_two_frontier_nodes to an earlier kept point of the 3 x 3
+ * cells around it is dropped; a node anchored to two key frames may become two nodes).  A cell that comes to hold more than 20 nodes:
+ * FS_E_RANGE, the node list as the reference's hash is left when it throws (up to and including that node) with no key node and no edge.
+ * nz > 1: FS_E_INVALID; no grid staged: FS_E_STATE.
+ * fs_roadmap_get_anchors: the pending nodes and the anchors in the order fs_roadmap_optimize consumes them (every id, present or
+ * not), kf_id [n_records], point_c [n_records][3]; call with NULL arrays for the sizes. */
+int fs_roadmap_set_keyframes(fs_ctx *ctx, int32_t n, const int32_t *kf_id, const double *pose7, int32_t *n_anchored, int32_t *n_orphaned);
+int fs_roadmap_optimize(fs_ctx *ctx);
+int fs_roadmap_get_anchors(fs_ctx *ctx, int32_t *n_pending, int64_t *n_records, int32_t *kf_id, float *point_c);
+
 /* ---------------------------------------------------------------- next goal (FullPathOptimizer::getNextGoal) */
 /* FullPathOptimizer::getNextGoal (DEP/src/FullPathOptimizer.cpp:548-661) on the roadmap the context holds.
  * Inputs: the frontier list as fs_roadmap_plan left it — goal_xyz [n][3], path_length_m [n], achievable [n], blacklisted [n] (may be

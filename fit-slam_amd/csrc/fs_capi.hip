@@ -163,7 +163,7 @@ struct fs_ctx {
     bool have_cls = false;
     DevBuf<uint32_t> d_cls_table, d_cls_pool;       // "ray.layout" 3: brick table + pool of distinct bricks (the sparse form of d_cls)
     bool have_sparse = false;
-    uint64_t sparse_bricks = 0, sparse_pool_bricks = 0;
+    int64_t sparse_bricks = 0, sparse_pool_bricks = 0;    // counters 1000 / 1001
     int32_t cls_ranges[4] = {0, 0, 0, 0};
     int32_t nx = 0, ny = 0, nz = 0;
     double origin[3] = {0, 0, 0};
@@ -501,6 +501,99 @@ struct ScopedTimer {
     }
 };
 
+// ---------------------------------------------------------------- planner host helpers
+// The planners' relaxations (the NavFn field, the roadmap and tour trees, the anchor de-duplication, the refine fields) are
+// deterministic Jacobi rounds: a round after a quiet round is quiet too.  Rounds are therefore launched in batches without a host
+// synchronisation in between, and a batch that overshoots the last round costs launches, never a different result.
+#define PLAN_BATCH_FIRST 8
+#define PLAN_BATCH 16
+#define PLAN_MAX_ROUNDS (1 << 22)
+
+// Polls `cols` relaxations that run in lockstep: `launch(r0, count)` enqueues rounds r0 .. r0 + count - 1, round k of the batch
+// writing its "something changed" words at words + k * cols (cleared here before every batch; words holds
+// max(first, batch) * cols).  A column's last round is the first quiet one; the call ends once every column has one.  After a
+// batch that leaves a column unsettled, "rounds launched >= limit" fails as "<what> did not settle in <shown> rounds".
+// rounds[f]: the rounds of column f, the quiet one included.
+template <class Launch>
+int poll_rounds(fs_ctx *c, int32_t *words, int first, int batch, int cols, int64_t limit, const char *what, int64_t shown,
+                Launch launch, int64_t *rounds)
+{
+    std::vector<int32_t> any((size_t)std::max(first, batch) * cols);
+    std::fill(rounds, rounds + cols, -1);
+    int64_t r = 0;
+    for (int count = first;; count = batch) {
+        FS_HIP(c, hipMemsetAsync(words, 0, sizeof(int32_t) * count * cols, c->stream));
+        const int rc = launch(r, count);
+        if (rc) return rc;
+        r += count;
+        FS_HIP(c, hipMemcpyAsync(any.data(), words, sizeof(int32_t) * count * cols, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        bool done = true;
+        for (int f = 0; f < cols; ++f) {
+            if (rounds[f] >= 0) continue;
+            int k = 0;
+            while (k < count && any[(size_t)k * cols + f]) ++k;
+            if (k < count) rounds[f] = r - count + k + 1;           // the first quiet round of the batch
+            else done = false;
+        }
+        if (done) break;
+        if (r >= limit) return fail(c, FS_E_HIP, "%s did not settle in %lld rounds", what, (long long)shown);
+    }
+    return FS_OK;
+}
+
+// Costmap2D::worldToMap on the staged grid
+bool grid_world_to_map(const fs_ctx *c, double wx, double wy, int32_t &mx, int32_t &my)
+{
+    if (wx < c->origin[0] || wy < c->origin[1]) return false;
+    const double qx = (wx - c->origin[0]) / c->res, qy = (wy - c->origin[1]) / c->res;
+    if (!(qx < 4294967296.0) || !(qy < 4294967296.0)) return false;
+    const unsigned ux = static_cast<unsigned>(qx), uy = static_cast<unsigned>(qy);
+    if (ux >= (unsigned)c->nx || uy >= (unsigned)c->ny) return false;
+    mx = (int32_t)ux; my = (int32_t)uy;
+    return true;
+}
+
+// The device bound, a grid staged and that grid 2-D: what every planner stage needs (`what` names the stage in the error)
+int grid2d_check(fs_ctx *c, const char *what)
+{
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (c->nz != 1) return fail(c, FS_E_INVALID, "%s is defined on a 2-D costmap (nz == 1)", what);
+    return FS_OK;
+}
+
+// fs_frontier_clusters' kernels (fs_launch_frontier_clusters), shared with the frontier search: every buffer they use, then the
+// launch from the robot's cell.  `labels`: the label image is written too; max_clusters: room for cluster records (0: none).
+int fc_ensure(fs_ctx *c, bool labels, int32_t max_clusters)
+{
+    const size_t cells = (size_t)c->nx * c->ny;
+    FS_HIP(c, c->d_fc_parent_t.ensure(cells)); FS_HIP(c, c->d_fc_parent_f.ensure(cells)); FS_HIP(c, c->d_fc_aux.ensure(cells));
+    FS_HIP(c, c->d_fc_queue.ensure(cells)); FS_HIP(c, c->d_fc_visited.ensure(cells)); FS_HIP(c, c->d_fc_state.ensure(8));
+    if (labels) FS_HIP(c, c->d_fc_labels.ensure(cells));
+    FS_HIP(c, c->d_fc_clusters.ensure((size_t)std::max(max_clusters, 1))); FS_HIP(c, c->d_fc_sums.ensure(2 * (size_t)std::max(max_clusters, 1)));
+    return FS_OK;
+}
+
+int fc_launch(fs_ctx *c, const double robot_xy[2], int32_t robot_cell, double max_frontier_distance, int32_t max_frontier_cluster_size,
+              int32_t lethal_threshold, bool labels, int32_t max_clusters)
+{
+    const double reach = max_frontier_distance + (max_frontier_cluster_size * c->res * 1.414);      // DEP/src/FrontierSearch.cpp:67
+    ScopedTimer t(c, 5);
+    FS_HIP(c, fs_launch_frontier_clusters(c->d_cells.p, c->nx, c->ny, c->origin[0], c->origin[1], c->res, robot_xy[0], robot_xy[1],
+                                          robot_cell, reach, lethal_threshold, c->d_fc_parent_t.p, c->d_fc_parent_f.p, c->d_fc_aux.p,
+                                          c->d_fc_queue.p, c->d_fc_visited.p, c->d_fc_state.p, labels ? c->d_fc_labels.p : nullptr,
+                                          max_clusters, c->d_fc_clusters.p, c->d_fc_sums.p, c->stream));
+    return FS_OK;
+}
+
+// Output block of a planner's path columns (d_nav_out, d_rm_out and their host copies): path length | length in m | heading |
+// achievable.
+struct PlanOutLayout {
+    size_t len, len_m, head, ach, total;
+    explicit PlanOutLayout(size_t n) : len(0), len_m(8 * n), head(16 * n), ach(24 * n), total(24 * n + ((n + 15) & ~(size_t)15)) {}
+};
+
 // ---------------------------------------------------------------- lookup-table math (host, float32)
 // FIP/src/fisher_information/FisherInformationHelpers.cpp:71-96,114-123 with Q = I.
 float information_of_point_local(const float p[3])
@@ -734,7 +827,7 @@ int build_sparse_class_image(fs_ctx *c)
     FS_HIP(c, hipMemcpyAsync(c->d_cls_table.p, table.data(), table.size() * 4, hipMemcpyHostToDevice, c->stream));
     FS_HIP(c, hipMemcpyAsync(c->d_cls_pool.p, pool.data(), pool.size() * 4, hipMemcpyHostToDevice, c->stream));
     FS_HIP(c, hipStreamSynchronize(c->stream));
-    c->sparse_bricks = bricks; c->sparse_pool_bricks = pool.size() / 32;
+    c->sparse_bricks = (int64_t)bricks; c->sparse_pool_bricks = (int64_t)(pool.size() / 32);
     c->have_sparse = true;
     ++c->epoch;
     return FS_OK;
@@ -1231,41 +1324,22 @@ int fs_frontier_clusters(fs_ctx *c, const double robot_xy[2], int32_t lethal_thr
                          fs_frontier_cluster *clusters, int32_t *n_clusters, int64_t *n_cells)
 {
     if (!c || !robot_xy || !n_clusters || max_clusters < 0 || (max_clusters > 0 && !clusters)) return FS_E_INVALID;
-    FS_HIP(c, hipSetDevice(c->device));
-    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
-    if (c->nz != 1) return fail(c, FS_E_INVALID, "the frontier search is defined on a 2-D costmap (nz == 1)");
+    int rc = grid2d_check(c, "the frontier search");
+    if (rc) return rc;
     *n_clusters = 0;
     if (n_cells) *n_cells = 0;
     const size_t cells = (size_t)c->nx * c->ny;
     // :26-33 — worldToMap of the robot position; off the map: no frontiers
-    const double px = robot_xy[0], py = robot_xy[1];
-    bool on_map = !(px < c->origin[0] || py < c->origin[1]);
-    unsigned int mx = 0, my = 0;
-    if (on_map) {
-        const double qx = (px - c->origin[0]) / c->res, qy = (py - c->origin[1]) / c->res;
-        on_map = qx < 4294967296.0 && qy < 4294967296.0;
-        if (on_map) {
-            mx = static_cast<unsigned int>(qx); my = static_cast<unsigned int>(qy);
-            on_map = mx < (unsigned int)c->nx && my < (unsigned int)c->ny;
-        }
-    }
-    if (!on_map) {
+    int32_t mx = 0, my = 0;
+    if (!grid_world_to_map(c, robot_xy[0], robot_xy[1], mx, my)) {
         if (labels) std::fill(labels, labels + cells, -1);
         return FS_OK;
     }
-    FS_HIP(c, c->d_fc_parent_t.ensure(cells)); FS_HIP(c, c->d_fc_parent_f.ensure(cells)); FS_HIP(c, c->d_fc_aux.ensure(cells));
-    FS_HIP(c, c->d_fc_queue.ensure(cells)); FS_HIP(c, c->d_fc_visited.ensure(cells)); FS_HIP(c, c->d_fc_state.ensure(8));
-    if (labels) FS_HIP(c, c->d_fc_labels.ensure(cells));
-    FS_HIP(c, c->d_fc_clusters.ensure((size_t)std::max(max_clusters, 1))); FS_HIP(c, c->d_fc_sums.ensure(2 * (size_t)std::max(max_clusters, 1)));
-    const double reach = max_frontier_distance + (max_frontier_cluster_size * c->res * 1.414);      // :67
-    {
-        ScopedTimer t(c, 5);
-        FS_HIP(c, fs_launch_frontier_clusters(c->d_cells.p, c->nx, c->ny, c->origin[0], c->origin[1], c->res, px, py,
-                                              (int32_t)(my * (unsigned int)c->nx + mx), reach, lethal_threshold,
-                                              c->d_fc_parent_t.p, c->d_fc_parent_f.p, c->d_fc_aux.p, c->d_fc_queue.p, c->d_fc_visited.p,
-                                              c->d_fc_state.p, labels ? c->d_fc_labels.p : nullptr, max_clusters, c->d_fc_clusters.p,
-                                              c->d_fc_sums.p, c->stream));
-    }
+    rc = fc_ensure(c, labels != nullptr, max_clusters);
+    if (rc) return rc;
+    rc = fc_launch(c, robot_xy, (int32_t)((unsigned int)my * (unsigned int)c->nx + (unsigned int)mx), max_frontier_distance,
+                   max_frontier_cluster_size, lethal_threshold, labels != nullptr, max_clusters);
+    if (rc) return rc;
     // results through the page-locked buffer: the counters, the first clusters (as many as a map of this size usually has) and
     // the labels are requested together and waited for once; only a map with more clusters costs a second round trip
     const size_t first = (size_t)std::min<int32_t>(max_clusters, 4096);
@@ -1309,9 +1383,8 @@ int search_enqueue(fs_ctx *c, const double robot_xy[2], int32_t lethal_threshold
     if (!robot_xy) return fail(c, FS_E_INVALID, "null robot position");
     if (min_size < 0 || max_size < 1) return fail(c, FS_E_INVALID, "min_frontier_cluster_size >= 0 and max_frontier_cluster_size >= 1");
     if (seeds && n_seeds < 0) return fail(c, FS_E_INVALID, "n_seeds < 0");
-    FS_HIP(c, hipSetDevice(c->device));
-    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
-    if (c->nz != 1) return fail(c, FS_E_INVALID, "the frontier search is defined on a 2-D costmap (nz == 1)");
+    int rc = grid2d_check(c, "the frontier search");
+    if (rc) return rc;
     const size_t cells = (size_t)c->nx * c->ny;
     if (seeds) {
         if ((size_t)n_seeds > cells) return fail(c, FS_E_INVALID, "more seeds than cells");
@@ -1319,22 +1392,12 @@ int search_enqueue(fs_ctx *c, const double robot_xy[2], int32_t lethal_threshold
             if (seeds[k] < 0 || (size_t)seeds[k] >= cells) return fail(c, FS_E_INVALID, "seed %d: cell %d is off the map", k, seeds[k]);
     }
     // :26-33 — worldToMap of the robot position (as fs_frontier_clusters)
-    const double px = robot_xy[0], py = robot_xy[1];
-    bool on_map = !(px < c->origin[0] || py < c->origin[1]);
-    unsigned int mx = 0, my = 0;
-    if (on_map) {
-        const double qx = (px - c->origin[0]) / c->res, qy = (py - c->origin[1]) / c->res;
-        on_map = qx < 4294967296.0 && qy < 4294967296.0;
-        if (on_map) {
-            mx = static_cast<unsigned int>(qx); my = static_cast<unsigned int>(qy);
-            on_map = mx < (unsigned int)c->nx && my < (unsigned int)c->ny;
-        }
-    }
-    if (!on_map) return FS_OK;
+    int32_t mx = 0, my = 0;
+    if (!grid_world_to_map(c, robot_xy[0], robot_xy[1], mx, my)) return FS_OK;
+    const int32_t robot_cell = (int32_t)((unsigned int)my * (unsigned int)c->nx + (unsigned int)mx);
     const size_t nb = (cells + 1023) / 1024, ne = std::max(cells, (size_t)(seeds ? n_seeds : 0)) + 1;
-    FS_HIP(c, c->d_fc_parent_t.ensure(cells)); FS_HIP(c, c->d_fc_parent_f.ensure(cells)); FS_HIP(c, c->d_fc_aux.ensure(cells));
-    FS_HIP(c, c->d_fc_queue.ensure(cells)); FS_HIP(c, c->d_fc_visited.ensure(cells)); FS_HIP(c, c->d_fc_state.ensure(8));
-    FS_HIP(c, c->d_fc_clusters.ensure(1)); FS_HIP(c, c->d_fc_sums.ensure(2));
+    rc = fc_ensure(c, false, 0);
+    if (rc) return rc;
     FS_HIP(c, c->d_fs_bcount.ensure(nb + 1)); FS_HIP(c, c->d_fs_cidx.ensure(cells)); FS_HIP(c, c->d_fs_root.ensure(cells));
     FS_HIP(c, c->d_fs_best_idx.ensure(cells)); FS_HIP(c, c->d_fs_csize.ensure(cells)); FS_HIP(c, c->d_fs_owner.ensure(cells));
     FS_HIP(c, c->d_fs_key.ensure(cells)); FS_HIP(c, c->d_fs_pos.ensure(cells)); FS_HIP(c, c->d_fs_q.ensure(cells));
@@ -1348,18 +1411,12 @@ int search_enqueue(fs_ctx *c, const double robot_xy[2], int32_t lethal_threshold
         FS_HIP(c, hipMemcpyAsync(c->d_fs_seeds.p, seeds, sizeof(int32_t) * (size_t)n_seeds, hipMemcpyHostToDevice, c->stream));
     }
     FS_HIP(c, hipMemsetAsync(c->d_fs_state.p, 0, 16 * sizeof(int32_t), c->stream));
-    const double reach = max_frontier_distance + (max_size * c->res * 1.414);      // :67
-    {
-        ScopedTimer t(c, 5);
-        FS_HIP(c, fs_launch_frontier_clusters(c->d_cells.p, c->nx, c->ny, c->origin[0], c->origin[1], c->res, px, py,
-                                              (int32_t)(my * (unsigned int)c->nx + mx), reach, lethal_threshold,
-                                              c->d_fc_parent_t.p, c->d_fc_parent_f.p, c->d_fc_aux.p, c->d_fc_queue.p, c->d_fc_visited.p,
-                                              c->d_fc_state.p, nullptr, 0, c->d_fc_clusters.p, c->d_fc_sums.p, c->stream));
-    }
+    rc = fc_launch(c, robot_xy, robot_cell, max_frontier_distance, max_size, lethal_threshold, false, 0);
+    if (rc) return rc;
     FsSearchArgs a{};
     a.parent_f = c->d_fc_parent_f.p; a.aux = c->d_fc_aux.p;
     a.nx = c->nx; a.ny = c->ny; a.ox = c->origin[0]; a.oy = c->origin[1]; a.res = c->res;
-    a.robot_cell = (int32_t)(my * (unsigned int)c->nx + mx);
+    a.robot_cell = robot_cell;
     // a component has at most nx * ny cells, so every max_size >= nx * ny cuts exactly as nx * ny does (and max + 1 cannot wrap)
     a.min_size = min_size; a.max_size = (int32_t)std::min<int64_t>(max_size, (int64_t)cells);
     a.n_seeds = seeds ? n_seeds : -1; a.seeds = c->d_fs_seeds.p;
@@ -1905,47 +1962,36 @@ int fs_set_option(fs_ctx *c, const char *key, double value)
 
 int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
 {
-    // host-side figures of the sparse class image ("ray.layout" 3): 1000 bricks of the grid, 1001 bricks its pool holds
-    if (c && value && (which == 1000 || which == 1001)) { *value = (int64_t)(which == 1000 ? c->sparse_bricks : c->sparse_pool_bricks); return FS_OK; }
-    // ... of the grid planner (fs_plan_paths): 1002 potential fields built, 1003 rounds of the last one, 1004 round launches in all
-    if (c && value && which >= 1002 && which <= 1004) {
-        *value = which == 1002 ? c->nav_builds : which == 1003 ? c->nav_rounds : c->nav_launches;
-        if (reset) { if (which == 1002) c->nav_builds = 0; else if (which == 1004) c->nav_launches = 0; }
-        return FS_OK;
-    }
-    // ... of the roadmap planner (fs_roadmap_plan): 1005 shortest-path trees built, 1006 rounds of the last one; 1007 segments the
-    // roadmap calls have walked (fs_roadmap_rebuild, fs_roadmap_connect)
-    if (c && value && which >= 1005 && which <= 1007) {
-        int64_t &v = which == 1005 ? c->rm_tree_builds : which == 1006 ? c->rm_tree_rounds : c->rm_traced;
-        *value = v;
-        if (reset && which != 1006) v = 0;
-        return FS_OK;
-    }
-    // ... of the key-frame anchors (fs_roadmap_set_keyframes / fs_roadmap_optimize): 1016 anchor records stored (never reset: the
-    // store is keyframe_mapping_), 1017 de-duplication rounds of the last optimise, 1018 points it de-duplicated
-    if (c && value && which >= 1016 && which <= 1018) {
-        *value = which == 1016 ? c->kf_records : which == 1017 ? c->kf_rounds : c->kf_points;
-        return FS_OK;
-    }
-    // ... of the next-goal search (fs_roadmap_next_goal): 1008 trees built, 1009 rounds of the last call's batch (its slowest tree),
-    // 1010 tours evaluated
-    if (c && value && which >= 1008 && which <= 1010) {
-        int64_t &v = which == 1008 ? c->tour_tree_builds : which == 1009 ? c->tour_tree_rounds : c->tour_evaluated;
-        *value = v;
-        if (reset && which != 1009) v = 0;
-        return FS_OK;
-    }
-    // ... of the leg refinement (fs_refine_paths / fs_refine_field): 1011 fields built, 1012 rounds of the last field built, 1013
-    // line-of-sight walks
-    if (c && value && which >= 1011 && which <= 1013) {
-        int64_t &v = which == 1011 ? c->rf_builds : which == 1012 ? c->rf_rounds : c->rf_walks;
-        *value = v;
-        if (reset && which != 1012) v = 0;
-        return FS_OK;
-    }
-    // ... of the frontier search (fs_search_frontiers): 1014 breadth-first levels of the last search's deepest component, 1015 its
-    // pieces whose median sort the guard stopped
-    if (c && value && (which == 1014 || which == 1015)) { *value = which == 1014 ? c->fs_levels : c->fs_guarded; return FS_OK; }
+    // host-side figures: the field behind each id and whether `reset` clears it
+    static const struct {
+        int id;
+        int64_t fs_ctx::*v;
+        bool reset;
+    } host[] = {
+        // the sparse class image ("ray.layout" 3): bricks of the grid, bricks its pool holds
+        {1000, &fs_ctx::sparse_bricks, false}, {1001, &fs_ctx::sparse_pool_bricks, false},
+        // the grid planner (fs_plan_paths): potential fields built, rounds of the last one, round launches in all
+        {1002, &fs_ctx::nav_builds, true}, {1003, &fs_ctx::nav_rounds, false}, {1004, &fs_ctx::nav_launches, true},
+        // the roadmap planner (fs_roadmap_plan): shortest-path trees built, rounds of the last one; segments the roadmap calls have
+        // walked (fs_roadmap_rebuild, fs_roadmap_connect)
+        {1005, &fs_ctx::rm_tree_builds, true}, {1006, &fs_ctx::rm_tree_rounds, false}, {1007, &fs_ctx::rm_traced, true},
+        // the next-goal search (fs_roadmap_next_goal): trees built, rounds of the last call's batch (its slowest tree), tours evaluated
+        {1008, &fs_ctx::tour_tree_builds, true}, {1009, &fs_ctx::tour_tree_rounds, false}, {1010, &fs_ctx::tour_evaluated, true},
+        // the leg refinement (fs_refine_paths / fs_refine_field): fields built, rounds of the last field built, line-of-sight walks
+        {1011, &fs_ctx::rf_builds, true}, {1012, &fs_ctx::rf_rounds, false}, {1013, &fs_ctx::rf_walks, true},
+        // the frontier search (fs_search_frontiers): breadth-first levels of the last search's deepest component, its pieces whose
+        // median sort the guard stopped
+        {1014, &fs_ctx::fs_levels, false}, {1015, &fs_ctx::fs_guarded, false},
+        // the key-frame anchors (fs_roadmap_set_keyframes / fs_roadmap_optimize): anchor records stored (the store is
+        // keyframe_mapping_), de-duplication rounds of the last optimise, points it de-duplicated
+        {1016, &fs_ctx::kf_records, false}, {1017, &fs_ctx::kf_rounds, false}, {1018, &fs_ctx::kf_points, false},
+    };
+    for (const auto &h : host)
+        if (c && value && which == h.id) {
+            *value = c->*h.v;
+            if (reset && h.reset) c->*h.v = 0;
+            return FS_OK;
+        }
     if (!c || !value || which < 0 || which >= FS_N_COUNTERS) return FS_E_INVALID;
     FS_HIP(c, hipSetDevice(c->device));
     *value = 0;
@@ -2905,25 +2951,6 @@ int fs_selftest_fp64(fs_ctx *c, int32_t max_abs, int64_t *mismatches)
 
 namespace {
 
-// Rounds are launched in batches without a host synchronisation in between; after a batch the host reads the batch's
-// "a tile changed" words.  A round after a quiet round is quiet too (no tile active, nothing to copy), so a batch that overshoots
-// the last round costs launches, never a different field.
-#define NAVFN_BATCH_FIRST 8
-#define NAVFN_BATCH 16
-#define NAVFN_MAX_ROUNDS (1 << 22)
-
-// Costmap2D::worldToMap on the staged grid
-bool nav_world_to_map(const fs_ctx *c, double wx, double wy, int32_t &mx, int32_t &my)
-{
-    if (wx < c->origin[0] || wy < c->origin[1]) return false;
-    const double qx = (wx - c->origin[0]) / c->res, qy = (wy - c->origin[1]) / c->res;
-    if (!(qx < 4294967296.0) || !(qy < 4294967296.0)) return false;
-    const unsigned ux = static_cast<unsigned>(qx), uy = static_cast<unsigned>(qy);
-    if (ux >= (unsigned)c->nx || uy >= (unsigned)c->ny) return false;
-    mx = (int32_t)ux; my = (int32_t)uy;
-    return true;
-}
-
 // CostCalculator.cpp:209-217: quatToEuler's yaw of the robot and the bearing of the goal, both in [0, 2 pi), the smaller way round
 double nav_heading(const double pose7[7], double gx, double gy)
 {
@@ -2940,10 +2967,7 @@ double nav_heading(const double pose7[7], double gx, double gy)
 int nav_check(fs_ctx *c, const double robot_pose7[7])
 {
     if (!robot_pose7) return fail(c, FS_E_INVALID, "null robot pose");
-    FS_HIP(c, hipSetDevice(c->device));
-    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
-    if (c->nz != 1) return fail(c, FS_E_INVALID, "the grid planner is defined on a 2-D costmap (nz == 1)");
-    return FS_OK;
+    return grid2d_check(c, "the grid planner");
 }
 
 // The field for (robot cell, allow_unknown) on the staged grid: the cached one, or built now (synchronises the stream).
@@ -2958,7 +2982,7 @@ int navfn_field(fs_ctx *c, int32_t rx, int32_t ry, int32_t allow, const float **
         FS_HIP(c, c->d_nav_cost.ensure(ns));
         FS_HIP(c, c->d_nav_pot.ensure(2 * ns));
         FS_HIP(c, c->d_nav_flags.ensure(2 * tiles));
-        FS_HIP(c, c->d_nav_any.ensure(NAVFN_BATCH));
+        FS_HIP(c, c->d_nav_any.ensure(PLAN_BATCH));
         float *buf[2] = {c->d_nav_pot.p, c->d_nav_pot.p + ns};
         uint32_t *flags[2] = {c->d_nav_flags.p, c->d_nav_flags.p + tiles};
         {
@@ -2966,28 +2990,22 @@ int navfn_field(fs_ctx *c, int32_t rx, int32_t ry, int32_t allow, const float **
             FS_HIP(c, fs_launch_navfn_costs(c->d_cells.p, nx, ny, allow, c->d_nav_cost.p, c->stream));
             FS_HIP(c, fs_launch_navfn_init(buf[0], buf[1], nx, ny, rx, ry, flags[0], c->stream));
         }
-        int64_t r = 0, rounds = 0;
-        for (int batch = NAVFN_BATCH_FIRST;; batch = NAVFN_BATCH) {
-            FS_HIP(c, hipMemsetAsync(c->d_nav_any.p, 0, sizeof(int32_t) * batch, c->stream));
+        int64_t rounds = 0, launched = 0;
+        const auto launch = [&](int64_t r0, int count) -> int {
             {
                 ScopedTimer t(c, 7);
-                for (int k = 0; k < batch; ++k, ++r)
+                for (int64_t k = 0, r = r0; k < count; ++k, ++r)
                     FS_HIP(c, fs_launch_navfn_round(buf[r & 1], buf[(r + 1) & 1], c->d_nav_cost.p, flags[r & 1], flags[(r + 1) & 1], nx, ny,
                                                     c->d_nav_any.p + k, c->stream));
             }
-            c->nav_launches += batch;
-            int32_t any[NAVFN_BATCH] = {0};
-            FS_HIP(c, hipMemcpyAsync(any, c->d_nav_any.p, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, c->stream));
-            FS_HIP(c, hipStreamSynchronize(c->stream));
-            if (!any[batch - 1]) {
-                int k = 0;
-                while (any[k]) ++k;                  // the first quiet round of the batch: the field's last round
-                rounds = r - batch + k + 1;
-                break;
-            }
-            if (r >= NAVFN_MAX_ROUNDS) return fail(c, FS_E_HIP, "potential field did not settle in %d rounds", NAVFN_MAX_ROUNDS);
-        }
-        c->nav_buf = (int32_t)(r & 1);               // (after a quiet round both buffers hold the field)
+            c->nav_launches += count;
+            launched = r0 + count;
+            return FS_OK;
+        };
+        const int rc = poll_rounds(c, c->d_nav_any.p, PLAN_BATCH_FIRST, PLAN_BATCH, 1, PLAN_MAX_ROUNDS, "potential field", PLAN_MAX_ROUNDS,
+                                   launch, &rounds);
+        if (rc) return rc;
+        c->nav_buf = (int32_t)(launched & 1);        // (after a quiet round both buffers hold the field)
         c->nav_valid = true;
         c->nav_gen = c->grid_gen; c->nav_rx = rx; c->nav_ry = ry; c->nav_allow = allow;
         c->nav_rounds = rounds;
@@ -2997,44 +3015,34 @@ int navfn_field(fs_ctx *c, int32_t rx, int32_t ry, int32_t allow, const float **
     return FS_OK;
 }
 
-// Output block of the path kernel in d_nav_out: path length | length in m | heading | achievable.
-struct NavOutLayout {
-    size_t len, len_m, head, ach, total;
-    explicit NavOutLayout(size_t n) : len(0), len_m(8 * n), head(16 * n), ach(24 * n), total(24 * n + ((n + 15) & ~(size_t)15)) {}
+// Staging block of the path kernel in h_nav_in / d_nav_in: goal cells | headings.
+struct NavInLayout {
+    size_t cell, head, total;
+    explicit NavInLayout(size_t n) : cell(0), head((4 * n + 7) & ~(size_t)7), total(head + 8 * n) {}
 };
 
-// Goal cells and headings staged, the field (cached or built), the path kernel: the four columns land in d_nav_out on the
-// context's stream.  Not synchronised.
-int navfn_plan_enqueue(fs_ctx *c, const double robot7[7], int32_t allow, int32_t n, const double *goal_xyz, const uint8_t *achievable_in)
+int32_t navfn_max_cycles(const fs_ctx *c) { return 4 * std::max(c->nx, c->ny); }      // CostCalculator.cpp:284
+
+// every buffer a plan of nn goals uses is sized before a pointer into any of them is taken
+int navfn_ensure(fs_ctx *c, size_t nn)
 {
-    const size_t nn = (size_t)n;
-    const int32_t max_cycles = 4 * std::max(c->nx, c->ny);      // CostCalculator.cpp:284
-    const size_t i_cell = 0, i_head = (4 * nn + 7) & ~(size_t)7, total_in = i_head + 8 * nn;
-    const NavOutLayout O(nn);
-    // every buffer this call uses is sized before a pointer into any of them is taken
-    FS_HIP(c, c->h_nav_in.ensure(total_in)); FS_HIP(c, c->d_nav_in.ensure(total_in));
-    FS_HIP(c, c->d_nav_out.ensure(O.total));
-    FS_HIP(c, c->d_nav_path.ensure(nn * 2 * (size_t)max_cycles));
-    int32_t rx = 0, ry = 0;
-    const bool robot_on = nav_world_to_map(c, robot7[0], robot7[1], rx, ry);
-    int32_t *cell = reinterpret_cast<int32_t *>(c->h_nav_in.p + i_cell);
-    double *head = reinterpret_cast<double *>(c->h_nav_in.p + i_head);
-    bool need_field = false;
-    for (size_t i = 0; i < nn; ++i) {
-        int32_t gx = 0, gy = 0;
-        const bool planned = (!achievable_in || achievable_in[i]) && robot_on && nav_world_to_map(c, goal_xyz[3 * i], goal_xyz[3 * i + 1], gx, gy);
-        cell[i] = planned ? gy * c->nx + gx : -1;
-        head[i] = planned ? nav_heading(robot7, goal_xyz[3 * i], goal_xyz[3 * i + 1]) : 0.0;
-        need_field |= planned;
-    }
-    const float *field = nullptr;
-    if (need_field) { const int rc = navfn_field(c, rx, ry, allow, &field); if (rc) return rc; }
-    FS_HIP(c, hipMemcpyAsync(c->d_nav_in.p, c->h_nav_in.p, total_in, hipMemcpyHostToDevice, c->stream));
+    const NavInLayout I(nn);
+    FS_HIP(c, c->h_nav_in.ensure(I.total)); FS_HIP(c, c->d_nav_in.ensure(I.total));
+    FS_HIP(c, c->d_nav_out.ensure(PlanOutLayout(nn).total));
+    FS_HIP(c, c->d_nav_path.ensure(nn * 2 * (size_t)navfn_max_cycles(c)));
+    return FS_OK;
+}
+
+// The path kernel on `field` for the goal cells and headings in d_nav_in: the four columns land in d_nav_out.
+int navfn_paths(fs_ctx *c, const float *field, int32_t n, int32_t rx, int32_t ry)
+{
+    const NavInLayout I((size_t)n);
+    const PlanOutLayout O((size_t)n);
     FsNavfnPathArgs a{};
     a.pot = field; a.nx = c->nx; a.ny = c->ny; a.n = n;
-    a.goal_cell = reinterpret_cast<const int32_t *>(c->d_nav_in.p + i_cell);
-    a.heading_in = reinterpret_cast<const double *>(c->d_nav_in.p + i_head);
-    a.robot_x = rx; a.robot_y = ry; a.max_cycles = max_cycles;
+    a.goal_cell = reinterpret_cast<const int32_t *>(c->d_nav_in.p + I.cell);
+    a.heading_in = reinterpret_cast<const double *>(c->d_nav_in.p + I.head);
+    a.robot_x = rx; a.robot_y = ry; a.max_cycles = navfn_max_cycles(c);
     a.scratch = c->d_nav_path.p;
     a.ox = c->origin[0]; a.oy = c->origin[1]; a.res = c->res;
     a.path_length = reinterpret_cast<double *>(c->d_nav_out.p + O.len);
@@ -3046,39 +3054,94 @@ int navfn_plan_enqueue(fs_ctx *c, const double robot7[7], int32_t allow, int32_t
     return FS_OK;
 }
 
+// Goal cells and headings staged, the field (cached or built), the path kernel: the four columns land in d_nav_out on the
+// context's stream.  Not synchronised.
+int navfn_plan_enqueue(fs_ctx *c, const double robot7[7], int32_t allow, int32_t n, const double *goal_xyz, const uint8_t *achievable_in)
+{
+    const size_t nn = (size_t)n;
+    const NavInLayout I(nn);
+    int rc = navfn_ensure(c, nn);
+    if (rc) return rc;
+    int32_t rx = 0, ry = 0;
+    const bool robot_on = grid_world_to_map(c, robot7[0], robot7[1], rx, ry);
+    int32_t *cell = reinterpret_cast<int32_t *>(c->h_nav_in.p + I.cell);
+    double *head = reinterpret_cast<double *>(c->h_nav_in.p + I.head);
+    bool need_field = false;
+    for (size_t i = 0; i < nn; ++i) {
+        int32_t gx = 0, gy = 0;
+        const bool planned = (!achievable_in || achievable_in[i]) && robot_on && grid_world_to_map(c, goal_xyz[3 * i], goal_xyz[3 * i + 1], gx, gy);
+        cell[i] = planned ? gy * c->nx + gx : -1;
+        head[i] = planned ? nav_heading(robot7, goal_xyz[3 * i], goal_xyz[3 * i + 1]) : 0.0;
+        need_field |= planned;
+    }
+    const float *field = nullptr;
+    if (need_field) { rc = navfn_field(c, rx, ry, allow, &field); if (rc) return rc; }
+    FS_HIP(c, hipMemcpyAsync(c->d_nav_in.p, c->h_nav_in.p, I.total, hipMemcpyHostToDevice, c->stream));
+    return navfn_paths(c, field, n, rx, ry);
+}
+
 // navfn_plan_enqueue for goal points that lie in device memory (fs_get_frontier_costs_searched: the search wrote them): the goal
 // cells are computed on the device; only the headings come from the host, where setPlanForFrontier's heading is defined with the
 // host's libm (h_heading [n], used where a plan succeeds).  Every goal is planned (no achievable_in).  Not synchronised.
 int navfn_plan_enqueue_dev(fs_ctx *c, const double robot7[7], int32_t allow, int32_t n, const double *d_goal_xyz, const double *h_heading)
 {
     const size_t nn = (size_t)n;
-    const int32_t max_cycles = 4 * std::max(c->nx, c->ny);      // CostCalculator.cpp:284
-    const size_t i_cell = 0, i_head = (4 * nn + 7) & ~(size_t)7, total_in = i_head + 8 * nn;
-    const NavOutLayout O(nn);
-    FS_HIP(c, c->h_nav_in.ensure(total_in)); FS_HIP(c, c->d_nav_in.ensure(total_in));
-    FS_HIP(c, c->d_nav_out.ensure(O.total));
-    FS_HIP(c, c->d_nav_path.ensure(nn * 2 * (size_t)max_cycles));
+    const NavInLayout I(nn);
+    int rc = navfn_ensure(c, nn);
+    if (rc) return rc;
     int32_t rx = 0, ry = 0;
-    const bool robot_on = nav_world_to_map(c, robot7[0], robot7[1], rx, ry);
+    const bool robot_on = grid_world_to_map(c, robot7[0], robot7[1], rx, ry);
     const float *field = nullptr;
-    if (robot_on && n > 0) { const int rc = navfn_field(c, rx, ry, allow, &field); if (rc) return rc; }
-    std::memcpy(c->h_nav_in.p + i_head, h_heading, 8 * nn);
-    FS_HIP(c, hipMemcpyAsync(c->d_nav_in.p + i_head, c->h_nav_in.p + i_head, 8 * nn, hipMemcpyHostToDevice, c->stream));
-    int32_t *d_cell = reinterpret_cast<int32_t *>(c->d_nav_in.p + i_cell);
-    FS_HIP(c, fs_launch_goal_cells(d_goal_xyz, n, c->nx, c->ny, c->origin[0], c->origin[1], c->res, robot_on ? 1 : 0, d_cell, c->stream));
-    FsNavfnPathArgs a{};
-    a.pot = field; a.nx = c->nx; a.ny = c->ny; a.n = n;
-    a.goal_cell = d_cell;
-    a.heading_in = reinterpret_cast<const double *>(c->d_nav_in.p + i_head);
-    a.robot_x = rx; a.robot_y = ry; a.max_cycles = max_cycles;
-    a.scratch = c->d_nav_path.p;
-    a.ox = c->origin[0]; a.oy = c->origin[1]; a.res = c->res;
-    a.path_length = reinterpret_cast<double *>(c->d_nav_out.p + O.len);
-    a.path_length_m = reinterpret_cast<double *>(c->d_nav_out.p + O.len_m);
-    a.path_heading = reinterpret_cast<double *>(c->d_nav_out.p + O.head);
-    a.achievable = reinterpret_cast<uint8_t *>(c->d_nav_out.p + O.ach);
-    ScopedTimer t(c, 8);
-    FS_HIP(c, fs_launch_navfn_paths(a, c->stream));
+    if (robot_on && n > 0) { rc = navfn_field(c, rx, ry, allow, &field); if (rc) return rc; }
+    std::memcpy(c->h_nav_in.p + I.head, h_heading, 8 * nn);
+    FS_HIP(c, hipMemcpyAsync(c->d_nav_in.p + I.head, c->h_nav_in.p + I.head, 8 * nn, hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, fs_launch_goal_cells(d_goal_xyz, n, c->nx, c->ny, c->origin[0], c->origin[1], c->res, robot_on ? 1 : 0,
+                                   reinterpret_cast<int32_t *>(c->d_nav_in.p + I.cell), c->stream));
+    return navfn_paths(c, field, n, rx, ry);
+}
+
+// A planner's four columns for the caller: `enqueue()` plans n goals into d_out, the columns come up through h_out (synchronises
+// the stream).
+template <class Enqueue>
+int plan_to_host(fs_ctx *c, const DevBuf<char> &d_out, PinnedBuf &h_out, int32_t n, Enqueue enqueue, double *path_length,
+                 double *path_length_m, double *path_heading, uint8_t *achievable)
+{
+    const int rc = enqueue();
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    const size_t nn = (size_t)n;
+    const PlanOutLayout O(nn);
+    FS_HIP(c, h_out.ensure(O.total));
+    FS_HIP(c, hipMemcpyAsync(h_out.p, d_out.p, O.total, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    std::memcpy(path_length, h_out.p + O.len, 8 * nn);
+    std::memcpy(path_length_m, h_out.p + O.len_m, 8 * nn);
+    std::memcpy(path_heading, h_out.p + O.head, 8 * nn);
+    std::memcpy(achievable, h_out.p + O.ach, nn);
+    return FS_OK;
+}
+
+// Ranking on a planner's device columns: `enqueue()` plans n goals into d_out, `rank(cols)` scores and ranks on the columns where
+// the planner wrote them (scoring reads its achievability, ranking its path columns); path_length_m, if asked for, comes up
+// through h_out, which is sized before the plan is enqueued.
+template <class Enqueue, class Rank>
+int rank_on_plan(fs_ctx *c, const DevBuf<char> &d_out, PinnedBuf &h_out, int32_t n, Enqueue enqueue, Rank rank, double *path_length_m)
+{
+    const size_t nn = (size_t)n;
+    const PlanOutLayout O(nn);
+    FS_HIP(c, h_out.ensure(O.total));
+    int rc = enqueue();
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (path_length_m) FS_HIP(c, hipMemcpyAsync(h_out.p + O.len_m, d_out.p + O.len_m, 8 * nn, hipMemcpyDeviceToHost, c->stream));
+    const PlannedCols cols{reinterpret_cast<const uint8_t *>(d_out.p + O.ach), reinterpret_cast<const double *>(d_out.p + O.len),
+                           reinterpret_cast<const double *>(d_out.p + O.head)};
+    rc = rank(cols);
+    if (rc) {
+        // (frontier_costs_core can fail before its own synchronisation: the copy into h_out above must have landed before a later
+        // call may grow that buffer)
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    if (path_length_m) std::memcpy(path_length_m, h_out.p + O.len_m, 8 * nn);
     return FS_OK;
 }
 
@@ -3093,7 +3156,7 @@ int fs_navfn_potential(fs_ctx *c, const double robot_pose7[7], int32_t allow_unk
     int rc = nav_check(c, robot_pose7);
     if (rc) return rc;
     int32_t rx = 0, ry = 0;
-    if (!nav_world_to_map(c, robot_pose7[0], robot_pose7[1], rx, ry)) return fail(c, FS_E_INVALID, "the robot is off the costmap: no potential field");
+    if (!grid_world_to_map(c, robot_pose7[0], robot_pose7[1], rx, ry)) return fail(c, FS_E_INVALID, "the robot is off the costmap: no potential field");
     const float *field = nullptr;
     rc = navfn_field(c, rx, ry, allow_unknown, &field);
     if (rc) return rc;
@@ -3110,18 +3173,9 @@ int fs_plan_paths(fs_ctx *c, const double robot_pose7[7], int32_t allow_unknown,
     int rc = nav_check(c, robot_pose7);
     if (rc) return rc;
     if (n == 0) return FS_OK;
-    rc = navfn_plan_enqueue(c, robot_pose7, allow_unknown, n, goal_xyz, achievable_in);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    const size_t nn = (size_t)n;
-    const NavOutLayout O(nn);
-    FS_HIP(c, c->h_nav_out.ensure(O.total));
-    FS_HIP(c, hipMemcpyAsync(c->h_nav_out.p, c->d_nav_out.p, O.total, hipMemcpyDeviceToHost, c->stream));
-    FS_HIP(c, hipStreamSynchronize(c->stream));
-    std::memcpy(path_length, c->h_nav_out.p + O.len, 8 * nn);
-    std::memcpy(path_length_m, c->h_nav_out.p + O.len_m, 8 * nn);
-    std::memcpy(path_heading, c->h_nav_out.p + O.head, 8 * nn);
-    std::memcpy(achievable, c->h_nav_out.p + O.ach, nn);
-    return FS_OK;
+    return plan_to_host(c, c->d_nav_out, c->h_nav_out, n,
+                        [&] { return navfn_plan_enqueue(c, robot_pose7, allow_unknown, n, goal_xyz, achievable_in); },
+                        path_length, path_length_m, path_heading, achievable);
 }
 
 int fs_get_frontier_costs_planned(fs_ctx *c, const double robot_pose7[7], int32_t allow_unknown, int32_t n, const double *goal_xyz,
@@ -3136,25 +3190,13 @@ int fs_get_frontier_costs_planned(fs_ctx *c, const double robot_pose7[7], int32_
     if (n == 0) return FS_OK;
     rc = check_scoring_state(c, true, with_fisher_information != 0);
     if (rc) return rc;
-    const size_t nn = (size_t)n;
-    const NavOutLayout O(nn);
-    FS_HIP(c, c->h_nav_out.ensure(O.total));
-    rc = navfn_plan_enqueue(c, robot_pose7, allow_unknown, n, goal_xyz, nullptr);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if (path_length_m) FS_HIP(c, hipMemcpyAsync(c->h_nav_out.p + O.len_m, c->d_nav_out.p + O.len_m, 8 * nn, hipMemcpyDeviceToHost, c->stream));
-    // the planner's columns stay where the path kernel wrote them: scoring reads its achievability, ranking its path columns
-    const PlannedCols cols{reinterpret_cast<const uint8_t *>(c->d_nav_out.p + O.ach), reinterpret_cast<const double *>(c->d_nav_out.p + O.len),
-                           reinterpret_cast<const double *>(c->d_nav_out.p + O.head)};
-    rc = frontier_costs_core(c, n, goal_xyz, frontier_size, blacklisted, nullptr, nullptr, nullptr, alpha, beta, max_vx, max_wz,
-                             with_fisher_information != 0, records, weighted_cost, arrival_utility, distance_utility, order, &cols);
-    if (rc) {
-        // (frontier_costs_core can fail before its own synchronisation: the copy into h_nav_out above must have landed before a
-        // later call may grow that buffer)
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    if (path_length_m) std::memcpy(path_length_m, c->h_nav_out.p + O.len_m, 8 * nn);
-    return FS_OK;
+    return rank_on_plan(
+        c, c->d_nav_out, c->h_nav_out, n, [&] { return navfn_plan_enqueue(c, robot_pose7, allow_unknown, n, goal_xyz, nullptr); },
+        [&](const PlannedCols &cols) {
+            return frontier_costs_core(c, n, goal_xyz, frontier_size, blacklisted, nullptr, nullptr, nullptr, alpha, beta, max_vx, max_wz,
+                                       with_fisher_information != 0, records, weighted_cost, arrival_utility, distance_utility, order, &cols);
+        },
+        path_length_m);
 }
 
 int fs_get_frontier_costs_searched(fs_ctx *c, const double robot_pose7[7], int32_t lethal_threshold, double max_frontier_distance,
@@ -3206,20 +3248,16 @@ int fs_get_frontier_costs_searched(fs_ctx *c, const double robot_pose7[7], int32
     // caller receives, the only column that goes up
     std::vector<double> heading((size_t)n);
     for (int32_t k = 0; k < n; ++k) heading[k] = nav_heading(robot_pose7, found[k].goal_x, found[k].goal_y);
-    const size_t nn = (size_t)n;
-    const NavOutLayout O(nn);
-    FS_HIP(c, c->h_nav_out.ensure(O.total));
-    rc = navfn_plan_enqueue_dev(c, robot_pose7, allow_unknown, n, c->d_fs_goal.p, heading.data());
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if (path_length_m) FS_HIP(c, hipMemcpyAsync(c->h_nav_out.p + O.len_m, c->d_nav_out.p + O.len_m, 8 * nn, hipMemcpyDeviceToHost, c->stream));
-    const PlannedCols cols{reinterpret_cast<const uint8_t *>(c->d_nav_out.p + O.ach), reinterpret_cast<const double *>(c->d_nav_out.p + O.len),
-                           reinterpret_cast<const double *>(c->d_nav_out.p + O.head)};
-    const DevCols dev{c->d_fs_goal.p, c->d_fs_fsize.p, c->d_fs_black.p};
-    rc = frontier_costs_core(c, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, alpha, beta, max_vx, max_wz,
-                             with_fisher_information != 0, records, weighted_cost, arrival_utility, distance_utility, order, &cols, &dev);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if (path_length_m) std::memcpy(path_length_m, c->h_nav_out.p + O.len_m, 8 * nn);
-    std::memcpy(frontiers, found.data(), sizeof(fs_frontier_record) * nn);
+    rc = rank_on_plan(
+        c, c->d_nav_out, c->h_nav_out, n, [&] { return navfn_plan_enqueue_dev(c, robot_pose7, allow_unknown, n, c->d_fs_goal.p, heading.data()); },
+        [&](const PlannedCols &cols) {
+            const DevCols dev{c->d_fs_goal.p, c->d_fs_fsize.p, c->d_fs_black.p};
+            return frontier_costs_core(c, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, alpha, beta, max_vx, max_wz,
+                                       with_fisher_information != 0, records, weighted_cost, arrival_utility, distance_utility, order, &cols, &dev);
+        },
+        path_length_m);
+    if (rc) return rc;
+    std::memcpy(frontiers, found.data(), sizeof(fs_frontier_record) * (size_t)n);
     return FS_OK;
 }
 
@@ -3233,15 +3271,6 @@ int fs_get_frontier_costs_searched(fs_ctx *c, const double robot_pose7[7], int32
 namespace {
 
 #define RM_MAX_PER_CELL 20          // populateNodes throws once a cell holds more (FrontierRoadmap.cpp:244-248)
-#define RM_TREE_BATCH 16
-
-int rm_check_grid(fs_ctx *c)
-{
-    FS_HIP(c, hipSetDevice(c->device));
-    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
-    if (c->nz != 1) return fail(c, FS_E_INVALID, "the roadmap is defined on a 2-D costmap (nz == 1)");
-    return FS_OK;
-}
 
 int32_t rm_nodes(const fs_ctx *c) { return (int32_t)(c->rm_xy.size() / 2); }
 
@@ -3352,7 +3381,7 @@ int rm_tree(fs_ctx *c, int32_t root, const double **d, const int32_t **pred)
         int rc = rm_device_graph(c);
         if (rc) return rc;
         FS_HIP(c, c->d_rm_d.ensure(2 * nn)); FS_HIP(c, c->d_rm_hops.ensure(2 * nn)); FS_HIP(c, c->d_rm_pred.ensure(2 * nn));
-        FS_HIP(c, c->d_rm_word.ensure(RM_TREE_BATCH));
+        FS_HIP(c, c->d_rm_word.ensure(PLAN_BATCH));
         FsRmTree t{n, root, c->d_rm_xy.p, c->d_rm_trow.p, c->d_rm_tcol.p, {c->d_rm_d.p, c->d_rm_d.p + nn}, {c->d_rm_hops.p, c->d_rm_hops.p + nn},
                    {c->d_rm_pred.p, c->d_rm_pred.p + nn}};
         FS_HIP(c, fs_launch_rm_tree_init(t, c->stream));
@@ -3367,20 +3396,12 @@ int rm_tree(fs_ctx *c, int32_t root, const double **d, const int32_t **pred)
             if (r < 0) return fail(c, FS_E_HIP, "the roadmap tree did not settle in %lld rounds", (long long)max_rounds);
             rounds = r;
         } else {
-            for (int64_t r = 0;;) {
-                FS_HIP(c, hipMemsetAsync(c->d_rm_word.p, 0, sizeof(int32_t) * RM_TREE_BATCH, c->stream));
-                for (int k = 0; k < RM_TREE_BATCH; ++k, ++r) FS_HIP(c, fs_launch_rm_tree_round(t, (int32_t)(r & 1), c->d_rm_word.p + k, c->stream));
-                int32_t any[RM_TREE_BATCH] = {0};
-                FS_HIP(c, hipMemcpyAsync(any, c->d_rm_word.p, sizeof any, hipMemcpyDeviceToHost, c->stream));
-                FS_HIP(c, hipStreamSynchronize(c->stream));
-                if (!any[RM_TREE_BATCH - 1]) {
-                    int k = 0;
-                    while (any[k]) ++k;                 // the first quiet round of the batch
-                    rounds = r - RM_TREE_BATCH + k + 1;
-                    break;
-                }
-                if (r >= max_rounds) return fail(c, FS_E_HIP, "the roadmap tree did not settle in %lld rounds", (long long)max_rounds);
-            }
+            const auto launch = [&](int64_t r0, int count) -> int {
+                for (int k = 0; k < count; ++k) FS_HIP(c, fs_launch_rm_tree_round(t, (int32_t)((r0 + k) & 1), c->d_rm_word.p + k, c->stream));
+                return FS_OK;
+            };
+            rc = poll_rounds(c, c->d_rm_word.p, PLAN_BATCH, PLAN_BATCH, 1, max_rounds, "the roadmap tree", max_rounds, launch, &rounds);
+            if (rc) return rc;
         }
         c->rm_tree_buf = (int32_t)(rounds & 1);        // (after the quiet round both buffers hold the tree)
         c->rm_tree_gen = c->rm_gen; c->rm_tree_root = root;
@@ -3392,18 +3413,12 @@ int rm_tree(fs_ctx *c, int32_t root, const double **d, const int32_t **pred)
     return FS_OK;
 }
 
-// Output block of the plan kernel in d_rm_out: path length | length in m | heading | achievable.
-struct RmOutLayout {
-    size_t len, len_m, head, ach, total;
-    explicit RmOutLayout(size_t n) : len(0), len_m(8 * n), head(16 * n), ach(24 * n), total(24 * n + ((n + 15) & ~(size_t)15)) {}
-};
-
 // Start node, tree (cached or built), goals staged, the plan kernel: the four columns land in d_rm_out on the context's stream.
 int roadmap_plan_enqueue(fs_ctx *c, const double robot7[7], int32_t n, const double *goal_xyz, const uint8_t *achievable_in)
 {
     const size_t nn = (size_t)n;
     const size_t i_goal = 0, i_head = 16 * nn, i_mode = 24 * nn, total_in = 24 * nn + nn;
-    const RmOutLayout O(nn);
+    const PlanOutLayout O(nn);
     FS_HIP(c, c->h_rm_in.ensure(total_in)); FS_HIP(c, c->d_rm_in.ensure(total_in));
     FS_HIP(c, c->d_rm_out.ensure(O.total));
     double *goal = reinterpret_cast<double *>(c->h_rm_in.p + i_goal), *head = reinterpret_cast<double *>(c->h_rm_in.p + i_head);
@@ -3476,7 +3491,7 @@ int64_t kf_bases(const fs_ctx *c, bool present_only, std::vector<int32_t> &base)
 }
 
 // the de-duplication rounds (fs_roadmap_kf.hip): one workgroup's loop up to kf_one_wg points, a round per launch above it, polled in
-// batches of RM_TREE_BATCH.  Returns the rounds run (the last one quiet) through *rounds.
+// batches of PLAN_BATCH.  Returns the rounds run (the last one quiet) through *rounds.
 int kf_dedup_rounds(fs_ctx *c, const FsKfDedup &d, int64_t *rounds)
 {
     const int64_t max_rounds = (int64_t)d.m + 1;
@@ -3485,20 +3500,13 @@ int kf_dedup_rounds(fs_ctx *c, const FsKfDedup &d, int64_t *rounds)
         *rounds = -2;                   // read from hdr[2] with the results
         return FS_OK;
     }
-    FS_HIP(c, c->d_kf_word.ensure(RM_TREE_BATCH));
-    int64_t r = 0;
-    int src = 0;
-    for (;;) {
-        FS_HIP(c, hipMemsetAsync(c->d_kf_word.p, 0, sizeof(int32_t) * RM_TREE_BATCH, c->stream));
-        for (int k = 0; k < RM_TREE_BATCH; ++k, src ^= 1) FS_HIP(c, fs_launch_kf_dedup_round(d, src, c->d_kf_word.p + k, c->stream));
-        int32_t any[RM_TREE_BATCH];
-        FS_HIP(c, hipMemcpyAsync(any, c->d_kf_word.p, sizeof any, hipMemcpyDeviceToHost, c->stream));
-        FS_HIP(c, hipStreamSynchronize(c->stream));
-        for (int k = 0; k < RM_TREE_BATCH; ++k)
-            if (!any[k]) { *rounds = r + k + 1; return FS_OK; }
-        r += RM_TREE_BATCH;
-        if (r > max_rounds) return fail(c, FS_E_HIP, "the de-duplication did not settle in %lld rounds", (long long)max_rounds);
-    }
+    FS_HIP(c, c->d_kf_word.ensure(PLAN_BATCH));
+    const auto launch = [&](int64_t r0, int count) -> int {
+        for (int k = 0; k < count; ++k) FS_HIP(c, fs_launch_kf_dedup_round(d, (int)((r0 + k) & 1), c->d_kf_word.p + k, c->stream));
+        return FS_OK;
+    };
+    // (fails once more than m + 1 rounds have run)
+    return poll_rounds(c, c->d_kf_word.p, PLAN_BATCH, PLAN_BATCH, 1, max_rounds + 1, "the de-duplication", max_rounds, launch, rounds);
 }
 
 }  // namespace
@@ -3566,7 +3574,7 @@ int fs_roadmap_add_nodes(fs_ctx *c, int32_t n, const double *xy, int32_t is_robo
 int fs_roadmap_rebuild(fs_ctx *c)
 {
     if (!c) return FS_E_INVALID;
-    int rc = rm_check_grid(c);
+    int rc = grid2d_check(c, "the roadmap");
     if (rc) return rc;
     const int32_t n = rm_nodes(c);
     ++c->rm_gen;
@@ -3620,7 +3628,7 @@ int fs_roadmap_connect(fs_ctx *c, int32_t n, const double *xy)
     if (!c) return FS_E_INVALID;
     if (n < 0 || (n > 0 && !xy)) return fail(c, FS_E_INVALID, "null pointer");
     if (!rm_finite_xy(xy, n, 2)) return fail(c, FS_E_INVALID, "non-finite point");
-    int rc = rm_check_grid(c);
+    int rc = grid2d_check(c, "the roadmap");
     if (rc) return rc;
     const int32_t nodes = rm_nodes(c);
     if (n == 0 || nodes == 0) return FS_OK;      // (an empty hash: the reference's closest-node search would not return)
@@ -3772,7 +3780,7 @@ int fs_roadmap_set_keyframes(fs_ctx *c, int32_t n, const int32_t *kf_id, const d
 int fs_roadmap_optimize(fs_ctx *c)
 {
     if (!c) return FS_E_INVALID;
-    int rc = rm_check_grid(c);
+    int rc = grid2d_check(c, "the roadmap");
     if (rc) return rc;
     // optimizeSHM's sequence: the records of the latest message's key frames in keyframe_mapping_'s order, re-placed
     std::vector<int32_t> tab;
@@ -3894,18 +3902,8 @@ int fs_roadmap_plan(fs_ctx *c, const double robot_pose7[7], int32_t n, const dou
         return fail(c, FS_E_INVALID, "null pointer");
     FS_HIP(c, hipSetDevice(c->device));
     if (n == 0) return FS_OK;
-    int rc = roadmap_plan_enqueue(c, robot_pose7, n, goal_xyz, achievable_in);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    const size_t nn = (size_t)n;
-    const RmOutLayout O(nn);
-    FS_HIP(c, c->h_rm_out.ensure(O.total));
-    FS_HIP(c, hipMemcpyAsync(c->h_rm_out.p, c->d_rm_out.p, O.total, hipMemcpyDeviceToHost, c->stream));
-    FS_HIP(c, hipStreamSynchronize(c->stream));
-    std::memcpy(path_length, c->h_rm_out.p + O.len, 8 * nn);
-    std::memcpy(path_length_m, c->h_rm_out.p + O.len_m, 8 * nn);
-    std::memcpy(path_heading, c->h_rm_out.p + O.head, 8 * nn);
-    std::memcpy(achievable, c->h_rm_out.p + O.ach, nn);
-    return FS_OK;
+    return plan_to_host(c, c->d_rm_out, c->h_rm_out, n, [&] { return roadmap_plan_enqueue(c, robot_pose7, n, goal_xyz, achievable_in); },
+                        path_length, path_length_m, path_heading, achievable);
 }
 
 int fs_get_frontier_costs_roadmap(fs_ctx *c, const double robot_pose7[7], int32_t n, const double *goal_xyz, const int32_t *frontier_size,
@@ -3919,20 +3917,13 @@ int fs_get_frontier_costs_roadmap(fs_ctx *c, const double robot_pose7[7], int32_
     if (n == 0) return FS_OK;
     int rc = check_scoring_state(c, true, with_fisher_information != 0);
     if (rc) return rc;
-    const size_t nn = (size_t)n;
-    const RmOutLayout O(nn);
-    FS_HIP(c, c->h_rm_out.ensure(O.total));
-    rc = roadmap_plan_enqueue(c, robot_pose7, n, goal_xyz, nullptr);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if (path_length_m) FS_HIP(c, hipMemcpyAsync(c->h_rm_out.p + O.len_m, c->d_rm_out.p + O.len_m, 8 * nn, hipMemcpyDeviceToHost, c->stream));
-    // the planner's columns stay where the plan kernel wrote them: scoring reads its achievability, ranking its path columns
-    const PlannedCols cols{reinterpret_cast<const uint8_t *>(c->d_rm_out.p + O.ach), reinterpret_cast<const double *>(c->d_rm_out.p + O.len),
-                           reinterpret_cast<const double *>(c->d_rm_out.p + O.head)};
-    rc = frontier_costs_core(c, n, goal_xyz, frontier_size, blacklisted, nullptr, nullptr, nullptr, alpha, beta, max_vx, max_wz,
-                             with_fisher_information != 0, records, weighted_cost, arrival_utility, distance_utility, order, &cols);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if (path_length_m) std::memcpy(path_length_m, c->h_rm_out.p + O.len_m, 8 * nn);
-    return FS_OK;
+    return rank_on_plan(
+        c, c->d_rm_out, c->h_rm_out, n, [&] { return roadmap_plan_enqueue(c, robot_pose7, n, goal_xyz, nullptr); },
+        [&](const PlannedCols &cols) {
+            return frontier_costs_core(c, n, goal_xyz, frontier_size, blacklisted, nullptr, nullptr, nullptr, alpha, beta, max_vx, max_wz,
+                                       with_fisher_information != 0, records, weighted_cost, arrival_utility, distance_utility, order, &cols);
+        },
+        path_length_m);
 }
 
 }  // extern "C"
@@ -4019,7 +4010,7 @@ int tour_enqueue(fs_ctx *c, const FsRmPairArgs &pa_in, int32_t K, const int32_t 
     const size_t nn = (size_t)n;
     FsRmPairArgs pa = pa_in;
     FS_HIP(c, c->d_tour_work.ensure(kTourWork)); FS_HIP(c, c->h_tour_out.ensure(kTourOut));
-    FS_HIP(c, c->d_tour_word.ensure(std::max(RM_TREE_BATCH, RM_TOUR_MAX_TREES)));
+    FS_HIP(c, c->d_tour_word.ensure(std::max(PLAN_BATCH, RM_TOUR_MAX_TREES)));
     *polled = false;
     *rounds_out = 0;
     if (K > 0) {
@@ -4039,20 +4030,12 @@ int tour_enqueue(fs_ctx *c, const FsRmPairArgs &pa_in, int32_t K, const int32_t 
                                      c->stream));
         } else {
             *polled = true;
-            for (int64_t r = 0;;) {
-                FS_HIP(c, hipMemsetAsync(c->d_tour_word.p, 0, sizeof(int32_t) * RM_TREE_BATCH, c->stream));
-                for (int q = 0; q < RM_TREE_BATCH; ++q, ++r) FS_HIP(c, fs_launch_rm_batch_round(B, (int32_t)(r & 1), c->d_tour_word.p + q, c->stream));
-                int32_t any[RM_TREE_BATCH] = {0};
-                FS_HIP(c, hipMemcpyAsync(any, c->d_tour_word.p, sizeof any, hipMemcpyDeviceToHost, c->stream));
-                FS_HIP(c, hipStreamSynchronize(c->stream));
-                if (!any[RM_TREE_BATCH - 1]) {
-                    int q = 0;
-                    while (any[q]) ++q;
-                    *rounds_out = r - RM_TREE_BATCH + q + 1;
-                    break;
-                }
-                if (r >= max_rounds) return fail(c, FS_E_HIP, "the tour trees did not settle in %lld rounds", (long long)max_rounds);
-            }
+            const auto launch = [&](int64_t r0, int count) -> int {
+                for (int k = 0; k < count; ++k) FS_HIP(c, fs_launch_rm_batch_round(B, (int32_t)((r0 + k) & 1), c->d_tour_word.p + k, c->stream));
+                return FS_OK;
+            };
+            rc = poll_rounds(c, c->d_tour_word.p, PLAN_BATCH, PLAN_BATCH, 1, max_rounds, "the tour trees", max_rounds, launch, rounds_out);
+            if (rc) return rc;
         }
         // (after its quiet round both buffers of a tree hold it: buffer 0 is read)
         pa.d = c->d_tour_d.p; pa.pred = c->d_tour_pred.p;
@@ -4180,16 +4163,10 @@ int fs_roadmap_next_goal(fs_ctx *c, const double robot_pose7[7], int32_t n, cons
 
 namespace {
 
-// Rounds are launched in batches and polled as the grid planner's are (a round after a quiet round is quiet too).
-#define RF_BATCH_FIRST 8
-#define RF_BATCH 16
-#define RF_MAX_ROUNDS (1 << 22)
-
 int rf_check(fs_ctx *c, double w_euc, double w_trav, int32_t corners)
 {
-    FS_HIP(c, hipSetDevice(c->device));
-    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
-    if (c->nz != 1) return fail(c, FS_E_INVALID, "the leg refinement is defined on a 2-D costmap (nz == 1)");
+    const int rc = grid2d_check(c, "the leg refinement");
+    if (rc) return rc;
     if (corners != 4 && corners != 8) return fail(c, FS_E_INVALID, "corners must be 4 or 8");
     // (w_euc > 0 makes the field's fixed point unique; the bounds keep DBL_MAX an absorbing "not reached")
     if (!(w_euc > 0.0 && w_euc <= 1e6) || !(w_trav >= 0.0 && w_trav <= 1e6)) return fail(c, FS_E_INVALID, "weights outside 0 < w_euc <= 1e6, 0 <= w_traversal <= 1e6");
@@ -4243,30 +4220,19 @@ int rf_fields(fs_ctx *c, const fs_ctx::RfKey &base, const std::vector<int32_t> &
     rf_moves(base.w_euc, a.e);
     const size_t tiles = (size_t)a.tx * (size_t)a.ty;
     FS_HIP(c, c->d_rf_flags.ensure(2 * (size_t)a.n * tiles));
-    FS_HIP(c, c->d_rf_any.ensure((size_t)RF_BATCH * a.n));
+    FS_HIP(c, c->d_rf_any.ensure((size_t)PLAN_BATCH * a.n));
     uint32_t *flags[2] = {c->d_rf_flags.p, c->d_rf_flags.p + (size_t)a.n * tiles};
     for (int i = 0; i < a.n; ++i) c->rf_gen[a.f[i].slot] = 0;      // (until the build has finished)
     FS_HIP(c, fs_launch_refine_init(a, flags[0], c->stream));
-    std::vector<int64_t> rounds((size_t)a.n, -1);
-    std::vector<int32_t> any((size_t)RF_BATCH * a.n);
-    int64_t r = 0;
-    for (int batch = RF_BATCH_FIRST;; batch = RF_BATCH) {
-        FS_HIP(c, hipMemsetAsync(c->d_rf_any.p, 0, sizeof(int32_t) * batch * a.n, c->stream));
-        for (int k = 0; k < batch; ++k, ++r)
+    const auto launch = [&](int64_t r0, int count) -> int {
+        for (int64_t k = 0, r = r0; k < count; ++k, ++r)
             FS_HIP(c, fs_launch_refine_round(a, flags[r & 1], flags[(r + 1) & 1], c->d_rf_any.p + (size_t)k * a.n, c->stream));
-        FS_HIP(c, hipMemcpyAsync(any.data(), c->d_rf_any.p, sizeof(int32_t) * batch * a.n, hipMemcpyDeviceToHost, c->stream));
-        FS_HIP(c, hipStreamSynchronize(c->stream));
-        bool done = true;
-        for (int f = 0; f < a.n; ++f) {
-            if (rounds[f] >= 0) continue;
-            int k = 0;
-            while (k < batch && any[(size_t)k * a.n + f]) ++k;
-            if (k < batch) rounds[f] = r - batch + k + 1;           // the first quiet round of the batch: the field's last round
-            else done = false;
-        }
-        if (done) break;
-        if (r >= RF_MAX_ROUNDS) return fail(c, FS_E_HIP, "cost field did not settle in %d rounds", RF_MAX_ROUNDS);
-    }
+        return FS_OK;
+    };
+    std::vector<int64_t> rounds((size_t)a.n);
+    const int rc = poll_rounds(c, c->d_rf_any.p, PLAN_BATCH_FIRST, PLAN_BATCH, a.n, PLAN_MAX_ROUNDS, "cost field", PLAN_MAX_ROUNDS, launch,
+                               rounds.data());
+    if (rc) return rc;
     for (int i = 0; i < a.n; ++i) {
         fs_ctx::RfKey k = base;
         k.src = a.f[i].src;
@@ -4296,7 +4262,7 @@ int fs_refine_field(fs_ctx *c, const double start_xy[2], int32_t allow_unknown, 
     int rc = rf_check(c, w_euc, w_traversal, corners);
     if (rc) return rc;
     int32_t sx = 0, sy = 0;
-    if (!nav_world_to_map(c, start_xy[0], start_xy[1], sx, sy)) return fail(c, FS_E_INVALID, "the start is off the costmap: no field");
+    if (!grid_world_to_map(c, start_xy[0], start_xy[1], sx, sy)) return fail(c, FS_E_INVALID, "the start is off the costmap: no field");
     fs_ctx::RfKey base;
     base.allow = allow_unknown ? 1 : 0; base.corners = corners; base.w_euc = w_euc; base.w_trav = w_traversal;
     std::vector<int32_t> slot;
@@ -4326,8 +4292,8 @@ int fs_refine_paths(fs_ctx *c, int32_t n, const double *start_xy, const double *
     std::map<int32_t, int32_t> seen;
     for (size_t i = 0; i < nn; ++i) {
         int32_t sx = 0, sy = 0, gx = 0, gy = 0;
-        if (!nav_world_to_map(c, start_xy[2 * i], start_xy[2 * i + 1], sx, sy)) { pre[i] = FS_REFINE_START_OFF_MAP; continue; }
-        if (!nav_world_to_map(c, goal_xy[2 * i], goal_xy[2 * i + 1], gx, gy)) { pre[i] = FS_REFINE_GOAL_OFF_MAP; continue; }
+        if (!grid_world_to_map(c, start_xy[2 * i], start_xy[2 * i + 1], sx, sy)) { pre[i] = FS_REFINE_START_OFF_MAP; continue; }
+        if (!grid_world_to_map(c, goal_xy[2 * i], goal_xy[2 * i + 1], gx, gy)) { pre[i] = FS_REFINE_GOAL_OFF_MAP; continue; }
         scell[i] = sy * nx + sx; gcell[i] = gy * nx + gx;
         auto it = seen.find(scell[i]);
         if (it == seen.end()) { it = seen.emplace(scell[i], (int32_t)srcs.size()).first; srcs.push_back(scell[i]); }

@@ -148,6 +148,39 @@ def test_plan_equals_tree_leg_and_astar_achievability(name, cells, origin):
         sc.close(); ref.close()
 
 
+def test_plan_on_a_large_roadmap_takes_the_round_per_launch_tree():
+    """Above RM_TREE_ONE_WG (16 384) nodes the tree is relaxed one round per launch, polled in batches; small cells and a short
+    edge radius keep the restatement's rebuild short."""
+    name, cells, origin = next(m for m in MAPS if m[0] == "plan11_1024")
+    ny, nx = cells.shape
+    rng = np.random.default_rng(16385)
+    gx, gy = np.meshgrid(np.arange(0.1, nx * RES, 0.27), np.arange(0.1, ny * RES, 0.27))
+    pts = np.stack([gx.ravel(), gy.ravel()], axis=1) + rng.uniform(-0.01, 0.01, (gx.size, 2))
+    ix, iy = (pts[:, 0] / RES).astype(int), (pts[:, 1] / RES).astype(int)
+    pts = pts[cells[iy, ix] == 0] + np.array(origin[:2])
+    sc = fsmod.FrontierScorer(device=0)
+    sc.upload_grid(cells[None], origin, RES)
+    sc.set_roadmap_params(grid_cell_size=0.5, radius_to_decide_edges=0.6)
+    ref = R.Roadmap(cells, origin, RES, grid_cell_size=0.5, radius=0.6)
+    try:
+        assert ref.populate(pts) == 0
+        sc.roadmap_add_nodes(pts)
+        ref.rebuild(); sc.roadmap_rebuild()
+        assert sc.roadmap_graph()["xy"].shape[0] > 16384
+        rx, ry = pts[rng.integers(pts.shape[0])]
+        pose = R.pose7(rx, ry, 0.4)
+        goals, ach = _goals(cells, origin, 16386, 2000, (rx, ry))
+        sc.get_counter(1006, reset=True)
+        got = sc.roadmap_plan(pose, goals, achievable_in=ach)
+        want = ref.plan(pose, goals, achievable_in=ach)
+        for k in ("path_length", "path_length_m", "path_heading", "achievable"):
+            assert got[k].tobytes() == want[k].tobytes(), k
+        assert sc.get_counter(1006) > 0
+        assert got["achievable"].sum() > 0
+    finally:
+        sc.close(); ref.close()
+
+
 def test_plan_on_an_empty_and_a_keyless_roadmap():
     cells = np.zeros((80, 80), dtype=np.uint8)
     origin = (0.0, 0.0, 0.0)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — candidate-goals scored per second (ray-cast + FIM) on a 512^3 grid (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -21,8 +21,15 @@ equal WORLD_SIZE or the run fails.  Rank 0 prints ONE JSON line.
 
 Timing: W untimed warm-up steps, then ONE timed window of exactly K steps, bracketed by barrier + torch.cuda.synchronize
 on both sides and reduced with MAX over the ranks; `ms_per_step` is that window over K and `value` the candidates it
-scored per second.  The per-kernel hipEvent pairs the roofline needs cost ~3 % of a step, so they ride on one more block
-of K steps after the timed window, never in it.
+scored per second.  The per-kernel hipEvent pairs the roofline needs cost ~3 % of a step, so under --full they ride on one
+more block of K steps after the timed window, never in it.
+
+Plain run and --full: a plain run sets up, warms up, times its K steps, writes --dump-outputs if asked and prints the line;
+nothing else.  --full adds, after the timed window and without changing it, everything that takes runs of its own: the
+per-kernel block behind `kernels_ms_per_step` and the roofline's launch figures, the CPU baselines and the parity gates
+against the oracle, the other operating points (host-buffer path, cold cost map, map updates, the other visibility volume),
+the ranked step, and at N > 1 the strong-scaling block and the all-gather timed by itself.  In a plain line those entries
+are null.
 
 Outputs: --dump-outputs DIR writes the records the timed path returned in its last timed step (the gathered list at
 N > 1) as DIR/<field>.npy, one float32 / float64 array per record field, every value finite: the -inf logdet of a
@@ -64,19 +71,20 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=20, help="timed steps: ms_per_step = the one timed window over this many steps")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the records of the last timed step as DIR/<field>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true", help="after the timed window, also measure and check everything beyond the headline: per-kernel times and the roofline, CPU baselines and parity gates, the other operating points, the ranked step, strong scaling and the all-gather at N > 1 (off: the line carries null there)")
     ap.add_argument("--pipeline", type=int, default=1, help="scorer contexts (HIP streams) per GPU; successive batches alternate over them (1, the default = one stream, batches strictly back to back; 2 measured +2 %% on C3, but the two FIM kernels then share the CUs and their per-launch durations no longer measure the kernel)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--workload", default="C3", help="C3 (headline) | C5 | REF2D (the reference's own 2-D operating point: 63 rays, L = 40) | C2 | C1")
     ap.add_argument("--depth-cells", type=int, default=0, help="ray length L in cells (0: the config's 40 = 2 m; BASELINE.md's secondary throughput run uses 160)")
-    ap.add_argument("--fim-angle", type=float, default=1.0, help="visibility cone half-angle in rad for the timed steps (1.0: the build's definition, SURVEY.md App. A.3; 4.0 = the reference's own request, FisherInfoManager.cpp:63-64: cone off).  The N = 1 line always carries the other one under other_operating_points.reference_request_visibility")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample time (three runs, median); 0 disables")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the strong-scaling block (160 k candidates split over the ranks) that follows the weak blocks")
+    ap.add_argument("--fim-angle", type=float, default=1.0, help="visibility cone half-angle in rad for the timed steps (1.0: the build's definition, SURVEY.md App. A.3; 4.0 = the reference's own request, FisherInfoManager.cpp:63-64: cone off).  The N = 1 line of --full carries the other one under other_operating_points.reference_request_visibility")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: target CPU-baseline sample time (three runs, median); 0 disables")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the parity gates and the other operating points")
+    ap.add_argument("--no-strong", action="store_true", help="--full at N > 1: skip the strong-scaling block (160 k candidates split over the ranks) that follows the weak blocks")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL over xGMI; the measured configuration) | gloo (rehearsal of the N > 1 path on one GPU: ranks share the device, records are gathered through host memory)")
     ap.add_argument("--option", action="append", default=[], metavar="KEY=VALUE", help="fs_set_option knobs, e.g. ray.layout=2")
     ap.add_argument("--latency", action="store_true", help="the drop-in operating point instead of the throughput line: p50 / p99 of ONE fs_score_candidates call (host buffers in, records out, synchronised) at 1 / 50 / 200 / 2000 frontiers on REF2D and C1, of fs_score_fim(n = 1) and of fs_frontier_clusters on a 512^2 costmap, each with the oracle's single-thread time beside it")
     ap.add_argument("--latency-calls", type=int, default=300, help="calls per latency figure")
-    ap.add_argument("--rehearse-multi", action="store_true", help="one rank, but through every code path of the N > 1 run: a one-rank RCCL group, the asynchronous all-gather in every step, the ranking on the gathered list, the multi_gpu keys and the block-sampled parity gate (what a one-GPU box can rehearse of the multi-GPU line; never a scaling figure)")
+    ap.add_argument("--rehearse-multi", action="store_true", help="one rank, but through every code path of the N > 1 run: a one-rank RCCL group, the asynchronous all-gather in every step, the multi_gpu keys and, with --full, the ranking on the gathered list, the all-gather by itself and the block-sampled parity gate (what a one-GPU box can rehearse of the multi-GPU line; never a scaling figure)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous rehearsal without a GPU: the ranks meet over gloo, all-gather a dummy record block and rank 0 prints a line marked dry_run (no value)")
     args = ap.parse_args(argv)
     if args.steps < 1:
@@ -820,16 +828,6 @@ def run_rank(args) -> int:
     timed_rec = shard.records_to_numpy(full) if rank == 0 else None
     # landmark tests per candidate on this rank, over the timed steps
     m_tested = sum(c.get_counter(0, reset=True) for c in scs) / (args.steps * n_local)
-    # Per-kernel hipEvent pairs cost ~0.035 ms per step (measured: 1.06 vs 1.024 ms), so the roofline's launch durations come
-    # from one more block of K steps after the timed window
-    for c in scs:
-        c.enable_kernel_timing(True)
-        for kind in range(5):
-            c.kernel_time(kind)
-    for _ in range(args.steps):
-        step()
-    fence()
-    n_steps_ev = args.steps                                          # steps of the block that carried the events
 
     def kernel_sum(kind):
         ms, n = 0.0, 0
@@ -838,13 +836,24 @@ def run_rank(args) -> int:
             ms, n = ms + a, n + b
         return ms, n
 
-    ray_ms, ray_n = kernel_sum(0)
-    fim_ms, fim_n = kernel_sum(1)
-    ovf_ms, ovf_n = kernel_sum(2)
-    sort_ms, sort_n = kernel_sum(4)
-    multipass, tier3 = sum(c.get_counter(4) for c in scs), sum(c.get_counter(5) for c in scs)
-    for c in scs:
-        c.enable_kernel_timing(False)
+    # A plain run has done its work (setup, warm-up, the timed window): what follows up to the result line runs under --full
+    # only, save the reduction of the timed window over the ranks at N > 1.
+    # Per-kernel hipEvent pairs cost ~0.035 ms per step (measured: 1.06 vs 1.024 ms), so the roofline's launch durations come
+    # from one more block of K steps after the timed window
+    kernels = None
+    if args.full:
+        for c in scs:
+            c.enable_kernel_timing(True)
+            for kind in range(5):
+                c.kernel_time(kind)
+        for _ in range(args.steps):
+            step()
+        fence()
+        kernels = {"steps": args.steps,                              # steps of the block that carried the events
+                   "ray": kernel_sum(0), "fim": kernel_sum(1), "ovf": kernel_sum(2), "sort": kernel_sum(4),
+                   "multipass": sum(c.get_counter(4) for c in scs), "tier3": sum(c.get_counter(5) for c in scs)}
+        for c in scs:
+            c.enable_kernel_timing(False)
 
     # Two more operating points of the same workload, outside the timed region (N = 1 only), for the record:
     #  * host-buffer path: fs_score_candidates with the candidate columns in host memory and the records back in host memory —
@@ -854,7 +863,7 @@ def run_rank(args) -> int:
     #    (DESIGN.md 4.1); the timed loop scores one list over and over, so its map is perfectly trained.  A call whose
     #    predecessor recorded nothing (option sort.costmap off for one call) sees the empty map of a first call on a new snapshot.
     extra = {}
-    if not multi_path and not args.no_parity:
+    if args.full and not multi_path and not args.no_parity:
         g_h, f_h, b_h = blk_goals, blk_fsize, blk_black
         for _ in range(3):
             sc.score_candidates(g_h, f_h, b_h)
@@ -901,7 +910,7 @@ def run_rank(args) -> int:
     # DEP/src/nav2_plugins/lethal_marker.cpp:305-325); fs_update_grid_region sends that window alone, fs_upload_grid the whole map.
     # Each followed by one scoring step (the snapshot's re-cuts the whole class image, the window's nothing but its bricks).  The
     # window holds the cells the map already has there, so the timed loop's map — and every figure above — is unchanged.
-    if not multi_path and not args.no_parity and wl_name != "C5":
+    if args.full and not multi_path and not args.no_parity and wl_name != "C5":
         nz_, ny_, nx_ = w.cells.shape
         sx_, sy_, sz_ = min(64, nx_), min(64, ny_), min(16, nz_)
         x0_, y0_, z0_ = (nx_ - sx_) // 2, (ny_ - sy_) // 2, (nz_ - sz_) // 2
@@ -930,7 +939,7 @@ def run_rank(args) -> int:
                                          "note": "fs_update_grid_region of one window (from a strided view of the host map) / fs_upload_grid of the whole map, "
                                                  "each followed by one synchronised scoring step; medians of 5; host map in pageable memory"}
 
-    if not multi_path and not args.no_parity:
+    if args.full and not multi_path and not args.no_parity:
         extra["reference_request_visibility" if args.fim_angle < np.pi else "build_cone_visibility"] = other_visibility(
             args, sc, w, n_local, d_goal, d_fsize, d_black, torch.zeros_like(d_recs[0]), dev, mx, arrival_kw)
 
@@ -940,7 +949,7 @@ def run_rank(args) -> int:
     # straight-line distance from the map's centre and the bearing as heading.  One block of K steps, same bracketing; reported
     # next to `value`, never instead of it.  (Path columns: see below.)
     ranked = None
-    if not multi_path or args.backend == "nccl":
+    if args.full and (not multi_path or args.backend == "nccl"):
         # (a function of the list index alone — a low-discrepancy sequence over [0.5, 30] m and [0, pi] rad — so that no rank
         # needs the other ranks' goal points and the columns are the same at every N)
         idx = np.arange(n_total, dtype=np.float64)
@@ -992,7 +1001,7 @@ def run_rank(args) -> int:
     # this workload, cut into `world` contiguous shares (fs_multi_shard_bounds' rule); a rank draws only the blocks its share
     # touches.  Same step (score + the one all-gather), same bracketing, MAX over the ranks, median of three blocks of K steps.
     strong = None
-    if multi_path and args.scaling == "weak" and not args.no_strong:
+    if args.full and multi_path and args.scaling == "weak" and not args.no_strong:
         per_blk = cfg["n_cand"]
         n_tot_s = 8 * per_blk
         lo_s, hi_s = shard.shard_bounds(n_tot_s, world, rank)
@@ -1091,7 +1100,7 @@ def run_rank(args) -> int:
         dist.all_gather(everyone, mine)
         loc = np.array([float(t[0]) for t in everyone])                           # [rank], seconds
         gather_ms = None
-        if args.backend == "nccl":
+        if args.full and args.backend == "nccl":
             with torch.cuda.stream(streams[0]):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 for _ in range(5):
@@ -1110,7 +1119,7 @@ def run_rank(args) -> int:
                  "barrier_skew_ms": float((loc.max() - loc.min()) * 1e3),
                  "barrier_skew_note": "timed window: last rank ready minus first rank ready (each after its own K steps and gathers)",
                  "all_gather_ms": gather_ms,
-                 "all_gather_note": f"one blocking all_gather_into_tensor of {n_total} x 32 B between an event pair on the scorer's stream, mean of 20, max over ranks (nccl backend only)"}
+                 "all_gather_note": f"one blocking all_gather_into_tensor of {n_total} x 32 B between an event pair on the scorer's stream, mean of 20, max over ranks (nccl backend and --full only)"}
 
     exit_code = 0
     if rank == 0:
@@ -1127,15 +1136,31 @@ def run_rank(args) -> int:
         b_ray = R * E * (L + 1) + (2 * r_fp + 1) ** 2
         n_chunks = -(-m // 64)
         b_fim = m_tested * 12 + 32
-        launches_per_step = fim_n / max(1, n_steps_ev)
-        fim_avg_s = (fim_ms / max(fim_n, 1)) * 1e-3
-        achieved = (n_local * b_fim / max(launches_per_step, 1e-9)) / fim_avg_s / 1e9 if fim_n else None
+        # the figures of the per-kernel block (--full): null in a plain line
+        launch = dict.fromkeys(("achieved", "frac", "candidates_per_launch", "launches_per_step", "avg_launch_ms", "launches",
+                                "multi_pass_candidates", "hbm_table_candidates"))
+        kernels_ms = None
+        if kernels:
+            n_ev = kernels["steps"]
+            (ray_ms, ray_n), (fim_ms, fim_n), (ovf_ms, _), (sort_ms, _) = kernels["ray"], kernels["fim"], kernels["ovf"], kernels["sort"]
+            launches_per_step = fim_n / max(1, n_ev)
+            fim_avg_s = (fim_ms / max(fim_n, 1)) * 1e-3
+            achieved = (n_local * b_fim / max(launches_per_step, 1e-9)) / fim_avg_s / 1e9 if fim_n else None
+            launch.update({"achieved": achieved, "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+                           "candidates_per_launch": n_local / max(launches_per_step, 1e-9), "launches_per_step": launches_per_step,
+                           "avg_launch_ms": fim_ms / max(fim_n, 1), "launches": fim_n,
+                           "multi_pass_candidates": kernels["multipass"], "hbm_table_candidates": kernels["tier3"]})
+            kernels_ms = {"fs_raymarch_kernel": ray_ms / n_ev, "fs_fim_kernel": fim_ms / n_ev,
+                          "fs_fim_overflow_kernel": ovf_ms / n_ev, "candidate_sort": sort_ms / n_ev,
+                          "raymarch_algorithmic_GBps": (n_local * b_ray) / ((ray_ms / n_ev) * 1e-3) / 1e9 if ray_n else None,
+                          "from": "one block of K steps with per-kernel hipEvents after the timed window; with --pipeline > 1 "
+                                  "a kernel's duration includes the time it shares the chip with the other stream's kernels"}
         prof = counter_profile(wl_name, args.depth_cells, args.fim_angle)
         gpu_rec = timed_rec if not args.no_parity else None
         cpu, parity = (None, None)
-        if not multi_path and args.cpu_seconds > 0:
+        if args.full and not multi_path and args.cpu_seconds > 0:
             cpu, parity = cpu_baseline(w, arrival_kw, n_total, args.cpu_seconds, gpu_rec, mx, args.fim_angle)
-        elif multi_path and gpu_rec is not None:
+        elif args.full and multi_path and gpu_rec is not None:
             # no CPU baseline at N > 1 (rank 0, N = 1 only), but the gathered list is still gated: 96 candidates out of every
             # rank's block against the oracle
             per_blk = 96
@@ -1159,21 +1184,22 @@ def run_rank(args) -> int:
             "bound": "hbm",
             "limited_by": (prof or {}).get("bound"),
             "bound_evidence": (prof or {}).get("bound_evidence", "no counter profile of these kernel sources is committed: nominal HBM roofline per SURVEY.md 8(d)"),
-            "kernel": "fs_fim_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+            "kernel": "fs_fim_kernel", "achieved": launch["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": launch["frac"],
             "traffic": (prof or {}).get("fs_fim_kernel_hbm_bytes_per_launch"),
             "algorithmic_bytes_per_candidate": b_fim, "m_tested_per_candidate": m_tested,
             "index_bytes_per_candidate_not_counted": n_chunks * 16,
             "bruteforce_bytes_per_candidate": m * 12 + 32,
-            "candidates_per_launch": n_local / max(launches_per_step, 1e-9), "launches_per_step": launches_per_step,
-            "avg_launch_ms": fim_ms / max(fim_n, 1), "launches": fim_n,
-            "multi_pass_candidates": multipass, "hbm_table_candidates": tier3,
+            "candidates_per_launch": launch["candidates_per_launch"], "launches_per_step": launch["launches_per_step"],
+            "avg_launch_ms": launch["avg_launch_ms"], "launches": launch["launches"],
+            "multi_pass_candidates": launch["multi_pass_candidates"], "hbm_table_candidates": launch["hbm_table_candidates"],
             "whole_step_frac": (n_local * (b_fim + b_ray) / (dt / args.steps)) / 1e9 / HBM_PEAK_GBS,
             "counters": ({k: prof[k] for k in ("source_hash", "valu_issue_utilisation", "valu_peak_wave_insts_per_cycle_per_simd",
                                                 "fs_fim_kernel", "collected_with") if k in prof} if prof else None),
             "note": "achieved = candidates per launch x (M_tested*12 + 32) B / average hipEvent launch time of fs_fim_kernel, "
                     "measured live on the scorer's stream; the 1.2 MB cloud is served from L2 after the first touch, so "
-                    "algorithmic GB/s is not HBM traffic (traffic = PMC bytes per launch when a matching profile exists)",
+                    "algorithmic GB/s is not HBM traffic (traffic = PMC bytes per launch when a matching profile exists); "
+                    "the launch figures come from the per-kernel block of --full and are null without it",
         }
         line = {
             "metric": METRIC,
@@ -1190,18 +1216,14 @@ def run_rank(args) -> int:
             "timing": {"timed_steps": args.steps, "timed_seconds_total": dt,
                        "value_from": "one window of --steps steps, barrier + synchronize on both sides, max over the ranks; no per-kernel events in it"},
             "roofline": roofline,
-            "kernels_ms_per_step": {"fs_raymarch_kernel": ray_ms / n_steps_ev, "fs_fim_kernel": fim_ms / n_steps_ev,
-                                    "fs_fim_overflow_kernel": ovf_ms / n_steps_ev, "candidate_sort": sort_ms / n_steps_ev,
-                                    "raymarch_algorithmic_GBps": (n_local * b_ray) / ((ray_ms / n_steps_ev) * 1e-3) / 1e9 if ray_n else None,
-                                    "from": "one block of K steps with per-kernel hipEvents after the timed window; with --pipeline > 1 "
-                                            "a kernel's duration includes the time it shares the chip with the other stream's kernels"},
+            "kernels_ms_per_step": kernels_ms,
             "cpu_baseline": cpu, "parity": parity,
             "ranked_step": ({"ms_per_step": ranked["dt"] / args.steps * 1e3, "candidate_goals_per_s": n_total * args.steps / ranked["dt"],
                              "rank_kernels_ms_per_step": ranked["rank_kernels_ms_per_step"], "range_error": ranked["range_error"],
                              "order_is_a_permutation": ranked["order_is_a_permutation"], "costs_ascending": ranked["costs_ascending"],
                              "note": "score (+ all-gather) + fs_rank_candidates_dev over the full list on the same stream, path columns resident; "
                                      "one block of K steps; never `value`"} if ranked else None),
-            "multi_gpu": multi, "strong_scaling": strong, "rehearse_multi": bool(args.rehearse_multi) or None,
+            "multi_gpu": multi, "strong_scaling": strong, "rehearse_multi": bool(args.rehearse_multi) or None, "full": bool(args.full),
             "other_operating_points": extra or None,
         }
         print(json.dumps(line), flush=True)

@@ -48,6 +48,15 @@ def test_defaults_are_the_headline_configuration():
     assert a.pipeline == 1 and b.parse(["--pipeline", "2"]).pipeline == 2
 
 
+def test_full_is_off_by_default():
+    """A plain run times the headline alone; everything that takes runs of its own waits for --full, which travels to the
+    ranks with the other arguments."""
+    b = _bench_module()
+    assert b.parse([]).full is False and b.parse(["--full"]).full is True
+    argv = ["--gpus", "2", "--full"]
+    assert b.launcher_command(b.parse(argv), argv, port=12345)[-1] == "--full"
+
+
 def test_steps_is_the_number_of_timed_steps():
     """--steps K is the whole timed window (ms_per_step = window / K): nothing may stretch it to more steps, and it has one."""
     b = _bench_module()

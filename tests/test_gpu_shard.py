@@ -77,7 +77,7 @@ def test_bench_rehearses_the_multi_gpu_line_on_one_gpu(fs, tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rehearse-multi", "--workload", "C2", "--steps", "3", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rehearse-multi", "--full", "--workload", "C2", "--steps", "3", "--warmup", "2",
                         "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out_lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

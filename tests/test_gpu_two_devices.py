@@ -111,7 +111,7 @@ def test_bench_two_ranks_over_rccl():
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     # the driver's own command shape: weak scaling as `value`, the strong-scaling block behind it in the same line
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-                        "--warmup", "2"], env=env, capture_output=True, text=True, timeout=900)
+                        "--warmup", "2", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

@@ -225,7 +225,7 @@ def main():
     bad = [a for i, a in enumerate(args.bench_arg) if a.startswith("--gpus") and (a not in ("--gpus", "--gpus=1") or (a == "--gpus" and args.bench_arg[i + 1:i + 2] != ["1"]))]
     if bad:
         raise SystemExit("pmc_collect.py profiles one process: --gpus other than 1 is refused (profile the rank program, not the launcher)")
-    bench = [os.path.realpath(sys.executable), os.path.join(ROOT, "bench.py"), "--workload", args.workload, "--cpu-seconds", "0", "--no-parity"]
+    bench = [os.path.realpath(sys.executable), os.path.join(ROOT, "bench.py"), "--full", "--workload", args.workload, "--cpu-seconds", "0", "--no-parity"]
     if args.depth_cells:
         bench += ["--depth-cells", str(args.depth_cells)]
     bench += args.bench_arg
@@ -237,7 +237,7 @@ def main():
             fim_angle = float(arg.split("=", 1)[1])
     summary = {"source_hash": source_hash(), "workload": args.workload, "depth_cells": args.depth_cells, "fim_angle": fim_angle,
                "collected_with": "tools/pmc_collect.py: rocprofv3 --pmc <one counter set per pass> --kernel-trace --output-format csv -- "
-                                 "python3 bench.py --steps 6 --warmup 2 --cpu-seconds 0 --no-parity; means over the last 6 dispatches",
+                                 "python3 bench.py --full --steps 6 --warmup 2 --cpu-seconds 0 --no-parity; means over the last 6 dispatches",
                "counters_missing": []}
 
     if not args.skip_stats:

@@ -6,6 +6,7 @@ fallback — if the HIP library cannot be built/loaded or no gfx950 device is pr
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -16,6 +17,8 @@ from . import _build
 FS_OK, FS_E_INVALID, FS_E_NO_DEVICE, FS_E_HIP, FS_E_STATE, FS_E_IO, FS_E_RANGE = 0, -1, -2, -3, -4, -5, -6
 STATUS_OK, STATUS_OFF_MAP, STATUS_BLACKLISTED = 0, 1, 2
 FS_MAX_ELEV = 16
+FS_SEEDS_NEAREST, FS_SEEDS_REFERENCE = 0, 1
+SEED_ORDERS = {"nearest": FS_SEEDS_NEAREST, "reference": FS_SEEDS_REFERENCE}
 
 # every symbol include/fitslam_frontier.h declares
 EXPORTED_SYMBOLS = [
@@ -35,7 +38,7 @@ EXPORTED_SYMBOLS = [
     "fs_set_roadmap_params", "fs_roadmap_add_nodes", "fs_roadmap_rebuild", "fs_roadmap_connect", "fs_roadmap_get_graph", "fs_roadmap_plan",
     "fs_get_frontier_costs_roadmap", "fs_roadmap_next_goal", "fs_refine_paths", "fs_refine_field",
     "fs_roadmap_set_keyframes", "fs_roadmap_optimize", "fs_roadmap_get_anchors",
-    "fs_search_frontiers", "fs_get_frontier_costs_searched",
+    "fs_search_frontiers", "fs_get_frontier_costs_searched", "fs_set_frontier_seed_order",
 ]
 
 RECORD_DTYPE = np.dtype([("arrival", "<i4"), ("argmax", "<i4"), ("yaw", "<f4"), ("info_ref", "<f4"),
@@ -179,6 +182,7 @@ def load_library(build: bool = True):
     L.fs_refine_paths.argtypes = [vp, i32, vp, vp, i32, dbl, dbl, i32, vp, vp, vp, vp, vp, vp]
     L.fs_refine_field.argtypes = [vp, C.POINTER(dbl * 2), i32, dbl, dbl, i32, vp]
     L.fs_search_frontiers.argtypes = [vp, C.POINTER(dbl * 2), i32, dbl, i32, i32, i32, vp, i32, vp, C.POINTER(i32), i64, vp, C.POINTER(i64)]
+    L.fs_set_frontier_seed_order.argtypes = [vp, i32]
     L.fs_get_frontier_costs_searched.argtypes = [vp, C.POINTER(dbl * 7), i32, dbl, i32, i32, i32, i32, vp, dbl, dbl, dbl, dbl, C.c_int,
                                                  i32, vp, C.POINTER(i32), vp, vp, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
@@ -222,6 +226,7 @@ class FrontierScorer:
         self._h = h
         self._elev = (0.0,)
         self._grid_shape = None          # (nz, ny, nx) of the staged grid: what fs_navfn_potential writes
+        self._seed_order = "nearest"     # the context's frontier seed order (fs_set_frontier_seed_order)
         self.n_yaw = self.n_elev = self.window = 0
 
     # -- plumbing
@@ -325,12 +330,40 @@ class FrontierScorer:
     # a longer one costs a second call with exact sizes instead of nx * ny zeroed records every time
     SEARCH_FIRST_RECORDS, SEARCH_FIRST_CELLS = 4096, 65536
 
+    def set_frontier_seed_order(self, order: str):
+        """The seeds of search_frontiers without seeds and of get_frontier_costs_searched (fs_set_frontier_seed_order):
+        "nearest" (a fresh context's) or "reference" (the reference's outer search decides seeds and list order)."""
+        if order not in SEED_ORDERS:
+            raise FsError(FS_E_INVALID, f"unknown frontier seed order {order!r} (nearest | reference)")
+        self._check(self._L.fs_set_frontier_seed_order(self._h, SEED_ORDERS[order]))
+        self._seed_order = order
+
+    @contextlib.contextmanager
+    def _seed_order_for_call(self, order):
+        """seed_order= of one call: set for the call, the context's own setting restored afterwards"""
+        if order is None:
+            yield
+            return
+        prev = self._seed_order
+        self.set_frontier_seed_order(order)
+        try:
+            yield
+        finally:
+            self.set_frontier_seed_order(prev)
+
     def search_frontiers(self, robot_xy, lethal_threshold=160, max_frontier_distance=50.0, min_frontier_cluster_size=1,
-                         max_frontier_cluster_size=20, seeds=None, max_records=None, want_every=True):
+                         max_frontier_cluster_size=20, seeds=None, max_records=None, want_every=True, seed_order=None):
         """FrontierSearch::searchFrom on the device, pieces and goal points included (fs_search_frontiers): returns (frontiers
-        (FRONTIER_RECORD_DTYPE, output order), every_xy [n_cells][2] or None).  seeds None: Nearest seeds; else the cells
-        (y * nx + x) that start one buildNewFrontier each, in order.  max_records None: every record (the buffers grow to what
-        the search reports, at most the grid's cell count); else at most that many (last_search_counts has the full counts)."""
+        (FRONTIER_RECORD_DTYPE, output order), every_xy [n_cells][2] or None).  seeds None: the context's seed order
+        (set_frontier_seed_order; seed_order= "nearest" / "reference" for this call only); else the cells (y * nx + x) that start
+        one buildNewFrontier each, in order.  max_records None: every record (the buffers grow to what the search reports, at most
+        the grid's cell count); else at most that many (last_search_counts has the full counts)."""
+        with self._seed_order_for_call(seed_order):
+            return self._search_frontiers(robot_xy, lethal_threshold, max_frontier_distance, min_frontier_cluster_size,
+                                          max_frontier_cluster_size, seeds, max_records, want_every)
+
+    def _search_frontiers(self, robot_xy, lethal_threshold, max_frontier_distance, min_frontier_cluster_size,
+                          max_frontier_cluster_size, seeds, max_records, want_every):
         _, ny, nx = self._staged_shape()
         sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1)
         xy = (C.c_double * 2)(float(robot_xy[0]), float(robot_xy[1]))
@@ -354,11 +387,19 @@ class FrontierScorer:
 
     def get_frontier_costs_searched(self, robot_pose7, lethal_threshold=160, max_frontier_distance=50.0, min_frontier_cluster_size=1,
                                     max_frontier_cluster_size=20, blacklist_xy=None, allow_unknown=False, with_fim=False, alpha=0.25,
-                                    beta=1.0, max_vx=0.5, max_wz=0.5, max_records=None):
+                                    beta=1.0, max_vx=0.5, max_wz=0.5, max_records=None, seed_order=None):
         """searchFrom -> plan -> score -> rank in one call (fs_get_frontier_costs_searched): returns (frontiers, the dict
         get_frontier_costs_planned returns).  blacklist_xy [k][2]: goal points to mark blacklisted (exact equality).
         max_records None: as many as the search finds (a longer list than the first round holds is searched again with exact
-        sizes); else more records than that raise FsError."""
+        sizes); else more records than that raise FsError.  seed_order: as search_frontiers'."""
+        with self._seed_order_for_call(seed_order):
+            return self._get_frontier_costs_searched(robot_pose7, lethal_threshold, max_frontier_distance, min_frontier_cluster_size,
+                                                     max_frontier_cluster_size, blacklist_xy, allow_unknown, with_fim, alpha, beta,
+                                                     max_vx, max_wz, max_records)
+
+    def _get_frontier_costs_searched(self, robot_pose7, lethal_threshold, max_frontier_distance, min_frontier_cluster_size,
+                                     max_frontier_cluster_size, blacklist_xy, allow_unknown, with_fim, alpha, beta, max_vx, max_wz,
+                                     max_records):
         _, ny, nx = self._staged_shape()
         cap = min(nx * ny, self.SEARCH_FIRST_RECORDS) if max_records is None else int(max_records)
         pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])

@@ -272,6 +272,9 @@ struct fs_ctx {
     DevBuf<double> d_fs_every, d_fs_goal, d_fs_black_xy;
     DevBuf<uint8_t> d_fs_black;
     int64_t fs_levels = 0, fs_guarded = 0;      // counters 1014 / 1015 of the last search
+    int32_t fs_seed_order = FS_SEEDS_NEAREST;   // fs_set_frontier_seed_order: the seeds of a search without caller seeds
+    bool fs_outer = false;                      // the search in flight walks the outer search (Reference seeds)
+    int64_t fs_outer_levels = 0, fs_outer_popped = 0;   // counters 1019 / 1020 of the last Reference search
     // "cloud.order": where the landmark cloud is put into its k-d leaf order — 0 on the host, 2 on the device (fs_cloud.hip), 1 (default)
     // on the device from FS_CLOUD_DEVICE_FROM landmarks on: fs_upload_landmarks 1.2 ms at C3's 100 k landmarks, 4.4 ms at 500 k on the
     // device (the host form: 4.4 / 20.2 ms with its top levels on threads of their own, 13.3 / 78.9 ms on one thread —
@@ -1393,6 +1396,8 @@ int search_enqueue(fs_ctx *c, const double robot_xy[2], int32_t lethal_threshold
     }
     // :26-33 — worldToMap of the robot position (as fs_frontier_clusters)
     int32_t mx = 0, my = 0;
+    c->fs_outer = !seeds && c->fs_seed_order == FS_SEEDS_REFERENCE;
+    if (c->fs_outer) c->fs_outer_levels = c->fs_outer_popped = 0;
     if (!grid_world_to_map(c, robot_xy[0], robot_xy[1], mx, my)) return FS_OK;
     const int32_t robot_cell = (int32_t)((unsigned int)my * (unsigned int)c->nx + (unsigned int)mx);
     const size_t nb = (cells + 1023) / 1024, ne = std::max(cells, (size_t)(seeds ? n_seeds : 0)) + 1;
@@ -1420,6 +1425,7 @@ int search_enqueue(fs_ctx *c, const double robot_xy[2], int32_t lethal_threshold
     // a component has at most nx * ny cells, so every max_size >= nx * ny cuts exactly as nx * ny does (and max + 1 cannot wrap)
     a.min_size = min_size; a.max_size = (int32_t)std::min<int64_t>(max_size, (int64_t)cells);
     a.n_seeds = seeds ? n_seeds : -1; a.seeds = c->d_fs_seeds.p;
+    a.outer = c->fs_outer ? 1 : 0; a.parent_t = c->d_fc_parent_t.p; a.fc_state = c->d_fc_state.p;
     a.bcount = c->d_fs_bcount.p; a.cidx = c->d_fs_cidx.p; a.comp_root = c->d_fs_root.p; a.best_idx = c->d_fs_best_idx.p;
     a.csize = c->d_fs_csize.p; a.owner = c->d_fs_owner.p; a.best_d2 = c->d_fs_best_d2.p;
     a.emit_comp = c->d_fs_emit_comp.p; a.emit_seed = c->d_fs_emit_seed.p; a.emit_base = c->d_fs_emit_base.p; a.rec_base = c->d_fs_rec_base.p;
@@ -1451,6 +1457,8 @@ int search_results(fs_ctx *c, int32_t max_records, fs_frontier_record *records, 
     std::memcpy(state, c->h_out.p, sizeof state);
     c->fs_levels = state[FSS_LEVELS];
     c->fs_guarded = state[FSS_GUARDED];
+    if (c->fs_outer) { c->fs_outer_levels = state[FSS_OUTER_LEVELS]; c->fs_outer_popped = state[FSS_OUTER_POPPED]; }
+    if (state[FSS_ERROR] == 2) return fail(c, FS_E_HIP, "internal error: the outer search did not meet every component the clustering found");
     if (state[FSS_ERROR]) return fail(c, FS_E_INVALID, "a seed is not a frontier cell the search found, or two seeds share a component");
     const int32_t n = state[FSS_RECORDS], stored = std::min(n, max_records);
     if (stored > 0) {
@@ -1485,6 +1493,14 @@ int fs_search_frontiers(fs_ctx *c, const double robot_xy[2], int32_t lethal_thre
     if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
     if (!on_map) return FS_OK;
     return search_results(c, max_records, records, n_records, max_every, every_xy, n_cells);
+}
+
+int fs_set_frontier_seed_order(fs_ctx *c, int32_t order)
+{
+    if (!c) return FS_E_INVALID;
+    if (order != FS_SEEDS_NEAREST && order != FS_SEEDS_REFERENCE) return fail(c, FS_E_INVALID, "unknown frontier seed order %d", order);
+    c->fs_seed_order = order;
+    return FS_OK;
 }
 
 int fs_set_arrival_limits(fs_ctx *c, double max_gt, double min_gt)
@@ -1985,6 +2001,8 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
         // the key-frame anchors (fs_roadmap_set_keyframes / fs_roadmap_optimize): anchor records stored (the store is
         // keyframe_mapping_), de-duplication rounds of the last optimise, points it de-duplicated
         {1016, &fs_ctx::kf_records, false}, {1017, &fs_ctx::kf_rounds, false}, {1018, &fs_ctx::kf_points, false},
+        // the outer search of the last Reference-seeded frontier search: levels walked, cells popped
+        {1019, &fs_ctx::fs_outer_levels, false}, {1020, &fs_ctx::fs_outer_popped, false},
     };
     for (const auto &h : host)
         if (c && value && which == h.id) {

@@ -114,15 +114,19 @@ hipError_t fs_launch_frontier_clusters(const uint8_t *d_map, int nx, int ny, dou
 // found (launched with max_clusters = 0, so that aux[root] == -2 marks a found component).  Every scratch array holds nx * ny
 // entries (emit_* / rec_base: max(nx * ny, n_seeds) + 1); state [16] zeroed before the launch.
 struct fs_msort_elem;                     // fs_median_sort.h
-enum { FSS_COMPONENTS = 0, FSS_EMITTED = 1, FSS_CELLS = 2, FSS_RECORDS = 3, FSS_ERROR = 4, FSS_LEVELS = 5, FSS_GUARDED = 6 };
+// FSS_ERROR: 1 a refused caller seed, 2 a found component the outer search never met (internal)
+enum { FSS_COMPONENTS = 0, FSS_EMITTED = 1, FSS_CELLS = 2, FSS_RECORDS = 3, FSS_ERROR = 4, FSS_LEVELS = 5, FSS_GUARDED = 6,
+       FSS_OUTER_LEVELS = 7, FSS_OUTER_POPPED = 8 };
 struct FsSearchArgs {
     const int32_t *parent_f, *aux;
     int32_t nx, ny;
     double ox, oy, res;
     int32_t robot_cell;
     int32_t min_size, max_size;
-    int32_t n_seeds;                      // < 0: Nearest seeds
+    int32_t n_seeds;                      // < 0: Nearest seeds, or Reference seeds when `outer`
     const int32_t *seeds;                 // [n_seeds] (device)
+    int32_t outer;                        // 1: Reference seeds, from the outer search's walk (n_seeds < 0)
+    const int32_t *parent_t, *fc_state;   // the clusters kernels' expandable-cell roots and state (state[0]: the start cell)
     int32_t *bcount, *cidx, *comp_root, *best_idx, *csize, *owner;
     unsigned long long *best_d2;
     int32_t *emit_comp, *emit_seed, *emit_base, *rec_base;

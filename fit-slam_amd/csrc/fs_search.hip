@@ -4,6 +4,10 @@
 // leaving the device:
 //   components   found roots compacted in ascending label order (a deterministic scan);
 //   seeds        Nearest: per component the cell nearest the robot's cell (squared cell distance, ties to the smaller index);
+//                Reference: searchFrom's outer search (:44-94) walked level by level over the expanded cells from the start
+//                cell in nhood4 order, a cell going to its first claimant (the smallest queue position: one parent reaches a
+//                cell through one slot only); each component's seed is the frontier neighbour of a popped cell at the smallest
+//                (queue position, slot), and the components are emitted in that order;
 //                or the caller's list, validated on the device (a found frontier cell, one seed per component);
 //   queue order  per seed the breadth-first walk in nhood8 order, level-synchronous and exact: every unvisited neighbour n of a
 //                level-L cell at queue position t takes atomicMin(key[n], 8 t + slot); a parent's won slots, in slot order, after
@@ -12,6 +16,7 @@
 //   goal points  getCentroidOfCells in queue order, SortByMedianFunctor's angles and libstdc++'s std::sort restated
 //                (fs_median_sort.h), the middle element — one lane per piece.
 // One workgroup walks one component at a time with its queue in global memory; every loop is bounded by the component's size.
+// The outer walk is one workgroup too, its queue in the same array before the components' walks use it.
 #include "fs_internal.h"
 #include "fs_median_sort.h"
 
@@ -19,9 +24,14 @@ namespace {
 
 constexpr int SCAN_THREADS = 1024;
 constexpr int BFS_THREADS = 256;
+constexpr int OUTER_THREADS = 1024;
 constexpr int32_t KEY_NONE = 0x7fffffff;
 
 __device__ __forceinline__ int32_t ld_agent(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned long long ld_agent64(const unsigned long long *p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 // exclusive scan over the workgroup (blockDim.x a multiple of 64, at most 1024); *total = the sum
 __device__ int block_exclusive_scan(int v, int *s_wave, int *total)
@@ -63,6 +73,18 @@ __device__ __forceinline__ int nb8(int idx, int j, int nx, int ny)
     case 5: return (l && d) ? idx - 1 + nx : -1;
     case 6: return (r && u) ? idx + 1 - nx : -1;
     default: return (r && d) ? idx + 1 + nx : -1;
+    }
+}
+
+// nhood4's slots (Helpers.cpp:185-216): left, right, -nx, +nx; -1 off the map
+__device__ __forceinline__ int nb4(int idx, int j, int nx, int ny)
+{
+    const int y = idx / nx, x = idx - y * nx;
+    switch (j) {
+    case 0: return x > 0 ? idx - 1 : -1;
+    case 1: return x < nx - 1 ? idx + 1 : -1;
+    case 2: return y > 0 ? idx - nx : -1;
+    default: return y < ny - 1 ? idx + nx : -1;
     }
 }
 
@@ -131,16 +153,18 @@ __global__ void fss_scatter_kernel(const FsSearchArgs a)
     }
 }
 
-// per cell: component sizes; Nearest: the smallest squared distance to the robot's cell
+// per cell: component sizes; Nearest: the smallest squared distance to the robot's cell; Reference: the outer walk's cell classes
 __global__ void fss_member_kernel(const FsSearchArgs a)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.nx * a.ny) return;
     int r;
-    if (!found_cell(a, i, &r)) return;
+    const bool found = found_cell(a, i, &r);
+    if (a.outer) a.best_idx[i] = a.parent_t[i] >= 0 ? -1 : found ? a.cidx[r] : -2;      // the outer walk's cell classes
+    if (!found) return;
     const int c = a.cidx[r];
     atomicAdd(&a.csize[c], 1);
-    if (a.n_seeds < 0) {
+    if (a.n_seeds < 0 && !a.outer) {
         const long long ry = a.robot_cell / a.nx, rx = a.robot_cell - ry * a.nx;
         const long long y = i / a.nx, x = i - y * a.nx;
         const unsigned long long d2 = (unsigned long long)((x - rx) * (x - rx) + (y - ry) * (y - ry));
@@ -182,6 +206,91 @@ __global__ void fss_emit_kernel(const FsSearchArgs a)
         if (c < 0) atomicExch(&a.state[FSS_ERROR], 1);
         a.emit_comp[k] = c;
         a.emit_seed[k] = s;
+    }
+}
+
+// Reference seeds: searchFrom's outer search (DEP/src/FrontierSearch.cpp:44-94), one workgroup, level by level over E (the cells the
+// clusters kernels mark expandable, parent_t >= 0, plus the start cell), from the start cell (clusters state[0]).  Scratch: the queue
+// in q; per cell its class in best_idx (fss_member_kernel: -1 in E, c >= 0 a cell of found component c, -2 neither) and its claim
+// in key (reset by fss_count_kernel); the components' first hits in best_d2 (reset by fss_scatter_kernel).  Per level:
+//   claims  every E neighbour of a popped cell at queue position t takes atomicMin(key, t) — one parent reaches a cell through one
+//           slot only, so t alone is the reference's (position, slot) order; a cell claimed at an earlier level (or the start
+//           cell, key -1) keeps its smaller key, so the claim is also the visited mark;
+//   hits    a frontier neighbour of found component C takes atomicMin(hit[C], 4 t + slot) (64-bit);
+//   order   each parent counts, in slot order, the cells it won and the components it hit first; an exclusive scan over the level's
+//           parents in queue order gives the next level's queue positions and the components' emission ranks.
+// A component first hit at level L is final once level L is done, so the walk ends when every found component has been hit (exact);
+// a found component never hit is an internal error (state[FSS_ERROR] = 2).  Levels and popped cells go to the state.
+__global__ void __launch_bounds__(OUTER_THREADS) fss_outer_kernel(const FsSearchArgs a)
+{
+    __shared__ int s_wave[16];
+    const int n = a.nx * a.ny, n_comp = a.state[FSS_COMPONENTS];
+    if (n_comp == 0) return;                                          // (nothing to order: no levels walked)
+    const int start = a.fc_state[0];
+    const int32_t *cls = a.best_idx;
+    unsigned long long *hit = a.best_d2;
+    if (threadIdx.x == 0) { a.q[0] = start; a.key[start] = -1; }
+    __syncthreads();
+    int lo = 0, hi = 1, levels = 0, ranked = 0;
+    for (int iter = 0; iter < n && lo < hi && ranked < n_comp; ++iter) {
+        // a level of at most blockDim.x cells (the common case) keeps each lane's parent, neighbours and classes in registers
+        // from the first pass to the second
+        const bool one = hi - lo <= (int)blockDim.x;
+        int nb[4] = {-1, -1, -1, -1}, cl[4] = {-2, -2, -2, -2};
+        auto load = [&](int t) {
+            const int p = a.q[t];
+            for (int j = 0; j < 4; ++j) {
+                nb[j] = nb4(p, j, a.nx, a.ny);
+                cl[j] = nb[j] >= 0 ? cls[nb[j]] : -2;
+            }
+        };
+        for (int t = lo + (int)threadIdx.x; t < hi; t += blockDim.x) {
+            load(t);
+            for (int j = 0; j < 4; ++j) {
+                if (cl[j] == -1) atomicMin(&a.key[nb[j]], t);
+                else if (cl[j] >= 0) atomicMin(&hit[cl[j]], (unsigned long long)t * 4 + j);
+            }
+        }
+        __syncthreads();
+        // (a claim or hit key names one parent position, which is never reused, so a key of an earlier level cannot match)
+        int carry_c = 0, carry_h = 0;
+        for (int t0 = lo; t0 < hi; t0 += blockDim.x) {
+            const int t = t0 + (int)threadIdx.x;
+            int won = 0, first = 0;
+            if (t < hi) {
+                if (!one) load(t);
+                for (int j = 0; j < 4; ++j) {
+                    if (cl[j] == -1 && ld_agent(&a.key[nb[j]]) == t) won |= 1 << j;
+                    else if (cl[j] >= 0 && ld_agent64(&hit[cl[j]]) == (unsigned long long)t * 4 + j) first |= 1 << j;
+                }
+            }
+            // both counts in one scan: per pass of blockDim.x parents each sum is at most 4 * 1024 < 2^16
+            int total;
+            const int off = block_exclusive_scan(__popc(won) | __popc(first) << 16, s_wave, &total);
+            int w = hi + carry_c + (off & 0xffff), k = ranked + carry_h + (off >> 16);
+            for (int j = 0; j < 4; ++j) {
+                if ((won >> j) & 1) {
+                    if (w < n) a.q[w] = nb[j];
+                    ++w;
+                } else if ((first >> j) & 1) {
+                    if (k < n_comp) { a.emit_comp[k] = cl[j]; a.emit_seed[k] = nb[j]; }
+                    ++k;
+                }
+            }
+            carry_c += total & 0xffff;
+            carry_h += total >> 16;
+        }
+        __syncthreads();
+        ++levels;
+        lo = hi;
+        hi = min(hi + carry_c, n);
+        ranked += carry_h;
+    }
+    if (threadIdx.x == 0) {
+        a.state[FSS_OUTER_LEVELS] = levels;
+        a.state[FSS_OUTER_POPPED] = lo;
+        if (ranked != n_comp) atomicExch(&a.state[FSS_ERROR], 2);
+        a.key[start] = KEY_NONE;                                      // (the start cell may be a frontier cell the walks below claim)
     }
 }
 
@@ -397,8 +506,12 @@ hipError_t fs_launch_frontier_search(const FsSearchArgs &a, hipStream_t s)
     hipLaunchKernelGGL(fss_scan_blocks_kernel, dim3(1), scan_block, 0, s, a, nb);
     hipLaunchKernelGGL(fss_scatter_kernel, cells_grid, scan_block, 0, s, a);
     hipLaunchKernelGGL(fss_member_kernel, cells_grid, scan_block, 0, s, a);
-    if (a.n_seeds < 0) hipLaunchKernelGGL(fss_nearest_kernel, cells_grid, scan_block, 0, s, a);
-    hipLaunchKernelGGL(fss_emit_kernel, dim3(64), dim3(256), 0, s, a);
+    if (a.outer) {
+        hipLaunchKernelGGL(fss_outer_kernel, dim3(1), dim3(OUTER_THREADS), 0, s, a);
+    } else {
+        if (a.n_seeds < 0) hipLaunchKernelGGL(fss_nearest_kernel, cells_grid, scan_block, 0, s, a);
+        hipLaunchKernelGGL(fss_emit_kernel, dim3(64), dim3(256), 0, s, a);
+    }
     hipLaunchKernelGGL(fss_scan_emit_kernel, dim3(1), scan_block, 0, s, a);
     hipLaunchKernelGGL(fss_bfs_kernel, dim3(1024), dim3(BFS_THREADS), 0, s, a);
     hipLaunchKernelGGL(fss_pieces_kernel, dim3(256), dim3(64), 0, s, a);

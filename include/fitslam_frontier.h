@@ -176,10 +176,13 @@ int fs_frontier_clusters(fs_ctx *ctx, const double robot_xy[2], int32_t lethal_t
  * max_frontier_cluster_size + 1 cells in the order of that queue, the remainder if it exceeds min_frontier_cluster_size, per piece
  * the angular-median goal point (getCentroidOfCells, SortByMedianFunctor, libstdc++'s std::sort, the middle element) — and
  * searchFrom's size filter.  The label image never leaves the device.
- *   seeds     NULL (n_seeds ignored): per component (ascending label) its cell nearest the robot's cell, squared cell distance,
- *             ties to the smaller index.  Otherwise n_seeds cells (y * nx + x), each starting one buildNewFrontier, records in list
- *             order: the reference's own order when the seeds are the cells its outer search met first.  A seed that is not a
- *             frontier cell the search found, or a second seed in one component: FS_E_INVALID, nothing written.
+ *   seeds     NULL (n_seeds ignored): the context's seed order (fs_set_frontier_seed_order).  FS_SEEDS_NEAREST (the default):
+ *             per component (ascending label) its cell nearest the robot's cell, squared cell distance, ties to the smaller index.
+ *             FS_SEEDS_REFERENCE: searchFrom's own outer search (:44-94) on the device, so the records equal the reference's list,
+ *             order, seeds and goal points included.  Otherwise n_seeds cells (y * nx + x), each starting one buildNewFrontier,
+ *             records in list order, whatever the seed order: the reference's own order when the seeds are the cells its outer
+ *             search met first.  A seed that is not a frontier cell the search found, or a second seed in one component:
+ *             FS_E_INVALID, nothing written.
  *   records   [max_records]; *n_records = records found (may exceed max_records: the first ones are stored)
  *   every_xy  [max_every][2] or NULL: every_frontier_list, the world coordinates of every collected cell in emission order (cells of
  *             dropped pieces included); *n_cells = its length (may exceed max_every)
@@ -197,6 +200,14 @@ int fs_search_frontiers(fs_ctx *ctx, const double robot_xy[2], int32_t lethal_th
                         int32_t min_frontier_cluster_size, int32_t max_frontier_cluster_size, int32_t n_seeds, const int32_t *seeds,
                         int32_t max_records, fs_frontier_record *records, int32_t *n_records,
                         int64_t max_every, double *every_xy, int64_t *n_cells);
+
+/* The seeds of fs_search_frontiers without caller seeds and of fs_get_frontier_costs_searched, per context.  FS_SEEDS_NEAREST (a
+ * fresh context's): each component from its cell nearest the robot's cell, components in label order.  FS_SEEDS_REFERENCE: the
+ * reference's outer breadth-first search from the robot (DEP/src/FrontierSearch.cpp:44-94) decides each component's seed and the
+ * order of the list, walked level by level on the device.  Any other value: FS_E_INVALID, the setting unchanged. */
+#define FS_SEEDS_NEAREST   0
+#define FS_SEEDS_REFERENCE 1
+int fs_set_frontier_seed_order(fs_ctx *ctx, int32_t order);
 
 /* Replaces double FrontierCostCalculator::setMaxArrivalInformation() (DEP/include/.../CostCalculator.hpp:58,
  * DEP/src/CostCalculator.cpp:123-191): geometric maximum of the FOV window on an obstacle-free fan from
@@ -450,7 +461,8 @@ int fs_get_frontier_costs_planned(fs_ctx *ctx, const double robot_pose7[7], int3
                   const int32_t *frontier_size, const uint8_t *blacklisted, double alpha, double beta, double max_vx, double max_wz,
                   int with_fisher_information, fs_record *records, double *weighted_cost, double *arrival_utility,
                   double *distance_utility, int32_t *order, double *path_length_m);
-/* searchFrom -> plan -> score -> rank in one call: fs_search_frontiers with Nearest seeds from the pose's xy, then
+/* searchFrom -> plan -> score -> rank in one call: fs_search_frontiers with the context's seed order (fs_set_frontier_seed_order)
+ * and no caller seeds from the pose's xy, then
  * fs_get_frontier_costs_planned on its records (goal_xyz = (goal_x, goal_y, 0), frontier_size = size, blacklisted = the goal point
  * equals one of blacklist_xy [n_blacklist][2] bit for bit: FrontierGoalPointEquality, the key of frontier_blacklist_).  Every
  * column after frontiers [max_records] has *n_frontiers entries.  More records than max_records: FS_E_INVALID with *n_frontiers

@@ -79,7 +79,9 @@ int  fs_set_option(fs_ctx *ctx, const char *key, double value);
  * refinement built (fs_refine_paths / fs_refine_field: a cached field adds nothing), 1012 = rounds of the last field built,
  * 1013 = line-of-sight walks of the legs (1011 and 1013 are reset by `reset`); 1014 = breadth-first levels of the deepest
  * component of the last fs_search_frontiers, 1015 = pieces of the last search whose median sort stopped a scan at either end of
- * the array (fs_median_sort.h's guard: a cyclic order on which the reference's std::sort leaves the array). */
+ * the array (fs_median_sort.h's guard: a cyclic order on which the reference's std::sort leaves the array); 1019 / 1020 = levels
+ * walked / cells popped by the outer search of the last search with FS_SEEDS_REFERENCE (levels counted from 1 at the start cell;
+ * the walk stops after the level in which the last component is first met, so 1020 is at most the expanded region's size). */
 int  fs_get_counter(fs_ctx *ctx, int which, int64_t *value, int reset);
 
 /* ---------------------------------------------------------------- self test */

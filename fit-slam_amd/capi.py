@@ -19,6 +19,8 @@ STATUS_OK, STATUS_OFF_MAP, STATUS_BLACKLISTED = 0, 1, 2
 FS_MAX_ELEV = 16
 FS_SEEDS_NEAREST, FS_SEEDS_REFERENCE = 0, 1
 SEED_ORDERS = {"nearest": FS_SEEDS_NEAREST, "reference": FS_SEEDS_REFERENCE}
+FS_ROADMAP_SEARCH_TREE, FS_ROADMAP_SEARCH_REFERENCE = 0, 1
+ROADMAP_SEARCHES = {"tree": FS_ROADMAP_SEARCH_TREE, "reference": FS_ROADMAP_SEARCH_REFERENCE}
 
 # every symbol include/fitslam_frontier.h declares
 EXPORTED_SYMBOLS = [
@@ -38,7 +40,7 @@ EXPORTED_SYMBOLS = [
     "fs_set_roadmap_params", "fs_roadmap_add_nodes", "fs_roadmap_rebuild", "fs_roadmap_connect", "fs_roadmap_get_graph", "fs_roadmap_plan",
     "fs_get_frontier_costs_roadmap", "fs_roadmap_next_goal", "fs_refine_paths", "fs_refine_field",
     "fs_roadmap_set_keyframes", "fs_roadmap_optimize", "fs_roadmap_get_anchors",
-    "fs_search_frontiers", "fs_get_frontier_costs_searched", "fs_set_frontier_seed_order",
+    "fs_search_frontiers", "fs_get_frontier_costs_searched", "fs_set_frontier_seed_order", "fs_set_roadmap_search",
 ]
 
 RECORD_DTYPE = np.dtype([("arrival", "<i4"), ("argmax", "<i4"), ("yaw", "<f4"), ("info_ref", "<f4"),
@@ -183,6 +185,7 @@ def load_library(build: bool = True):
     L.fs_refine_field.argtypes = [vp, C.POINTER(dbl * 2), i32, dbl, dbl, i32, vp]
     L.fs_search_frontiers.argtypes = [vp, C.POINTER(dbl * 2), i32, dbl, i32, i32, i32, vp, i32, vp, C.POINTER(i32), i64, vp, C.POINTER(i64)]
     L.fs_set_frontier_seed_order.argtypes = [vp, i32]
+    L.fs_set_roadmap_search.argtypes = [vp, i32]
     L.fs_get_frontier_costs_searched.argtypes = [vp, C.POINTER(dbl * 7), i32, dbl, i32, i32, i32, i32, vp, dbl, dbl, dbl, dbl, C.c_int,
                                                  i32, vp, C.POINTER(i32), vp, vp, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
@@ -227,6 +230,7 @@ class FrontierScorer:
         self._elev = (0.0,)
         self._grid_shape = None          # (nz, ny, nx) of the staged grid: what fs_navfn_potential writes
         self._seed_order = "nearest"     # the context's frontier seed order (fs_set_frontier_seed_order)
+        self._roadmap_search = "tree"    # the context's roadmap search (fs_set_roadmap_search)
         self.n_yaw = self.n_elev = self.window = 0
 
     # -- plumbing
@@ -687,8 +691,32 @@ class FrontierScorer:
         self._check(self._L.fs_roadmap_get_anchors(self._h, C.byref(k), C.byref(r), _p(ids), _p(pts)))
         return dict(n_pending=k.value, kf_id=ids, point_c=pts)
 
-    def roadmap_plan(self, robot_pose7, goal_xyz, achievable_in=None):
-        """setPlanForFrontierRoadmap for every goal: one shortest-path tree from the robot's closest key node."""
+    def set_roadmap_search(self, name: str):
+        """How roadmap_plan, get_frontier_costs_roadmap and roadmap_next_goal's pair lengths search the roadmap
+        (fs_set_roadmap_search): "tree" (a fresh context's: one shortest-path tree per start node) or "reference" (the reference's
+        per-goal A*, bit for bit)."""
+        if name not in ROADMAP_SEARCHES:
+            raise FsError(FS_E_INVALID, f"unknown roadmap search {name!r} (tree | reference)")
+        self._check(self._L.fs_set_roadmap_search(self._h, ROADMAP_SEARCHES[name]))
+        self._roadmap_search = name
+
+    @contextlib.contextmanager
+    def _roadmap_search_for_call(self, name):
+        """search= of one call: set for the call, the context's own setting restored afterwards"""
+        if name is None:
+            yield
+            return
+        prev = self._roadmap_search
+        self.set_roadmap_search(name)
+        try:
+            yield
+        finally:
+            self.set_roadmap_search(prev)
+
+    def roadmap_plan(self, robot_pose7, goal_xyz, achievable_in=None, search=None):
+        """setPlanForFrontierRoadmap for every goal, by the context's roadmap search (set_roadmap_search; search= "tree" /
+        "reference" for this call only): one shortest-path tree from the robot's closest key node, or the reference's A* per goal
+        node."""
         pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
         goal = np.ascontiguousarray(goal_xyz, dtype=np.float64).reshape(-1, 3)
         n = goal.shape[0]
@@ -697,12 +725,14 @@ class FrontierScorer:
             raise ValueError(f"achievable_in has {ai.shape[0]} entries for {n} goals")
         pl, plm, ph = np.zeros(n), np.zeros(n), np.zeros(n)
         ach = np.zeros(n, dtype=np.uint8)
-        self._check(self._L.fs_roadmap_plan(self._h, C.byref(pose), n, _p(goal), _p(ai), _p(pl), _p(plm), _p(ph), _p(ach)))
+        with self._roadmap_search_for_call(search):
+            self._check(self._L.fs_roadmap_plan(self._h, C.byref(pose), n, _p(goal), _p(ai), _p(pl), _p(plm), _p(ph), _p(ach)))
         return dict(path_length=pl, path_length_m=plm, path_heading=ph, achievable=ach)
 
     def get_frontier_costs_roadmap(self, robot_pose7, goal_xyz, frontier_size=None, blacklisted=None, with_fim=False,
-                                   alpha=0.25, beta=1.0, max_vx=0.5, max_wz=0.5):
-        """get_frontier_costs with the path columns planned on the roadmap in the same call (plan -> score -> rank)."""
+                                   alpha=0.25, beta=1.0, max_vx=0.5, max_wz=0.5, search=None):
+        """get_frontier_costs with the path columns planned on the roadmap in the same call (plan -> score -> rank); search= as
+        roadmap_plan's."""
         pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
         goal = np.ascontiguousarray(goal_xyz, dtype=np.float64).reshape(-1, 3)
         n = goal.shape[0]
@@ -710,17 +740,21 @@ class FrontierScorer:
         bl = None if blacklisted is None else np.ascontiguousarray(blacklisted, dtype=np.uint8)
         rec = np.zeros(n, dtype=RECORD_DTYPE)
         cost = np.zeros(n); au = np.zeros(n); du = np.zeros(n); order = np.zeros(n, dtype=np.int32); plm = np.zeros(n)
-        self._check(self._L.fs_get_frontier_costs_roadmap(self._h, C.byref(pose), n, _p(goal), _p(fs), _p(bl), alpha, beta, max_vx, max_wz,
-                                                          1 if with_fim else 0, _p(rec), _p(cost), _p(au), _p(du), _p(order), _p(plm)))
+        with self._roadmap_search_for_call(search):
+            self._check(self._L.fs_get_frontier_costs_roadmap(self._h, C.byref(pose), n, _p(goal), _p(fs), _p(bl), alpha, beta, max_vx,
+                                                              max_wz, 1 if with_fim else 0, _p(rec), _p(cost), _p(au), _p(du), _p(order),
+                                                              _p(plm)))
         return dict(records=rec, weighted_cost=cost, arrival_utility=au, distance_utility=du, order=order, path_length_m=plm)
 
     def roadmap_next_goal(self, robot_pose7, goal_xyz, path_length_m, achievable, blacklisted=None, blacklist_xy=None,
-                          n_local=5, local_radius=12.0, fi_pose7=None, fi_threshold=550.0, want_matrix=False, want_selection=False):
+                          n_local=5, local_radius=12.0, fi_pose7=None, fi_threshold=550.0, want_matrix=False, want_selection=False,
+                          search=None):
         """FullPathOptimizer::getNextGoal on the staged roadmap: the selection, the pair matrix over [robot, locals, closest global]
         and the exhaustive tour search over the locals.  dict(next_index (-1: the zero frontier), status (0 SAFE, 1 UNSAFE,
         2 UNDETERMINED), tour (input indices: the locals in visiting order, then the closest global), tour_length, n_tied, n_locals),
         plus selection [n] (1 local, 2 global, | 4 closest global) with want_selection and pair_length_m [(k + 2)][(k + 2)] (None
-        without locals) with want_matrix.  fi_pose7 None: no Fisher-information check."""
+        without locals) with want_matrix.  fi_pose7 None: no Fisher-information check.  The pair lengths by the context's roadmap
+        search; search= as roadmap_plan's."""
         pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
         goal = np.ascontiguousarray(goal_xyz, dtype=np.float64).reshape(-1, 3)
         n = goal.shape[0]
@@ -739,10 +773,11 @@ class FrontierScorer:
         tour = np.zeros(max(nl, 0) + 1, dtype=np.int32)
         sel = np.zeros(n, dtype=np.uint8)
         mat = np.zeros(room * room) if want_matrix else None
-        self._check(self._L.fs_roadmap_next_goal(self._h, C.byref(pose), n, _p(goal), _p(plm), _p(ach), _p(bl), circ.shape[0],
-                                                 _p(circ) if circ.shape[0] else None, nl, float(local_radius), _p(fi),
-                                                 float(fi_threshold), C.byref(nxt), C.byref(st), _p(tour), C.byref(tsz), C.byref(tl),
-                                                 C.byref(nt), _p(sel), _p(mat)))
+        with self._roadmap_search_for_call(search):
+            self._check(self._L.fs_roadmap_next_goal(self._h, C.byref(pose), n, _p(goal), _p(plm), _p(ach), _p(bl), circ.shape[0],
+                                                     _p(circ) if circ.shape[0] else None, nl, float(local_radius), _p(fi),
+                                                     float(fi_threshold), C.byref(nxt), C.byref(st), _p(tour), C.byref(tsz), C.byref(tl),
+                                                     C.byref(nt), _p(sel), _p(mat)))
         k = int(np.count_nonzero((sel & 3) == 1))
         out = dict(next_index=nxt.value, status=st.value, tour=tour[:tsz.value].copy(), tour_length=tl.value, n_tied=nt.value,
                    n_locals=k)

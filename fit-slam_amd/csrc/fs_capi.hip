@@ -4,6 +4,7 @@
 // launches the HIP kernels of fs_raymarch.hip / fs_fim.hip / fs_rank.hip or fails.
 #include "fs_internal.h"
 #include "fs_median_sort.h"
+#include "fs_roadmap_astar.h"
 
 #include <algorithm>
 #include <atomic>
@@ -334,6 +335,20 @@ struct fs_ctx {
     DevBuf<int32_t> d_rm_hops, d_rm_pred, d_rm_word;
     DevBuf<char> d_rm_in, d_rm_out;   // goals | headings | modes;  path length | length in m | heading | achievable
     PinnedBuf h_rm_in, h_rm_out;
+    // the REFERENCE roadmap search (fs_set_roadmap_search): per-goal A* queries (fs_roadmap_astar.h).  The plan's goal node of every
+    // frontier, the goal-node marks and their scan (query indices), the query list, results and stats; the global route's pool;
+    // h_as_io holds the stats read back and the next-goal search's query list.  as_args / as_plan: the last call's launches, which
+    // rm_astar_settle repeats on a grown pool.
+    int32_t rm_search = FS_ROADMAP_SEARCH_TREE;
+    int32_t astar_lds_entries = 2048;         // "roadmap.astar_lds_entries": records of a query in LDS (0: the global route only)
+    int32_t astar_cap = 16384;                // records of a query on the global route (grows when one outgrows it)
+    int64_t as_queries = 0, as_max_pops = 0, as_global = 0;
+    DevBuf<int32_t> d_as_gnode, d_as_mark, d_as_qidx, d_as_src, d_as_dst, d_as_status, d_as_stats;
+    DevBuf<double> d_as_len;
+    DevBuf<char> d_as_pool;
+    PinnedBuf h_as_io;
+    FsRmAstarArgs as_args{};
+    FsRmPlanArgs as_plan{};
     // next goal (fs_roadmap_next_goal): a batch of trees with buffers of its own (the single tree above stays
     // cached), the pair matrix, the tour search's winners
     int32_t tour_one_wg = RM_TREE_ONE_WG;     // "roadmap.tour_one_wg": above this many nodes the batch runs a round per launch
@@ -1052,6 +1067,8 @@ void fs_ctx_destroy(fs_ctx *c)
     c->d_rm_trow.release(); c->d_rm_tcol.release(); c->d_rm_tmp.release(); c->d_rm_cell_start.release(); c->d_rm_cell_nodes.release();
     c->d_rm_cand_off.release(); c->d_rm_cand.release(); c->d_rm_hops.release(); c->d_rm_pred.release(); c->d_rm_word.release();
     c->d_rm_in.release(); c->d_rm_out.release(); c->h_rm_in.release(); c->h_rm_out.release();
+    c->d_as_gnode.release(); c->d_as_mark.release(); c->d_as_qidx.release(); c->d_as_src.release(); c->d_as_dst.release();
+    c->d_as_status.release(); c->d_as_stats.release(); c->d_as_len.release(); c->d_as_pool.release(); c->h_as_io.release();
     c->d_tour_d.release(); c->d_tour_hops.release(); c->d_tour_pred.release(); c->d_tour_word.release(); c->d_tour_work.release();
     c->h_tour_out.release();
     c->d_kf_rt.release(); c->d_kf_rec_p.release(); c->d_kf_pts.release(); c->d_kf_out.release(); c->d_kf_queue.release();
@@ -1968,6 +1985,7 @@ int fs_set_option(fs_ctx *c, const char *key, double value)
     if (std::strcmp(key, "fim.skip32") == 0 && value >= 1 && value <= 32) { c->opt_skip32 = (int)value; return FS_OK; }
     if (std::strcmp(key, "fim.headroom") == 0 && value >= 8 && value <= 64) { c->opt_headroom = (int)value; return FS_OK; }
     if (std::strcmp(key, "roadmap.tour_one_wg") == 0 && value >= 0 && value <= RM_TREE_ONE_WG) { c->tour_one_wg = (int32_t)value; return FS_OK; }
+    if (std::strcmp(key, "roadmap.astar_lds_entries") == 0 && value >= 0 && value <= 2048) { c->astar_lds_entries = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "roadmap.dedup_one_wg") == 0 && value >= 0 && value <= FS_KF_DEDUP_ONE_WG) { c->kf_one_wg = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "refine.max_fields") == 0 && value >= 1 && value <= RF_MAX_FIELDS) {
         if ((int32_t)value != c->rf_max_fields) { c->rf_max_fields = (int32_t)value; c->rf_key.clear(); c->rf_gen.clear(); }
@@ -2003,6 +2021,8 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
         {1016, &fs_ctx::kf_records, false}, {1017, &fs_ctx::kf_rounds, false}, {1018, &fs_ctx::kf_points, false},
         // the outer search of the last Reference-seeded frontier search: levels walked, cells popped
         {1019, &fs_ctx::fs_outer_levels, false}, {1020, &fs_ctx::fs_outer_popped, false},
+        // the REFERENCE roadmap search: A* queries run, pops of the last call's largest query, queries that took the global route
+        {1021, &fs_ctx::as_queries, true}, {1022, &fs_ctx::as_max_pops, false}, {1023, &fs_ctx::as_global, true},
     };
     for (const auto &h : host)
         if (c && value && which == h.id) {
@@ -3431,7 +3451,107 @@ int rm_tree(fs_ctx *c, int32_t root, const double **d, const int32_t **pred)
     return FS_OK;
 }
 
+// ---- the REFERENCE search (fs_set_roadmap_search): one A* per distinct (start, goal) pair, one wave per query
+
+// records of a query in LDS for a roadmap of n nodes: the option, capped by what fits beside the per-node state (0: global route only)
+int32_t rm_astar_lds_cap(const fs_ctx *c, int32_t n)
+{
+    const int64_t fit = ((int64_t)RM_ASTAR_LDS_BYTES - 5 * (int64_t)n - 16) / 28;
+    const int64_t cap = std::min<int64_t>(c->astar_lds_entries, fit);
+    return cap >= 16 ? (int32_t)cap : 0;
+}
+
+// The query launches on `a` (n_nodes, the graph, the query list, nq and the LDS cap filled in by the caller): the global route's
+// pool sized, the stats cleared, the LDS route then the global route, the stats copied to h_as_io.  Nothing synchronises.
+int rm_astar_enqueue(fs_ctx *c, FsRmAstarArgs &a, int32_t max_q)
+{
+    const size_t slot = fs_rm_astar_bytes(c->astar_cap, a.n_nodes);
+    FS_HIP(c, c->d_as_pool.ensure(slot * RM_ASTAR_SLOTS)); FS_HIP(c, c->d_as_stats.ensure(8)); FS_HIP(c, c->h_as_io.ensure(64));
+    a.pool = c->d_as_pool.p; a.slot_bytes = slot; a.slots = RM_ASTAR_SLOTS; a.cap = c->astar_cap;
+    a.stats = c->d_as_stats.p;
+    FS_HIP(c, hipMemsetAsync(c->d_as_stats.p, 0, 8 * sizeof(int32_t), c->stream));
+    FS_HIP(c, fs_launch_rm_astar(a, max_q, c->stream));
+    FS_HIP(c, hipMemcpyAsync(c->h_as_io.p, c->d_as_stats.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    c->as_args = a;
+    return FS_OK;
+}
+
+// After the caller's synchronisation: the counters from the stats; queries that outgrew the global route's pool run again on a
+// pool four times larger, each round followed by `redo()` (the launches that read the query results) and a synchronisation.
+// *redone: whether that happened.
+template <class Redo>
+int rm_astar_settle(fs_ctx *c, Redo redo, bool *redone)
+{
+    int32_t st[4];
+    std::memcpy(st, c->h_as_io.p, sizeof st);
+    c->as_queries += st[0]; c->as_global += st[2];
+    int64_t pops = st[1];
+    *redone = false;
+    while (st[3] > 0) {
+        if (c->astar_cap > (1 << 28) / 4) return fail(c, FS_E_HIP, "an A* query outgrew %d records", c->astar_cap);
+        c->astar_cap *= 4;
+        FsRmAstarArgs &a = c->as_args;
+        const size_t slot = fs_rm_astar_bytes(c->astar_cap, a.n_nodes);
+        FS_HIP(c, c->d_as_pool.ensure(slot * RM_ASTAR_SLOTS));
+        a.pool = c->d_as_pool.p; a.slot_bytes = slot; a.cap = c->astar_cap;
+        FS_HIP(c, hipMemsetAsync(c->d_as_stats.p, 0, 8 * sizeof(int32_t), c->stream));
+        FS_HIP(c, fs_launch_rm_astar_global(a, c->stream));
+        const int rc = redo();
+        if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+        FS_HIP(c, hipMemcpyAsync(c->h_as_io.p, c->d_as_stats.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        std::memcpy(st, c->h_as_io.p, sizeof st);
+        pops = std::max<int64_t>(pops, st[1]);
+        *redone = true;
+    }
+    c->as_max_pops = pops;
+    return FS_OK;
+}
+
+// roadmap_plan_enqueue's REFERENCE form: the goal nodes marked and scanned into distinct queries from the start node, the queries,
+// then the columns from their results.  The tree and its cache are not touched.
+int roadmap_astar_enqueue(fs_ctx *c, FsRmPlanArgs &a)
+{
+    const int32_t nodes = a.n_nodes;
+    FsRmAstarArgs q{};
+    q.n_nodes = nodes; q.root = a.root;
+    const size_t nn = (size_t)nodes;
+    FS_HIP(c, c->d_as_gnode.ensure((size_t)a.n)); FS_HIP(c, c->d_as_mark.ensure(nn)); FS_HIP(c, c->d_as_qidx.ensure(nn + 1));
+    const int32_t max_q = a.root >= 0 ? std::min(a.n, nodes) : 0;
+    FS_HIP(c, c->d_as_dst.ensure((size_t)std::max(max_q, 1))); FS_HIP(c, c->d_as_status.ensure((size_t)std::max(max_q, 1)));
+    FS_HIP(c, c->d_as_len.ensure((size_t)std::max(max_q, 1)));
+    if (max_q > 0) {
+        const int rc = rm_device_graph(c);
+        if (rc) return rc;
+        a.xy = c->d_rm_xy.p; a.key = c->d_rm_key.p;
+        FS_HIP(c, hipMemsetAsync(c->d_as_mark.p, 0, sizeof(int32_t) * nn, c->stream));
+    }
+    FS_HIP(c, fs_launch_rm_astar_goals(a, c->d_as_gnode.p, c->d_as_mark.p, c->stream));
+    if (max_q > 0) {
+        FS_HIP(c, fs_launch_rm_scan(c->d_as_mark.p, nodes, c->d_as_qidx.p, c->stream));
+        FS_HIP(c, fs_launch_rm_astar_list(nodes, c->d_as_mark.p, c->d_as_qidx.p, c->d_as_dst.p, c->stream));
+        q.xy = c->d_rm_xy.p; q.row = c->d_rm_row.p; q.col = c->d_rm_col.p;
+    } else {
+        FS_HIP(c, hipMemsetAsync(c->d_as_qidx.p, 0, sizeof(int32_t) * (nn + 1), c->stream));
+    }
+    q.nq = c->d_as_qidx.p + nodes; q.dst = c->d_as_dst.p; q.status = c->d_as_status.p; q.len = c->d_as_len.p;
+    q.lds_cap = rm_astar_lds_cap(c, nodes);
+    int rc = rm_astar_enqueue(c, q, max_q);
+    if (rc) return rc;
+    c->as_plan = a;
+    FS_HIP(c, fs_launch_rm_astar_cols(a, c->d_as_gnode.p, c->d_as_qidx.p, c->d_as_status.p, c->d_as_len.p, c->stream));
+    return FS_OK;
+}
+
+// the columns again from the settled query results (rm_astar_settle's redo for the plan)
+int roadmap_astar_cols(fs_ctx *c)
+{
+    FS_HIP(c, fs_launch_rm_astar_cols(c->as_plan, c->d_as_gnode.p, c->d_as_qidx.p, c->d_as_status.p, c->d_as_len.p, c->stream));
+    return FS_OK;
+}
+
 // Start node, tree (cached or built), goals staged, the plan kernel: the four columns land in d_rm_out on the context's stream.
+// REFERENCE search: the A* queries instead of the tree (their stats in h_as_io: rm_astar_settle after the synchronisation).
 int roadmap_plan_enqueue(fs_ctx *c, const double robot7[7], int32_t n, const double *goal_xyz, const uint8_t *achievable_in)
 {
     const size_t nn = (size_t)n;
@@ -3452,9 +3572,10 @@ int roadmap_plan_enqueue(fs_ctx *c, const double robot7[7], int32_t n, const dou
     }
     const int32_t nodes = rm_nodes(c);
     const int32_t root = fs_rm_closest(c->rm_xy.data(), c->rm_key.data(), nodes, c->rm_cell, robot7[0], robot7[1]);
+    const bool reference = c->rm_search == FS_ROADMAP_SEARCH_REFERENCE;
     const double *d = nullptr;
     const int32_t *pred = nullptr;
-    if (need_tree && root >= 0) { const int rc = rm_tree(c, root, &d, &pred); if (rc) return rc; }
+    if (!reference && need_tree && root >= 0) { const int rc = rm_tree(c, root, &d, &pred); if (rc) return rc; }
     FS_HIP(c, hipMemcpyAsync(c->d_rm_in.p, c->h_rm_in.p, total_in, hipMemcpyHostToDevice, c->stream));
     FsRmPlanArgs a{};
     a.n_nodes = nodes; a.xy = c->d_rm_xy.p; a.key = c->d_rm_key.p; a.cell = c->rm_cell;
@@ -3467,6 +3588,10 @@ int roadmap_plan_enqueue(fs_ctx *c, const double robot7[7], int32_t n, const dou
     a.path_length_m = reinterpret_cast<double *>(c->d_rm_out.p + O.len_m);
     a.path_heading = reinterpret_cast<double *>(c->d_rm_out.p + O.head);
     a.achievable = reinterpret_cast<uint8_t *>(c->d_rm_out.p + O.ach);
+    if (reference) {
+        if (!need_tree) a.root = -1;                    // (no goal is searched)
+        return roadmap_astar_enqueue(c, a);
+    }
     FS_HIP(c, fs_launch_rm_plan(a, c->stream));
     return FS_OK;
 }
@@ -3912,6 +4037,14 @@ int fs_roadmap_get_graph(fs_ctx *c, int32_t *n_nodes, int64_t *n_edges, double *
     return FS_OK;
 }
 
+int fs_set_roadmap_search(fs_ctx *c, int32_t search)
+{
+    if (!c) return FS_E_INVALID;
+    if (search != FS_ROADMAP_SEARCH_TREE && search != FS_ROADMAP_SEARCH_REFERENCE) return fail(c, FS_E_INVALID, "unknown roadmap search %d", search);
+    c->rm_search = search;
+    return FS_OK;
+}
+
 int fs_roadmap_plan(fs_ctx *c, const double robot_pose7[7], int32_t n, const double *goal_xyz, const uint8_t *achievable_in,
                     double *path_length, double *path_length_m, double *path_heading, uint8_t *achievable)
 {
@@ -3920,8 +4053,13 @@ int fs_roadmap_plan(fs_ctx *c, const double robot_pose7[7], int32_t n, const dou
         return fail(c, FS_E_INVALID, "null pointer");
     FS_HIP(c, hipSetDevice(c->device));
     if (n == 0) return FS_OK;
-    return plan_to_host(c, c->d_rm_out, c->h_rm_out, n, [&] { return roadmap_plan_enqueue(c, robot_pose7, n, goal_xyz, achievable_in); },
-                        path_length, path_length_m, path_heading, achievable);
+    int rc = plan_to_host(c, c->d_rm_out, c->h_rm_out, n, [&] { return roadmap_plan_enqueue(c, robot_pose7, n, goal_xyz, achievable_in); },
+                          path_length, path_length_m, path_heading, achievable);
+    if (rc || c->rm_search != FS_ROADMAP_SEARCH_REFERENCE) return rc;
+    bool redone = false;
+    rc = rm_astar_settle(c, [&] { return roadmap_astar_cols(c); }, &redone);
+    if (rc || !redone) return rc;
+    return plan_to_host(c, c->d_rm_out, c->h_rm_out, n, [] { return FS_OK; }, path_length, path_length_m, path_heading, achievable);
 }
 
 int fs_get_frontier_costs_roadmap(fs_ctx *c, const double robot_pose7[7], int32_t n, const double *goal_xyz, const int32_t *frontier_size,
@@ -3935,13 +4073,18 @@ int fs_get_frontier_costs_roadmap(fs_ctx *c, const double robot_pose7[7], int32_
     if (n == 0) return FS_OK;
     int rc = check_scoring_state(c, true, with_fisher_information != 0);
     if (rc) return rc;
-    return rank_on_plan(
-        c, c->d_rm_out, c->h_rm_out, n, [&] { return roadmap_plan_enqueue(c, robot_pose7, n, goal_xyz, nullptr); },
-        [&](const PlannedCols &cols) {
-            return frontier_costs_core(c, n, goal_xyz, frontier_size, blacklisted, nullptr, nullptr, nullptr, alpha, beta, max_vx, max_wz,
-                                       with_fisher_information != 0, records, weighted_cost, arrival_utility, distance_utility, order, &cols);
-        },
-        path_length_m);
+    const auto rank = [&](const PlannedCols &cols) {
+        return frontier_costs_core(c, n, goal_xyz, frontier_size, blacklisted, nullptr, nullptr, nullptr, alpha, beta, max_vx, max_wz,
+                                   with_fisher_information != 0, records, weighted_cost, arrival_utility, distance_utility, order, &cols);
+    };
+    rc = rank_on_plan(c, c->d_rm_out, c->h_rm_out, n, [&] { return roadmap_plan_enqueue(c, robot_pose7, n, goal_xyz, nullptr); }, rank,
+                      path_length_m);
+    if (rc || c->rm_search != FS_ROADMAP_SEARCH_REFERENCE) return rc;
+    // (the ranking synchronised; a query that outgrew the global route's pool leaves columns to be written again, and ranked again)
+    bool redone = false;
+    rc = rm_astar_settle(c, [&] { return roadmap_astar_cols(c); }, &redone);
+    if (rc || !redone) return rc;
+    return rank_on_plan(c, c->d_rm_out, c->h_rm_out, n, [] { return FS_OK; }, rank, path_length_m);
 }
 
 }  // extern "C"
@@ -4075,6 +4218,47 @@ int tour_enqueue(fs_ctx *c, const FsRmPairArgs &pa_in, int32_t K, const int32_t 
     return FS_OK;
 }
 
+// The REFERENCE search's pair lengths: pair (i, j), i < j, is the A* from start[i] to start[j] (distinct pairs run once; equal
+// points and points without a key node run none).  The queries are enqueued and pa points the pair kernel at their results.
+int tour_astar_enqueue(fs_ctx *c, FsRmPairArgs &pa)
+{
+    const int32_t m = pa.m, nodes = rm_nodes(c);
+    std::vector<int32_t> qs, qd;
+    for (int32_t l = 0; l < m * m; ++l) pa.query[l] = -1;
+    for (int32_t i = 0; i < m; ++i)
+        for (int32_t j = i + 1; j < m; ++j) {
+            if ((pa.pxy[2 * i] == pa.pxy[2 * j] && pa.pxy[2 * i + 1] == pa.pxy[2 * j + 1]) || pa.start[i] < 0 || pa.start[j] < 0) continue;
+            size_t q = 0;
+            while (q < qs.size() && !(qs[q] == pa.start[i] && qd[q] == pa.start[j])) ++q;
+            if (q == qs.size()) { qs.push_back(pa.start[i]); qd.push_back(pa.start[j]); }
+            pa.query[i * m + j] = (int32_t)q;
+        }
+    const int32_t nq = (int32_t)qs.size();
+    // the query list staged behind the stats in h_as_io: nq | src [nq] | dst [nq]
+    FS_HIP(c, c->h_as_io.ensure(64 + 4 * (1 + 2 * (size_t)nq)));
+    FS_HIP(c, c->d_as_src.ensure(1 + 2 * (size_t)nq));
+    FS_HIP(c, c->d_as_status.ensure((size_t)std::max(nq, 1))); FS_HIP(c, c->d_as_len.ensure((size_t)std::max(nq, 1)));
+    int32_t *h = reinterpret_cast<int32_t *>(c->h_as_io.p + 64);
+    h[0] = nq;
+    std::copy(qs.begin(), qs.end(), h + 1);
+    std::copy(qd.begin(), qd.end(), h + 1 + nq);
+    FS_HIP(c, hipMemcpyAsync(c->d_as_src.p, h, 4 * (1 + 2 * (size_t)nq), hipMemcpyHostToDevice, c->stream));
+    FsRmAstarArgs q{};
+    q.n_nodes = nodes;
+    if (nq > 0) {
+        const int rc = rm_device_graph(c);
+        if (rc) return rc;
+        q.xy = c->d_rm_xy.p; q.row = c->d_rm_row.p; q.col = c->d_rm_col.p;
+    }
+    q.nq = c->d_as_src.p; q.src = c->d_as_src.p + 1; q.dst = c->d_as_src.p + 1 + nq;
+    q.status = c->d_as_status.p; q.len = c->d_as_len.p;
+    q.lds_cap = rm_astar_lds_cap(c, nodes);
+    const int rc = rm_astar_enqueue(c, q, nq);
+    if (rc) return rc;
+    pa.q_status = c->d_as_status.p; pa.q_len = c->d_as_len.p;
+    return FS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4132,7 +4316,8 @@ int fs_roadmap_next_goal(fs_ctx *c, const double robot_pose7[7], int32_t n, cons
         pa.start[i] = fs_rm_closest(c->rm_xy.data(), c->rm_key.data(), nodes, c->rm_cell, g[0], g[1]);
     }
     int32_t roots[RM_TOUR_MAX_TREES], K = 0;
-    for (int32_t i = 0; i < m - 1; ++i) {
+    const bool reference = c->rm_search == FS_ROADMAP_SEARCH_REFERENCE;
+    for (int32_t i = 0; i < m - 1 && !reference; ++i) {
         pa.tree[i] = 0;
         if (pa.start[i] < 0) continue;
         int32_t b = 0;
@@ -4142,9 +4327,15 @@ int fs_roadmap_next_goal(fs_ctx *c, const double robot_pose7[7], int32_t n, cons
     }
     bool polled = false;
     int64_t rounds = 0;
-    int rc = tour_enqueue(c, pa, K, roots, k, &polled, &rounds);
+    int rc = reference ? tour_astar_enqueue(c, pa) : FS_OK;
+    if (!rc) rc = tour_enqueue(c, pa, K, roots, k, &polled, &rounds);
     if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
     FS_HIP(c, hipStreamSynchronize(c->stream));
+    if (reference) {
+        bool redone = false;
+        rc = rm_astar_settle(c, [&] { return tour_enqueue(c, pa, 0, roots, k, &polled, &rounds); }, &redone);
+        if (rc) return rc;
+    }
     if (!polled) {
         for (int32_t b = 0; b < K; ++b) {
             int32_t r = 0;

@@ -305,6 +305,42 @@ struct FsRmPlanArgs {
 };
 hipError_t fs_launch_rm_plan(const FsRmPlanArgs &a, hipStream_t s);
 
+// ---- the REFERENCE roadmap search: FrontierRoadmapAStar::getPlan per distinct (start, goal) pair, one wave per
+// query (fs_roadmap_astar.h).  A query's heap, records and per-node state sit in LDS while they fit (lds_cap records); a query that
+// outgrows them, or every query when lds_cap is 0, runs again on the global route: `slots` waves, each with a slot of the pool
+// holding `cap` records.  A query that outgrows that too keeps status FS_ASTAR_OVERFLOW and is counted in stats[3]; the host grows
+// the pool and launches the global route again.
+struct FsRmAstarArgs {
+    int32_t n_nodes;
+    const double *xy;
+    const int32_t *row, *col;       // the roadmap's adjacency lists (CSR, the reference's order)
+    const int32_t *nq;              // [1] queries (a device word)
+    const int32_t *src;             // [q] start node, or nullptr: `root` for every query
+    int32_t root;
+    const int32_t *dst;             // [q] goal node
+    int32_t *status;                // [q] FS_ASTAR_FOUND / NO_PATH / OVERFLOW
+    double *len;                    // [q] path length (FOUND)
+    int32_t *stats;                 // [0] queries, [1] pops of the largest query, [2] queries sent to the global route, [3] queries
+                                    //     that outgrew the global route's capacity
+    int32_t lds_cap;                // records in LDS (0: every query takes the global route)
+    char *pool;                     // global route: slot b at pool + b * slot_bytes
+    size_t slot_bytes;
+    int32_t slots, cap;
+};
+#define RM_ASTAR_LDS_BYTES 65536
+#define RM_ASTAR_SLOTS 32
+// bytes of one query's storage: heap (f, record), records (g, node, parent), best record and closed flag of every node
+inline size_t fs_rm_astar_bytes(int32_t cap, int32_t n) { return ((size_t)28 * (size_t)cap + (size_t)5 * (size_t)n + 15) & ~(size_t)15; }
+// the LDS route over queries 0 .. nq - 1 (grid: max_q workgroups, an upper bound of nq), then the global route
+hipError_t fs_launch_rm_astar(const FsRmAstarArgs &a, int32_t max_q, hipStream_t s);
+hipError_t fs_launch_rm_astar_global(const FsRmAstarArgs &a, hipStream_t s);
+// the plan's queries: every frontier's goal node (mode 2, a start node) marked, the marks scanned into query indices, the query
+// list; then the path columns from the query results
+hipError_t fs_launch_rm_astar_goals(const FsRmPlanArgs &p, int32_t *d_gnode, int32_t *d_mark, hipStream_t s);
+hipError_t fs_launch_rm_astar_list(int32_t n_nodes, const int32_t *d_mark, const int32_t *d_qidx, int32_t *d_dst, hipStream_t s);
+hipError_t fs_launch_rm_astar_cols(const FsRmPlanArgs &p, const int32_t *d_gnode, const int32_t *d_qidx, const int32_t *d_status,
+                                   const double *d_len, hipStream_t s);
+
 // ---- next goal (FullPathOptimizer::getNextGoal): the pair matrix over [robot, locals, closest global] and the
 // exhaustive tour search over the locals' orders
 #define RM_TOUR_MAX_LOCAL 12                          // 12! < 2^31
@@ -333,6 +369,10 @@ struct FsRmPairArgs {
     int32_t start[RM_TOUR_MAX_NODES];       // closest key node of each point (-1: none)
     int32_t tree[RM_TOUR_MAX_NODES];        // the tree rooted at start[i] (sources 0..m-2)
     double *M;                              // [m][m], symmetric, 0 on the diagonal
+    // REFERENCE search (q_status != nullptr): pair (i, j), i < j, is A* query query[i * m + j] (-1: no start node)
+    const int32_t *q_status;
+    const double *q_len;
+    int32_t query[RM_TOUR_MAX_NODES * RM_TOUR_MAX_NODES];
 };
 hipError_t fs_launch_rm_pairs(const FsRmPairArgs &a, hipStream_t s);
 // the tour search: lane chunks of lexicographic ranks, one (length, robot leg, rank, count) per block, then one workgroup over the

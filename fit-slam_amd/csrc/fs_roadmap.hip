@@ -17,6 +17,7 @@
 // monotone, so d converges to the minimum over paths of the left-to-right sums whatever the schedule, and hops / predecessor to the
 // shortest tight in-edge chain / its least index (DESIGN.md 4.10 states when that is unique); no atomic decides a predecessor.
 #include "fs_internal.h"
+#include "fs_roadmap_astar.h"
 
 #include <float.h>
 
@@ -292,6 +293,9 @@ __global__ __launch_bounds__(256) void rm_pairs_kernel(const FsRmPairArgs a)
     double len = a.charge;
     if (a.pxy[2 * i] == a.pxy[2 * j] && a.pxy[2 * i + 1] == a.pxy[2 * j + 1]) {
         len = 0.0;
+    } else if (a.q_status) {
+        const int32_t q = a.query[l];
+        if (q >= 0 && a.q_status[q] == FS_ASTAR_FOUND) len = a.q_len[q];
     } else {
         const int32_t root = a.start[i];
         int32_t v = a.start[j];
@@ -530,5 +534,224 @@ hipError_t fs_launch_rm_tour(const FsRmTourArgs &a, int32_t blocks, double *d_ou
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rm_tour_reduce_kernel, dim3(1), dim3(kTourThreads), 0, s, a, blocks, d_out);
+    return hipGetLastError();
+}
+
+
+// ---- the REFERENCE search: FrontierRoadmapAStar::getPlan per distinct (start, goal) pair, one wave per query
+
+namespace {
+
+constexpr int kAstarThreads = 64;
+
+// one query's storage laid out from `base` (fs_rm_astar_bytes(cap, n) bytes, 16-byte aligned): doubles first
+__device__ __forceinline__ fs_astar_mem astar_carve(char *base, int32_t cap, int32_t n)
+{
+    fs_astar_mem m;
+    m.heap_f = reinterpret_cast<double *>(base);
+    m.rec_g = m.heap_f + cap;
+    m.heap_rec = reinterpret_cast<int32_t *>(m.rec_g + cap);
+    m.rec_node = m.heap_rec + cap;
+    m.rec_parent = m.rec_node + cap;
+    m.best = m.rec_parent + cap;
+    m.closed = reinterpret_cast<uint8_t *>(m.best + n);
+    m.cap = cap;
+    return m;
+}
+
+// fs_astar_run by one wave: lane 0 owns the heap and the records; the lanes evaluate a popped node's successors 64 at a time (g, h,
+// f and the closed / best-g test), and the accepted ones are committed one at a time in adjacency order, each re-tested at commit
+// (an earlier commit of the same chunk can only lower a best g, so a successor rejected at evaluation stays rejected).  The
+// workgroup is this one wave: its barriers order lane 0's stores before the other lanes' loads, in LDS and in global memory alike.
+__device__ __forceinline__ int astar_wave(const fs_astar_graph &G, const fs_astar_mem &m, int32_t start, int32_t goal, double *len,
+                                          int32_t *pops)
+{
+    const int lane = threadIdx.x;
+    for (int32_t v = lane; v < G.n; v += kAstarThreads) { m.best[v] = -1; m.closed[v] = 0; }
+    __syncthreads();
+    int32_t nrec = 0, hsize = 0;                                    // (lane 0's)
+    if (lane == 0) fs_astar_begin(m, start, nrec, hsize);
+    __syncthreads();
+    const double gx = G.xy[2 * goal], gy = G.xy[2 * goal + 1];
+    int32_t np = 0;
+    double L = 0.0;
+    int result = FS_ASTAR_NO_PATH;
+    for (;;) {
+        int32_t r = -1;
+        if (lane == 0 && hsize > 0) r = fs_astar_pop(m.heap_f, m.heap_rec, hsize);
+        r = __shfl(r, 0);
+        if (r < 0) break;
+        ++np;
+        const int32_t cur = m.rec_node[r];
+        if (G.xy[2 * cur] == gx && G.xy[2 * cur + 1] == gy) {
+            if (lane == 0) L = fs_astar_length(m, G.xy, m.best[cur]);
+            result = FS_ASTAR_FOUND;
+            break;
+        }
+        const double cg = m.rec_g[r];
+        if (lane == 0) m.closed[cur] = 1;
+        __syncthreads();
+        const int32_t b = G.row[cur], e = G.row[cur + 1];
+        bool ovf = false;
+        for (int32_t j0 = b; j0 < e && !ovf; j0 += kAstarThreads) {
+            const int32_t j = j0 + lane;
+            int32_t nb = 0;
+            double g = 0.0, f = 0.0;
+            bool cand = false;
+            if (j < e) {
+                nb = G.col[j];
+                g = cg + fs_astar_sq(G.xy, cur, nb);
+                const double h = fs_astar_sq(G.xy, nb, goal);
+                f = g + h;
+                cand = fs_astar_accepts(m, nb, g);
+            }
+            uint64_t mask = __ballot(cand);
+            while (mask) {
+                const int t = __builtin_ctzll(mask);
+                mask &= mask - 1;
+                const int32_t nb_t = __shfl(nb, t);
+                const double g_t = __shfl(g, t), f_t = __shfl(f, t);
+                int full = 0;
+                if (lane == 0 && fs_astar_accepts(m, nb_t, g_t) && !fs_astar_commit(m, cur, nb_t, g_t, f_t, nrec, hsize)) full = 1;
+                if (__shfl(full, 0)) { ovf = true; break; }
+            }
+            __syncthreads();
+        }
+        if (ovf) { result = FS_ASTAR_OVERFLOW; break; }
+    }
+    *len = L;
+    *pops = np;
+    return result;
+}
+
+__device__ __forceinline__ int32_t astar_src(const FsRmAstarArgs &a, int32_t q) { return a.src ? a.src[q] : a.root; }
+
+// the LDS route, one workgroup (one wave) per query
+__global__ __launch_bounds__(kAstarThreads) void rm_astar_lds_kernel(const FsRmAstarArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int32_t q = blockIdx.x, nq = a.nq[0];
+    if (q == 0 && threadIdx.x == 0) a.stats[0] = nq;
+    if (q >= nq) return;
+    int st = FS_ASTAR_OVERFLOW;
+    double len = 0.0;
+    int32_t pops = 0;
+    if (a.lds_cap > 0) {
+        const fs_astar_graph G{a.n_nodes, a.xy, a.row, a.col};
+        st = astar_wave(G, astar_carve(smem, a.lds_cap, a.n_nodes), astar_src(a, q), a.dst[q], &len, &pops);
+    }
+    if (threadIdx.x == 0) {
+        a.status[q] = st;
+        if (st == FS_ASTAR_OVERFLOW) {
+            atomicAdd(&a.stats[2], 1);
+        } else {
+            a.len[q] = len;
+            atomicMax(&a.stats[1], pops);
+        }
+    }
+}
+
+// the global route: `slots` workgroups take the queries left with FS_ASTAR_OVERFLOW in turn, each in its slot of the pool
+__global__ __launch_bounds__(kAstarThreads) void rm_astar_global_kernel(const FsRmAstarArgs a)
+{
+    const int32_t nq = a.nq[0];
+    const fs_astar_graph G{a.n_nodes, a.xy, a.row, a.col};
+    const fs_astar_mem m = astar_carve(a.pool + (size_t)blockIdx.x * a.slot_bytes, a.cap, a.n_nodes);
+    for (int32_t q = blockIdx.x; q < nq; q += gridDim.x) {
+        if (a.status[q] != FS_ASTAR_OVERFLOW) continue;
+        double len = 0.0;
+        int32_t pops = 0;
+        const int st = astar_wave(G, m, astar_src(a, q), a.dst[q], &len, &pops);
+        if (threadIdx.x == 0) {
+            if (st == FS_ASTAR_OVERFLOW) {
+                atomicAdd(&a.stats[3], 1);
+            } else {
+                a.status[q] = st;
+                a.len[q] = len;
+                atomicMax(&a.stats[1], pops);
+            }
+        }
+        __syncthreads();                // (the slot is reused by the next query)
+    }
+}
+
+// every planned frontier's goal node (getClosestNodeInRoadMap of the goal), marked as a query
+__global__ void rm_astar_goals_kernel(const FsRmPlanArgs a, int32_t *__restrict__ gnode, int32_t *__restrict__ mark)
+{
+    const int32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= a.n) return;
+    int32_t v = -1;
+    if (a.mode[f] == 2 && a.root >= 0) v = fs_rm_closest(a.xy, a.key, a.n_nodes, a.cell, a.goal[2 * f], a.goal[2 * f + 1]);
+    gnode[f] = v;
+    if (v >= 0) mark[v] = 1;
+}
+
+__global__ void rm_astar_list_kernel(int32_t n, const int32_t *__restrict__ mark, const int32_t *__restrict__ qidx, int32_t *__restrict__ dst)
+{
+    const int32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v < n && mark[v]) dst[qidx[v]] = v;
+}
+
+// rm_plan_kernel's columns from the goal node's query
+__global__ void rm_astar_cols_kernel(const FsRmPlanArgs a, const int32_t *__restrict__ gnode, const int32_t *__restrict__ qidx,
+                                     const int32_t *__restrict__ status, const double *__restrict__ qlen)
+{
+    const int32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= a.n) return;
+    const double dmax = DBL_MAX;
+    double len = dmax, head = dmax;
+    uint8_t ok = 0;
+    if (a.mode[f] == 1) {
+        len = 0.0; head = a.heading_in[f]; ok = 1;
+    } else if (a.mode[f] == 2 && gnode[f] >= 0) {
+        const int32_t q = qidx[gnode[f]];
+        if (status[q] == FS_ASTAR_FOUND) { len = qlen[q]; head = a.heading_in[f]; ok = 1; }
+    }
+    a.path_length[f] = len;
+    a.path_length_m[f] = len;
+    a.path_heading[f] = head;
+    a.achievable[f] = ok;
+}
+
+}  // namespace
+
+hipError_t fs_launch_rm_astar(const FsRmAstarArgs &a, int32_t max_q, hipStream_t s)
+{
+    if (max_q > 0) {
+        const size_t lds = a.lds_cap > 0 ? fs_rm_astar_bytes(a.lds_cap, a.n_nodes) : 0;
+        if (lds > RM_ASTAR_LDS_BYTES) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(rm_astar_lds_kernel, dim3((unsigned)max_q), dim3(kAstarThreads), lds, s, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return fs_launch_rm_astar_global(a, s);
+}
+
+hipError_t fs_launch_rm_astar_global(const FsRmAstarArgs &a, hipStream_t s)
+{
+    if (a.slots < 1 || a.cap < 1 || !a.pool) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rm_astar_global_kernel, dim3((unsigned)a.slots), dim3(kAstarThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_rm_astar_goals(const FsRmPlanArgs &p, int32_t *d_gnode, int32_t *d_mark, hipStream_t s)
+{
+    if (p.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rm_astar_goals_kernel, dim3((unsigned)((p.n + 63) / 64)), dim3(64), 0, s, p, d_gnode, d_mark);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_rm_astar_list(int32_t n_nodes, const int32_t *d_mark, const int32_t *d_qidx, int32_t *d_dst, hipStream_t s)
+{
+    if (n_nodes <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rm_astar_list_kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, s, n_nodes, d_mark, d_qidx, d_dst);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_rm_astar_cols(const FsRmPlanArgs &p, const int32_t *d_gnode, const int32_t *d_qidx, const int32_t *d_status,
+                                   const double *d_len, hipStream_t s)
+{
+    if (p.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rm_astar_cols_kernel, dim3((unsigned)((p.n + 63) / 64)), dim3(64), 0, s, p, d_gnode, d_qidx, d_status, d_len);
     return hipGetLastError();
 }

@@ -483,6 +483,15 @@ int fs_get_frontier_costs_searched(fs_ctx *ctx, const double robot_pose7[7], int
  * 1.5 * radius (DEP/src/planners/FrontierRoadmap.cpp:20).  A new parameter set starts an empty roadmap. */
 int fs_set_roadmap_params(fs_ctx *ctx, double grid_cell_size, double radius_to_decide_edges, double min_distance_between_two_frontier_nodes,
                           double min_distance_between_robot_pose_and_node);
+/* How fs_roadmap_plan, fs_get_frontier_costs_roadmap and the pair lengths of fs_roadmap_next_goal search the roadmap, per context
+ * (fs_set_roadmap_params leaves it).  FS_ROADMAP_SEARCH_TREE (a fresh context's): ONE shortest-path tree per (roadmap, start node)
+ * under squared segment lengths.  FS_ROADMAP_SEARCH_REFERENCE: the reference's per-goal A* (FrontierRoadmapAStar::getPlan,
+ * astar.cpp:42-93) for every distinct (start, goal) node pair — std::priority_queue's heap order, the squared heuristic, the closed
+ * set tested on successors only — so the lengths are the reference's (DESIGN.md 4.10 records where the tree differs).  Any other
+ * value: FS_E_INVALID, the setting unchanged. */
+#define FS_ROADMAP_SEARCH_TREE      0
+#define FS_ROADMAP_SEARCH_REFERENCE 1
+int fs_set_roadmap_search(fs_ctx *ctx, int32_t search);
 /* FrontierRoadMap::populateNodes(populateClosest = true) (FrontierRoadmap.cpp:185-252) — addNodes (is_robot_pose 0) or
  * addRobotPoseAsNode (1): a point closer than the minimum distance to a node of the 3 x 3 hash cells around it is dropped.  xy [n][2].
  * A cell that comes to hold more than 20 nodes: FS_E_RANGE, that node added, the rest of the list not (the reference throws). */
@@ -501,15 +510,19 @@ int fs_roadmap_connect(fs_ctx *ctx, int32_t n, const double *xy);
 int fs_roadmap_get_graph(fs_ctx *ctx, int32_t *n_nodes, int64_t *n_edges, double *xy, uint8_t *key, int32_t *row_ptr, int32_t *col);
 /* FrontierCostCalculator::setPlanForFrontierRoadmap ("RoadmapPlannerDistance", DEP/src/CostCalculator.cpp:395-438) for n frontiers:
  * the start is the key node closest to the robot, each goal's end node the key node closest to it (getClosestNodeInRoadMap,
- * FrontierRoadmap.cpp:506-543), the route the shortest-path tree from the start under squared segment lengths — ONE tree per
- * (roadmap, start node), kept until the roadmap changes — where the reference runs an A* per frontier (astar.cpp:42-93; DESIGN.md
- * 4.10 records where the two differ).  Outputs [n]: path_length = path_length_m (metres, summed from the goal end), path_heading,
- * achievable.  achievable_in 0, no key node or goal node not reached: achievable 0 and DBL_MAX in the three columns; a goal at the
- * robot's exact position: length 0. */
+ * FrontierRoadmap.cpp:506-543).  The route, by the context's roadmap search (fs_set_roadmap_search): FS_ROADMAP_SEARCH_TREE, the
+ * shortest-path tree from the start under squared segment lengths — ONE tree per (roadmap, start node), kept until the roadmap
+ * changes — where the reference runs an A* per frontier (astar.cpp:42-93; DESIGN.md 4.10 records where the two differ);
+ * FS_ROADMAP_SEARCH_REFERENCE, that A* once per distinct goal node, one wave per query on the device, bit for bit the reference's
+ * lengths (the tree and its cache are not touched).  Outputs [n]: path_length = path_length_m (metres, summed from the goal end),
+ * path_heading, achievable.  achievable_in 0, no key node or goal node not reached: achievable 0 and DBL_MAX in the three columns; a
+ * goal at the robot's exact position: length 0.  One synchronisation (the tree's round polling above one workgroup's size, or a
+ * query that outgrows the A*'s global pool, adds more). */
 int fs_roadmap_plan(fs_ctx *ctx, const double robot_pose7[7], int32_t n, const double *goal_xyz, const uint8_t *achievable_in,
                     double *path_length, double *path_length_m, double *path_heading, uint8_t *achievable);
 /* fs_get_frontier_costs with the path columns planned on the roadmap in the same call: plan -> arrival (+ Fisher) -> U1 -> order.
- * Same results, bit for bit, as fs_roadmap_plan followed by fs_get_frontier_costs on its columns; the path columns never visit the host. */
+ * Same results, bit for bit, as fs_roadmap_plan followed by fs_get_frontier_costs on its columns, under either roadmap search
+ * (fs_set_roadmap_search); the path columns never visit the host. */
 int fs_get_frontier_costs_roadmap(fs_ctx *ctx, const double robot_pose7[7], int32_t n, const double *goal_xyz, const int32_t *frontier_size,
                   const uint8_t *blacklisted, double alpha, double beta, double max_vx, double max_wz, int with_fisher_information,
                   fs_record *records, double *weighted_cost, double *arrival_utility, double *distance_utility, int32_t *order,
@@ -548,8 +561,9 @@ int fs_roadmap_get_anchors(fs_ctx *ctx, int32_t *n_pending, int64_t *n_records, 
  * NULL) — and blacklist_xy [n_blacklist_circles][2], the circle centres isInBlacklistedRegion tests (distance < 1.7 m).
  * getFilteredFrontiersN (:157-227) splits the eligible frontiers into at most n_local (1..12; the reference's 5) locals of path length
  * <= local_radius (the reference's 12.0) and globals, with every quirk of the reference; ties in path length go to the lower index.
- * The pair lengths over the nodes [robot, locals in selection order, closest global] are getPlan(i, true, j, true) for i < j — one
- * shortest-path tree per source, all in one launch —, local_radius * 100000 where there is no path; the tour search tries every
+ * The pair lengths over the nodes [robot, locals in selection order, closest global] are getPlan(i, true, j, true) for i < j — by
+ * the context's roadmap search (fs_set_roadmap_search): one shortest-path tree per source, all in one launch, or the reference's A*
+ * from closest(i) to closest(j) per distinct pair —, 0 for equal points, local_radius * 100000 where there is no path; the tour search tries every
  * order of the locals (robot -> locals -> closest global) and keeps the shortest, ties to the shortest robot leg, then the first
  * order in lexicographic order of the selection positions.  fi_pose7 NULL: use_fi false; otherwise isRobotPoseSafe on it through the
  * info-only scorer (unsafe unless info_ref > fi_threshold) on the reference's two branches.

@@ -65,7 +65,10 @@ int  fs_kernel_time(fs_ctx *ctx, int kind, double *total_ms, int64_t *launches);
  * "fim.specialise" (default 1): 0 = always the general FIM worker (no INFO_ONLY / YAW_ONLY instantiation; identical integers,
  * float sums to the last bits) — the A/B switch of tests/test_gpu_reference_visibility.py.
  * "refine.max_fields" (default 16, 1..32): how many cost fields fs_refine_paths relaxes together and keeps cached (8 B per cell per
- * field); a call with more distinct starts runs its legs group by group (identical results). */
+ * field); a call with more distinct starts runs its legs group by group (identical results).
+ * "roadmap.astar_lds_entries" (default 2048, 0..2048): records (heap entries) of an A* query of the REFERENCE roadmap search held in
+ * LDS, further capped by what fits in 64 KiB beside 5 B per roadmap node; a query that outgrows them runs again on the global route
+ * (counter 1023).  0 = every query on the global route.  Identical results. */
 int  fs_set_option(fs_ctx *ctx, const char *key, double value);
 /* Device-side counters: 0 = landmark visibility tests performed (M_tested summed over candidates),
  * 4 = candidates scored in several voxel-partitioned passes, 5 = candidates re-scored with the table in HBM,
@@ -81,7 +84,9 @@ int  fs_set_option(fs_ctx *ctx, const char *key, double value);
  * component of the last fs_search_frontiers, 1015 = pieces of the last search whose median sort stopped a scan at either end of
  * the array (fs_median_sort.h's guard: a cyclic order on which the reference's std::sort leaves the array); 1019 / 1020 = levels
  * walked / cells popped by the outer search of the last search with FS_SEEDS_REFERENCE (levels counted from 1 at the start cell;
- * the walk stops after the level in which the last component is first met, so 1020 is at most the expanded region's size). */
+ * the walk stops after the level in which the last component is first met, so 1020 is at most the expanded region's size);
+ * 1021 = A* queries the REFERENCE roadmap search ran (one per distinct (start, goal) node pair of a call), 1022 = records popped by
+ * the largest query of the last such call, 1023 = queries that took the global route (1021 and 1023 are reset by `reset`). */
 int  fs_get_counter(fs_ctx *ctx, int which, int64_t *value, int reset);
 
 /* ---------------------------------------------------------------- self test */

@@ -3,14 +3,18 @@
 host code, and how far the tree's paths are from the per-goal A*'s.
 
     python tools/roadmap_probe.py deviation [--out DIR]   # CPU only: tree vs reference_astar on the test maps -> astar_vs_tree.json
-    python tools/roadmap_probe.py gpu       [--out DIR]   # on the MI355X -> gpu_ref2d.json and cpu_ref2d.json
+    python tools/roadmap_probe.py gpu       [--out DIR] [--search tree|reference]   # on the MI355X -> gpu_ref2d.json and cpu_ref2d.json
+    python tools/roadmap_probe.py astar     [--out DIR]   # on the MI355X: both roadmap searches -> astar_gpu_ref2d.json
 
 `gpu` grows a roadmap on REF2D the way UpdateRoadmapBT does — per simulated tick, the goal points of fs_frontier_clusters' clusters
 from the robot added as nodes, the robot pose added, both connected (constructNewEdges) — and after every tick times (host wall
 clock, medians) fs_roadmap_rebuild, fs_roadmap_connect of the tick's list, fs_roadmap_plan for 50 and 2 000 frontiers with a fresh
 and a cached tree, and fs_get_frontier_costs_roadmap for 50 frontiers.  The restatement's legs (rebuild, connect, the per-goal A*)
 are timed on ONE core in a child process (`cpu-legs`) on the same node lists; the one-call form is compared with the restatement's
-A* followed by fs_get_frontier_costs.  Output directory: profiles/roadmap (default).
+A* followed by fs_get_frontier_costs.  --search reference plans with the reference's per-goal A* (fs_set_roadmap_search) and
+writes gpu_ref2d_reference.json instead.  `astar` times, on REF2D's roadmap of the tests (nodes on free cells, rebuilt), the two
+roadmap searches side by side — fs_roadmap_plan at 50 and 2 000 frontiers, fs_get_frontier_costs_roadmap at 50, fs_roadmap_next_goal
+at k = 5 — and the restatement's per-goal A* for the same 50 goals on one core.  Output directory: profiles/roadmap (default).
 """
 from __future__ import annotations
 
@@ -101,7 +105,7 @@ def cpu_legs(ticks_file):
     print(json.dumps(rows))
 
 
-def gpu(out_dir):
+def gpu(out_dir, search="tree"):
     fs = importlib.import_module("fit-slam_amd")
     w = ref2d()
     cells = w.cells[0]
@@ -118,6 +122,7 @@ def gpu(out_dir):
     sc.set_ray_params(max_camera_depth=w.max_camera_depth, delta_theta=w.delta_theta, camera_fov=w.camera_fov,
                       robot_radius=w.robot_radius, n_rays=w.n_yaw, elev=w.elev, polygon=w.polygon)
     sc.upload_grid(w.cells, w.origin, w.resolution)
+    sc.set_roadmap_search(search)
     mx = sc.max_arrival()
     sc.set_arrival_limits(4000.0, mx["min_gt"])
     rows = []
@@ -175,10 +180,10 @@ def gpu(out_dir):
     crossover = next((r["nodes"] for r, c in zip(rows, cpu_rows) if r["rebuild_ms"] < c["rebuild_ms"]), None)
     res = dict(what="REF2D (512^2, 0.05 m), roadmap grown over %d simulated ticks (fs_frontier_clusters goal points + robot pose, "
                     "connected each tick); host wall ms, medians" % len(ticks),
-               ticks=rows, host_astar_then_costs_50_final_ms=host_then_costs,
+               search=search, ticks=rows, host_astar_then_costs_50_final_ms=host_then_costs,
                rebuild_faster_than_one_core_from_nodes=crossover)
     os.makedirs(out_dir, exist_ok=True)
-    json.dump(res, open(os.path.join(out_dir, "gpu_ref2d.json"), "w"), indent=1)
+    json.dump(res, open(os.path.join(out_dir, "gpu_ref2d.json" if search == "tree" else f"gpu_ref2d_{search}.json"), "w"), indent=1)
     json.dump(dict(what="the restatement's legs on one core, same node lists, host wall ms (rebuild / A*: medians of 3)", ticks=cpu_rows),
               open(os.path.join(out_dir, "cpu_ref2d.json"), "w"), indent=1)
     print(json.dumps(res))
@@ -237,16 +242,98 @@ def deviation(out_dir):
     print(json.dumps({k: v for k, v in res.items() if k != "per_map"}))
 
 
+def astar_cpu(ticks_file):
+    """child process pinned to one core: the restatement's per-goal A* and its tree leg for the 50 goals of `astar`"""
+    os.sched_setaffinity(0, {sorted(os.sched_getaffinity(0))[0]})
+    d = np.load(ticks_file)
+    cells, origin = d["cells"], tuple(float(v) for v in d["origin"])
+    ref = R.Roadmap(cells, origin, RES)
+    ref.populate(d["pts"])
+    ref.rebuild()
+    pose, g50 = d["pose"], d["g50"]
+    out = {}
+    for leg, key in ((R.REFERENCE_ASTAR, "host_astar_50_ms"), (R.TREE, "host_tree_50_ms")):
+        xs = []
+        for _ in range(7):
+            t0 = time.perf_counter(); ref.plan(pose, g50, leg=leg); xs.append(time.perf_counter() - t0)
+        out[key] = med_ms(xs)
+    print(json.dumps(out))
+
+
+def astar(out_dir):
+    """the two roadmap searches side by side on REF2D's roadmap of the tests"""
+    fs = importlib.import_module("fit-slam_amd")
+    w = ref2d()
+    cells, origin = np.ascontiguousarray(w.cells[0]), tuple(float(v) for v in w.origin)
+    rng = np.random.default_rng(2024)
+    k_nodes = int(min(1500, max(40, cells.size * RES * RES / 2)))
+    xs, ys = P.free_cells(cells, rng, k_nodes)
+    pts = np.stack([origin[0] + (xs + rng.uniform(0, 1, k_nodes)) * RES, origin[1] + (ys + rng.uniform(0, 1, k_nodes)) * RES], axis=1)
+    sc = fs.FrontierScorer(device=0)
+    sc.set_ray_params(max_camera_depth=w.max_camera_depth, delta_theta=w.delta_theta, camera_fov=w.camera_fov,
+                      robot_radius=w.robot_radius, n_rays=w.n_yaw, elev=w.elev, polygon=w.polygon)
+    sc.upload_grid(w.cells, w.origin, w.resolution)
+    mx = sc.max_arrival()
+    sc.set_arrival_limits(4000.0, mx["min_gt"])
+    sc.roadmap_add_nodes(pts)
+    sc.roadmap_rebuild()
+    g = sc.roadmap_graph()
+    poses = [R.pose7(*pts[0], 0.7), R.pose7(*pts[len(pts) // 2], 0.7)]
+    g50, g2000 = goals_of(w, 50, 0), goals_of(w, 2000, 0)
+    rg = np.random.default_rng(5)
+    fx, fy = P.free_cells(cells, rg, 10)
+    ng = np.zeros((10, 3))
+    ng[:, 0] = origin[0] + (fx + 0.5) * RES
+    ng[:, 1] = origin[1] + (fy + 0.5) * RES
+    nplm = np.concatenate([np.sort(rg.uniform(0.5, 12.0, 6)), rg.uniform(12.5, 50.0, 4)])
+    nach = np.ones(10, np.uint8)
+    res = dict(what="REF2D (512^2, 0.05 m), %d nodes / %d edges (nodes on free cells, rebuilt); host wall ms, medians of 15 after "
+                    "one warm-up call; every plan call alternates two start nodes (the tree: a fresh tree per call)"
+                    % (g["xy"].shape[0], g["col"].size),
+               nodes=int(g["xy"].shape[0]), edges=int(g["col"].size), searches={})
+    for search in ("tree", "reference"):
+        sc.set_roadmap_search(search)
+        row = {}
+        for n, gl in ((50, g50), (2000, g2000)):
+            sc.roadmap_plan(poses[1], gl)
+            row[f"plan_{n}_ms"] = timed(lambda i: sc.roadmap_plan(poses[i & 1], gl), 15)
+            if search == "reference":
+                sc.get_counter(1021, reset=True)
+                sc.roadmap_plan(poses[0], gl)
+                row[f"plan_{n}_queries"] = sc.get_counter(1021, reset=True)
+                row[f"plan_{n}_largest_query_pops"] = sc.get_counter(1022)
+                row[f"plan_{n}_global_route_queries"] = sc.get_counter(1023, reset=True)
+        sc.get_frontier_costs_roadmap(poses[1], g50)
+        row["fused_50_ms"] = timed(lambda i: sc.get_frontier_costs_roadmap(poses[i & 1], g50), 15)
+        sc.roadmap_next_goal(poses[0], ng, nplm, nach, n_local=5)
+        row["next_goal_k5_ms"] = timed(lambda i: sc.roadmap_next_goal(poses[i & 1], ng, nplm, nach, n_local=5), 15)
+        res["searches"][search] = row
+    sc.set_roadmap_search("tree")
+    sc.close()
+    tf = os.path.join(tempfile.mkdtemp(prefix="roadmap_probe_"), "astar.npz")
+    np.savez(tf, cells=cells, origin=np.array(origin), pts=pts, pose=poses[0], g50=g50)
+    cpu = subprocess.run([sys.executable, os.path.abspath(__file__), "astar-cpu", "--ticks", tf], check=True, capture_output=True, text=True)
+    res["one_core"] = json.loads(cpu.stdout.strip().splitlines()[-1])
+    os.makedirs(out_dir, exist_ok=True)
+    json.dump(res, open(os.path.join(out_dir, "astar_gpu_ref2d.json"), "w"), indent=1)
+    print(json.dumps(res))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["deviation", "gpu", "cpu-legs"])
+    ap.add_argument("mode", choices=["deviation", "gpu", "astar", "cpu-legs", "astar-cpu"])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "roadmap"))
     ap.add_argument("--ticks")
+    ap.add_argument("--search", choices=["tree", "reference"], default="tree")
     a = ap.parse_args()
     if a.mode == "deviation":
         deviation(a.out)
     elif a.mode == "gpu":
-        gpu(a.out)
+        gpu(a.out, a.search)
+    elif a.mode == "astar":
+        astar(a.out)
+    elif a.mode == "astar-cpu":
+        astar_cpu(a.ticks)
     else:
         cpu_legs(a.ticks)
     return 0

@@ -48,6 +48,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tour"))
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--search", choices=["tree", "reference"], default="tree",
+                    help="the roadmap search of the pair lengths (fs_set_roadmap_search); reference writes *_reference.json")
     args = ap.parse_args()
     import torch  # noqa: F401  (the same load order as bench.py)
     fs = importlib.import_module("fit-slam_amd")
@@ -62,6 +64,8 @@ def main():
     sc.upload_grid(cells[None], origin, res)
     sc.roadmap_add_nodes(pts)
     sc.roadmap_rebuild()
+    sc.set_roadmap_search(args.search)
+    suffix = "" if args.search == "tree" else "_" + args.search
     ref = R.Roadmap(cells, origin, res)
     ref.populate(pts)
     ref.rebuild()
@@ -89,20 +93,21 @@ def main():
     cg = np.flatnonzero(sel & 4)
     nodes = np.concatenate([robot[None], goal[loc, :2], goal[cg, :2]])
     M_ref = T.pair_matrix(ref, nodes)
-    assert out["pair_length_m"].tobytes() == M_ref.tobytes(), "device pair matrix differs from the restatement"
+    if args.search == "tree":
+        assert out["pair_length_m"].tobytes() == M_ref.tobytes(), "device pair matrix differs from the restatement"
     sources = nodes[:-1]
     pairs = dict(
-        map="REF2D", roadmap_nodes=n_nodes, roadmap_edges=n_edges, k=5, trees=int(sources.shape[0]),
-        matrix_bit_equal_to_restatement=True,
+        map="REF2D", search=args.search, roadmap_nodes=n_nodes, roadmap_edges=n_edges, k=5, trees=int(sources.shape[0]),
+        matrix_bit_equal_to_restatement=bool(out["pair_length_m"].tobytes() == M_ref.tobytes()),
         host_restatement=med_ms(lambda: T.pair_matrix(ref, nodes), max(3, args.reps // 4)),
         device_next_goal_call=med_ms(lambda: sc.roadmap_next_goal(R.pose7(*robot), goal, plm, ach, n_local=5), args.reps),
         device_one_plan_per_source=med_ms(lambda: [sc.roadmap_plan(R.pose7(*s), goal[:1]) for s in sources], args.reps),
         tree_rounds_of_the_batch=sc.get_counter(1009),
     )
-    json.dump(pairs, open(os.path.join(args.out, "pairs_ref2d.json"), "w"), indent=1)
+    json.dump(pairs, open(os.path.join(args.out, f"pairs_ref2d{suffix}.json"), "w"), indent=1)
     print(json.dumps(pairs))
     # ---- the tour search at k = 5, 8, 10, 12
-    tours = dict(map="REF2D", roadmap_nodes=n_nodes, roadmap_edges=n_edges, rows=[])
+    tours = dict(map="REF2D", search=args.search, roadmap_nodes=n_nodes, roadmap_edges=n_edges, rows=[])
     for k in (5, 8, 10, 12):
         goal, plm, ach = frontier_list(k)
         reps = args.reps if k < 12 else max(5, args.reps // 2)
@@ -123,7 +128,7 @@ def main():
             row["host_reference_loop_equal"] = bool(L == out["tour_length"] and cnt == out["n_tied"])
         tours["rows"].append(row)
         print(json.dumps(row))
-    json.dump(tours, open(os.path.join(args.out, "tours_ref2d.json"), "w"), indent=1)
+    json.dump(tours, open(os.path.join(args.out, f"tours_ref2d{suffix}.json"), "w"), indent=1)
     sc.close()
     ref.close()
 

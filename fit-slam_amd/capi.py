@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = [
     "fs_multi_set_option", "fs_multi_set_ray_params", "fs_multi_upload_grid", "fs_multi_update_grid_region", "fs_multi_upload_landmarks", "fs_multi_lookup_generate",
     "fs_multi_lookup_load", "fs_multi_set_fim_params", "fs_multi_max_arrival", "fs_multi_score_arrival", "fs_multi_score_candidates",
     "fs_multi_score_fim", "fs_multi_get_frontier_costs", "fs_multi_gather_mode",
-    "fs_plan_paths", "fs_navfn_potential", "fs_get_frontier_costs_planned",
+    "fs_plan_paths", "fs_navfn_potential", "fs_get_frontier_costs_planned", "fs_plan_paths_information",
     "fs_set_roadmap_params", "fs_roadmap_add_nodes", "fs_roadmap_rebuild", "fs_roadmap_connect", "fs_roadmap_get_graph", "fs_roadmap_plan",
     "fs_get_frontier_costs_roadmap", "fs_roadmap_next_goal", "fs_refine_paths", "fs_refine_field",
     "fs_roadmap_set_keyframes", "fs_roadmap_optimize", "fs_roadmap_get_anchors",
@@ -51,6 +51,10 @@ assert RECORD_DTYPE.itemsize == 32
 class KeyframeParamsC(C.Structure):
     _fields_ = [("max_depth", C.c_double), ("hfov", C.c_double), ("max_depth_error", C.c_double),
                 ("q_diag", C.c_float), ("radius", C.c_double)]
+
+
+class PathInfoParamsC(C.Structure):
+    _fields_ = [("sample_distance_m", C.c_double), ("lookahead_points", C.c_int32), ("fi_threshold", C.c_double)]
 
 
 class FrontierClusterC(C.Structure):
@@ -168,6 +172,8 @@ def load_library(build: bool = True):
     L.fs_multi_gather_mode.argtypes = [vp]
     L.fs_plan_paths.argtypes = [vp, C.POINTER(dbl * 7), i32, i32, vp, vp, vp, vp, vp, vp]
     L.fs_navfn_potential.argtypes = [vp, C.POINTER(dbl * 7), i32, vp]
+    L.fs_plan_paths_information.argtypes = [vp, C.POINTER(dbl * 7), i32, i32, vp, vp, C.POINTER(PathInfoParamsC), vp, vp, vp, vp, vp, vp, vp, vp,
+                                            i64, C.POINTER(i64), vp, vp, vp]
     L.fs_get_frontier_costs_planned.argtypes = [vp, C.POINTER(dbl * 7), i32, i32, vp, vp, vp, dbl, dbl, dbl, dbl, C.c_int, vp, vp, vp, vp, vp, vp]
     L.fs_set_roadmap_params.argtypes = [vp, dbl, dbl, dbl, dbl]
     L.fs_roadmap_add_nodes.argtypes = [vp, i32, vp, i32]
@@ -609,6 +615,50 @@ class FrontierScorer:
         ach = np.zeros(n, dtype=np.uint8)
         self._check(self._L.fs_plan_paths(self._h, C.byref(pose), 1 if allow_unknown else 0, n, _p(goal), _p(ai), _p(pl), _p(plm), _p(ph), _p(ach)))
         return dict(path_length=pl, path_length_m=plm, path_heading=ph, achievable=ach)
+
+    def plan_paths_information(self, robot_pose7, goal_xyz, achievable_in=None, allow_unknown=False, sample_distance=1.5, lookahead=10,
+                               fi_threshold=550.0, want_waypoints=False):
+        """plan_paths, and the Fisher information along every planned path: setPlanForFrontier's way points (one once more than
+        int(sample_distance / resolution) path points have gone by, looking `lookahead` points ahead), isPoseSafe's scalar at each.
+        Per frontier: n_waypoints, info_mean, info_min, first_unsafe (-1: every way point is above fi_threshold).
+        want_waypoints: also waypoint_offset [n + 1], waypoint_pose7 [total][7] and waypoint_info [total], in list order."""
+        pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
+        goal = np.ascontiguousarray(goal_xyz, dtype=np.float64).reshape(-1, 3)
+        n = goal.shape[0]
+        ai = None if achievable_in is None else np.ascontiguousarray(achievable_in, dtype=np.uint8).reshape(-1)
+        if ai is not None and ai.shape[0] != n:
+            raise ValueError(f"achievable_in has {ai.shape[0]} entries for {n} goals")
+        prm = PathInfoParamsC(float(sample_distance), int(lookahead), float(fi_threshold))
+        pl, plm, ph = np.zeros(n), np.zeros(n), np.zeros(n)
+        ach = np.zeros(n, dtype=np.uint8)
+        nwp = np.zeros(n, dtype=np.int32)
+        mean = np.zeros(n)
+        mn = np.zeros(n, dtype=np.float32)
+        unsafe = np.zeros(n, dtype=np.int32)
+        out = dict(path_length=pl, path_length_m=plm, path_heading=ph, achievable=ach, n_waypoints=nwp, info_mean=mean, info_min=mn,
+                   first_unsafe=unsafe)
+
+        def call(room, total, off, poses, info):
+            return self._L.fs_plan_paths_information(self._h, C.byref(pose), 1 if allow_unknown else 0, n, _p(goal), _p(ai), C.byref(prm),
+                                                     _p(pl), _p(plm), _p(ph), _p(ach), _p(nwp), _p(mean), _p(mn), _p(unsafe), room,
+                                                     total, _p(off), _p(poses), _p(info))
+        if not want_waypoints:
+            self._check(call(0, None, None, None, None))
+            return out
+        # the room of the first try: the default sampling leaves a way point per 1.5 m; a longer list costs a second call
+        total = C.c_int64()
+        off = np.zeros(n + 1, dtype=np.int32)
+        room = 64 * n + 64
+        for _ in range(2):
+            poses = np.zeros((room, 7))
+            info = np.zeros(room, dtype=np.float32)
+            rc = call(room, C.byref(total), off, poses, info)
+            if rc != FS_E_RANGE or total.value <= room:
+                break
+            room = total.value
+        self._check(rc)
+        out.update(waypoint_offset=off, waypoint_pose7=poses[:total.value], waypoint_info=info[:total.value])
+        return out
 
     def navfn_potential(self, robot_pose7, allow_unknown=False) -> np.ndarray:
         """The potential field plan_paths descends, float32 [ny][nx] of the grid this scorer staged."""

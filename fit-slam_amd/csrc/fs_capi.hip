@@ -316,6 +316,18 @@ struct fs_ctx {
     DevBuf<char> d_nav_in, d_nav_out; // goal cells | headings;  path length | length in m | heading | achievable
     PinnedBuf h_nav_in, h_nav_out;
 
+    // Fisher information along the planned paths (fs_pathinfo.hip)
+    bool opt_pi_dedup = true;         // "pathinfo.dedup": one pose record per distinct (from cell, to cell) (0: one per way point)
+    int64_t pi_waypoints = 0, pi_distinct = 0;      // way points of the last call, pose records it scored
+    DevBuf<int32_t> d_pi_off;         // count [n + 1] | offset [n + 1]
+    DevBuf<uint64_t> d_pi_key;        // [2][bound]
+    DevBuf<int32_t> d_pi_idx;         // [5][bound]: way point in / out of the sort, head, rank, slot
+    DevBuf<float> d_pi_rt;            // [bound][12]
+    DevBuf<double> d_pi_pose;         // [bound][7] (dump)
+    DevBuf<float> d_pi_val;           // [bound] (dump)
+    DevBuf<char> d_pi_temp, d_pi_out; // rocPRIM's scratch;  hdr [2] | info_mean | info_min | first_unsafe | n_waypoints
+    PinnedBuf h_pi_out;
+
     // frontier roadmap (fs_roadmap.hip).  The host keeps FrontierRoadMap's two containers — the spatial hash (cell ->
     // node ids in insertion order) and roadmap_ (a key flag and an adjacency list in append order per node) — and the device a copy
     // of them as CSR.  Every mutation bumps rm_gen; the device copy, its transpose and the shortest-path tree (kept per root node)
@@ -611,6 +623,13 @@ struct PlanOutLayout {
     size_t len, len_m, head, ach, total;
     explicit PlanOutLayout(size_t n) : len(0), len_m(8 * n), head(16 * n), ach(24 * n), total(24 * n + ((n + 15) & ~(size_t)15)) {}
 };
+
+// Output block of fs_plan_paths_information in d_pi_out / h_pi_out: total, records | info_mean | info_min | first_unsafe
+struct PathInfoOutLayout {
+    size_t hdr, mean, min, unsafe, total;
+    explicit PathInfoOutLayout(size_t n) : hdr(0), mean(16), min(16 + 8 * n), unsafe(16 + 12 * n), total(16 + 16 * n) {}
+};
+#define PI_BOUND_DIRECT (1 << 19)     // way points the call makes room for before it knows how many there are
 
 // ---------------------------------------------------------------- lookup-table math (host, float32)
 // FIP/src/fisher_information/FisherInformationHelpers.cpp:71-96,114-123 with Q = I.
@@ -1063,6 +1082,8 @@ void fs_ctx_destroy(fs_ctx *c)
     c->d_fs_goal.release(); c->d_fs_black_xy.release(); c->d_fs_black.release();
     c->d_nav_cost.release(); c->d_nav_pot.release(); c->d_nav_flags.release(); c->d_nav_any.release(); c->d_nav_path.release();
     c->d_nav_in.release(); c->d_nav_out.release(); c->h_nav_in.release(); c->h_nav_out.release();
+    c->d_pi_off.release(); c->d_pi_key.release(); c->d_pi_idx.release(); c->d_pi_rt.release(); c->d_pi_pose.release(); c->d_pi_val.release();
+    c->d_pi_temp.release(); c->d_pi_out.release(); c->h_pi_out.release();
     c->d_rm_xy.release(); c->d_rm_d.release(); c->d_rm_key.release(); c->d_rm_cell_key.release(); c->d_rm_row.release(); c->d_rm_col.release();
     c->d_rm_trow.release(); c->d_rm_tcol.release(); c->d_rm_tmp.release(); c->d_rm_cell_start.release(); c->d_rm_cell_nodes.release();
     c->d_rm_cand_off.release(); c->d_rm_cand.release(); c->d_rm_hops.release(); c->d_rm_pred.release(); c->d_rm_word.release();
@@ -1987,6 +2008,7 @@ int fs_set_option(fs_ctx *c, const char *key, double value)
     if (std::strcmp(key, "roadmap.tour_one_wg") == 0 && value >= 0 && value <= RM_TREE_ONE_WG) { c->tour_one_wg = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "roadmap.astar_lds_entries") == 0 && value >= 0 && value <= 2048) { c->astar_lds_entries = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "roadmap.dedup_one_wg") == 0 && value >= 0 && value <= FS_KF_DEDUP_ONE_WG) { c->kf_one_wg = (int32_t)value; return FS_OK; }
+    if (std::strcmp(key, "pathinfo.dedup") == 0) { c->opt_pi_dedup = value != 0.0; return FS_OK; }
     if (std::strcmp(key, "refine.max_fields") == 0 && value >= 1 && value <= RF_MAX_FIELDS) {
         if ((int32_t)value != c->rf_max_fields) { c->rf_max_fields = (int32_t)value; c->rf_key.clear(); c->rf_gen.clear(); }
         return FS_OK;
@@ -2023,6 +2045,8 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
         {1019, &fs_ctx::fs_outer_levels, false}, {1020, &fs_ctx::fs_outer_popped, false},
         // the REFERENCE roadmap search: A* queries run, pops of the last call's largest query, queries that took the global route
         {1021, &fs_ctx::as_queries, true}, {1022, &fs_ctx::as_max_pops, false}, {1023, &fs_ctx::as_global, true},
+        // the path information (fs_plan_paths_information): way points of the last call, distinct poses it scored
+        {1024, &fs_ctx::pi_waypoints, false}, {1025, &fs_ctx::pi_distinct, false},
     };
     for (const auto &h : host)
         if (c && value && which == h.id) {
@@ -3214,6 +3238,153 @@ int fs_plan_paths(fs_ctx *c, const double robot_pose7[7], int32_t allow_unknown,
     return plan_to_host(c, c->d_nav_out, c->h_nav_out, n,
                         [&] { return navfn_plan_enqueue(c, robot_pose7, allow_unknown, n, goal_xyz, achievable_in); },
                         path_length, path_length_m, path_heading, achievable);
+}
+
+int fs_plan_paths_information(fs_ctx *c, const double robot_pose7[7], int32_t allow_unknown, int32_t n, const double *goal_xyz,
+                              const uint8_t *achievable_in, const fs_path_info_params *params, double *path_length,
+                              double *path_length_m, double *path_heading, uint8_t *achievable, int32_t *n_waypoints, double *info_mean,
+                              float *info_min, int32_t *first_unsafe, int64_t max_waypoints, int64_t *n_total, int32_t *waypoint_offset,
+                              double *waypoint_pose7, float *waypoint_info)
+{
+    if (!c) return FS_E_INVALID;
+    if (n < 0 || (n > 0 && (!goal_xyz || !path_length || !path_length_m || !path_heading || !achievable || !n_waypoints || !info_mean ||
+                            !info_min || !first_unsafe)))
+        return fail(c, FS_E_INVALID, "null pointer");
+    const int dump_ptrs = (n_total ? 1 : 0) + (waypoint_offset ? 1 : 0) + (waypoint_pose7 ? 1 : 0) + (waypoint_info ? 1 : 0);
+    if (dump_ptrs != 0 && dump_ptrs != 4) return fail(c, FS_E_INVALID, "the way-point dump takes all four pointers or none");
+    const bool dump = dump_ptrs == 4;
+    if (dump && max_waypoints < 0) return fail(c, FS_E_INVALID, "negative max_waypoints");
+    const fs_path_info_params def = {1.5, 10, 550.0};        // CostCalculator.cpp:328, :332; FisherInfoBTPlugin.cpp:20
+    const fs_path_info_params prm = params ? *params : def;
+    if (!(prm.sample_distance_m >= 0.0)) return fail(c, FS_E_INVALID, "sample_distance_m must not be negative");
+    if (prm.lookahead_points < 0) return fail(c, FS_E_INVALID, "lookahead_points must not be negative");
+    if (!std::isfinite(prm.fi_threshold)) return fail(c, FS_E_INVALID, "fi_threshold must be finite");
+    int rc = nav_check(c, robot_pose7);
+    if (rc) return rc;
+    rc = check_scoring_state(c, false, true);
+    if (rc) return rc;
+    c->pi_waypoints = 0; c->pi_distinct = 0;
+    if (dump) { *n_total = 0; waypoint_offset[0] = 0; }
+    if (n == 0) return FS_OK;
+    const size_t nn = (size_t)n;
+    // s = (int)(sample_distance / resolution) (:328); a quotient beyond the int range samples nothing, as no path is that long
+    const double cut = prm.sample_distance_m / c->res;
+    const int64_t step = (cut < 2147483647.0 ? (int64_t)(int)cut : (int64_t)2147483647) + 1;
+    const int64_t per_path = (int64_t)navfn_max_cycles(c) / step;       // a path has at most max_cycles points
+    if ((int64_t)n * per_path > (int64_t)INT32_MAX) return fail(c, FS_E_INVALID, "%d paths of up to %lld way points: beyond 2^31", n, (long long)per_path);
+    int64_t bound = (int64_t)n * per_path;
+    const PlanOutLayout O(nn);
+    const PathInfoOutLayout P(nn);
+    // every buffer whose size is known before the plan is sized before a pointer into any of them is taken
+    FS_HIP(c, c->h_nav_out.ensure(O.total));
+    FS_HIP(c, c->d_pi_off.ensure(2 * (nn + 1)));
+    FS_HIP(c, c->d_pi_out.ensure(P.total)); FS_HIP(c, c->h_pi_out.ensure(P.total));
+    // (an error after the first launch waits for the stream: the next call may grow what the launches still use)
+    const auto stop = [&](int code) { (void)hipStreamSynchronize(c->stream); return code; };
+    rc = navfn_plan_enqueue(c, robot_pose7, allow_unknown, n, goal_xyz, achievable_in);
+    if (rc) return stop(rc);
+    FS_HIP(c, hipMemcpyAsync(c->h_nav_out.p, c->d_nav_out.p, O.total, hipMemcpyDeviceToHost, c->stream));
+    FsPathInfoArgs a{};
+    a.n = n; a.nx = c->nx; a.ny = c->ny; a.max_cycles = navfn_max_cycles(c);
+    a.step = step; a.lookahead = prm.lookahead_points;
+    a.ox = c->origin[0]; a.oy = c->origin[1]; a.res = c->res;
+    a.path = c->d_nav_path.p;
+    a.path_length = reinterpret_cast<const double *>(c->d_nav_out.p + O.len);
+    a.achievable = reinterpret_cast<const uint8_t *>(c->d_nav_out.p + O.ach);
+    a.dedup = c->opt_pi_dedup ? 1 : 0;
+    a.fi_threshold = prm.fi_threshold;
+    int64_t *hdr = reinterpret_cast<int64_t *>(c->h_pi_out.p + P.hdr);
+    const auto bind = [&]() {      // (after the last growth of d_pi_temp)
+        a.count = c->d_pi_off.p; a.offset = c->d_pi_off.p + nn + 1;
+        a.hdr = reinterpret_cast<int64_t *>(c->d_pi_out.p + P.hdr);
+        a.info_mean = reinterpret_cast<double *>(c->d_pi_out.p + P.mean);
+        a.info_min = reinterpret_cast<float *>(c->d_pi_out.p + P.min);
+        a.first_unsafe = reinterpret_cast<int32_t *>(c->d_pi_out.p + P.unsafe);
+        a.temp = c->d_pi_temp.p; a.temp_bytes = c->d_pi_temp.cap;
+    };
+    const auto ensure_temp = [&](int64_t room) -> int {
+        const size_t bytes = fs_pathinfo_temp_bytes(a, room, c->stream);
+        if (bytes == 0) return fail(c, FS_E_HIP, "rocPRIM refused the size query");
+        FS_HIP(c, c->d_pi_temp.ensure(bytes));
+        return FS_OK;
+    };
+    const bool direct = bound <= PI_BOUND_DIRECT;
+    rc = ensure_temp(direct ? bound : 0);
+    if (rc) return stop(rc);
+    bind();
+    if (fs_launch_pathinfo_offsets(a, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "way-point offsets: launch failed"));
+    if (!direct) {
+        // a list whose paths could hold more way points than the call makes room for unseen (a sample distance of a few cells on a
+        // large map): the total is read first, at the price of one more synchronisation
+        FS_HIP(c, hipMemcpyAsync(hdr, a.offset + n, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        int32_t total32 = 0;
+        std::memcpy(&total32, hdr, sizeof total32);
+        bound = total32;
+        rc = ensure_temp(bound);
+        if (rc) return stop(rc);
+        bind();
+    }
+    const size_t room = (size_t)bound;
+    if (bound > 0) {
+        if (a.dedup) { FS_HIP(c, c->d_pi_key.ensure(2 * room)); }
+        FS_HIP(c, c->d_pi_idx.ensure(5 * room));
+        FS_HIP(c, c->d_pi_rt.ensure(12 * room));
+        if (dump) { FS_HIP(c, c->d_pi_pose.ensure(7 * room)); FS_HIP(c, c->d_pi_val.ensure(room)); }
+        a.bound = bound;
+        a.key_in = c->d_pi_key.p; a.key_out = c->d_pi_key.p + room;
+        a.wp_in = c->d_pi_idx.p; a.wp_out = a.wp_in + room; a.head = a.wp_out + room; a.rank = a.head + room; a.slot = a.rank + room;
+        a.rt = c->d_pi_rt.p;
+        a.pose7 = dump ? c->d_pi_pose.p : nullptr;
+        a.wp_info = dump ? c->d_pi_val.p : nullptr;
+        if (fs_launch_pathinfo_prepare(a, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "way points: launch failed"));
+        FS_HIP(c, hipMemcpyAsync(hdr, a.hdr, 16, hipMemcpyDeviceToHost, c->stream));
+    }
+    // THE mid-call synchronisation: the worker's item count (and the room its per-item scratch needs) must be on the host
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    const int64_t total = bound > 0 ? hdr[0] : 0, distinct = bound > 0 ? hdr[1] : 0;
+    c->pi_waypoints = total; c->pi_distinct = distinct;
+    if (dump) *n_total = total;
+    if (dump && total > max_waypoints) return fail(c, FS_E_RANGE, "%lld way points, room for %lld", (long long)total, (long long)max_waypoints);
+    if (distinct > 0) {
+        // fs_score_fim's launch sequence on the records: what decides the size of the per-item scratch (maybe_split) comes before
+        // any pointer into it
+        rc = ensure_candidate_scratch(c, (size_t)distinct, false);
+        if (rc) return rc;
+        FsFimArgs fa{};
+        if (const int rc_args = fill_fim_args(c, fa)) return rc_args;
+        fa.n = (int32_t)distinct;
+        fa.info_only = c->opt_special ? 1 : 0;
+        if (fa.info_only && fa.skip32 < 20) fa.skip32 = 20;        // (as fs_score_fim_begin)
+        rc = maybe_split(c, fa, (size_t)distinct, false);
+        if (rc) return stop(rc);
+        fa.Rt = c->d_pi_rt.p;
+        bind_fim_outputs(c, fa);
+        rc = run_fim_tier1(c, fa, nullptr, 0, fa.n << fa.split_shift);
+        if (rc) return stop(rc);
+        rc = run_fim_rest(c, fa);
+        if (rc) return stop(rc);
+        a.info = fa.info_ref;
+    }
+    if (fs_launch_pathinfo_finish(a, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "path information columns: launch failed"));
+    FS_HIP(c, hipMemcpyAsync(c->h_pi_out.p + P.mean, c->d_pi_out.p + P.mean, P.total - P.mean, hipMemcpyDeviceToHost, c->stream));
+    if (dump) {
+        FS_HIP(c, hipMemcpyAsync(waypoint_offset, a.offset, sizeof(int32_t) * (nn + 1), hipMemcpyDeviceToHost, c->stream));
+        if (total > 0) {
+            FS_HIP(c, hipMemcpyAsync(waypoint_pose7, a.pose7, sizeof(double) * 7 * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+            FS_HIP(c, hipMemcpyAsync(waypoint_info, a.wp_info, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    FS_HIP(c, hipMemcpyAsync(n_waypoints, a.count, sizeof(int32_t) * nn, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    std::memcpy(path_length, c->h_nav_out.p + O.len, 8 * nn);
+    std::memcpy(path_length_m, c->h_nav_out.p + O.len_m, 8 * nn);
+    std::memcpy(path_heading, c->h_nav_out.p + O.head, 8 * nn);
+    std::memcpy(achievable, c->h_nav_out.p + O.ach, nn);
+    std::memcpy(info_mean, c->h_pi_out.p + P.mean, 8 * nn);
+    std::memcpy(info_min, c->h_pi_out.p + P.min, 4 * nn);
+    std::memcpy(first_unsafe, c->h_pi_out.p + P.unsafe, 4 * nn);
+    return FS_OK;
 }
 
 int fs_get_frontier_costs_planned(fs_ctx *c, const double robot_pose7[7], int32_t allow_unknown, int32_t n, const double *goal_xyz,

@@ -452,6 +452,41 @@ struct FsKfArgs {
 };
 hipError_t fs_launch_kf_info(const FsKfArgs &a, int pool, hipStream_t s);
 
+// ---- Fisher information along the planned paths (fs_pathinfo.hip): setPlanForFrontier's way points, one pose record
+// per distinct (from cell, to cell), the per-frontier columns
+struct FsPathInfoArgs {
+    int32_t n;                        // frontiers
+    int32_t nx, ny, max_cycles;       // the grid; the stride of a path's x / y arrays in `path`
+    int64_t step;                     // s + 1, s = (int)(sample_distance / resolution): a way point every `step` path points
+    int32_t lookahead;                // the pose looks at the point this many further on (towards the frontier)
+    double ox, oy, res;
+    const float *path;                // navfn_paths_kernel's scratch [n][2][max_cycles]
+    const double *path_length;        // [n] the planner's columns
+    const uint8_t *achievable;        // [n]
+    int32_t dedup;                    // 1: one record per distinct key; 0: one per way point
+    int64_t bound;                    // room for way points in every array below, and the size of the launches
+    int32_t *count, *offset;          // [n + 1]; offset[n] = total
+    uint64_t *key_in, *key_out;       // [bound] (dedup)
+    int32_t *wp_in, *wp_out, *head, *rank;   // [bound] (dedup): way point of a key, head of a run of equal keys, heads up to here
+    int32_t *slot;                    // [bound] way point -> record
+    float *rt;                        // [bound][12] the pose records the FIM worker reads
+    double *pose7;                    // [bound][7] or nullptr: the dump
+    int64_t *hdr;                     // [2]: total, records
+    void *temp;                       // rocPRIM's scratch
+    size_t temp_bytes;
+    // finish
+    const float *info;                // [records] the worker's info_ref column
+    float *wp_info;                   // [bound] or nullptr: the dump
+    double fi_threshold;
+    double *info_mean;                // [n]
+    float *info_min;                  // [n]
+    int32_t *first_unsafe;            // [n]
+};
+size_t fs_pathinfo_temp_bytes(const FsPathInfoArgs &a, int64_t bound, hipStream_t s);    // rocPRIM's scratch for n, nx, ny and that room; 0: it refused
+hipError_t fs_launch_pathinfo_offsets(const FsPathInfoArgs &a, hipStream_t s);            // count, offset
+hipError_t fs_launch_pathinfo_prepare(const FsPathInfoArgs &a, hipStream_t s);            // keys ... records, hdr
+hipError_t fs_launch_pathinfo_finish(const FsPathInfoArgs &a, hipStream_t s);             // the per-frontier columns
+
 // ---- landmark staging (fs_capi.hip), split so that fs_multi orders a cloud once for all its devices
 struct FsStagedCloud {
     int32_t m = 0, n_chunks = 0;

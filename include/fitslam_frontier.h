@@ -461,6 +461,35 @@ int fs_get_frontier_costs_planned(fs_ctx *ctx, const double robot_pose7[7], int3
                   const int32_t *frontier_size, const uint8_t *blacklisted, double alpha, double beta, double max_vx, double max_wz,
                   int with_fisher_information, fs_record *records, double *weighted_cost, double *arrival_utility,
                   double *distance_utility, int32_t *order, double *path_length_m);
+/* Fisher information along every planned path: will SLAM keep tracking on the way to the frontier?  The sampling
+ * is setPlanForFrontier's (DEP/src/CostCalculator.cpp:302-366, 382-390: a way point once more than (int)(sample_distance /
+ * resolution) path points have gone by, turned towards the point `lookahead` further on by getRelativePoseGivenTwoPoints, the
+ * sum of the positive values over the number of way points); the value of a way point is isPoseSafe's scalar
+ * (FIP/src/fisher_information/FisherInfoManager.cpp:31-37, over a path in DEP/src/FullPathOptimizer.cpp:308-340): fs_score_fim's
+ * info_ref at that pose under the context's landmarks, table and fs_set_fim_params. */
+typedef struct fs_path_info_params {
+    double  sample_distance_m;  /* 1.5  (CostCalculator.cpp:328) */
+    int32_t lookahead_points;   /* 10   (:332) */
+    double  fi_threshold;       /* 550.0 (FisherInfoBTPlugin.cpp:20); a way point is unsafe unless info > threshold */
+} fs_path_info_params;
+/* The plan is fs_plan_paths' own (same field cache, same four columns, bit for bit).  params NULL: the defaults above.
+ * Path f of len points (point 0 at the frontier, len - 1 at the robot) has len / (s + 1) way points, s = (int)(sample_distance_m /
+ * resolution); way point k, counted from the robot, stands on the cell centre of point j = len - (k + 1)(s + 1), z = 0, and looks
+ * at the cell centre of point max(j - lookahead_points, 0) (the same cell: yaw 0).
+ * Per frontier [n]: n_waypoints; info_mean = (the fp64 sum of the values > 0, in way-point order) / n_waypoints, 0 without way
+ * points; info_min (+inf without); first_unsafe = the first k with !(info > fi_threshold), -1 if none.  A frontier that is not
+ * planned: 0, 0, +inf, -1.
+ * The dump — n_total, waypoint_offset [n + 1], waypoint_pose7 [max_waypoints][7], waypoint_info [max_waypoints]: all four or all
+ * NULL — lists every way point in list order; a pose of the dump handed to fs_score_fim makes the same pose record.  More way
+ * points than max_waypoints: FS_E_RANGE with *n_total set and nothing else written.
+ * FS_E_INVALID: sample_distance_m NaN or negative, lookahead_points negative, fi_threshold not finite; otherwise refuses what
+ * fs_plan_paths and fs_score_fim refuse, with their codes.  Synchronises twice (the number of distinct poses sizes the scoring
+ * launch), plus the round polling of a field that is not cached. */
+int fs_plan_paths_information(fs_ctx *ctx, const double robot_pose7[7], int32_t allow_unknown, int32_t n, const double *goal_xyz,
+                  const uint8_t *achievable_in, const fs_path_info_params *params, double *path_length, double *path_length_m,
+                  double *path_heading, uint8_t *achievable, int32_t *n_waypoints, double *info_mean, float *info_min,
+                  int32_t *first_unsafe, int64_t max_waypoints, int64_t *n_total, int32_t *waypoint_offset, double *waypoint_pose7,
+                  float *waypoint_info);
 /* searchFrom -> plan -> score -> rank in one call: fs_search_frontiers with the context's seed order (fs_set_frontier_seed_order)
  * and no caller seeds from the pose's xy, then
  * fs_get_frontier_costs_planned on its records (goal_xyz = (goal_x, goal_y, 0), frontier_size = size, blacklisted = the goal point

@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "fs_get_frontier_costs_roadmap", "fs_roadmap_next_goal", "fs_refine_paths", "fs_refine_field",
     "fs_roadmap_set_keyframes", "fs_roadmap_optimize", "fs_roadmap_get_anchors",
     "fs_search_frontiers", "fs_get_frontier_costs_searched", "fs_set_frontier_seed_order", "fs_set_roadmap_search",
+    "fs_roadmap_routes",
 ]
 
 RECORD_DTYPE = np.dtype([("arrival", "<i4"), ("argmax", "<i4"), ("yaw", "<f4"), ("info_ref", "<f4"),
@@ -55,6 +56,10 @@ class KeyframeParamsC(C.Structure):
 
 class PathInfoParamsC(C.Structure):
     _fields_ = [("sample_distance_m", C.c_double), ("lookahead_points", C.c_int32), ("fi_threshold", C.c_double)]
+
+
+class RouteParamsC(C.Structure):
+    _fields_ = [("refine", C.c_int32), ("with_information", C.c_int32), ("fi_threshold", C.c_double)]
 
 
 class FrontierClusterC(C.Structure):
@@ -182,6 +187,8 @@ def load_library(build: bool = True):
     L.fs_roadmap_get_graph.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), vp, vp, vp, vp]
     L.fs_roadmap_plan.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, vp, vp, vp, vp]
     L.fs_get_frontier_costs_roadmap.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, vp, dbl, dbl, dbl, dbl, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.fs_roadmap_routes.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, C.POINTER(RouteParamsC), vp, vp, vp, vp, vp, i32, C.POINTER(i32),
+                                    vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64), vp, vp, C.POINTER(i64), vp, vp, vp, vp]
     L.fs_roadmap_next_goal.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, vp, vp, i32, vp, i32, dbl, vp, dbl,
                                        C.POINTER(i32), C.POINTER(i32), vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(i64), vp, vp]
     L.fs_roadmap_set_keyframes.argtypes = [vp, i32, vp, vp, C.POINTER(i32), C.POINTER(i32)]
@@ -778,6 +785,62 @@ class FrontierScorer:
         with self._roadmap_search_for_call(search):
             self._check(self._L.fs_roadmap_plan(self._h, C.byref(pose), n, _p(goal), _p(ai), _p(pl), _p(plm), _p(ph), _p(ach)))
         return dict(path_length=pl, path_length_m=plm, path_heading=ph, achievable=ach)
+
+    def roadmap_routes(self, robot_pose7, goal_xyz, achievable_in=None, refine=True, with_information=True, fi_threshold=550.0,
+                       want_nodes=False, want_legs=False, search=None):
+        """roadmap_plan, and the routes behind its numbers (fs_roadmap_routes): one route per distinct goal node the plan reached —
+        getPlan's node list, refinePath's shortcut of it on the staged grid (refine) and the Fisher information of the legs of
+        the refined (or raw) list (with_information).  Per frontier: roadmap_plan's columns and route_of; per route: goal_node,
+        complete, n_legs and, with_information, info_mean, info_min, first_unsafe.  want_nodes: node_offset / node and, with refine,
+        refined_offset / refined_node (CSR).  want_legs: leg_pose7 [legs][7] and leg_info [legs], route by route."""
+        pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
+        goal = np.ascontiguousarray(goal_xyz, dtype=np.float64).reshape(-1, 3)
+        n = goal.shape[0]
+        ai = None if achievable_in is None else np.ascontiguousarray(achievable_in, dtype=np.uint8).reshape(-1)
+        if ai is not None and ai.shape[0] != n:
+            raise ValueError(f"achievable_in has {ai.shape[0]} entries for {n} goals")
+        prm = RouteParamsC(1 if refine else 0, 1 if with_information else 0, float(fi_threshold))
+        pl, plm, ph = np.zeros(n), np.zeros(n), np.zeros(n)
+        ach = np.zeros(n, dtype=np.uint8)
+        route_of = np.zeros(n, dtype=np.int32)
+        n_routes, total, total_ref = C.c_int32(), C.c_int64(), C.c_int64()
+        dump = want_nodes or want_legs
+        room_r, room_n = max(n, 1), (64 * n + 64) if dump else 0
+        with self._roadmap_search_for_call(search):
+            for _ in range(2):
+                gn, nl = np.zeros(room_r, dtype=np.int32), np.zeros(room_r, dtype=np.int32)
+                comp = np.zeros(room_r, dtype=np.uint8)
+                mean = np.zeros(room_r) if with_information else None
+                mn = np.zeros(room_r, dtype=np.float32) if with_information else None
+                unsafe = np.zeros(room_r, dtype=np.int32) if with_information else None
+                off = np.zeros(room_r + 1, dtype=np.int64) if dump else None
+                nodes = np.zeros(max(room_n, 1), dtype=np.int32) if dump else None
+                ref = want_nodes and refine
+                roff = np.zeros(room_r + 1, dtype=np.int64) if ref else None
+                rnodes = np.zeros(max(room_n, 1), dtype=np.int32) if ref else None
+                p7 = np.zeros((max(room_n, 1), 7)) if want_legs else None
+                li = np.zeros(max(room_n, 1), dtype=np.float32) if want_legs else None
+                rc = self._L.fs_roadmap_routes(self._h, C.byref(pose), n, _p(goal), _p(ai), C.byref(prm), _p(pl), _p(plm), _p(ph), _p(ach),
+                                               _p(route_of), room_r, C.byref(n_routes), _p(gn), _p(comp), _p(nl), _p(mean), _p(mn),
+                                               _p(unsafe), room_n, C.byref(total) if dump else None, _p(off), _p(nodes),
+                                               C.byref(total_ref) if ref else None, _p(roff), _p(rnodes), _p(p7), _p(li))
+                if rc != FS_E_RANGE or (n_routes.value <= room_r and total.value <= room_n):
+                    break
+                room_r, room_n = max(n_routes.value, 1), total.value
+        self._check(rc)
+        k = n_routes.value
+        out = dict(path_length=pl, path_length_m=plm, path_heading=ph, achievable=ach, route_of=route_of, goal_node=gn[:k],
+                   complete=comp[:k], n_legs=nl[:k])
+        if with_information:
+            out.update(info_mean=mean[:k], info_min=mn[:k], first_unsafe=unsafe[:k])
+        if want_nodes:
+            out.update(node_offset=off[:k + 1], node=nodes[:total.value])
+            if refine:
+                out.update(refined_offset=roff[:k + 1], refined_node=rnodes[:total_ref.value])
+        if want_legs:
+            legs = int(nl[:k].sum())
+            out.update(leg_pose7=p7[:legs], leg_info=li[:legs])
+        return out
 
     def get_frontier_costs_roadmap(self, robot_pose7, goal_xyz, frontier_size=None, blacklisted=None, with_fim=False,
                                    alpha=0.25, beta=1.0, max_vx=0.5, max_wz=0.5, search=None):

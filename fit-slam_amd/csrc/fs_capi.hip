@@ -361,6 +361,21 @@ struct fs_ctx {
     PinnedBuf h_as_io;
     FsRmAstarArgs as_args{};
     FsRmPlanArgs as_plan{};
+    // roadmap routes (fs_roadmap_routes).  rt_chains: the plan in flight is that call's, so the A* queries also emit
+    // their node chains into d_rt_pool (rt_pool_cap slots in use; "routes.pool_nodes" sets it, a call that overflows it grows it to
+    // what it needed and runs the queries again).  rt_plan / rt_max_q: the plan's arguments and query bound, for the launches that
+    // follow it.
+    bool opt_rt_dedup = true;                 // "routes.dedup": one pose record per distinct (from node, to node) (0: one per leg)
+    bool rt_chains = false;
+    int64_t rt_pool_cap = 1 << 16;
+    int64_t rt_routes = 0, rt_walks = 0, rt_poses = 0, rt_retries = 0;     // counters 1026-1029
+    FsRmPlanArgs rt_plan{};
+    int32_t rt_max_q = 0;
+    DevBuf<int32_t> d_rt_chain_len, d_rt_pool, d_rt_idx, d_rt_of, d_rt_node, d_rt_refined;
+    DevBuf<int64_t> d_rt_chain_base, d_rt_off;
+    DevBuf<unsigned long long> d_rt_cursor;   // [2]: the chain pool's cursor, the refinement's walks
+    DevBuf<uint8_t> d_rt_complete;
+    PinnedBuf h_rt, h_rt_list;
     // next goal (fs_roadmap_next_goal): a batch of trees with buffers of its own (the single tree above stays
     // cached), the pair matrix, the tour search's winners
     int32_t tour_one_wg = RM_TREE_ONE_WG;     // "roadmap.tour_one_wg": above this many nodes the batch runs a round per launch
@@ -1090,6 +1105,9 @@ void fs_ctx_destroy(fs_ctx *c)
     c->d_rm_in.release(); c->d_rm_out.release(); c->h_rm_in.release(); c->h_rm_out.release();
     c->d_as_gnode.release(); c->d_as_mark.release(); c->d_as_qidx.release(); c->d_as_src.release(); c->d_as_dst.release();
     c->d_as_status.release(); c->d_as_stats.release(); c->d_as_len.release(); c->d_as_pool.release(); c->h_as_io.release();
+    c->d_rt_chain_len.release(); c->d_rt_pool.release(); c->d_rt_idx.release(); c->d_rt_of.release(); c->d_rt_node.release();
+    c->d_rt_refined.release(); c->d_rt_chain_base.release(); c->d_rt_off.release(); c->d_rt_cursor.release(); c->d_rt_complete.release();
+    c->h_rt.release(); c->h_rt_list.release();
     c->d_tour_d.release(); c->d_tour_hops.release(); c->d_tour_pred.release(); c->d_tour_word.release(); c->d_tour_work.release();
     c->h_tour_out.release();
     c->d_kf_rt.release(); c->d_kf_rec_p.release(); c->d_kf_pts.release(); c->d_kf_out.release(); c->d_kf_queue.release();
@@ -2009,6 +2027,8 @@ int fs_set_option(fs_ctx *c, const char *key, double value)
     if (std::strcmp(key, "roadmap.astar_lds_entries") == 0 && value >= 0 && value <= 2048) { c->astar_lds_entries = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "roadmap.dedup_one_wg") == 0 && value >= 0 && value <= FS_KF_DEDUP_ONE_WG) { c->kf_one_wg = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "pathinfo.dedup") == 0) { c->opt_pi_dedup = value != 0.0; return FS_OK; }
+    if (std::strcmp(key, "routes.dedup") == 0) { c->opt_rt_dedup = value != 0.0; return FS_OK; }
+    if (std::strcmp(key, "routes.pool_nodes") == 0 && value >= 1 && value <= (double)(1 << 30)) { c->rt_pool_cap = (int64_t)value; return FS_OK; }
     if (std::strcmp(key, "refine.max_fields") == 0 && value >= 1 && value <= RF_MAX_FIELDS) {
         if ((int32_t)value != c->rf_max_fields) { c->rf_max_fields = (int32_t)value; c->rf_key.clear(); c->rf_gen.clear(); }
         return FS_OK;
@@ -2047,6 +2067,9 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
         {1021, &fs_ctx::as_queries, true}, {1022, &fs_ctx::as_max_pops, false}, {1023, &fs_ctx::as_global, true},
         // the path information (fs_plan_paths_information): way points of the last call, distinct poses it scored
         {1024, &fs_ctx::pi_waypoints, false}, {1025, &fs_ctx::pi_distinct, false},
+        // the roadmap routes (fs_roadmap_routes): distinct routes of the last call, isConnectable walks of its refinement, distinct
+        // leg poses it scored; calls that ran the A* again on a grown chain pool
+        {1026, &fs_ctx::rt_routes, false}, {1027, &fs_ctx::rt_walks, false}, {1028, &fs_ctx::rt_poses, false}, {1029, &fs_ctx::rt_retries, true},
     };
     for (const auto &h : host)
         if (c && value && which == h.id) {
@@ -3707,6 +3730,15 @@ int roadmap_astar_enqueue(fs_ctx *c, FsRmPlanArgs &a)
     }
     q.nq = c->d_as_qidx.p + nodes; q.dst = c->d_as_dst.p; q.status = c->d_as_status.p; q.len = c->d_as_len.p;
     q.lds_cap = rm_astar_lds_cap(c, nodes);
+    if (c->rt_chains) {
+        const size_t mq = (size_t)std::max(max_q, 1);
+        FS_HIP(c, c->d_rt_chain_len.ensure(mq)); FS_HIP(c, c->d_rt_chain_base.ensure(mq));
+        FS_HIP(c, c->d_rt_pool.ensure((size_t)c->rt_pool_cap)); FS_HIP(c, c->d_rt_cursor.ensure(2));
+        FS_HIP(c, hipMemsetAsync(c->d_rt_cursor.p, 0, sizeof(unsigned long long), c->stream));
+        q.chain_len = c->d_rt_chain_len.p; q.chain_base = c->d_rt_chain_base.p; q.chain_pool = c->d_rt_pool.p;
+        q.chain_cap = c->rt_pool_cap; q.chain_cursor = c->d_rt_cursor.p;
+        c->rt_max_q = max_q;
+    }
     int rc = rm_astar_enqueue(c, q, max_q);
     if (rc) return rc;
     c->as_plan = a;
@@ -3761,8 +3793,10 @@ int roadmap_plan_enqueue(fs_ctx *c, const double robot7[7], int32_t n, const dou
     a.achievable = reinterpret_cast<uint8_t *>(c->d_rm_out.p + O.ach);
     if (reference) {
         if (!need_tree) a.root = -1;                    // (no goal is searched)
+        c->rt_plan = a;
         return roadmap_astar_enqueue(c, a);
     }
+    c->rt_plan = a;
     FS_HIP(c, fs_launch_rm_plan(a, c->stream));
     return FS_OK;
 }
@@ -4256,6 +4290,277 @@ int fs_get_frontier_costs_roadmap(fs_ctx *c, const double robot_pose7[7], int32_
     rc = rm_astar_settle(c, [&] { return roadmap_astar_cols(c); }, &redone);
     if (rc || !redone) return rc;
     return rank_on_plan(c, c->d_rm_out, c->h_rm_out, n, [] { return FS_OK; }, rank, path_length_m);
+}
+
+
+// The routes of the plan.  Launch order: the plan (under the REFERENCE search its queries also emit their chains) ->
+// route lengths, numbering, route_of -> [sizes on the host: offsets, the FS_E_RANGE checks] -> the lists -> refinePath -> the legs'
+// keys, sort, heads, records (fs_pathinfo.hip) -> [distinct poses on the host] -> the info-only scorer -> the per-route columns.
+int fs_roadmap_routes(fs_ctx *c, const double robot_pose7[7], int32_t n, const double *goal_xyz, const uint8_t *achievable_in,
+                      const fs_route_params *params, double *path_length, double *path_length_m, double *path_heading,
+                      uint8_t *achievable, int32_t *route_of, int32_t max_routes, int32_t *n_routes, int32_t *goal_node,
+                      uint8_t *complete, int32_t *n_legs, double *info_mean, float *info_min, int32_t *first_unsafe, int64_t max_nodes,
+                      int64_t *n_nodes_total, int64_t *node_offset, int32_t *node, int64_t *n_refined_total, int64_t *refined_offset,
+                      int32_t *refined_node, double *leg_pose7, float *leg_info)
+{
+    if (!c) return FS_E_INVALID;
+    if (!robot_pose7 || n < 0 || (n > 0 && (!goal_xyz || !path_length || !path_length_m || !path_heading || !achievable || !route_of || !n_routes)))
+        return fail(c, FS_E_INVALID, "null pointer");
+    if (max_routes < 0 || max_nodes < 0) return fail(c, FS_E_INVALID, "negative max_routes / max_nodes");
+    if (max_routes > 0 && (!goal_node || !complete || !n_legs)) return fail(c, FS_E_INVALID, "null pointer");
+    const fs_route_params def = {1, 1, 550.0};               // FisherInfoBTPlugin.cpp:20
+    const fs_route_params prm = params ? *params : def;
+    if (!std::isfinite(prm.fi_threshold)) return fail(c, FS_E_INVALID, "fi_threshold must be finite");
+    const bool refine = prm.refine != 0, with_info = prm.with_information != 0;
+    const int raw_ptrs = (n_nodes_total ? 1 : 0) + (node_offset ? 1 : 0) + (node ? 1 : 0);
+    const int ref_ptrs = (n_refined_total ? 1 : 0) + (refined_offset ? 1 : 0) + (refined_node ? 1 : 0);
+    const int leg_ptrs = (leg_pose7 ? 1 : 0) + (leg_info ? 1 : 0);
+    if ((raw_ptrs != 0 && raw_ptrs != 3) || (ref_ptrs != 0 && ref_ptrs != 3) || (leg_ptrs != 0 && leg_ptrs != 2))
+        return fail(c, FS_E_INVALID, "a dump takes all the pointers of its group or none");
+    const bool dump_raw = raw_ptrs == 3, dump_ref = ref_ptrs == 3, dump_leg = leg_ptrs == 2;
+    if (dump_ref && !refine) return fail(c, FS_E_INVALID, "the refined dump needs params->refine");
+    if (!with_info && (dump_leg || info_mean || info_min || first_unsafe))
+        return fail(c, FS_E_INVALID, "information outputs need params->with_information");
+    if (with_info && max_routes > 0 && (!info_mean || !info_min || !first_unsafe)) return fail(c, FS_E_INVALID, "null pointer");
+    FS_HIP(c, hipSetDevice(c->device));
+    int rc = FS_OK;
+    if (refine && (rc = grid2d_check(c, "refinePath"))) return rc;
+    if (with_info && (rc = check_scoring_state(c, false, true))) return rc;
+    c->rt_routes = 0; c->rt_walks = 0; c->rt_poses = 0;
+    if (n == 0) {
+        if (n_routes) *n_routes = 0;
+        if (dump_raw) { *n_nodes_total = 0; node_offset[0] = 0; }
+        if (dump_ref) { *n_refined_total = 0; refined_offset[0] = 0; }
+        return FS_OK;
+    }
+    const size_t nn = (size_t)n, nodes = (size_t)rm_nodes(c);
+    const bool reference = c->rm_search == FS_ROADMAP_SEARCH_REFERENCE;
+    const PlanOutLayout O(nn);
+    // page-locked block: n_routes | cursor, walks | route_len | goal_node | route_of | refined_len | complete | node_off
+    const size_t h_cnt = 0, h_u64 = 8, h_len = 24, h_goal = h_len + 4 * nodes, h_of = h_goal + 4 * nodes, h_rlen = h_of + 4 * nn,
+                 h_comp = h_rlen + 4 * nodes, h_off = (h_comp + nodes + 7) & ~(size_t)7, h_total = h_off + 8 * (nodes + 1);
+    FS_HIP(c, c->h_rt.ensure(h_total)); FS_HIP(c, c->h_rm_out.ensure(O.total));
+    // device words: len | has | ridx [nodes + 1] | goal_node | route_len | route_q | refined_len
+    FS_HIP(c, c->d_rt_idx.ensure(7 * nodes + 1)); FS_HIP(c, c->d_rt_of.ensure(nn)); FS_HIP(c, c->d_rt_off.ensure(nodes + 1));
+    FS_HIP(c, c->d_rt_complete.ensure(std::max<size_t>(nodes, 1))); FS_HIP(c, c->d_rt_cursor.ensure(2));
+    FS_HIP(c, c->d_as_gnode.ensure(nn)); FS_HIP(c, c->d_as_mark.ensure(std::max<size_t>(nodes, 1))); FS_HIP(c, c->d_as_qidx.ensure(nodes + 1));
+    // (an error after the first launch waits for the stream: the next call may grow what the launches still use)
+    const auto stop = [&](int code) { (void)hipStreamSynchronize(c->stream); return code; };
+    c->rt_chains = reference;
+    rc = roadmap_plan_enqueue(c, robot_pose7, n, goal_xyz, achievable_in);
+    c->rt_chains = false;
+    if (rc) return stop(rc);
+    FsRmRouteArgs ra{};
+    ra.n_nodes = (int32_t)nodes;
+    ra.mark = c->d_as_mark.p;
+    ra.len = c->d_rt_idx.p; ra.has = ra.len + nodes; int32_t *ridx = ra.has + nodes; ra.ridx = ridx;
+    ra.goal_node = ridx + nodes + 1; ra.route_len = ra.goal_node + nodes; ra.route_q = ra.route_len + nodes;
+    int32_t *d_rlen = ra.route_q + nodes;
+    ra.n = n; ra.gnode = c->d_as_gnode.p; ra.route_of = c->d_rt_of.p;
+    if (reference) {
+        ra.qidx = c->d_as_qidx.p; ra.status = c->d_as_status.p; ra.chain_len = c->d_rt_chain_len.p; ra.chain_base = c->d_rt_chain_base.p;
+        // (a plan without a start node or a searched goal makes no query and leaves the marks as they were)
+        if (c->rt_plan.root < 0 && nodes > 0) FS_HIP(c, hipMemsetAsync(c->d_as_mark.p, 0, sizeof(int32_t) * nodes, c->stream));
+    } else {
+        // the plan's goal nodes and their marks, as the REFERENCE plan makes them
+        if (nodes > 0) FS_HIP(c, hipMemsetAsync(c->d_as_mark.p, 0, sizeof(int32_t) * nodes, c->stream));
+        FS_HIP(c, fs_launch_rm_astar_goals(c->rt_plan, c->d_as_gnode.p, c->d_as_mark.p, c->stream));
+        ra.d = c->rt_plan.d; ra.pred = c->rt_plan.pred;
+        ra.hops = c->rt_plan.d ? c->d_rm_hops.p + (size_t)c->rm_tree_buf * nodes : nullptr;
+    }
+    // stage 1, and everything the host sizes the rest by
+    const auto stage1 = [&]() -> int {
+        ra.chain_pool = c->d_rt_pool.p;
+        FS_HIP(c, fs_launch_rm_route_lengths(ra, c->stream));
+        if (nodes > 0) FS_HIP(c, fs_launch_rm_scan(ra.has, (int32_t)nodes, ridx, c->stream));
+        else FS_HIP(c, hipMemsetAsync(ridx, 0, sizeof(int32_t), c->stream));
+        FS_HIP(c, fs_launch_rm_route_index(ra, c->stream));
+        FS_HIP(c, hipMemcpyAsync(c->h_rt.p + h_cnt, ridx + nodes, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (reference) FS_HIP(c, hipMemcpyAsync(c->h_rt.p + h_u64, c->d_rt_cursor.p, 8, hipMemcpyDeviceToHost, c->stream));
+        if (nodes > 0) {
+            FS_HIP(c, hipMemcpyAsync(c->h_rt.p + h_len, ra.route_len, 4 * nodes, hipMemcpyDeviceToHost, c->stream));
+            FS_HIP(c, hipMemcpyAsync(c->h_rt.p + h_goal, ra.goal_node, 4 * nodes, hipMemcpyDeviceToHost, c->stream));
+        }
+        FS_HIP(c, hipMemcpyAsync(c->h_rt.p + h_of, ra.route_of, 4 * nn, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipMemcpyAsync(c->h_rm_out.p, c->d_rm_out.p, O.total, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        return FS_OK;
+    };
+    if ((rc = stage1())) return stop(rc);
+    if (reference) {
+        // a query that outgrew the A*'s record pool ran again (its chain with it); a call whose chains outgrew the chain pool runs
+        // every query again on a pool of the size the cursor asks for — the chains then sit where this run's atomics put them, and
+        // the gather below orders them, so the lists do not depend on the schedule
+        bool redone = false;
+        rc = rm_astar_settle(c, [&] { return roadmap_astar_cols(c); }, &redone);
+        if (rc) return rc;
+        unsigned long long cursor = 0;
+        if (redone) {
+            FS_HIP(c, hipMemcpyAsync(c->h_rt.p + h_u64, c->d_rt_cursor.p, 8, hipMemcpyDeviceToHost, c->stream));
+            FS_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        std::memcpy(&cursor, c->h_rt.p + h_u64, 8);
+        if ((int64_t)cursor > c->rt_pool_cap) {
+            if (cursor > (1ull << 30)) return fail(c, FS_E_RANGE, "%llu route nodes: beyond the chain pool's limit", cursor);
+            ++c->rt_retries;
+            c->rt_pool_cap = (int64_t)cursor;
+            FS_HIP(c, c->d_rt_pool.ensure((size_t)cursor));
+            FsRmAstarArgs &q = c->as_args;
+            q.chain_pool = c->d_rt_pool.p; q.chain_cap = c->rt_pool_cap;
+            FS_HIP(c, hipMemsetAsync(c->d_rt_cursor.p, 0, 8, c->stream));
+            FS_HIP(c, hipMemsetAsync(c->d_as_stats.p, 0, 8 * sizeof(int32_t), c->stream));
+            FS_HIP(c, fs_launch_rm_astar(q, c->rt_max_q, c->stream));
+            redone = true;
+        }
+        if (redone && (rc = stage1())) return stop(rc);
+    }
+    int32_t routes = 0;
+    std::memcpy(&routes, c->h_rt.p + h_cnt, sizeof routes);
+    const int32_t *h_route_len = reinterpret_cast<const int32_t *>(c->h_rt.p + h_len);
+    int64_t *h_node_off = reinterpret_cast<int64_t *>(c->h_rt.p + h_off);
+    h_node_off[0] = 0;
+    for (int32_t r = 0; r < routes; ++r) h_node_off[r + 1] = h_node_off[r] + h_route_len[r];
+    const int64_t total = h_node_off[routes];
+    c->rt_routes = routes;
+    *n_routes = routes;
+    if (dump_raw) *n_nodes_total = total;
+    if (dump_ref) *n_refined_total = total;                  // (its upper bound: what FS_E_RANGE reports before any list is made)
+    if (routes > max_routes) return fail(c, FS_E_RANGE, "%d routes, room for %d", routes, max_routes);
+    if ((dump_raw || dump_ref || dump_leg) && total > max_nodes)
+        return fail(c, FS_E_RANGE, "%lld route nodes, room for %lld", (long long)total, (long long)max_nodes);
+    const int64_t leg_bound = total - routes;                // (every route holds at least one node)
+    if (leg_bound > (int64_t)INT32_MAX) return fail(c, FS_E_INVALID, "%lld route legs: beyond 2^31", (long long)leg_bound);
+    const size_t nr = (size_t)routes, nt = (size_t)total;
+    // stage 2: the lists, then refinePath
+    FS_HIP(c, c->d_rt_node.ensure(std::max<size_t>(nt, 1)));
+    if (refine) { FS_HIP(c, c->d_rt_refined.ensure(std::max<size_t>(nt, 1))); FS_HIP(c, c->h_rt_list.ensure(4 * std::max<size_t>(nt, 1))); }
+    FS_HIP(c, hipMemcpyAsync(c->d_rt_off.p, h_node_off, 8 * (nr + 1), hipMemcpyHostToDevice, c->stream));
+    ra.n_routes = routes; ra.node_off = c->d_rt_off.p; ra.node = c->d_rt_node.p; ra.chain_pool = c->d_rt_pool.p;
+    FS_HIP(c, fs_launch_rm_route_emit(ra, c->stream));
+    FS_HIP(c, hipMemsetAsync(c->d_rt_cursor.p + 1, 0, 8, c->stream));
+    if (refine) {
+        FsRouteRefineArgs fa{};
+        fa.grid = grid_dev(c);
+        fa.max_length = (double)(unsigned)(c->rm_radius * 1.5 / c->res);
+        fa.unknown_limit = rm_unknown_limit(c);
+        fa.xy = c->d_rm_xy.p;
+        fa.n_routes = routes; fa.node_off = c->d_rt_off.p; fa.node = c->d_rt_node.p;
+        fa.refined = c->d_rt_refined.p; fa.refined_len = d_rlen; fa.complete = c->d_rt_complete.p;
+        fa.walks = c->d_rt_cursor.p + 1;
+        FS_HIP(c, fs_launch_route_refine(fa, c->stream));
+        if (nr > 0) {
+            FS_HIP(c, hipMemcpyAsync(c->h_rt.p + h_rlen, d_rlen, 4 * nr, hipMemcpyDeviceToHost, c->stream));
+            FS_HIP(c, hipMemcpyAsync(c->h_rt.p + h_comp, c->d_rt_complete.p, nr, hipMemcpyDeviceToHost, c->stream));
+        }
+        if (dump_ref && nt > 0) FS_HIP(c, hipMemcpyAsync(c->h_rt_list.p, c->d_rt_refined.p, 4 * nt, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipMemcpyAsync(c->h_rt.p + h_u64 + 8, c->d_rt_cursor.p + 1, 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (dump_raw && nt > 0) FS_HIP(c, hipMemcpyAsync(node, c->d_rt_node.p, 4 * nt, hipMemcpyDeviceToHost, c->stream));
+    const int32_t *d_list_len = refine ? d_rlen : ra.route_len;
+    const PathInfoOutLayout P(nr);
+    FsPathInfoArgs a{};
+    int64_t legs = 0, distinct = 0;
+    if (with_info) {
+        // the legs through fs_plan_paths_information's route: a "frontier" is a route, a "way point" a leg
+        FS_HIP(c, c->d_pi_off.ensure(2 * (nr + 1)));
+        FS_HIP(c, c->d_pi_out.ensure(P.total)); FS_HIP(c, c->h_pi_out.ensure(P.total));
+        a.n = routes;
+        a.node_xy = c->d_rm_xy.p; a.n_nodes = (int32_t)nodes;
+        a.list = refine ? c->d_rt_refined.p : c->d_rt_node.p; a.list_off = c->d_rt_off.p; a.list_len = d_list_len;
+        a.dedup = c->opt_rt_dedup ? 1 : 0;
+        a.fi_threshold = prm.fi_threshold;
+        const size_t bytes = fs_pathinfo_temp_bytes(a, leg_bound, c->stream);
+        if (bytes == 0) return stop(fail(c, FS_E_HIP, "rocPRIM refused the size query"));
+        FS_HIP(c, c->d_pi_temp.ensure(bytes));
+        a.count = c->d_pi_off.p; a.offset = c->d_pi_off.p + nr + 1;
+        a.hdr = reinterpret_cast<int64_t *>(c->d_pi_out.p + P.hdr);
+        a.info_mean = reinterpret_cast<double *>(c->d_pi_out.p + P.mean);
+        a.info_min = reinterpret_cast<float *>(c->d_pi_out.p + P.min);
+        a.first_unsafe = reinterpret_cast<int32_t *>(c->d_pi_out.p + P.unsafe);
+        a.temp = c->d_pi_temp.p; a.temp_bytes = c->d_pi_temp.cap;
+        if (fs_launch_pathinfo_offsets(a, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "leg offsets: launch failed"));
+        int64_t *hdr = reinterpret_cast<int64_t *>(c->h_pi_out.p + P.hdr);
+        if (leg_bound > 0) {
+            const size_t room = (size_t)leg_bound;
+            if (a.dedup) { FS_HIP(c, c->d_pi_key.ensure(2 * room)); }
+            FS_HIP(c, c->d_pi_idx.ensure(5 * room));
+            FS_HIP(c, c->d_pi_rt.ensure(12 * room));
+            if (dump_leg) { FS_HIP(c, c->d_pi_pose.ensure(7 * room)); FS_HIP(c, c->d_pi_val.ensure(room)); }
+            a.bound = leg_bound;
+            a.key_in = c->d_pi_key.p; a.key_out = c->d_pi_key.p + room;
+            a.wp_in = c->d_pi_idx.p; a.wp_out = a.wp_in + room; a.head = a.wp_out + room; a.rank = a.head + room; a.slot = a.rank + room;
+            a.rt = c->d_pi_rt.p;
+            a.pose7 = dump_leg ? c->d_pi_pose.p : nullptr;
+            a.wp_info = dump_leg ? c->d_pi_val.p : nullptr;
+            if (fs_launch_pathinfo_prepare(a, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "route legs: launch failed"));
+            FS_HIP(c, hipMemcpyAsync(hdr, a.hdr, 16, hipMemcpyDeviceToHost, c->stream));
+        }
+        // the scoring launch is sized by the number of distinct poses
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        legs = leg_bound > 0 ? hdr[0] : 0; distinct = leg_bound > 0 ? hdr[1] : 0;
+        c->rt_poses = distinct;
+        if (distinct > 0) {
+            rc = ensure_candidate_scratch(c, (size_t)distinct, false);
+            if (rc) return rc;
+            FsFimArgs fa{};
+            if (const int rc_args = fill_fim_args(c, fa)) return rc_args;
+            fa.n = (int32_t)distinct;
+            fa.info_only = c->opt_special ? 1 : 0;
+            if (fa.info_only && fa.skip32 < 20) fa.skip32 = 20;        // (as fs_score_fim_begin)
+            rc = maybe_split(c, fa, (size_t)distinct, false);
+            if (rc) return stop(rc);
+            fa.Rt = c->d_pi_rt.p;
+            bind_fim_outputs(c, fa);
+            rc = run_fim_tier1(c, fa, nullptr, 0, fa.n << fa.split_shift);
+            if (rc) return stop(rc);
+            rc = run_fim_rest(c, fa);
+            if (rc) return stop(rc);
+            a.info = fa.info_ref;
+        }
+        if (fs_launch_pathinfo_finish(a, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "route information columns: launch failed"));
+        FS_HIP(c, hipMemcpyAsync(c->h_pi_out.p + P.mean, c->d_pi_out.p + P.mean, P.total - P.mean, hipMemcpyDeviceToHost, c->stream));
+        if (dump_leg && legs > 0) {
+            FS_HIP(c, hipMemcpyAsync(leg_pose7, a.pose7, sizeof(double) * 7 * (size_t)legs, hipMemcpyDeviceToHost, c->stream));
+            FS_HIP(c, hipMemcpyAsync(leg_info, a.wp_info, sizeof(float) * (size_t)legs, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    // everything is on the host: the caller's arrays
+    std::memcpy(path_length, c->h_rm_out.p + O.len, 8 * nn);
+    std::memcpy(path_length_m, c->h_rm_out.p + O.len_m, 8 * nn);
+    std::memcpy(path_heading, c->h_rm_out.p + O.head, 8 * nn);
+    std::memcpy(achievable, c->h_rm_out.p + O.ach, nn);
+    std::memcpy(route_of, c->h_rt.p + h_of, 4 * nn);
+    const int32_t *h_list_len = refine ? reinterpret_cast<const int32_t *>(c->h_rt.p + h_rlen) : h_route_len;
+    if (nr > 0) {
+        std::memcpy(goal_node, c->h_rt.p + h_goal, 4 * nr);
+        if (refine) std::memcpy(complete, c->h_rt.p + h_comp, nr);
+        else std::memset(complete, 1, nr);
+        for (size_t r = 0; r < nr; ++r) n_legs[r] = h_list_len[r] - 1;
+        if (with_info) {
+            std::memcpy(info_mean, c->h_pi_out.p + P.mean, 8 * nr);
+            std::memcpy(info_min, c->h_pi_out.p + P.min, 4 * nr);
+            std::memcpy(first_unsafe, c->h_pi_out.p + P.unsafe, 4 * nr);
+        }
+    }
+    if (refine) {
+        unsigned long long walks = 0;
+        std::memcpy(&walks, c->h_rt.p + h_u64 + 8, 8);
+        c->rt_walks = (int64_t)walks;
+    }
+    if (dump_raw) std::memcpy(node_offset, h_node_off, 8 * (nr + 1));
+    if (dump_ref) {
+        const int32_t *src = reinterpret_cast<const int32_t *>(c->h_rt_list.p);
+        int64_t k = 0;
+        for (size_t r = 0; r < nr; ++r) {
+            refined_offset[r] = k;
+            std::memcpy(refined_node + k, src + h_node_off[r], 4 * (size_t)h_list_len[r]);
+            k += h_list_len[r];
+        }
+        refined_offset[nr] = k;
+        *n_refined_total = k;
+    }
+    return FS_OK;
 }
 
 }  // extern "C"

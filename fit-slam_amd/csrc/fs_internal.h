@@ -326,6 +326,14 @@ struct FsRmAstarArgs {
     char *pool;                     // global route: slot b at pool + b * slot_bytes
     size_t slot_bytes;
     int32_t slots, cap;
+    // the node chain of a FOUND query (fs_roadmap_routes), or chain_len == nullptr: not emitted.  The query takes
+    // chain_len[q] slots of chain_pool from chain_base[q] = the cursor before its atomic bump, goal node first; a chain that would
+    // end beyond chain_cap is not written (the cursor still counts it: the host grows the pool to the cursor and runs again).
+    int32_t *chain_len;             // [q]
+    int64_t *chain_base;            // [q]
+    int32_t *chain_pool;
+    int64_t chain_cap;
+    unsigned long long *chain_cursor;   // [1]
 };
 #define RM_ASTAR_LDS_BYTES 65536
 #define RM_ASTAR_SLOTS 32
@@ -340,6 +348,52 @@ hipError_t fs_launch_rm_astar_goals(const FsRmPlanArgs &p, int32_t *d_gnode, int
 hipError_t fs_launch_rm_astar_list(int32_t n_nodes, const int32_t *d_mark, const int32_t *d_qidx, int32_t *d_dst, hipStream_t s);
 hipError_t fs_launch_rm_astar_cols(const FsRmPlanArgs &p, const int32_t *d_gnode, const int32_t *d_qidx, const int32_t *d_status,
                                    const double *d_len, hipStream_t s);
+
+// ---- roadmap routes (fs_roadmap_routes): the node list of every distinct goal node the plan reached, its
+// refinePath shortcut (FrontierRoadmap.cpp:657-714) and, through fs_pathinfo.hip, the Fisher information of its legs.
+// Stage 1 (before the host knows any size): a node's route length — hops + 1 under the tree, the A* chain's length under the
+// REFERENCE search, 0 where no planned frontier ends or the goal was not reached — the nodes with a route numbered in ascending
+// order (fs_launch_rm_scan of `has`), the routes' goal nodes and lengths, every frontier's route.
+struct FsRmRouteArgs {
+    int32_t n_nodes;
+    const int32_t *mark;            // [n_nodes] fs_launch_rm_astar_goals' marks: a planned frontier ends at this node
+    // TREE: the converged tree (d == nullptr: no route at all)
+    const double *d;
+    const int32_t *hops, *pred;
+    // REFERENCE (status != nullptr): the queries' results and chains
+    const int32_t *qidx, *status, *chain_len;
+    const int64_t *chain_base;
+    const int32_t *chain_pool;
+    int32_t *len, *has;             // [n_nodes] the node's route length; 1 where it is positive
+    const int32_t *ridx;            // [n_nodes + 1] exclusive scan of `has`
+    int32_t *goal_node, *route_len, *route_q;   // [routes] (route_q: the route's query, REFERENCE)
+    int32_t n;                      // frontiers
+    const int32_t *gnode;           // [n] fs_launch_rm_astar_goals' goal nodes
+    int32_t *route_of;              // [n]
+    // stage 2 (the host has scanned route_len into node_off): the lists, start node first
+    int32_t n_routes;
+    const int64_t *node_off;        // [n_routes + 1]
+    int32_t *node;
+};
+hipError_t fs_launch_rm_route_lengths(const FsRmRouteArgs &a, hipStream_t s);      // len, has
+hipError_t fs_launch_rm_route_index(const FsRmRouteArgs &a, hipStream_t s);        // goal_node, route_len, route_q, route_of
+hipError_t fs_launch_rm_route_emit(const FsRmRouteArgs &a, hipStream_t s);         // node
+// refinePath on every route (fs_raymarch.hip, beside the segment walker): one wave per route, lane l walks P[kk] -> P[kk + 1 + l]
+// by isConnectable on the staged grid, a ballot finds the first failure.  refined lists sit at the raw lists' offsets.
+struct FsRouteRefineArgs {
+    FsGridDev grid;
+    double max_length;              // isConnectable's (unsigned)(1.5 * radius / resolution)
+    double unknown_limit;           // 0.3 * radius / resolution
+    const double *xy;               // [n_nodes][2]
+    int32_t n_routes;
+    const int64_t *node_off;
+    const int32_t *node;
+    int32_t *refined;               // route r's list from node_off[r] on
+    int32_t *refined_len;           // [n_routes]
+    uint8_t *complete;              // [n_routes] 0: the shortcut stopped at a node that cannot see its successor
+    unsigned long long *walks;      // [1] segment walks (added to)
+};
+hipError_t fs_launch_route_refine(const FsRouteRefineArgs &a, hipStream_t s);
 
 // ---- next goal (FullPathOptimizer::getNextGoal): the pair matrix over [robot, locals, closest global] and the
 // exhaustive tour search over the locals' orders
@@ -453,7 +507,7 @@ struct FsKfArgs {
 hipError_t fs_launch_kf_info(const FsKfArgs &a, int pool, hipStream_t s);
 
 // ---- Fisher information along the planned paths (fs_pathinfo.hip): setPlanForFrontier's way points, one pose record
-// per distinct (from cell, to cell), the per-frontier columns
+// per distinct (from cell, to cell), the per-frontier columns; and along the legs of roadmap routes
 struct FsPathInfoArgs {
     int32_t n;                        // frontiers
     int32_t nx, ny, max_cycles;       // the grid; the stride of a path's x / y arrays in `path`
@@ -481,6 +535,14 @@ struct FsPathInfoArgs {
     double *info_mean;                // [n]
     float *info_min;                  // [n]
     int32_t *first_unsafe;            // [n]
+    // Route legs instead of grid-path way points (fs_roadmap_routes; node_xy != nullptr): "frontier" f is the node
+    // list list[list_off[f] .. + list_len[f]), its way point k the leg (list[k], list[k + 1]) — pose at the first node looking at
+    // the second, key = first * n_nodes + second.  path, path_length, achievable, step, lookahead and the grid fields are unused.
+    const double *node_xy;            // [n_nodes][2]
+    int32_t n_nodes;
+    const int32_t *list;
+    const int64_t *list_off;          // [n]
+    const int32_t *list_len;          // [n]
 };
 size_t fs_pathinfo_temp_bytes(const FsPathInfoArgs &a, int64_t bound, hipStream_t s);    // rocPRIM's scratch for n, nx, ny and that room; 0: it refused
 hipError_t fs_launch_pathinfo_offsets(const FsPathInfoArgs &a, hipStream_t s);            // count, offset

@@ -16,6 +16,10 @@
 //   records    one lane per sorted way point: its pose's slot; the head of a run of equal keys writes the pose record
 //   finish     one lane per frontier: the way points' values in order -> mean, minimum, first unsafe way point; the value dump
 // Launches are sized by `bound`, the room the host made (it does not know the total yet); lanes beyond the total only pad the sort.
+//
+// The same route scores the legs of roadmap routes (fs_roadmap_routes; FsPathInfoArgs::node_xy set): a "frontier" is
+// a node list, its way point k the leg (node k, node k + 1) — isPathSafe's isPoseSafe(point_from, point_to) over consecutive route
+// nodes — and the key a node pair instead of a cell pair.  Only `count`, `waypoints` and the pose of a key differ.
 #include "fs_internal.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -33,22 +37,47 @@ __global__ void pathinfo_count_kernel(FsPathInfoArgs a)
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f > a.n) return;
     int32_t cnt = 0;
-    if (f < a.n && a.achievable[f]) cnt = (int32_t)((int64_t)a.path_length[f] / a.step);
+    if (f < a.n && a.node_xy) cnt = a.list_len[f] > 0 ? a.list_len[f] - 1 : 0;
+    else if (f < a.n && a.achievable[f]) cnt = (int32_t)((int64_t)a.path_length[f] / a.step);
     a.count[f] = cnt;                     // (count[n] = 0: the scan's last output is the total)
 }
 
 // the cell the reference's mapToWorld(unsigned, unsigned) reads out of a path point: truncation, as path_length_m's
 __device__ __forceinline__ uint32_t point_cell(float v) { return (uint32_t)(int64_t)v; }
 
-// getRelativePoseGivenTwoPoints on the centres of two cells: position = from, yaw = atan2(to - from), orientationAroundZAxis
-__device__ void pose_of_cells(const FsPathInfoArgs &a, uint32_t fx, uint32_t fy, uint32_t tx, uint32_t ty, double pose7[7])
+// getRelativePoseGivenTwoPoints: position = from, yaw = atan2(to - from), orientationAroundZAxis
+__device__ void pose_of_points(double from_x, double from_y, double to_x, double to_y, double pose7[7])
 {
-    const double from_x = a.ox + ((double)fx + 0.5) * a.res, from_y = a.oy + ((double)fy + 0.5) * a.res;
-    const double to_x = a.ox + ((double)tx + 0.5) * a.res, to_y = a.oy + ((double)ty + 0.5) * a.res;
     const double yaw = atan2(to_y - from_y, to_x - from_x);
     const double half = yaw * 0.5;
     pose7[0] = from_x; pose7[1] = from_y; pose7[2] = 0.0;
     pose7[3] = 0.0; pose7[4] = 0.0; pose7[5] = sin(half); pose7[6] = cos(half);
+}
+
+// ... on the centres of two cells
+__device__ void pose_of_cells(const FsPathInfoArgs &a, uint32_t fx, uint32_t fy, uint32_t tx, uint32_t ty, double pose7[7])
+{
+    const double from_x = a.ox + ((double)fx + 0.5) * a.res, from_y = a.oy + ((double)fy + 0.5) * a.res;
+    const double to_x = a.ox + ((double)tx + 0.5) * a.res, to_y = a.oy + ((double)ty + 0.5) * a.res;
+    pose_of_points(from_x, from_y, to_x, to_y, pose7);
+}
+
+// ... on two roadmap nodes
+__device__ void pose_of_nodes(const FsPathInfoArgs &a, int32_t from, int32_t to, double pose7[7])
+{
+    pose_of_points(a.node_xy[2 * from], a.node_xy[2 * from + 1], a.node_xy[2 * to], a.node_xy[2 * to + 1], pose7);
+}
+
+// the pose a key stands for: (from cell, to cell) of the grid, or (from node, to node) of the roadmap
+__device__ void pose_of_key(const FsPathInfoArgs &a, uint64_t key, double pose7[7])
+{
+    if (a.node_xy) {
+        pose_of_nodes(a, (int32_t)(key / (uint64_t)a.n_nodes), (int32_t)(key % (uint64_t)a.n_nodes), pose7);
+        return;
+    }
+    const uint64_t cells = (uint64_t)a.nx * (uint64_t)a.ny;
+    const uint64_t from = key / cells, to = key % cells;
+    pose_of_cells(a, (uint32_t)(from % a.nx), (uint32_t)(from / a.nx), (uint32_t)(to % a.nx), (uint32_t)(to / a.nx), pose7);
 }
 
 // pose_to_rt of fs_capi.hip (getTransformFromPose): float translation, Eigen::Quaternionf -> rotation
@@ -83,18 +112,25 @@ __global__ void pathinfo_waypoints_kernel(FsPathInfoArgs a)
     }
     const int f = lo;
     const int64_t k = w - a.offset[f];
-    const int64_t len = (int64_t)a.path_length[f];
-    const int64_t j = len - (k + 1) * a.step;                      // in [0, len - step]: k < len / step
-    const int64_t jt = j > a.lookahead ? j - a.lookahead : 0;
-    const float *px = a.path + (int64_t)f * 2 * a.max_cycles, *py = px + a.max_cycles;
-    const uint32_t fx = point_cell(px[j]), fy = point_cell(py[j]), tx = point_cell(px[jt]), ty = point_cell(py[jt]);
+    uint64_t key;
+    if (a.node_xy) {
+        const int32_t *L = a.list + a.list_off[f];
+        key = (uint64_t)L[k] * (uint64_t)a.n_nodes + (uint64_t)L[k + 1];
+    } else {
+        const int64_t len = (int64_t)a.path_length[f];
+        const int64_t j = len - (k + 1) * a.step;                      // in [0, len - step]: k < len / step
+        const int64_t jt = j > a.lookahead ? j - a.lookahead : 0;
+        const float *px = a.path + (int64_t)f * 2 * a.max_cycles, *py = px + a.max_cycles;
+        const uint32_t fx = point_cell(px[j]), fy = point_cell(py[j]), tx = point_cell(px[jt]), ty = point_cell(py[jt]);
+        const uint64_t cells = (uint64_t)a.nx * (uint64_t)a.ny;
+        key = ((uint64_t)fy * a.nx + fx) * cells + ((uint64_t)ty * a.nx + tx);
+    }
     double pose7[7];
-    if (a.pose7 || !a.dedup) pose_of_cells(a, fx, fy, tx, ty, pose7);
+    if (a.pose7 || !a.dedup) pose_of_key(a, key, pose7);
     if (a.pose7)
         for (int q = 0; q < 7; ++q) a.pose7[w * 7 + q] = pose7[q];
     if (a.dedup) {
-        const uint64_t cells = (uint64_t)a.nx * (uint64_t)a.ny;
-        a.key_in[w] = ((uint64_t)fy * a.nx + fx) * cells + ((uint64_t)ty * a.nx + tx);
+        a.key_in[w] = key;
         a.wp_in[w] = (int32_t)w;
     } else {
         a.slot[w] = (int32_t)w;
@@ -120,10 +156,8 @@ __global__ void pathinfo_records_kernel(FsPathInfoArgs a)
     const int32_t id = a.rank[i] - 1;
     a.slot[a.wp_out[i]] = id;
     if (!a.head[i]) return;
-    const uint64_t cells = (uint64_t)a.nx * (uint64_t)a.ny;
-    const uint64_t from = key / cells, to = key % cells;
     double pose7[7];
-    pose_of_cells(a, (uint32_t)(from % a.nx), (uint32_t)(from / a.nx), (uint32_t)(to % a.nx), (uint32_t)(to / a.nx), pose7);
+    pose_of_key(a, key, pose7);
     pose_record(pose7, a.rt + (int64_t)id * 12);
 }
 
@@ -151,7 +185,7 @@ __global__ void pathinfo_finish_kernel(FsPathInfoArgs a)
 
 int key_bits(const FsPathInfoArgs &a)
 {
-    const uint64_t cells = (uint64_t)a.nx * (uint64_t)a.ny;
+    const uint64_t cells = a.node_xy ? (uint64_t)a.n_nodes : (uint64_t)a.nx * (uint64_t)a.ny;
     const uint64_t top = cells * cells - 1;     // (the pad key has every bit set: it must stay behind whatever the sort looks at)
     int bits = 1;
     while (bits < 64 && (top >> bits) != 0) ++bits;

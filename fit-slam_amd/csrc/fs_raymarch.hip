@@ -519,39 +519,100 @@ void fs_raymarch_kernel(const FsRayArgs a)
     }
 }
 
-// One lane per segment: getTracedCells(sx, sy, wx, wy, visitor, max_length, costmap) for arbitrary end points
+// One segment: getTracedCells(sx, sy, wx, wy, visitor, max_length, costmap) for arbitrary end points
 // (DEP/src/Helpers.cpp:32-96) with every RayTracedCells accessor (Helpers.hpp:83-101).  Unlike the arrival
 // fan the walk never stops early: unknown_cells_ and all_cells_count_ keep counting behind an obstacle.
+struct SegResult {
+    int traced, unknown, all;
+    bool hit, ok;
+};
+
 template <typename Walk>
-__global__ void fs_segments_kernel(const FsSegArgs s)
+__device__ __forceinline__ SegResult segment_walk(const FsGridDev &g, double sx, double sy, double sz, double wx, double wy, double wz,
+                                                  double max_length, int obst_min, int obst_max, int trace_min, int trace_max)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= s.n) return;
-    FsRayArgs a{};
-    a.grid = s.grid;
-    const FsGridDev &g = s.grid;
     uint32_t x1, y1, z1, x0, y0, z0;
-    const double sx = s.start[3 * i], sy = s.start[3 * i + 1], sz = s.start[3 * i + 2];
-    const double wx = s.end[3 * i], wy = s.end[3 * i + 1], wz = s.end[3 * i + 2];
     int traced = 0, unknown = 0, all = 0;
     bool hit = false, ok = false;
     if (world_to_map(g, wx, wy, wz, x1, y1, z1) && world_to_map(g, sx, sy, sz, x0, y0, z0)) {
         ok = true;
         Walk w;
-        walk_init(w, g, x0, y0, z0, x1, y1, z1, s.max_length);
+        walk_init(w, g, x0, y0, z0, x1, y1, z1, max_length);
         for (uint32_t v = 0; v <= w.end; ++v) {
             const int c = walk_cell(g, w);
             {
-                ++all;                                                        // Helpers.hpp:62
-                if (c <= s.trace_max && c >= s.trace_min && !hit) ++traced;   // :64-67
-                if (c >= s.obst_min && c <= s.obst_max) hit = true;           // :68-71
-                if (c == 255) ++unknown;                                      // :72-75
+                ++all;                                                    // Helpers.hpp:62
+                if (c <= trace_max && c >= trace_min && !hit) ++traced;   // :64-67
+                if (c >= obst_min && c <= obst_max) hit = true;           // :68-71
+                if (c == 255) ++unknown;                                  // :72-75
             }
             walk_step(w);
         }
     }
-    s.ok[i] = ok; s.hit[i] = hit;
-    s.traced[i] = traced; s.unknown[i] = unknown; s.all[i] = all;
+    return SegResult{traced, unknown, all, hit, ok};
+}
+
+// One lane per segment
+template <typename Walk>
+__global__ void fs_segments_kernel(const FsSegArgs s)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= s.n) return;
+    const SegResult r = segment_walk<Walk>(s.grid, s.start[3 * i], s.start[3 * i + 1], s.start[3 * i + 2], s.end[3 * i], s.end[3 * i + 1],
+                                           s.end[3 * i + 2], s.max_length, s.obst_min, s.obst_max, s.trace_min, s.trace_max);
+    s.ok[i] = r.ok; s.hit[i] = r.hit;
+    s.traced[i] = r.traced; s.unknown[i] = r.unknown; s.all[i] = r.all;
+}
+
+// FrontierRoadMap::refinePath (DEP/src/planners/FrontierRoadmap.cpp:657-714) on every route of fs_roadmap_routes,
+// one wave per route.  From the kept node P[kk] the reference tries P[kk + 1], P[kk + 2], ... in turn and stops at the first that
+// isConnectable (:716-737: walk ok, nothing in 253..254, unknown cells <= the limit) refuses; the last one it accepted is kept
+// next.  Here lane l walks P[kk] -> P[next + l], 64 candidates a round, and a ballot finds the first refusal: the lanes behind
+// it have walked for nothing, the verdicts in front of it are the sequential scan's.  A node that cannot see its own successor
+// ends the list (complete = 0).
+__global__ __launch_bounds__(256) void fs_route_refine_kernel(const FsRouteRefineArgs a)
+{
+    const int32_t r = (int32_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= a.n_routes) return;
+    const int64_t base = a.node_off[r];
+    const int32_t m = (int32_t)(a.node_off[r + 1] - base);
+    const int32_t *P = a.node + base;
+    int32_t *R = a.refined + base;
+    const double oz = a.grid.oz;
+    int32_t kk = 0, nr = m > 0 ? 1 : 0;
+    uint8_t complete = 1;
+    unsigned long long walks = 0;
+    if (lane == 0 && m > 0) R[0] = P[0];
+    while (kk < m - 1) {
+        const int32_t from = P[kk];
+        const double fx = a.xy[2 * from], fy = a.xy[2 * from + 1];
+        int32_t next = kk + 1;
+        bool refused = false;
+        while (next < m && !refused) {
+            const int32_t j = next + lane;
+            bool bad = false;
+            if (j < m) {
+                const int32_t to = P[j];
+                const SegResult s = segment_walk<WalkLinear>(a.grid, fx, fy, oz, a.xy[2 * to], a.xy[2 * to + 1], oz, a.max_length, 253, 254, 0, 255);
+                bad = !(s.ok && !s.hit && !((double)s.unknown > a.unknown_limit));
+            }
+            const int32_t tried = m - next < 64 ? m - next : 64;
+            walks += (unsigned long long)tried;
+            const uint64_t mask = __ballot(bad);
+            if (mask) { next += __builtin_ctzll(mask); refused = true; }
+            else next += tried;
+        }
+        if (next - 1 == kk) { complete = 0; break; }
+        if (lane == 0) R[nr] = P[next - 1];
+        ++nr;
+        kk = next - 1;
+    }
+    if (lane == 0) {
+        a.refined_len[r] = nr;
+        a.complete[r] = complete;
+        if (walks) atomicAdd(a.walks, walks);
+    }
 }
 
 __global__ void fs_selftest_kernel(int32_t max_abs, double *out_sqrt, double *out_div)
@@ -585,6 +646,13 @@ hipError_t fs_launch_segments(const FsSegArgs &a, hipStream_t s)
     if (a.n <= 0) return hipSuccess;
     // (the segment visitor reports unknown cells separately from its ranges: it needs the costs, hence the byte image)
     hipLaunchKernelGGL(fs_segments_kernel<WalkLinear>, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_route_refine(const FsRouteRefineArgs &a, hipStream_t s)
+{
+    if (a.n_routes <= 0) return hipSuccess;
+    hipLaunchKernelGGL(fs_route_refine_kernel, dim3((unsigned)((a.n_routes + 3) / 4)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

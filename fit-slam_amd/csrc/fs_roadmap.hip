@@ -564,7 +564,7 @@ __device__ __forceinline__ fs_astar_mem astar_carve(char *base, int32_t cap, int
 // (an earlier commit of the same chunk can only lower a best g, so a successor rejected at evaluation stays rejected).  The
 // workgroup is this one wave: its barriers order lane 0's stores before the other lanes' loads, in LDS and in global memory alike.
 __device__ __forceinline__ int astar_wave(const fs_astar_graph &G, const fs_astar_mem &m, int32_t start, int32_t goal, double *len,
-                                          int32_t *pops)
+                                          int32_t *pops, int32_t *goal_rec)
 {
     const int lane = threadIdx.x;
     for (int32_t v = lane; v < G.n; v += kAstarThreads) { m.best[v] = -1; m.closed[v] = 0; }
@@ -585,6 +585,7 @@ __device__ __forceinline__ int astar_wave(const fs_astar_graph &G, const fs_asta
         const int32_t cur = m.rec_node[r];
         if (G.xy[2 * cur] == gx && G.xy[2 * cur + 1] == gy) {
             if (lane == 0) L = fs_astar_length(m, G.xy, m.best[cur]);
+            *goal_rec = m.best[cur];
             result = FS_ASTAR_FOUND;
             break;
         }
@@ -626,6 +627,20 @@ __device__ __forceinline__ int astar_wave(const fs_astar_graph &G, const fs_asta
 
 __device__ __forceinline__ int32_t astar_src(const FsRmAstarArgs &a, int32_t q) { return a.src ? a.src[q] : a.root; }
 
+// the FOUND query's path (astar.cpp:57-69) while its records are still there: the chain from record r up the parents, goal node
+// first, into the query's slots of the chain pool (lane 0).  The cursor is bumped by every chain, written or not.
+__device__ __forceinline__ void astar_chain(const FsRmAstarArgs &a, const fs_astar_mem &m, int32_t q, int32_t r)
+{
+    int32_t L = 0;
+    for (int32_t p = r; p >= 0; p = m.rec_parent[p]) ++L;
+    const int64_t base = (int64_t)atomicAdd(a.chain_cursor, (unsigned long long)L);
+    a.chain_len[q] = L;
+    a.chain_base[q] = base;
+    if (base + L > a.chain_cap) return;
+    int64_t k = base;
+    for (int32_t p = r; p >= 0; p = m.rec_parent[p]) a.chain_pool[k++] = m.rec_node[p];
+}
+
 // the LDS route, one workgroup (one wave) per query
 __global__ __launch_bounds__(kAstarThreads) void rm_astar_lds_kernel(const FsRmAstarArgs a)
 {
@@ -635,10 +650,12 @@ __global__ __launch_bounds__(kAstarThreads) void rm_astar_lds_kernel(const FsRmA
     if (q >= nq) return;
     int st = FS_ASTAR_OVERFLOW;
     double len = 0.0;
-    int32_t pops = 0;
+    int32_t pops = 0, rec = -1;
     if (a.lds_cap > 0) {
         const fs_astar_graph G{a.n_nodes, a.xy, a.row, a.col};
-        st = astar_wave(G, astar_carve(smem, a.lds_cap, a.n_nodes), astar_src(a, q), a.dst[q], &len, &pops);
+        const fs_astar_mem m = astar_carve(smem, a.lds_cap, a.n_nodes);
+        st = astar_wave(G, m, astar_src(a, q), a.dst[q], &len, &pops, &rec);
+        if (a.chain_len && st == FS_ASTAR_FOUND && threadIdx.x == 0) astar_chain(a, m, q, rec);
     }
     if (threadIdx.x == 0) {
         a.status[q] = st;
@@ -660,9 +677,10 @@ __global__ __launch_bounds__(kAstarThreads) void rm_astar_global_kernel(const Fs
     for (int32_t q = blockIdx.x; q < nq; q += gridDim.x) {
         if (a.status[q] != FS_ASTAR_OVERFLOW) continue;
         double len = 0.0;
-        int32_t pops = 0;
-        const int st = astar_wave(G, m, astar_src(a, q), a.dst[q], &len, &pops);
+        int32_t pops = 0, rec = -1;
+        const int st = astar_wave(G, m, astar_src(a, q), a.dst[q], &len, &pops, &rec);
         if (threadIdx.x == 0) {
+            if (a.chain_len && st == FS_ASTAR_FOUND) astar_chain(a, m, q, rec);
             if (st == FS_ASTAR_OVERFLOW) {
                 atomicAdd(&a.stats[3], 1);
             } else {
@@ -713,7 +731,85 @@ __global__ void rm_astar_cols_kernel(const FsRmPlanArgs a, const int32_t *__rest
     a.achievable[f] = ok;
 }
 
+
+// ---- routes
+
+// a node's route: hops + 1 nodes under the tree, the chain of its query under the REFERENCE search; 0 where no planned frontier
+// ends or the goal was not reached
+__global__ void rm_route_lengths_kernel(const FsRmRouteArgs a)
+{
+    const int32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= a.n_nodes) return;
+    int32_t len = 0;
+    if (a.mark[v]) {
+        if (a.status) {
+            const int32_t q = a.qidx[v];
+            if (a.status[q] == FS_ASTAR_FOUND) len = a.chain_len[q];
+        } else if (a.d && a.d[v] < INFINITY) {
+            len = a.hops[v] + 1;
+        }
+    }
+    a.len[v] = len;
+    a.has[v] = len > 0 ? 1 : 0;
+}
+
+// lanes over the nodes, then over the frontiers: route ridx[v] ends at node v; a frontier's route is its goal node's
+__global__ void rm_route_index_kernel(const FsRmRouteArgs a)
+{
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.n_nodes && a.has[i]) {
+        const int32_t r = a.ridx[i];
+        a.goal_node[r] = i;
+        a.route_len[r] = a.len[i];
+        a.route_q[r] = a.status ? a.qidx[i] : -1;
+    }
+    if (i < a.n) {
+        const int32_t v = a.gnode[i];
+        a.route_of[i] = (v >= 0 && a.has[v]) ? a.ridx[v] : -1;
+    }
+}
+
+// one wave per route, start node first: the tree's predecessors from the goal node back (lane 0: the chain is sequential), or
+// the query's chain out of the pool, reversed (every lane)
+__global__ __launch_bounds__(256) void rm_route_emit_kernel(const FsRmRouteArgs a)
+{
+    const int32_t r = (int32_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= a.n_routes) return;
+    const int64_t base = a.node_off[r];
+    const int32_t m = (int32_t)(a.node_off[r + 1] - base);
+    if (a.status) {
+        const int64_t src = a.chain_base[a.route_q[r]];
+        for (int32_t k = lane; k < m; k += 64) a.node[base + k] = a.chain_pool[src + (m - 1 - k)];
+    } else if (lane == 0) {
+        int32_t v = a.goal_node[r];
+        for (int32_t k = m - 1; k >= 0; --k) { a.node[base + k] = v; v = a.pred[v]; }
+    }
+}
+
 }  // namespace
+
+hipError_t fs_launch_rm_route_lengths(const FsRmRouteArgs &a, hipStream_t s)
+{
+    if (a.n_nodes <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rm_route_lengths_kernel, dim3((unsigned)((a.n_nodes + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_rm_route_index(const FsRmRouteArgs &a, hipStream_t s)
+{
+    const int32_t lanes = a.n_nodes > a.n ? a.n_nodes : a.n;
+    if (lanes <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rm_route_index_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_rm_route_emit(const FsRmRouteArgs &a, hipStream_t s)
+{
+    if (a.n_routes <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rm_route_emit_kernel, dim3((unsigned)((a.n_routes + 3) / 4)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t fs_launch_rm_astar(const FsRmAstarArgs &a, int32_t max_q, hipStream_t s)
 {

@@ -556,6 +556,53 @@ int fs_get_frontier_costs_roadmap(fs_ctx *ctx, const double robot_pose7[7], int3
                   const uint8_t *blacklisted, double alpha, double beta, double max_vx, double max_wz, int with_fisher_information,
                   fs_record *records, double *weighted_cost, double *arrival_utility, double *distance_utility, int32_t *order,
                   double *path_length_m);
+/* The routes behind fs_roadmap_plan's numbers: RoadmapPlanResult::path of getPlan (FrontierRoadmap.cpp:550-635,
+ * astar.cpp:57-69 — what the reference publishes as frontier_roadmap_nav2_plan), its line-of-sight shortcut
+ * FrontierRoadMap::refinePath (:657-714) on the staged grid, and FullPathOptimizer::isPathSafe's question (FullPathOptimizer.cpp:
+ * 308-340) — does SLAM keep tracking on the way? — as the Fisher information of every leg. */
+typedef struct fs_route_params {
+    int32_t refine;            /* 1: the legs that are scored are refinePath's list; 0: getPlan's */
+    int32_t with_information;  /* 0: routes only (no landmarks / table needed; the information columns and the leg dump must be NULL) */
+    double  fi_threshold;      /* 550.0 (FisherInfoBTPlugin.cpp:20): a leg is unsafe unless info > threshold */
+} fs_route_params;             /* NULL: {1, 1, 550.0} */
+/* path_length .. achievable [n] are fs_roadmap_plan's own, bit for bit, under the context's roadmap search; the tree cache and the
+ * counters 1005-1006 / 1021-1023 move as that call moves them.
+ * Routes.  One route per DISTINCT goal node that a planned frontier's plan reached, in ascending node index (indices are
+ * fs_roadmap_get_graph's): goal_node, complete, n_legs, info_mean, info_min, first_unsafe [max_routes], *n_routes of them;
+ * route_of [n] = the frontier's route, -1 where achievable is 0 or the goal is the robot's exact position (length 0: the
+ * reference returns an empty path).  FS_ROADMAP_SEARCH_TREE: root, ..., v — the predecessors from the goal's closest key node v back
+ * to the root, reversed, hops[v] + 1 nodes.  FS_ROADMAP_SEARCH_REFERENCE: the A*'s path — the record chain from allNodes[goal] along
+ * parent, reversed, start first (stale records included).  Either way the route's segment lengths summed from the goal end are
+ * path_length_m, bit for bit.
+ * refinePath on route P[0..m-1]: R = [P[0]], kk = 0; while kk < m - 1: next = kk + 1; while next < m and isConnectable(P[kk],
+ * P[next]): ++next; if next - 1 == kk: stop (complete = 0, R is truncated); append P[next - 1], kk = next - 1.  The scan stops at
+ * the first refusal, isConnectable walks FROM P[kk] (the direction matters) and is fs_roadmap_rebuild's predicate on the grid
+ * staged NOW.  complete = 1 and R = [P[0]] for m = 1.  params->refine needs a 2-D grid (else fs_roadmap_rebuild's refusal);
+ * without it no grid is read, complete is 1 and the refined dump must be NULL.
+ * Legs.  The scored list L is R (refine) or P; leg k is (L[k], L[k + 1]), n_legs = len(L) - 1.  Its pose is
+ * getRelativePoseGivenTwoPoints: (x, y, 0) of L[k], yaw atan2 towards L[k + 1], quaternion (0, 0, sin(yaw / 2), cos(yaw / 2)); its
+ * value fs_score_fim's info_ref at that pose under the context's landmarks, table and fs_set_fim_params.  Equal (from, to) pairs
+ * are scored once ("routes.dedup", default 1).  info_mean, info_min, first_unsafe as fs_plan_paths_information defines them over
+ * the legs in order (0, +inf, -1 without legs).  The reference's literal isPathSafe tests pathToFollow[0] -> [1] on every
+ * iteration: that is leg 0's value here (first_unsafe == 0 is its verdict); its trailing robot-pose overlap gate is not part of
+ * this call.
+ * Dumps, each group all or none: {n_nodes_total, node_offset [max_routes + 1], node [max_nodes]} the raw lists as CSR;
+ * {n_refined_total, refined_offset [max_routes + 1], refined_node [max_nodes]} the refined ones; {leg_pose7 [max_nodes][7],
+ * leg_info [max_nodes]} the legs route by route (route r's first leg is at offset_L[r] - r).  n_routes may be NULL only when
+ * n == 0.  More routes than max_routes, or (with a dump) more raw nodes than max_nodes: FS_E_RANGE with *n_routes and the given
+ * totals set and nothing else written.
+ * FS_E_INVALID: a dump group half given, a dump that the params switch off, fi_threshold not finite, max_routes / max_nodes
+ * negative; otherwise refuses what fs_roadmap_plan refuses and, with_information, what fs_score_fim refuses, with their codes.
+ * Counters (fs_get_counter): 1026 distinct routes of the last call, 1027 isConnectable walks of its refinement, 1028 distinct leg
+ * poses it scored, 1029 times a call ran the A* again because the chain pool was too small (fs_set_option "routes.pool_nodes":
+ * its size to begin with, 65536 nodes; it grows to what a call needed).  Synchronises three times (the
+ * routes' sizes, the number of distinct poses, the results); twice without information. */
+int fs_roadmap_routes(fs_ctx *ctx, const double robot_pose7[7], int32_t n, const double *goal_xyz, const uint8_t *achievable_in,
+                  const fs_route_params *params, double *path_length, double *path_length_m, double *path_heading,
+                  uint8_t *achievable, int32_t *route_of, int32_t max_routes, int32_t *n_routes, int32_t *goal_node,
+                  uint8_t *complete, int32_t *n_legs, double *info_mean, float *info_min, int32_t *first_unsafe, int64_t max_nodes,
+                  int64_t *n_nodes_total, int64_t *node_offset, int32_t *node, int64_t *n_refined_total, int64_t *refined_offset,
+                  int32_t *refined_node, double *leg_pose7, float *leg_info);
 
 /* Key-frame anchors (FrontierRoadMap's loop-closure correction).  Every node fs_roadmap_add_nodes accepts — the one
  * that trips its FS_E_RANGE included — is queued as pending (no_kf_parent_queue_); fs_set_roadmap_params clears the queue, the key

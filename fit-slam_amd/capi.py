@@ -21,6 +21,9 @@ FS_SEEDS_NEAREST, FS_SEEDS_REFERENCE = 0, 1
 SEED_ORDERS = {"nearest": FS_SEEDS_NEAREST, "reference": FS_SEEDS_REFERENCE}
 FS_ROADMAP_SEARCH_TREE, FS_ROADMAP_SEARCH_REFERENCE = 0, 1
 ROADMAP_SEARCHES = {"tree": FS_ROADMAP_SEARCH_TREE, "reference": FS_ROADMAP_SEARCH_REFERENCE}
+FS_ALLOC_HUNGARIAN, FS_ALLOC_MINPOS = 0, 1
+ALLOC_METHODS = {"hungarian": FS_ALLOC_HUNGARIAN, "minpos": FS_ALLOC_MINPOS}
+FS_ALLOC_MAX_ROBOTS, FS_ALLOC_MAX_TASKS = 64, 4096
 
 # every symbol include/fitslam_frontier.h declares
 EXPORTED_SYMBOLS = [
@@ -42,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "fs_roadmap_set_keyframes", "fs_roadmap_optimize", "fs_roadmap_get_anchors",
     "fs_search_frontiers", "fs_get_frontier_costs_searched", "fs_set_frontier_seed_order", "fs_set_roadmap_search",
     "fs_roadmap_routes",
+    "fs_allocate_tasks", "fs_allocate_tasks_dev", "fs_fleet_allocate_roadmap",
 ]
 
 RECORD_DTYPE = np.dtype([("arrival", "<i4"), ("argmax", "<i4"), ("yaw", "<f4"), ("info_ref", "<f4"),
@@ -201,6 +205,9 @@ def load_library(build: bool = True):
     L.fs_set_roadmap_search.argtypes = [vp, i32]
     L.fs_get_frontier_costs_searched.argtypes = [vp, C.POINTER(dbl * 7), i32, dbl, i32, i32, i32, i32, vp, dbl, dbl, dbl, dbl, C.c_int,
                                                  i32, vp, C.POINTER(i32), vp, vp, vp, vp, vp, vp]
+    L.fs_allocate_tasks.argtypes = [vp, i32, i32, vp, vp, i32, vp, C.POINTER(dbl), vp, vp]
+    L.fs_allocate_tasks_dev.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.fs_fleet_allocate_roadmap.argtypes = [vp, i32, vp, i32, vp, vp, vp, dbl, dbl, dbl, dbl, i32, vp, C.POINTER(dbl), vp, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         f = getattr(L, name)
         if name not in ("fs_ctx_destroy", "fs_last_error", "fs_multi_destroy", "fs_multi_last_error", "fs_multi_ctx"):
@@ -858,6 +865,74 @@ class FrontierScorer:
                                                               max_wz, 1 if with_fim else 0, _p(rec), _p(cost), _p(au), _p(du), _p(order),
                                                               _p(plm)))
         return dict(records=rec, weighted_cost=cost, arrival_utility=au, distance_utility=du, order=order, path_length_m=plm)
+
+    def allocate_tasks(self, cost, distance=None, method="hungarian", want_rank=False):
+        """The reference's TaskAllocator on cost [R][n] (robot-major, as addRobotTasks pushes the rows): "hungarian"
+        (solveAllocationHungarian) or "minpos" (solveAllocationMinPos, which needs distance [R][n]), bit for bit.
+        dict(assignment [R] (-1: none), total_cost), plus rank [R][n] (MinPos' P) and modified_cost [R][n] with want_rank under
+        "minpos"."""
+        if method not in ALLOC_METHODS:
+            raise FsError(FS_E_INVALID, f"unknown allocation method {method!r} (hungarian | minpos)")
+        cost = np.ascontiguousarray(cost, dtype=np.float64)
+        if cost.ndim != 2:
+            raise ValueError("cost must be [robots][tasks]")
+        R, n = cost.shape
+        dist = None if distance is None else np.ascontiguousarray(distance, dtype=np.float64)
+        if dist is not None and dist.shape != cost.shape:
+            raise ValueError(f"distance is {dist.shape}, cost {cost.shape}")
+        assignment = np.full(R, -2, dtype=np.int32)
+        total = C.c_double(float("nan"))
+        wanted = want_rank and method == "minpos"
+        rank = np.zeros((R, n), dtype=np.int32) if wanted else None
+        mod = np.zeros((R, n)) if wanted else None
+        self._check(self._L.fs_allocate_tasks(self._h, R, n, _p(cost), _p(dist), ALLOC_METHODS[method], _p(assignment), C.byref(total),
+                                              _p(rank), _p(mod)))
+        out = dict(assignment=assignment, total_cost=total.value)
+        if wanted:
+            out.update(rank=rank, modified_cost=mod)
+        return out
+
+    def allocate_tasks_dev(self, n_robots, n_tasks, d_cost, d_distance, method, d_assignment, d_total_cost, d_status, d_rank=0,
+                           d_modified_cost=0):
+        """allocate_tasks on device pointers (integers), enqueued on the context's stream and not waited for; d_status [1] int32."""
+        self._check(self._L.fs_allocate_tasks_dev(self._h, int(n_robots), int(n_tasks), C.c_void_p(d_cost), C.c_void_p(d_distance or None),
+                                                  ALLOC_METHODS[method], C.c_void_p(d_assignment), C.c_void_p(d_total_cost),
+                                                  C.c_void_p(d_rank or None), C.c_void_p(d_modified_cost or None), C.c_void_p(d_status)))
+
+    def fleet_allocate_roadmap(self, robot_poses, goal_xyz, frontier_size=None, blacklisted=None, method="hungarian", search=None,
+                               want_matrix=False, want_records=False, alpha=0.25, beta=1.0, max_vx=0.5, max_wz=0.5):
+        """One tick of a fleet on the shared map: every robot's get_frontier_costs_roadmap rows (robot_poses [R][7]) built on the
+        device — arrival information once, a tree per distinct start node, one plan launch — and allocate_tasks on them with
+        distance = path_length_m.  dict(assignment [R], total_cost, assigned_cost [R] (DBL_MAX: a dead frontier, NaN for -1)), plus
+        weighted_cost, path_length_m, achievable [R][n] with want_matrix and records [n] (scored with achievable_in = all) with
+        want_records.  search= as roadmap_plan's."""
+        if method not in ALLOC_METHODS:
+            raise FsError(FS_E_INVALID, f"unknown allocation method {method!r} (hungarian | minpos)")
+        poses = np.ascontiguousarray(robot_poses, dtype=np.float64).reshape(-1, 7)
+        goal = np.ascontiguousarray(goal_xyz, dtype=np.float64).reshape(-1, 3)
+        R, n = poses.shape[0], goal.shape[0]
+        fs = None if frontier_size is None else np.ascontiguousarray(frontier_size, dtype=np.int32).reshape(-1)
+        bl = None if blacklisted is None else np.ascontiguousarray(blacklisted, dtype=np.uint8).reshape(-1)
+        for name, a in (("frontier_size", fs), ("blacklisted", bl)):
+            if a is not None and a.shape[0] != n:
+                raise ValueError(f"{name} has {a.shape[0]} entries for {n} goals")
+        assignment = np.full(R, -2, dtype=np.int32)
+        total = C.c_double(float("nan"))
+        assigned = np.zeros(R)
+        rec = np.zeros(n, dtype=RECORD_DTYPE) if want_records else None
+        cost = np.zeros((R, n)) if want_matrix else None
+        plm = np.zeros((R, n)) if want_matrix else None
+        ach = np.zeros((R, n), dtype=np.uint8) if want_matrix else None
+        with self._roadmap_search_for_call(search):
+            self._check(self._L.fs_fleet_allocate_roadmap(self._h, R, _p(poses), n, _p(goal), _p(fs), _p(bl), alpha, beta, max_vx, max_wz,
+                                                          ALLOC_METHODS[method], _p(assignment), C.byref(total), _p(assigned), _p(rec),
+                                                          _p(cost), _p(plm), _p(ach)))
+        out = dict(assignment=assignment, total_cost=total.value, assigned_cost=assigned)
+        if want_matrix:
+            out.update(weighted_cost=cost, path_length_m=plm, achievable=ach)
+        if want_records:
+            out["records"] = rec
+        return out
 
     def roadmap_next_goal(self, robot_pose7, goal_xyz, path_length_m, achievable, blacklisted=None, blacklist_xy=None,
                           n_local=5, local_radius=12.0, fi_pose7=None, fi_threshold=550.0, want_matrix=False, want_selection=False,

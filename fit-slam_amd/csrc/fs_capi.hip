@@ -423,6 +423,18 @@ struct fs_ctx {
     DevBuf<char> d_rf_out, d_rf_pts;          // per-leg columns | vertex and pose slots (when the page-locked buffer is not mapped)
     PinnedBuf h_rf_in, h_rf_out, h_rf_pts;
 
+    // task allocation (fs_allocate.hip).  d_al_work: the working copy | MinPos' matrix | MinPos' P; d_al_out: the
+    // packed result (AllocOut); d_al_stats: status and counters 1030-1032 of the last solve (read when fs_get_counter asks).
+    // The fleet call keeps its trees, plans and matrix in buffers of its own: the single-robot tree cache and d_rm_out stay as
+    // fs_roadmap_plan left them.
+    DevBuf<char> d_al_in, d_al_work, d_al_out;
+    DevBuf<int32_t> d_al_stats;
+    PinnedBuf h_al_in, h_al_out;
+    DevBuf<double> d_fl_d;
+    DevBuf<int32_t> d_fl_hops, d_fl_pred, d_fl_word;
+    DevBuf<char> d_fl_in, d_fl_plan, d_fl_out;   // the staged inputs;  path length | heading, [R][n] each;  the packed results
+    PinnedBuf h_fl_in, h_fl_out;
+
     // timing
     bool timing = false;
     std::vector<TimedLaunch> launches;
@@ -1115,6 +1127,9 @@ void fs_ctx_destroy(fs_ctx *c)
     c->d_kf_word.release(); c->d_kf_cell_key.release(); c->d_kf_hkey.release(); c->d_kf_state.release(); c->h_kf.release();
     c->d_rf_g.release(); c->d_rf_flags.release(); c->d_rf_any.release(); c->d_rf_in.release(); c->d_rf_scratch.release();
     c->d_rf_out.release(); c->d_rf_pts.release(); c->h_rf_in.release(); c->h_rf_out.release(); c->h_rf_pts.release();
+    c->d_al_in.release(); c->d_al_work.release(); c->d_al_out.release(); c->d_al_stats.release(); c->h_al_in.release(); c->h_al_out.release();
+    c->d_fl_d.release(); c->d_fl_hops.release(); c->d_fl_pred.release(); c->d_fl_word.release(); c->d_fl_in.release(); c->d_fl_plan.release();
+    c->d_fl_out.release(); c->h_fl_in.release(); c->h_fl_out.release();
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -2071,6 +2086,18 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
         // leg poses it scored; calls that ran the A* again on a grown chain pool
         {1026, &fs_ctx::rt_routes, false}, {1027, &fs_ctx::rt_walks, false}, {1028, &fs_ctx::rt_poses, false}, {1029, &fs_ctx::rt_retries, true},
     };
+    // the task allocator (fs_allocate_tasks, fs_allocate_tasks_dev, fs_fleet_allocate_roadmap): augmentations, step-5 runs and
+    // step-3 primes of the last solve.  The solve leaves them on the device (the device form is not waited for): read here
+    if (c && value && which >= 1030 && which <= 1032) {
+        FS_HIP(c, hipSetDevice(c->device));
+        *value = 0;
+        if (!c->d_al_stats.p) return FS_OK;
+        int32_t v = 0;
+        FS_HIP(c, hipMemcpyAsync(&v, c->d_al_stats.p + 1 + (which - 1030), sizeof v, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        *value = v;
+        return FS_OK;
+    }
     for (const auto &h : host)
         if (c && value && which == h.id) {
             *value = c->*h.v;
@@ -5072,6 +5099,277 @@ int fs_refine_paths(fs_ctx *c, int32_t n, const double *start_xy, const double *
         vo += (size_t)n_vertices[i];
         po += (size_t)n_poses[i];
     }
+    return FS_OK;
+}
+
+}  // extern "C"
+
+// ================================================================== multi-robot task allocation (fs_allocate.hip)
+// TaskAllocator (DEPX/frontier_multirobot_allocator/taskAllocator.cpp:7-66): every robot's cost and distance rows, then MinPos and /
+// or Munkres, in one launch of one workgroup; and the fleet call, which builds those rows on the device — arrival information scored
+// once for the list, one shortest-path tree per distinct start node, one plan launch over R x n, U1 per robot — and solves on them
+// where they lie.
+
+namespace {
+
+// the packed result of a solve at the head of d_al_out / d_fl_out
+struct AllocHeader {
+    double total;
+    double assigned[FS_ALLOC_MAX_ROBOTS];
+    int32_t assignment[FS_ALLOC_MAX_ROBOTS];
+    int32_t status, err, pad[2];
+};
+constexpr size_t kAllocHeader = 1024;
+static_assert(sizeof(AllocHeader) <= kAllocHeader, "the header block holds the header");
+
+int alloc_check(fs_ctx *c, int32_t R, int32_t n, int32_t method)
+{
+    if (R < 1 || R > FS_ALLOC_MAX_ROBOTS) return fail(c, FS_E_INVALID, "n_robots must be 1..%d", FS_ALLOC_MAX_ROBOTS);
+    if (n < 1 || n > FS_ALLOC_MAX_TASKS) return fail(c, FS_E_INVALID, "n_tasks must be 1..%d", FS_ALLOC_MAX_TASKS);
+    if (method != FS_ALLOC_HUNGARIAN && method != FS_ALLOC_MINPOS) return fail(c, FS_E_INVALID, "unknown allocation method %d", method);
+    return FS_OK;
+}
+
+// The solve on device matrices, on the stream, not waited for.  d_modified may be nullptr (MINPOS then keeps its matrix in the
+// context's scratch); d_assigned may be nullptr.  The counters of the solve stay in d_al_stats until fs_get_counter asks.
+int alloc_enqueue(fs_ctx *c, int32_t R, int32_t n, const double *d_cost, const double *d_distance, int32_t method, int32_t *d_assignment,
+                  double *d_total, double *d_assigned, int32_t *d_rank, double *d_modified, int32_t *d_status)
+{
+    const size_t rn = (size_t)R * (size_t)n;
+    const bool minpos = method == FS_ALLOC_MINPOS;
+    FS_HIP(c, c->d_al_work.ensure(8 * rn * ((minpos && !d_modified) ? 2 : 1)));
+    if (!c->d_al_stats.p) {
+        FS_HIP(c, c->d_al_stats.ensure(4));
+        FS_HIP(c, hipMemsetAsync(c->d_al_stats.p, 0, 4 * sizeof(int32_t), c->stream));
+    }
+    FsAllocArgs a{};
+    a.n_robots = R; a.n_tasks = n; a.method = method;
+    a.cost = d_cost; a.distance = minpos ? d_distance : nullptr;
+    a.rank = minpos ? d_rank : nullptr;
+    a.work = reinterpret_cast<double *>(c->d_al_work.p);
+    a.modified = !minpos ? nullptr : d_modified ? d_modified : a.work + rn;
+    a.assignment = d_assignment; a.total_cost = d_total; a.assigned_cost = d_assigned;
+    a.status = d_status; a.stats = c->d_al_stats.p + 1;
+    FS_HIP(c, fs_launch_allocate(a, c->stream));
+    return FS_OK;
+}
+
+int alloc_status(fs_ctx *c, int32_t status, int32_t R, int32_t n)
+{
+    if (status == FS_E_INVALID) return fail(c, FS_E_INVALID, "a cost or distance entry is NaN, infinite or negative");
+    if (status == FS_E_RANGE)
+        return fail(c, FS_E_RANGE, "step 5 ran more than (%d + 1) * (%d + 1) times", (int)R, (int)std::min(R, n));
+    if (status != FS_OK) return fail(c, FS_E_HIP, "the allocator returned status %d", (int)status);
+    return FS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fs_allocate_tasks_dev(fs_ctx *c, int32_t n_robots, int32_t n_tasks, const double *d_cost, const double *d_distance, int32_t method,
+                          int32_t *d_assignment, double *d_total_cost, int32_t *d_rank, double *d_modified_cost, int32_t *d_status)
+{
+    if (!c) return FS_E_INVALID;
+    const int rc = alloc_check(c, n_robots, n_tasks, method);
+    if (rc) return rc;
+    if (!d_cost || !d_assignment || !d_total_cost || !d_status) return fail(c, FS_E_INVALID, "null device pointer");
+    if (method == FS_ALLOC_MINPOS && !d_distance) return fail(c, FS_E_INVALID, "FS_ALLOC_MINPOS needs the distance matrix");
+    FS_HIP(c, hipSetDevice(c->device));
+    return alloc_enqueue(c, n_robots, n_tasks, d_cost, d_distance, method, d_assignment, d_total_cost, nullptr, d_rank, d_modified_cost, d_status);
+}
+
+int fs_allocate_tasks(fs_ctx *c, int32_t n_robots, int32_t n_tasks, const double *cost, const double *distance, int32_t method,
+                      int32_t *assignment, double *total_cost, int32_t *rank, double *modified_cost)
+{
+    if (!c) return FS_E_INVALID;
+    int rc = alloc_check(c, n_robots, n_tasks, method);
+    if (rc) return rc;
+    if (!cost || !assignment || !total_cost) return fail(c, FS_E_INVALID, "null pointer");
+    const bool minpos = method == FS_ALLOC_MINPOS;
+    if (minpos && !distance) return fail(c, FS_E_INVALID, "FS_ALLOC_MINPOS needs the distance matrix");
+    FS_HIP(c, hipSetDevice(c->device));
+    const size_t R = (size_t)n_robots, rn = R * (size_t)n_tasks;
+    // in: cost | distance;  out: header | MinPos' matrix | MinPos' P
+    const size_t total_in = 8 * rn * (minpos ? 2 : 1), o_mod = kAllocHeader, o_rank = o_mod + 8 * rn, total_out = o_rank + 4 * rn;
+    const bool want_matrices = minpos && (rank || modified_cost);
+    FS_HIP(c, c->h_al_in.ensure(total_in)); FS_HIP(c, c->d_al_in.ensure(total_in));
+    FS_HIP(c, c->h_al_out.ensure(total_out)); FS_HIP(c, c->d_al_out.ensure(total_out));
+    std::memcpy(c->h_al_in.p, cost, 8 * rn);
+    if (minpos) std::memcpy(c->h_al_in.p + 8 * rn, distance, 8 * rn);
+    FS_HIP(c, hipMemcpyAsync(c->d_al_in.p, c->h_al_in.p, total_in, hipMemcpyHostToDevice, c->stream));
+    AllocHeader *dh = reinterpret_cast<AllocHeader *>(c->d_al_out.p);
+    rc = alloc_enqueue(c, n_robots, n_tasks, reinterpret_cast<const double *>(c->d_al_in.p), reinterpret_cast<const double *>(c->d_al_in.p + 8 * rn),
+                       method, dh->assignment, &dh->total, nullptr, reinterpret_cast<int32_t *>(c->d_al_out.p + o_rank),
+                       reinterpret_cast<double *>(c->d_al_out.p + o_mod), &dh->status);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    FS_HIP(c, hipMemcpyAsync(c->h_al_out.p, c->d_al_out.p, want_matrices ? total_out : kAllocHeader, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    const AllocHeader *h = reinterpret_cast<const AllocHeader *>(c->h_al_out.p);
+    rc = alloc_status(c, h->status, n_robots, n_tasks);
+    if (rc) return rc;
+    std::memcpy(assignment, h->assignment, 4 * R);
+    *total_cost = h->total;
+    if (minpos && rank) std::memcpy(rank, c->h_al_out.p + o_rank, 4 * rn);
+    if (minpos && modified_cost) std::memcpy(modified_cost, c->h_al_out.p + o_mod, 8 * rn);
+    return FS_OK;
+}
+
+int fs_fleet_allocate_roadmap(fs_ctx *c, int32_t n_robots, const double *robot_pose7, int32_t n, const double *goal_xyz,
+                              const int32_t *frontier_size, const uint8_t *blacklisted, double alpha, double beta, double max_vx, double max_wz,
+                              int32_t method, int32_t *assignment, double *total_cost, double *assigned_cost, fs_record *records,
+                              double *weighted_cost, double *path_length_m, uint8_t *achievable)
+{
+    if (!c) return FS_E_INVALID;
+    int rc = alloc_check(c, n_robots, n, method);
+    if (rc) return rc;
+    if (!robot_pose7 || !goal_xyz || !assignment || !total_cost || !assigned_cost) return fail(c, FS_E_INVALID, "null pointer");
+    FS_HIP(c, hipSetDevice(c->device));
+    rc = check_scoring_state(c, true, false);
+    if (rc) return rc;
+    const int32_t R = n_robots, nodes = rm_nodes(c);
+    const size_t nn = (size_t)n, rn = (size_t)R * nn, pad_n = (nn + 15) & ~(size_t)15, pad_rn = (rn + 15) & ~(size_t)15, nnodes = (size_t)nodes;
+    const bool reference = c->rm_search == FS_ROADMAP_SEARCH_REFERENCE;
+    // in: goal xy | headings [R][n] | plan descriptors [R] | goal xyz | frontier size | blacklist | modes [R][n]
+    const size_t i_goal2 = 0, i_head = i_goal2 + 16 * nn, i_desc = i_head + 8 * rn, i_goal3 = (i_desc + sizeof(FsRmPlanArgs) * (size_t)R + 15) & ~(size_t)15;
+    const size_t i_fsize = i_goal3 + 24 * nn, i_black = (i_fsize + 4 * nn + 15) & ~(size_t)15, i_mode = i_black + pad_n, total_in = i_mode + pad_rn;
+    // out: header | records | cost [R][n] | length in m [R][n] | achievable [R][n];  scratch: path length | heading, [R][n] each
+    const size_t o_rec = kAllocHeader, o_cost = o_rec + sizeof(fs_record) * nn, o_lenm = o_cost + 8 * rn, o_ach = o_lenm + 8 * rn, total_out = o_ach + pad_rn;
+    FS_HIP(c, c->h_fl_in.ensure(total_in)); FS_HIP(c, c->d_fl_in.ensure(total_in));
+    FS_HIP(c, c->h_fl_out.ensure(total_out)); FS_HIP(c, c->d_fl_out.ensure(total_out)); FS_HIP(c, c->d_fl_plan.ensure(16 * rn));
+    char *h = c->h_fl_in.p;
+    double *goal2 = reinterpret_cast<double *>(h + i_goal2), *head = reinterpret_cast<double *>(h + i_head);
+    uint8_t *mode = reinterpret_cast<uint8_t *>(h + i_mode);
+    std::memcpy(h + i_goal3, goal_xyz, 24 * nn);
+    if (frontier_size) std::memcpy(h + i_fsize, frontier_size, 4 * nn); else std::memset(h + i_fsize, 0, 4 * nn);
+    if (blacklisted) std::memcpy(h + i_black, blacklisted, nn); else std::memset(h + i_black, 0, nn);
+    for (size_t i = 0; i < nn; ++i) { goal2[2 * i] = goal_xyz[3 * i]; goal2[2 * i + 1] = goal_xyz[3 * i + 1]; }
+    // every robot's start node, modes and headings as roadmap_plan_enqueue takes them; a tree per distinct start node that a robot
+    // with a goal to search stands at
+    std::vector<int32_t> root((size_t)R), tree((size_t)R, -1), roots;
+    for (int32_t r = 0; r < R; ++r) {
+        const double *pose = robot_pose7 + 7 * (size_t)r;
+        bool need_tree = false;
+        for (size_t i = 0; i < nn; ++i) {
+            const double gx = goal2[2 * i], gy = goal2[2 * i + 1];
+            const uint8_t m = (pose[0] == gx && pose[1] == gy) ? 1 : 2;
+            mode[(size_t)r * nn + i] = m;
+            head[(size_t)r * nn + i] = nav_heading(pose, gx, gy);
+            need_tree |= m == 2;
+        }
+        root[(size_t)r] = fs_rm_closest(c->rm_xy.data(), c->rm_key.data(), nodes, c->rm_cell, pose[0], pose[1]);
+        if (reference || !need_tree || root[(size_t)r] < 0) continue;
+        size_t b = 0;
+        while (b < roots.size() && roots[b] != root[(size_t)r]) ++b;
+        if (b == roots.size()) roots.push_back(root[(size_t)r]);
+        tree[(size_t)r] = (int32_t)b;
+    }
+    const int32_t K = (int32_t)roots.size();
+    char *din = c->d_fl_in.p, *dout = c->d_fl_out.p;
+    double *d_len = reinterpret_cast<double *>(c->d_fl_plan.p), *d_head = d_len + rn;
+    double *d_cost = reinterpret_cast<double *>(dout + o_cost), *d_lenm = reinterpret_cast<double *>(dout + o_lenm);
+    uint8_t *d_ach = reinterpret_cast<uint8_t *>(dout + o_ach);
+    if (K > 0) {
+        rc = rm_device_graph(c);
+        if (rc) return rc;
+        FS_HIP(c, c->d_fl_d.ensure(2 * nnodes * K)); FS_HIP(c, c->d_fl_hops.ensure(2 * nnodes * K)); FS_HIP(c, c->d_fl_pred.ensure(2 * nnodes * K));
+        FS_HIP(c, c->d_fl_word.ensure((size_t)std::max<int32_t>(PLAN_BATCH, FS_ALLOC_MAX_ROBOTS)));
+    }
+    FsRmPlanArgs *desc = reinterpret_cast<FsRmPlanArgs *>(h + i_desc);
+    for (int32_t r = 0; r < R; ++r) {
+        FsRmPlanArgs a{};
+        const size_t o = (size_t)r * nn;
+        a.n_nodes = nodes; a.xy = c->d_rm_xy.p; a.key = c->d_rm_key.p; a.cell = c->rm_cell; a.root = root[(size_t)r];
+        if (tree[(size_t)r] >= 0) {       // (after its quiet round both buffers of a tree hold it: buffer 0 is read)
+            a.d = c->d_fl_d.p + 2 * nnodes * (size_t)tree[(size_t)r];
+            a.pred = c->d_fl_pred.p + 2 * nnodes * (size_t)tree[(size_t)r];
+        }
+        a.n = n;
+        a.goal = reinterpret_cast<const double *>(din + i_goal2);
+        a.heading_in = reinterpret_cast<const double *>(din + i_head) + o;
+        a.mode = reinterpret_cast<const uint8_t *>(din + i_mode) + o;
+        a.path_length = d_len + o; a.path_length_m = d_lenm + o; a.path_heading = d_head + o; a.achievable = d_ach + o;
+        desc[r] = a;
+    }
+    FS_HIP(c, hipMemcpyAsync(din, h, total_in, hipMemcpyHostToDevice, c->stream));
+    // ---- the plans
+    bool block_route = false;
+    if (reference) {
+        // the A* queries robot by robot through the single-robot path (its buffers are one robot's), each settled before the next;
+        // the four columns move into the robot's rows on the device
+        const PlanOutLayout O(nn);
+        for (int32_t r = 0; r < R; ++r) {
+            const size_t o = (size_t)r * nn;
+            rc = roadmap_plan_enqueue(c, robot_pose7 + 7 * (size_t)r, n, goal_xyz, nullptr);
+            if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+            FS_HIP(c, hipStreamSynchronize(c->stream));
+            bool redone = false;
+            rc = rm_astar_settle(c, [&] { return roadmap_astar_cols(c); }, &redone);
+            if (rc) return rc;
+            const char *src = c->d_rm_out.p;
+            FS_HIP(c, hipMemcpyAsync(d_len + o, src + O.len, 8 * nn, hipMemcpyDeviceToDevice, c->stream));
+            FS_HIP(c, hipMemcpyAsync(d_lenm + o, src + O.len_m, 8 * nn, hipMemcpyDeviceToDevice, c->stream));
+            FS_HIP(c, hipMemcpyAsync(d_head + o, src + O.head, 8 * nn, hipMemcpyDeviceToDevice, c->stream));
+            FS_HIP(c, hipMemcpyAsync(d_ach + o, src + O.ach, nn, hipMemcpyDeviceToDevice, c->stream));
+        }
+    } else {
+        // the trees in batches of RM_TOUR_MAX_TREES, with the fleet's own buffers (the single-robot tree cache is neither read nor replaced)
+        const int64_t max_rounds = 2 * (int64_t)nodes + 2;        // as rm_tree
+        block_route = nodes <= c->tour_one_wg;
+        for (int32_t k0 = 0; k0 < K; k0 += RM_TOUR_MAX_TREES) {
+            FsRmTreeBatch B{};
+            const size_t o = 2 * nnodes * (size_t)k0;
+            B.t = FsRmTree{nodes, -1, c->d_rm_xy.p, c->d_rm_trow.p, c->d_rm_tcol.p, {c->d_fl_d.p + o, nullptr}, {c->d_fl_hops.p + o, nullptr},
+                           {c->d_fl_pred.p + o, nullptr}};
+            B.k = std::min<int32_t>(RM_TOUR_MAX_TREES, K - k0);
+            for (int32_t b = 0; b < B.k; ++b) B.root[b] = roots[(size_t)(k0 + b)];
+            FS_HIP(c, fs_launch_rm_batch_init(B, c->stream));
+            if (block_route) {
+                FS_HIP(c, fs_launch_rm_batch_block(B, (int32_t)max_rounds, c->d_fl_word.p + k0, c->stream));
+            } else {
+                const auto launch = [&](int64_t r0, int count) -> int {
+                    for (int k = 0; k < count; ++k) FS_HIP(c, fs_launch_rm_batch_round(B, (int32_t)((r0 + k) & 1), c->d_fl_word.p + k, c->stream));
+                    return FS_OK;
+                };
+                int64_t rounds = 0;
+                rc = poll_rounds(c, c->d_fl_word.p, PLAN_BATCH, PLAN_BATCH, 1, max_rounds, "the fleet's trees", max_rounds, launch, &rounds);
+                if (rc) return rc;
+            }
+        }
+        FS_HIP(c, fs_launch_rm_fleet_plan(reinterpret_cast<const FsRmPlanArgs *>(din + i_desc), R, n, c->stream));
+    }
+    // ---- arrival information, once for the list (achievable_in = all), then every robot's U1 row and the solve where the rows lie
+    AllocHeader *dh = reinterpret_cast<AllocHeader *>(dout);
+    const uint8_t *d_black = reinterpret_cast<const uint8_t *>(din + i_black);
+    fs_record *d_rec = reinterpret_cast<fs_record *>(dout + o_rec);
+    rc = arrival_records_dev(c, n, reinterpret_cast<const double *>(din + i_goal3), reinterpret_cast<const int32_t *>(din + i_fsize), d_black,
+                             nullptr, d_rec);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    FS_HIP(c, hipMemsetAsync(&dh->err, 0, sizeof(int32_t), c->stream));
+    FS_HIP(c, fs_launch_fleet_costs(R, n, d_rec, d_black, d_ach, d_len, d_head, alpha, beta, max_vx, max_wz, c->max_gt, d_cost, &dh->err, c->stream));
+    rc = alloc_enqueue(c, R, n, d_cost, d_lenm, method, dh->assignment, &dh->total, dh->assigned, nullptr, nullptr, &dh->status);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    // one transfer out: the header, the records behind it if asked for, the matrices behind those if asked for
+    const size_t bytes_out = (weighted_cost || path_length_m || achievable) ? total_out : records ? o_cost : kAllocHeader;
+    FS_HIP(c, hipMemcpyAsync(c->h_fl_out.p, dout, bytes_out, hipMemcpyDeviceToHost, c->stream));
+    int32_t rounds_h[FS_ALLOC_MAX_ROBOTS];
+    if (block_route && K > 0) FS_HIP(c, hipMemcpyAsync(rounds_h, c->d_fl_word.p, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    if (block_route)
+        for (int32_t b = 0; b < K; ++b)
+            if (rounds_h[b] < 0) return fail(c, FS_E_HIP, "a tree of the fleet did not settle in %lld rounds", (long long)(2 * (int64_t)nodes + 2));
+    const char *ho = c->h_fl_out.p;
+    const AllocHeader *hh = reinterpret_cast<const AllocHeader *>(ho);
+    if (hh->err) return fail(c, FS_E_RANGE, "utility outside [0,1] (the reference throws: FrontierCostsManager.cpp:148-149,173-174)");
+    rc = alloc_status(c, hh->status, R, n);
+    if (rc) return rc;
+    std::memcpy(assignment, hh->assignment, 4 * (size_t)R);
+    std::memcpy(assigned_cost, hh->assigned, 8 * (size_t)R);
+    *total_cost = hh->total;
+    if (records) std::memcpy(records, ho + o_rec, sizeof(fs_record) * nn);
+    if (weighted_cost) std::memcpy(weighted_cost, ho + o_cost, 8 * rn);
+    if (path_length_m) std::memcpy(path_length_m, ho + o_lenm, 8 * rn);
+    if (achievable) std::memcpy(achievable, ho + o_ach, rn);
     return FS_OK;
 }
 

@@ -304,6 +304,8 @@ struct FsRmPlanArgs {
     uint8_t *achievable;
 };
 hipError_t fs_launch_rm_plan(const FsRmPlanArgs &a, hipStream_t s);
+// R plans in one launch (fs_fleet_allocate_roadmap): d_robots [n_robots] in device memory, each with n frontiers
+hipError_t fs_launch_rm_fleet_plan(const FsRmPlanArgs *d_robots, int32_t n_robots, int32_t n, hipStream_t s);
 
 // ---- the REFERENCE roadmap search: FrontierRoadmapAStar::getPlan per distinct (start, goal) pair, one wave per
 // query (fs_roadmap_astar.h).  A query's heap, records and per-node state sit in LDS while they fit (lds_cap records); a query that
@@ -696,6 +698,28 @@ extern "C" int fs_score_arrival_end(fs_ctx *c);
 extern "C" int fs_score_fim_begin(fs_ctx *c, int32_t n, const double *pose7, float *info_ref, float *fim21, float *trace, float *logdet,
                                   int32_t *n_visible, int32_t *n_voxels);
 extern "C" int fs_score_fim_end(fs_ctx *c);
+
+// ---- multi-robot task allocation (fs_allocate.hip): MinPos and Munkres in one launch of one workgroup
+struct FsAllocArgs {
+    int32_t n_robots, n_tasks, method;
+    const double *cost;               // [R][n] row-major
+    const double *distance;           // [R][n] (MINPOS)
+    int32_t *rank;                    // [R][n] MinPos' P, or nullptr
+    double *modified;                 // [R][n] MinPos' matrix (MINPOS: never nullptr — the solve reads it)
+    double *work;                     // [R][n] the working copy
+    int32_t *assignment;              // [R]
+    double *total_cost;               // [1]
+    double *assigned_cost;            // [R] cost[r][assignment[r]] (NaN for -1), or nullptr
+    int32_t *status;                  // [1] FS_OK / FS_E_INVALID (an entry refused: nothing else written) / FS_E_RANGE (step 5's cap)
+    int32_t *stats;                   // [3] augmentations, step-5 runs, step-3 primes
+};
+hipError_t fs_launch_allocate(const FsAllocArgs &a, hipStream_t s);
+// the fleet's R x n cost matrix (fs_rank.hip, beside u1_cost): row r from robot r's plan columns at + r * n, one workgroup per
+// robot — normalisation over that robot's live set, then the U1 cost.  d_ach [R][n]: the plan's achievability in, AND the
+// record's achievable flag out (what the robot's own record carries).  err: |= 1 where a utility leaves [0, 1]
+hipError_t fs_launch_fleet_costs(int32_t n_robots, int32_t n, const fs_record *d_records, const uint8_t *d_black, uint8_t *d_ach,
+                                 const double *d_len, const double *d_head, double alpha, double beta, double max_vx, double max_wz,
+                                 double max_gt, double *d_cost, int32_t *d_err, hipStream_t s);
 
 // pieces of fs_multi_get_frontier_costs (defined in fs_capi.hip, sequenced by fs_multi.hip)
 hipStream_t fs_ctx_stream(fs_ctx *c);

@@ -192,7 +192,59 @@ void fs_rank_small_kernel(int32_t n, const fs_record *rec, const uint8_t *black,
     if (i == 0) *err = s_err;
 }
 
+// The fleet's cost matrix (fs_fleet_allocate_roadmap): workgroup r is robot r.  The records were scored once for
+// the list (achievable_in = all: their flag is what the scoring itself found); robot r's live set is what its own fs_get_frontier_costs_roadmap ranks — not blacklisted, record
+// achievable, r's plan achievable — and its normalisation factors and U1 costs are taken over that set exactly as the kernels
+// above take them (min / max are exact in any order, u1_cost is the one definition), so row r carries that call's bits.
+#define FS_FLEET_THREADS 256
+__global__ __launch_bounds__(FS_FLEET_THREADS)
+void fs_fleet_cost_kernel(int32_t n, const fs_record *rec, const uint8_t *black, uint8_t *ach, const double *len,
+                          const double *head, double alpha, double beta, double max_vx, double max_wz, double max_gt,
+                          double *cost, int32_t *err)
+{
+    __shared__ double s_min_d[FS_FLEET_THREADS / 64], s_max_d[FS_FLEET_THREADS / 64], s_min_i[FS_FLEET_THREADS / 64];
+    const size_t o = (size_t)blockIdx.x * (size_t)n;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double min_d = FS_DBL_MAX, max_d = -1.0, min_i = FS_DBL_MAX;
+    for (int i = threadIdx.x; i < n; i += FS_FLEET_THREADS) {
+        if ((black && black[i]) || !(rec[i].flags & FS_FLAG_ACHIEVABLE) || !ach[o + i]) continue;
+        const double l = len[o + i], a = (double)rec[i].arrival;
+        min_d = (l < min_d) ? l : min_d;
+        max_d = (max_d < l) ? l : max_d;
+        min_i = (a < min_i) ? a : min_i;
+    }
+    min_d = wave_min(min_d); max_d = wave_max(max_d); min_i = wave_min(min_i);
+    if (lane == 0) { s_min_d[wave] = min_d; s_max_d[wave] = max_d; s_min_i[wave] = min_i; }
+    __syncthreads();
+    for (int w = 0; w < FS_FLEET_THREADS / 64; ++w) {
+        min_d = (s_min_d[w] < min_d) ? s_min_d[w] : min_d;
+        max_d = (max_d < s_max_d[w]) ? s_max_d[w] : max_d;
+        min_i = (s_min_i[w] < min_i) ? s_min_i[w] : min_i;
+    }
+    for (int i = threadIdx.x; i < n; i += FS_FLEET_THREADS) {
+        // the robot's own record would carry "its plan achievable AND what the scoring found" (footprint, min_gt): that is the
+        // achievable column of the row, blacklisted or not
+        const bool reach = (rec[i].flags & FS_FLAG_ACHIEVABLE) && ach[o + i];
+        const bool live = !(black && black[i]) && reach;
+        ach[o + i] = reach ? 1 : 0;
+        double c, au, pu;
+        if (u1_cost(live, (double)rec[i].arrival, live ? len[o + i] : 0.0, live ? head[o + i] : 0.0, max_d, min_d, min_i,
+                    alpha, beta, max_vx, max_wz, max_gt, c, au, pu))
+            atomicOr(err, 1);
+        cost[o + i] = c;
+    }
+}
+
 }  // namespace
+
+hipError_t fs_launch_fleet_costs(int32_t n_robots, int32_t n, const fs_record *d_records, const uint8_t *d_black, uint8_t *d_ach,
+                                 const double *d_len, const double *d_head, double alpha, double beta, double max_vx, double max_wz,
+                                 double max_gt, double *d_cost, int32_t *d_err, hipStream_t s)
+{
+    hipLaunchKernelGGL(fs_fleet_cost_kernel, dim3((unsigned)n_robots), dim3(FS_FLEET_THREADS), 0, s, n, d_records, d_black, d_ach, d_len,
+                       d_head, alpha, beta, max_vx, max_wz, max_gt, d_cost, d_err);
+    return hipGetLastError();
+}
 
 hipError_t fs_launch_rank(int32_t n, const fs_record *d_records, const uint8_t *d_black,
                           const double *d_len, const double *d_head, double alpha, double beta,

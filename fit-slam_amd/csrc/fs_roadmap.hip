@@ -204,10 +204,8 @@ __global__ __launch_bounds__(256) void rm_tree_round_kernel(FsRmTree t, int32_t 
 
 // setPlanForFrontierRoadmap, one lane per frontier: the goal's closest key node, then the tree's predecessors back to the root,
 // the segment lengths summed from the goal end as astar.cpp:57-63 does
-__global__ void rm_plan_kernel(const FsRmPlanArgs a)
+__device__ __forceinline__ void plan_frontier(const FsRmPlanArgs &a, int32_t f)
 {
-    const int32_t f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= a.n) return;
     const double dmax = DBL_MAX;
     double len = dmax, head = dmax;
     uint8_t ok = 0;
@@ -230,6 +228,21 @@ __global__ void rm_plan_kernel(const FsRmPlanArgs a)
     a.path_length_m[f] = len;
     a.path_heading[f] = head;
     a.achievable[f] = ok;
+}
+
+__global__ void rm_plan_kernel(const FsRmPlanArgs a)
+{
+    const int32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < a.n) plan_frontier(a, f);
+}
+
+// the fleet's plan (fs_fleet_allocate_roadmap): blockIdx.y is the robot, robots[r] its own plan — its tree, root,
+// modes, headings and its row of the four columns; the goals are shared
+__global__ void rm_fleet_plan_kernel(const FsRmPlanArgs *__restrict__ robots)
+{
+    const FsRmPlanArgs a = robots[blockIdx.y];
+    const int32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < a.n) plan_frontier(a, f);
 }
 
 
@@ -486,6 +499,13 @@ hipError_t fs_launch_rm_plan(const FsRmPlanArgs &a, hipStream_t s)
 {
     if (a.n <= 0) return hipSuccess;
     hipLaunchKernelGGL(rm_plan_kernel, dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_rm_fleet_plan(const FsRmPlanArgs *d_robots, int32_t n_robots, int32_t n, hipStream_t s)
+{
+    if (n <= 0 || n_robots <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rm_fleet_plan_kernel, dim3((unsigned)((n + 63) / 64), (unsigned)n_robots), dim3(64), 0, s, d_robots);
     return hipGetLastError();
 }
 

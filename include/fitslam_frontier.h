@@ -677,6 +677,66 @@ int fs_refine_paths(fs_ctx *ctx, int32_t n, const double *start_xy, const double
 int fs_refine_field(fs_ctx *ctx, const double start_xy[2], int32_t allow_unknown, double w_euc, double w_traversal, int32_t corners,
                     double *g);
 
+/* ---------------------------------------------------------------- multi-robot task allocation (TaskAllocator) */
+/* The reference's shared TaskAllocator (DEPX/frontier_multirobot_allocator: taskAllocator.cpp:7-66, minPos/minPos.cpp:20-44,88-98,
+ * hungarian/Hungarian.cpp:25-395), which ProcessFrontierCostsBT feeds with every robot's cost and distance rows
+ * (DEP/src/ExplorationBT.cpp:418) and GetAllocatedGoalBT solves (:842-859).  cost and distance are [n_robots][n_tasks] row-major,
+ * robot-major as addRobotTasks pushes the rows.
+ * FS_ALLOC_HUNGARIAN: HungarianAlgorithm::Solve on cost.  FS_ALLOC_MINPOS: P[i][j] = robots k != i with distance[k][j] <
+ * distance[i][j] (strict), the modified matrix = cost where P == 0 and DBL_MAX elsewhere, Solve on the modified matrix.
+ * Semantics are the reference's bit for bit: Buehren's Munkres with its scan orders — rows (n_robots <= n_tasks) or columns reduced
+ * by their minimum, greedy stars in ascending order, step 3's passes over the columns in ascending order (first uncovered zero row of
+ * each uncovered column; a column uncovered to the right is still visited in the same pass), step 4's path on the stars as they were,
+ * step 5's h = smallest uncovered entry, added to every covered row and THEN subtracted from every uncovered column — and its zero
+ * test fabs(x) < DBL_EPSILON everywhere.  assignment [n_robots]: the robot's task, -1 = none (more robots than tasks).  total_cost:
+ * the assigned entries of the matrix that was solved (the modified one under MINPOS) summed in ascending robot order; +inf when two
+ * of them are DBL_MAX, as in the reference.  rank, modified_cost [n_robots][n_tasks] (may be NULL; written under MINPOS only):
+ * P and the modified matrix.
+ * One workgroup runs the whole solve in one launch; one transfer each way and one synchronisation.
+ * Limits and deliberate deviations from the reference, each FS_E_INVALID with nothing written:
+ *   - n_robots outside 1..FS_ALLOC_MAX_ROBOTS, n_tasks outside 1..FS_ALLOC_MAX_TASKS (the reference has no limit; an empty matrix
+ *     is undefined behaviour there);
+ *   - an entry of cost (or, under MINPOS, of distance) that is NaN or +-inf (the reference would compute inf - inf); DBL_MAX is
+ *     allowed — it is what U1 gives a dead frontier and what MinPos writes;
+ *   - a negative entry (the reference prints a warning and goes on);
+ *   - FS_ALLOC_MINPOS without distance (the reference's allocator always holds both matrices).
+ * FS_E_RANGE: step 5 ran more than (n_robots + 1) * (min(n_robots, n_tasks) + 1) times — in exact arithmetic every run leads to a
+ * row cover or an augmentation, which bounds the count by that product; the reference would loop on.  Nothing written.
+ * Counters 1030-1032 (fs_get_counter): augmentations, step-5 runs, step-3 primes of the last solve. */
+#define FS_ALLOC_HUNGARIAN 0   /* TaskAllocator::solveAllocationHungarian */
+#define FS_ALLOC_MINPOS    1   /* TaskAllocator::solveAllocationMinPos    */
+#define FS_ALLOC_MAX_ROBOTS 64
+#define FS_ALLOC_MAX_TASKS  4096
+int fs_allocate_tasks(fs_ctx *ctx, int32_t n_robots, int32_t n_tasks, const double *cost, const double *distance, int32_t method,
+                      int32_t *assignment, double *total_cost, int32_t *rank, double *modified_cost);
+/* The same with device pointers, enqueued on the context's stream and not waited for.  d_status [1]: FS_OK, FS_E_INVALID (an entry
+ * refused) or FS_E_RANGE as above, with nothing else written unless FS_OK — read it together with the results.  The argument
+ * checks (sizes, method, null pointers, MINPOS without d_distance) are made on the host and returned. */
+int fs_allocate_tasks_dev(fs_ctx *ctx, int32_t n_robots, int32_t n_tasks, const double *d_cost, const double *d_distance, int32_t method,
+                          int32_t *d_assignment, double *d_total_cost, int32_t *d_rank, double *d_modified_cost, int32_t *d_status);
+/* One exploration tick of a fleet on one shared map: the cost and distance rows of n_robots robots at robot_pose7 [n_robots][7]
+ * for the n frontiers, and the allocation on them, in one call.  Row r of weighted_cost, path_length_m and achievable
+ * [n_robots][n] (each may be NULL) is, bit for bit, what fs_get_frontier_costs_roadmap(ctx, robot_pose7[r], ...,
+ * with_fisher_information = 0, ...) gives that robot — weighted_cost, path_length_m and its records' achievable flag — under the
+ * context's roadmap search (fs_set_roadmap_search), TREE or REFERENCE; assignment [n_robots] and total_cost are fs_allocate_tasks
+ * on those rows with distance = path_length_m (the response's frontier_distances from getPathLengthInM, DEP/src/CostAssigner.cpp:96).
+ * assigned_cost [n_robots]: weighted_cost[r][assignment[r]] — DBL_MAX = a dead frontier was assigned, NaN for -1.  records [n] (may
+ * be NULL): the arrival records of the list, scored ONCE with achievable_in = all (a robot's own call also clears the achievable flag
+ * where its plan fails — achievable[r] is that flag; nothing else differs).
+ * On the device: arrival information once for the list; one shortest-path tree per DISTINCT start node (robots that share a
+ * closest key node share a tree) in batched launches of up to 13 trees, in buffers of the call's own — the single-robot tree cache
+ * is neither read nor replaced; one plan launch over n_robots x n; per robot the normalisation over ITS live set (not blacklisted,
+ * record achievable, its plan achievable) and the U1 cost; MinPos and the solve on the matrix where it lies.  One transfer in, one
+ * out, one synchronisation; the matrices visit the host only when asked for.  Under FS_ROADMAP_SEARCH_REFERENCE the A* queries are
+ * enqueued and settled robot by robot (one synchronisation per robot).  A robot without a start node gets a DBL_MAX row, which the
+ * solve takes as the reference would.  n_robots > n is allowed: some robots get -1.
+ * FS_E_INVALID: fs_allocate_tasks' limits on n_robots and n (n = 0 included) and method.  FS_E_RANGE: U1 out of bounds for any
+ * robot, as in fs_get_frontier_costs, or the solve's step-5 cap.  Otherwise refuses what fs_get_frontier_costs_roadmap refuses. */
+int fs_fleet_allocate_roadmap(fs_ctx *ctx, int32_t n_robots, const double *robot_pose7, int32_t n, const double *goal_xyz,
+                  const int32_t *frontier_size, const uint8_t *blacklisted, double alpha, double beta, double max_vx, double max_wz,
+                  int32_t method, int32_t *assignment, double *total_cost, double *assigned_cost, fs_record *records,
+                  double *weighted_cost, double *path_length_m, uint8_t *achievable);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,7 +86,10 @@ int  fs_set_option(fs_ctx *ctx, const char *key, double value);
  * walked / cells popped by the outer search of the last search with FS_SEEDS_REFERENCE (levels counted from 1 at the start cell;
  * the walk stops after the level in which the last component is first met, so 1020 is at most the expanded region's size);
  * 1021 = A* queries the REFERENCE roadmap search ran (one per distinct (start, goal) node pair of a call), 1022 = records popped by
- * the largest query of the last such call, 1023 = queries that took the global route (1021 and 1023 are reset by `reset`). */
+ * the largest query of the last such call, 1023 = queries that took the global route (1021 and 1023 are reset by `reset`);
+ * 1030 / 1031 / 1032 = augmentations (step 4), step-5 runs and step-3 primes of the last task allocation solve (the allocator
+ * of fitslam_frontier.h; they stay on the device until asked for, so reading them waits for the context's stream; 1031 is at most
+ * (R + 1) * (min(R, n) + 1)). */
 int  fs_get_counter(fs_ctx *ctx, int which, int64_t *value, int reset);
 
 /* ---------------------------------------------------------------- self test */

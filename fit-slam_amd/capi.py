@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "fs_roadmap_set_keyframes", "fs_roadmap_optimize", "fs_roadmap_get_anchors",
     "fs_search_frontiers", "fs_get_frontier_costs_searched", "fs_set_frontier_seed_order", "fs_set_roadmap_search",
     "fs_roadmap_routes",
+    "fs_roadmap_update", "fs_get_frontier_costs_searched_roadmap",
     "fs_allocate_tasks", "fs_allocate_tasks_dev", "fs_fleet_allocate_roadmap",
 ]
 
@@ -188,6 +189,9 @@ def load_library(build: bool = True):
     L.fs_roadmap_add_nodes.argtypes = [vp, i32, vp, i32]
     L.fs_roadmap_rebuild.argtypes = [vp]
     L.fs_roadmap_connect.argtypes = [vp, i32, vp]
+    L.fs_roadmap_update.argtypes = [vp, i32, vp, C.POINTER(dbl * 2), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
+    L.fs_get_frontier_costs_searched_roadmap.argtypes = [vp, C.POINTER(dbl * 7), i32, dbl, i32, i32, i32, i32, vp, dbl, dbl, dbl, dbl, C.c_int,
+                                                         i32, vp, C.POINTER(i32), vp, vp, vp, vp, vp, vp]
     L.fs_roadmap_get_graph.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), vp, vp, vp, vp]
     L.fs_roadmap_plan.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, vp, vp, vp, vp]
     L.fs_get_frontier_costs_roadmap.argtypes = [vp, C.POINTER(dbl * 7), i32, vp, vp, vp, dbl, dbl, dbl, dbl, C.c_int, vp, vp, vp, vp, vp, vp]
@@ -445,6 +449,39 @@ class FrontierScorer:
             self._check(rc)
             break
         k = n.value
+        return fr[:k].copy(), dict(records=rec[:k].copy(), weighted_cost=cost[:k].copy(), arrival_utility=au[:k].copy(),
+                                   distance_utility=du[:k].copy(), order=order[:k].copy(), path_length_m=plm[:k].copy())
+
+    def get_frontier_costs_searched_roadmap(self, robot_pose7, lethal_threshold=160, max_frontier_distance=50.0, min_frontier_cluster_size=1,
+                                            max_frontier_cluster_size=20, blacklist_xy=None, add_robot_pose=True, with_fim=False,
+                                            alpha=0.25, beta=1.0, max_vx=0.5, max_wz=0.5, max_records=None, seed_order=None, search=None):
+        """The default planner's tick in one call (fs_get_frontier_costs_searched_roadmap): search -> roadmap_update -> roadmap plan ->
+        score -> rank.  Returns (frontiers, the dict get_frontier_costs_roadmap returns).  max_records None: as many as the search finds (a list longer than the first
+        round holds is refused before the roadmap is touched, and searched again).  seed_order as search_frontiers', search as roadmap_plan's.  A cell overfilled by the update
+        raises FsError(FS_E_RANGE); self.last_searched_frontiers then holds the frontier records."""
+        _, ny, nx = self._staged_shape()
+        cap = min(nx * ny, self.SEARCH_FIRST_RECORDS) if max_records is None else int(max_records)
+        pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
+        bl = None if blacklist_xy is None else np.ascontiguousarray(np.asarray(blacklist_xy, dtype=np.float64).reshape(-1, 2))
+        with self._seed_order_for_call(seed_order), self._roadmap_search_for_call(search):
+            while True:
+                fr = np.zeros(max(cap, 0), dtype=FRONTIER_RECORD_DTYPE)
+                rec = np.zeros(max(cap, 0), dtype=RECORD_DTYPE)
+                cost = np.zeros(max(cap, 0)); au = np.zeros(max(cap, 0)); du = np.zeros(max(cap, 0))
+                order = np.zeros(max(cap, 0), dtype=np.int32); plm = np.zeros(max(cap, 0))
+                n = C.c_int32()
+                rc = self._L.fs_get_frontier_costs_searched_roadmap(self._h, C.byref(pose), int(lethal_threshold), float(max_frontier_distance),
+                                                                    int(min_frontier_cluster_size), int(max_frontier_cluster_size),
+                                                                    1 if add_robot_pose else 0, 0 if bl is None else bl.shape[0], _p(bl),
+                                                                    alpha, beta, max_vx, max_wz, 1 if with_fim else 0, cap, _p(fr), C.byref(n),
+                                                                    _p(rec), _p(cost), _p(au), _p(du), _p(order), _p(plm))
+                if rc == FS_E_INVALID and max_records is None and n.value > cap:      # (refused before the roadmap was touched)
+                    cap = n.value
+                    continue
+                break
+        k = min(n.value, cap)
+        self.last_searched_frontiers = fr[:k].copy()
+        self._check(rc)
         return fr[:k].copy(), dict(records=rec[:k].copy(), weighted_cost=cost[:k].copy(), arrival_utility=au[:k].copy(),
                                    distance_utility=du[:k].copy(), order=order[:k].copy(), path_length_m=plm[:k].copy())
 
@@ -721,6 +758,17 @@ class FrontierScorer:
         """constructNewEdges for the points xy [n][2] (append the robot pose for constructNewEdgeRobotPose)."""
         p = np.ascontiguousarray(np.asarray(xy, dtype=np.float64).reshape(-1, np.asarray(xy).shape[-1])[:, :2])
         self._check(self._L.fs_roadmap_connect(self._h, p.shape[0], _p(p)))
+
+    def roadmap_update(self, frontier_xy, robot_xy, add_robot_pose=True):
+        """UpdateRoadmapBT in one call, decided on the device (fs_roadmap_update): addNodes(frontier_xy), addRobotPoseAsNode(robot_xy) if
+        add_robot_pose, constructNewEdges(frontier_xy), constructNewEdgeRobotPose(robot_xy).  Returns dict(n_nodes_added, robot_added,
+        n_edges_added, n_walks).  A cell overfilled raises FsError(FS_E_RANGE) with the nodes up to the tripping one added."""
+        p = np.ascontiguousarray(np.asarray(frontier_xy, dtype=np.float64).reshape(-1, 2))
+        r = (C.c_double * 2)(*[float(v) for v in np.asarray(robot_xy, dtype=np.float64).reshape(-1)[:2]])
+        a, b, e = C.c_int32(), C.c_int32(), C.c_int64()
+        self._check(self._L.fs_roadmap_update(self._h, p.shape[0], _p(p), C.byref(r), 1 if add_robot_pose else 0, C.byref(a), C.byref(b),
+                                              C.byref(e)))
+        return dict(n_nodes_added=a.value, robot_added=bool(b.value), n_edges_added=e.value, n_walks=self.get_counter(1033))
 
     def roadmap_graph(self):
         """dict(xy [n][2], key [n], row_ptr [n + 1], col [n_edges]) of the roadmap as the context holds it."""

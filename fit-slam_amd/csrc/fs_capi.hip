@@ -402,6 +402,14 @@ struct fs_ctx {
     DevBuf<uint64_t> d_kf_cell_key, d_kf_hkey;
     DevBuf<uint8_t> d_kf_state;
     PinnedBuf h_kf;
+    // the per-tick update (fs_roadmap_update.hip): the extended node list and key flags, the points, the work arrays
+    // of FsRmUpdate, the result (header | kept positions | key flags | pairs) as the host reads it
+    int64_t ru_walks = 0, ru_owners = 0, ru_rounds = 0;     // the last update's walks, owners and keep rounds (counters 1033-1035)
+    DevBuf<double> d_ru_xy, d_ru_pts;
+    DevBuf<uint8_t> d_ru_key, d_ru_rejected;
+    DevBuf<uint64_t> d_ru_conf;
+    DevBuf<int32_t> d_ru_work, d_ru_rank_of, d_ru_cand;
+    PinnedBuf h_ru;
 
     // any-angle leg refinement (fs_refine.hip): a slab of rf_max_fields fp64 fields; slot s holds the field of
     // rf_key[s] for grid generation rf_gen[s] (0: empty).  Every staging call that writes the grid bumps grid_gen, which drops them.
@@ -1125,6 +1133,8 @@ void fs_ctx_destroy(fs_ctx *c)
     c->d_kf_rt.release(); c->d_kf_rec_p.release(); c->d_kf_pts.release(); c->d_kf_out.release(); c->d_kf_queue.release();
     c->d_kf_rec_h.release(); c->d_kf_rec_ord.release(); c->d_kf_tab.release(); c->d_kf_work.release(); c->d_kf_cand.release();
     c->d_kf_word.release(); c->d_kf_cell_key.release(); c->d_kf_hkey.release(); c->d_kf_state.release(); c->h_kf.release();
+    c->d_ru_xy.release(); c->d_ru_pts.release(); c->d_ru_key.release(); c->d_ru_rejected.release(); c->d_ru_conf.release();
+    c->d_ru_work.release(); c->d_ru_rank_of.release(); c->d_ru_cand.release(); c->h_ru.release();
     c->d_rf_g.release(); c->d_rf_flags.release(); c->d_rf_any.release(); c->d_rf_in.release(); c->d_rf_scratch.release();
     c->d_rf_out.release(); c->d_rf_pts.release(); c->h_rf_in.release(); c->h_rf_out.release(); c->h_rf_pts.release();
     c->d_al_in.release(); c->d_al_work.release(); c->d_al_out.release(); c->d_al_stats.release(); c->h_al_in.release(); c->h_al_out.release();
@@ -2085,6 +2095,8 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
         // the roadmap routes (fs_roadmap_routes): distinct routes of the last call, isConnectable walks of its refinement, distinct
         // leg poses it scored; calls that ran the A* again on a grown chain pool
         {1026, &fs_ctx::rt_routes, false}, {1027, &fs_ctx::rt_walks, false}, {1028, &fs_ctx::rt_poses, false}, {1029, &fs_ctx::rt_retries, true},
+        // the per-tick update (fs_roadmap_update): walks, owners (distinct closest nodes) and keep-rule rounds of the last call
+        {1033, &fs_ctx::ru_walks, false}, {1034, &fs_ctx::ru_owners, false}, {1035, &fs_ctx::ru_rounds, false},
     };
     // the task allocator (fs_allocate_tasks, fs_allocate_tasks_dev, fs_fleet_allocate_roadmap): augmentations, step-5 runs and
     // step-3 primes of the last solve.  The solve leaves them on the device (the device form is not waited for): read here
@@ -3599,9 +3611,8 @@ int rm_upload_nodes(fs_ctx *c, FsRoadmapDev &g, std::vector<uint64_t> &keys, std
     return FS_OK;
 }
 
-// the device's nodes, key flags and CSR for the current generation (uploaded from the host lists after a host-side mutation),
-// then its transpose
-int rm_device_graph(fs_ctx *c)
+// the device's nodes, key flags and CSR for the current generation (uploaded from the host lists after a host-side mutation) ...
+int rm_device_csr(fs_ctx *c)
 {
     const int32_t n = rm_nodes(c);
     if (c->rm_dev_gen != c->rm_gen) {
@@ -3616,6 +3627,15 @@ int rm_device_graph(fs_ctx *c)
         FS_HIP(c, hipStreamSynchronize(c->stream));
         c->rm_dev_gen = c->rm_gen;
     }
+    return FS_OK;
+}
+
+// ... then its transpose
+int rm_device_graph(fs_ctx *c)
+{
+    const int32_t n = rm_nodes(c);
+    const int rc = rm_device_csr(c);
+    if (rc) return rc;
     if (c->rm_t_gen != c->rm_gen) {
         size_t e = 0;
         for (const auto &l : c->rm_adj) e += l.size();
@@ -3884,6 +3904,112 @@ int kf_dedup_rounds(fs_ctx *c, const FsKfDedup &d, int64_t *rounds)
     return poll_rounds(c, c->d_kf_word.p, PLAN_BATCH, PLAN_BATCH, 1, max_rounds + 1, "the de-duplication", max_rounds, launch, rounds);
 }
 
+// UpdateRoadmapBT: the list at d_pts (device memory, point i at d_pts[stride * i]) and the robot pose, decided on
+// the device by fs_roadmap_update.hip and applied to the host mirror.  Two synchronisations: the sizes (header, candidate total),
+// then the result.  The caller has checked the grid and the input.
+struct RmUpdateOut {
+    int32_t kept = 0, robot = 0;
+    int64_t edges = 0;
+};
+
+int rm_update_core(fs_ctx *c, int32_t n, const double *d_pts, int32_t stride, const double robot_xy[2], bool add_robot, RmUpdateOut *out)
+{
+    const int32_t n_old = rm_nodes(c);
+    if (n > FS_RU_MAX_POINTS) return fail(c, FS_E_INVALID, "more than %d points in one roadmap update", FS_RU_MAX_POINTS);
+    if (n_old == 0 && n == 0 && !add_robot) return FS_OK;
+    if ((int64_t)n_old + n + 1 > (int64_t)INT32_MAX / 4) return fail(c, FS_E_RANGE, "too many roadmap nodes");
+    int rc = n_old > 0 ? rm_device_csr(c) : FS_OK;     // the nodes, key flags and lists of this generation (kept from the last plan)
+    if (rc) return rc;
+    const size_t nn = (size_t)n, m = nn + 1, cap = (size_t)n_old + m;
+    const int32_t words = (n + 63) / 64;
+    FS_HIP(c, c->d_ru_xy.ensure(2 * cap)); FS_HIP(c, c->d_ru_key.ensure(cap)); FS_HIP(c, c->d_ru_rank_of.ensure(cap));
+    FS_HIP(c, c->d_ru_rejected.ensure(nn)); FS_HIP(c, c->d_ru_conf.ensure(nn * (size_t)words));
+    // ints: occupants [n] | closest [m] | owner [m] | cand_count [m] | cand_off [m + 1] | hdr
+    const size_t o_closest = nn, o_owner = o_closest + m, o_count = o_owner + m, o_off = o_count + m, o_hdr = o_off + m + 1;
+    FS_HIP(c, c->d_ru_work.ensure(o_hdr + FS_RU_H_WORDS));
+    int32_t *w = c->d_ru_work.p;
+    if (n_old > 0) {
+        FS_HIP(c, hipMemcpyAsync(c->d_ru_xy.p, c->d_rm_xy.p, sizeof(double) * 2 * (size_t)n_old, hipMemcpyDeviceToDevice, c->stream));
+        FS_HIP(c, hipMemcpyAsync(c->d_ru_key.p, c->d_rm_key.p, (size_t)n_old, hipMemcpyDeviceToDevice, c->stream));
+    }
+    FS_HIP(c, hipMemsetAsync(c->d_ru_rank_of.p, 0x7f, sizeof(int32_t) * cap, c->stream));
+    FsRmUpdate u{};
+    u.n = n; u.pts = d_pts; u.stride = stride; u.rx = robot_xy[0]; u.ry = robot_xy[1]; u.add_robot = add_robot ? 1 : 0;
+    u.n_old = n_old; u.xy = c->d_ru_xy.p; u.key = c->d_ru_key.p; u.row = c->d_rm_row.p; u.col = c->d_rm_col.p;
+    u.cell = c->rm_cell; u.radius = c->rm_radius; u.min_frontier = c->rm_min_frontier; u.min_robot = c->rm_min_robot; u.oz = c->origin[2];
+    u.words = words; u.conf = c->d_ru_conf.p; u.rejected = c->d_ru_rejected.p; u.occupants = w; u.hdr = w + o_hdr;
+    u.closest = w + o_closest; u.rank_of = c->d_ru_rank_of.p; u.owner = w + o_owner; u.cand_count = w + o_count; u.cand_off = w + o_off;
+    FS_HIP(c, fs_launch_ru_nodes(u, c->stream));
+    FS_HIP(c, fs_launch_ru_owners(u, c->stream));
+    // the sizes: the candidate total (cand_off's last entry) and the header behind it
+    const size_t head_ints = 1 + FS_RU_H_WORDS;
+    FS_HIP(c, c->h_ru.ensure(sizeof(int32_t) * head_ints));
+    FS_HIP(c, hipMemcpyAsync(c->h_ru.p, w + o_off + m, sizeof(int32_t) * head_ints, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    int32_t head[1 + FS_RU_H_WORDS];
+    std::memcpy(head, c->h_ru.p, sizeof head);
+    const int32_t total = head[0], *hdr = head + 1;
+    const int32_t kept = hdr[FS_RU_H_KEPT], robot = hdr[FS_RU_H_ROBOT], tripped = hdr[FS_RU_H_TRIPPED], nodes = hdr[FS_RU_H_NODES];
+    if (hdr[FS_RU_H_ROUNDS] < 0) return fail(c, FS_E_HIP, "roadmap update: the keep rule did not settle in %d rounds", (int)n + 1);
+    if (kept < 0 || kept > n || robot < 0 || robot > 1 || nodes != n_old + kept + robot || total < 0 || (tripped && total != 0))
+        return fail(c, FS_E_HIP, "roadmap update: inconsistent header (%d kept of %d, %d candidates)", (int)kept, (int)n, (int)total);
+    const size_t added = (size_t)(kept + robot), tt = (size_t)total;
+    // the result: kept positions | pairs | inserted count | key flags
+    const size_t r_xy = 0, r_pairs = r_xy + 16 * added, r_ins = r_pairs + 8 * tt, r_key = r_ins + 8, r_total = r_key + (size_t)nodes;
+    FS_HIP(c, c->h_ru.ensure(r_total));
+    if (!tripped && total > 0) {
+        rc = rm_seg_ensure(c, tt);
+        if (rc) return rc;
+        // ints: tmp_q | tmp_order | cand | cand_rank | flag [total] | flag_off [total + 1] | pairs [total][2]
+        FS_HIP(c, c->d_ru_cand.ensure(8 * tt + 1));
+        int32_t *k = c->d_ru_cand.p;
+        u.tmp_q = k; u.tmp_order = k + tt; u.cand = k + 2 * tt; u.cand_rank = k + 3 * tt; u.flag = k + 4 * tt; u.flag_off = k + 5 * tt;
+        u.pairs = k + 6 * tt + 1;
+        u.seg_start = c->d_seg_start.p; u.seg_end = c->d_seg_end.p;
+        u.seg_ok = c->d_seg_ok.p; u.seg_hit = c->d_seg_hit.p; u.seg_unknown = c->d_seg_unknown.p; u.unknown_limit = rm_unknown_limit(c);
+        FS_HIP(c, fs_launch_ru_candidates(u, total, c->stream));
+        FS_HIP(c, fs_launch_segments(rm_seg_args(c, total), c->stream));
+        FS_HIP(c, fs_launch_ru_insert(u, total, c->stream));
+        FS_HIP(c, hipMemcpyAsync(c->h_ru.p + r_pairs, u.pairs, 8 * tt, hipMemcpyDeviceToHost, c->stream));
+    }
+    FS_HIP(c, hipMemcpyAsync(c->h_ru.p + r_ins, u.hdr + FS_RU_H_INSERTED, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (added) FS_HIP(c, hipMemcpyAsync(c->h_ru.p + r_xy, u.xy + 2 * (size_t)n_old, 16 * added, hipMemcpyDeviceToHost, c->stream));
+    if (!tripped && nodes > 0) FS_HIP(c, hipMemcpyAsync(c->h_ru.p + r_key, u.key, (size_t)nodes, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    int32_t inserted = 0;
+    std::memcpy(&inserted, c->h_ru.p + r_ins, sizeof inserted);
+    const int32_t *pairs = reinterpret_cast<const int32_t *>(c->h_ru.p + r_pairs);
+    if (inserted < 0 || inserted > total) return fail(c, FS_E_HIP, "roadmap update: %d pairs of %d candidates", (int)inserted, (int)total);
+    for (int32_t e = 0; e < 2 * inserted; ++e)
+        if (pairs[e] < 0 || pairs[e] >= nodes) return fail(c, FS_E_HIP, "roadmap update: a pair names node %d of %d", (int)pairs[e], (int)nodes);
+    // the mirror: the kept nodes as populateNodes appends them, the key flags, the pairs as constructNewEdges pushes them
+    ++c->rm_gen;
+    const double *axy = reinterpret_cast<const double *>(c->h_ru.p + r_xy);
+    int cx = 0, cy = 0;
+    for (size_t k = 0; k < added; ++k) {
+        const double x = axy[2 * k], y = axy[2 * k + 1];
+        cx = fs_rm_cell(x, c->rm_cell); cy = fs_rm_cell(y, c->rm_cell);
+        c->rm_hash[{cx, cy}].push_back(rm_nodes(c));
+        c->rm_xy.push_back(x); c->rm_xy.push_back(y);
+        c->rm_key.push_back(0);
+        c->rm_adj.emplace_back();
+        c->kf_queue.push_back(x); c->kf_queue.push_back(y);
+    }
+    out->kept = kept; out->robot = robot;
+    c->ru_walks = total; c->ru_owners = hdr[FS_RU_H_OWNERS]; c->ru_rounds = hdr[FS_RU_H_ROUNDS];
+    if (tripped)
+        return fail(c, FS_E_RANGE, "hash cell (%d, %d) holds more than %d nodes (the reference throws; the node stays added, the rest of the "
+                    "update is not run)", cx, cy, RM_MAX_PER_CELL);
+    if (nodes > 0) std::memcpy(c->rm_key.data(), c->h_ru.p + r_key, (size_t)nodes);
+    for (int32_t e = 0; e < inserted; ++e) {
+        const int32_t p = pairs[2 * e], q = pairs[2 * e + 1];
+        c->rm_adj[(size_t)p].push_back(q); c->rm_adj[(size_t)q].push_back(p);
+    }
+    out->edges = inserted;
+    c->rm_traced += total;
+    return FS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4052,6 +4178,27 @@ int fs_roadmap_connect(fs_ctx *c, int32_t n, const double *xy)
         }
     }
     return FS_OK;
+}
+
+int fs_roadmap_update(fs_ctx *c, int32_t n, const double *xy, const double robot_xy[2], int32_t add_robot_pose, int32_t *n_nodes_added,
+                      int32_t *robot_added, int64_t *n_edges_added)
+{
+    if (!c) return FS_E_INVALID;
+    if (n_nodes_added) *n_nodes_added = 0;
+    if (robot_added) *robot_added = 0;
+    if (n_edges_added) *n_edges_added = 0;
+    if (n < 0 || (n > 0 && !xy) || !robot_xy) return fail(c, FS_E_INVALID, "null pointer");
+    if (!rm_finite_xy(xy, n, 2) || !rm_finite_xy(robot_xy, 1, 2)) return fail(c, FS_E_INVALID, "non-finite point");
+    int rc = grid2d_check(c, "the roadmap");
+    if (rc) return rc;
+    FS_HIP(c, c->d_ru_pts.ensure(2 * (size_t)n));
+    if (n > 0) FS_HIP(c, hipMemcpyAsync(c->d_ru_pts.p, xy, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    RmUpdateOut out;
+    rc = rm_update_core(c, n, c->d_ru_pts.p, 2, robot_xy, add_robot_pose != 0, &out);
+    if (n_nodes_added) *n_nodes_added = out.kept;
+    if (robot_added) *robot_added = out.robot;
+    if (n_edges_added) *n_edges_added = out.edges;
+    return rc;
 }
 
 int fs_roadmap_set_keyframes(fs_ctx *c, int32_t n, const int32_t *kf_id, const double *pose7, int32_t *n_anchored, int32_t *n_orphaned)
@@ -4313,6 +4460,74 @@ int fs_get_frontier_costs_roadmap(fs_ctx *c, const double robot_pose7[7], int32_
                       path_length_m);
     if (rc || c->rm_search != FS_ROADMAP_SEARCH_REFERENCE) return rc;
     // (the ranking synchronised; a query that outgrew the global route's pool leaves columns to be written again, and ranked again)
+    bool redone = false;
+    rc = rm_astar_settle(c, [&] { return roadmap_astar_cols(c); }, &redone);
+    if (rc || !redone) return rc;
+    return rank_on_plan(c, c->d_rm_out, c->h_rm_out, n, [] { return FS_OK; }, rank, path_length_m);
+}
+
+
+// search -> roadmap update -> roadmap plan -> arrival (+ Fisher) -> U1 -> order: the update reads the goal column the
+// search left on the device, the plan takes its goals from the records the caller receives, the scorer the device columns
+int fs_get_frontier_costs_searched_roadmap(fs_ctx *c, const double robot_pose7[7], int32_t lethal_threshold, double max_frontier_distance,
+                                           int32_t min_frontier_cluster_size, int32_t max_frontier_cluster_size, int32_t add_robot_pose,
+                                           int32_t n_blacklist, const double *blacklist_xy, double alpha, double beta, double max_vx,
+                                           double max_wz, int with_fisher_information, int32_t max_records, fs_frontier_record *frontiers,
+                                           int32_t *n_frontiers, fs_record *records, double *weighted_cost, double *arrival_utility,
+                                           double *distance_utility, int32_t *order, double *path_length_m)
+{
+    if (!c) return FS_E_INVALID;
+    if (!robot_pose7 || !n_frontiers || max_records < 0 || (max_records > 0 && (!frontiers || !records || !weighted_cost)) ||
+        n_blacklist < 0 || (n_blacklist > 0 && !blacklist_xy))
+        return fail(c, FS_E_INVALID, "null pointer or negative count");
+    *n_frontiers = 0;
+    if (!rm_finite_xy(robot_pose7, 1, 2)) return fail(c, FS_E_INVALID, "non-finite robot position");
+    int rc = grid2d_check(c, "the roadmap");
+    if (rc) return rc;
+    rc = check_scoring_state(c, true, with_fisher_information != 0);
+    if (rc) return rc;
+    bool on_map = false;
+    FsSearchArgs sa{};
+    rc = search_enqueue(c, robot_pose7, lethal_threshold, max_frontier_distance, min_frontier_cluster_size, max_frontier_cluster_size,
+                        0, nullptr, false, &on_map, true, &sa);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    std::vector<fs_frontier_record> found;
+    int32_t n = 0;
+    if (on_map) {
+        const size_t cells = (size_t)c->nx * c->ny;
+        FS_HIP(c, c->d_fs_black.ensure(cells));
+        if (n_blacklist > 0) {
+            FS_HIP(c, c->d_fs_black_xy.ensure(2 * (size_t)n_blacklist));
+            FS_HIP(c, hipMemcpyAsync(c->d_fs_black_xy.p, blacklist_xy, 16 * (size_t)n_blacklist, hipMemcpyHostToDevice, c->stream));
+        }
+        FS_HIP(c, fs_launch_search_blacklist(sa, c->d_fs_black_xy.p, n_blacklist, c->d_fs_black.p, c->stream));
+        found.resize((size_t)std::min<int32_t>(max_records, 1024));
+        rc = search_results(c, (int32_t)found.size(), found.data(), &n, 0, nullptr, nullptr);
+        if (rc) return rc;
+        *n_frontiers = n;
+        if (n > max_records) return fail(c, FS_E_INVALID, "%d frontiers found, room for %d: no partial ranking", n, max_records);
+        if ((size_t)n > found.size()) {
+            const size_t have = found.size();
+            found.resize((size_t)n);
+            FS_HIP(c, hipMemcpyAsync(found.data() + have, c->d_fs_rec.p + have, sizeof(fs_frontier_record) * ((size_t)n - have), hipMemcpyDeviceToHost, c->stream));
+            FS_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        if (n > 0) std::memcpy(frontiers, found.data(), sizeof(fs_frontier_record) * (size_t)n);
+    }
+    // UpdateRoadmapBT on the searched list (a robot off the map found nothing: the update of an empty list)
+    RmUpdateOut upd;
+    rc = rm_update_core(c, n, c->d_fs_goal.p, 3, robot_pose7, add_robot_pose != 0, &upd);
+    if (rc || n == 0) return rc;
+    std::vector<double> goal(3 * (size_t)n);
+    for (int32_t k = 0; k < n; ++k) { goal[3 * (size_t)k] = found[(size_t)k].goal_x; goal[3 * (size_t)k + 1] = found[(size_t)k].goal_y; goal[3 * (size_t)k + 2] = 0.0; }
+    const auto rank = [&](const PlannedCols &cols) {
+        const DevCols dev{c->d_fs_goal.p, c->d_fs_fsize.p, c->d_fs_black.p};
+        return frontier_costs_core(c, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, alpha, beta, max_vx, max_wz,
+                                   with_fisher_information != 0, records, weighted_cost, arrival_utility, distance_utility, order, &cols, &dev);
+    };
+    rc = rank_on_plan(c, c->d_rm_out, c->h_rm_out, n, [&] { return roadmap_plan_enqueue(c, robot_pose7, n, goal.data(), nullptr); }, rank,
+                      path_length_m);
+    if (rc || c->rm_search != FS_ROADMAP_SEARCH_REFERENCE) return rc;
     bool redone = false;
     rc = rm_astar_settle(c, [&] { return roadmap_astar_cols(c); }, &redone);
     if (rc || !redone) return rc;

@@ -444,6 +444,53 @@ struct FsRmTourArgs {
 int32_t fs_rm_tour_blocks(int64_t total, int64_t *chunk);
 hipError_t fs_launch_rm_tour(const FsRmTourArgs &a, int32_t blocks, double *d_out, hipStream_t s);
 
+// ---- the per-tick roadmap update (fs_roadmap_update.hip): UpdateRoadmapBT's addNodes, addRobotPoseAsNode,
+// constructNewEdges and constructNewEdgeRobotPose decided on the device by the rules of fs_roadmap_update.h
+#define FS_RU_MAX_POINTS 16384      // points of one update (the conflict rows are n x n bits)
+enum : int32_t {                    // the header the host reads
+    FS_RU_H_KEPT = 0,               // points of the list added as nodes
+    FS_RU_H_TRIPPED,                // 0, 1: the list overfilled a cell, 2: the robot pose did
+    FS_RU_H_ROBOT,                  // the robot pose was added
+    FS_RU_H_NODES,                  // nodes after the additions
+    FS_RU_H_OWNERS,                 // distinct closest nodes
+    FS_RU_H_ROUNDS,                 // Jacobi rounds of the keep rule (-1: did not settle)
+    FS_RU_H_INSERTED,               // (p, q) pairs inserted
+    FS_RU_H_WORDS
+};
+struct FsRmUpdate {
+    int32_t n;                      // points of the list
+    const double *pts;              // device, point i at pts[stride * i], pts[stride * i + 1]
+    int32_t stride;
+    double rx, ry;                  // the robot pose
+    int32_t add_robot;
+    int32_t n_old;                  // nodes before the call
+    double *xy;                     // [n_old + n + 1][2]: the nodes, the kept points appended
+    uint8_t *key;                   // [n_old + n + 1]
+    const int32_t *row, *col;       // the adjacency lists before the call (CSR over n_old nodes)
+    double cell, radius, min_frontier, min_robot, oz;
+    int32_t words;                  // 64-bit words of a conflict row: (n + 63) / 64
+    uint64_t *conf;                 // [n][words]
+    uint8_t *rejected;              // [n] an existing node rejects the point
+    int32_t *occupants;             // [n] existing nodes in the point's cell
+    int32_t *hdr;                   // [FS_RU_H_WORDS]
+    int32_t *closest;               // [n + 1] closest hash node of every point, then of the robot pose
+    int32_t *rank_of;               // [n_old + n + 1] first query of a node, then its owner rank (>= n + 1: not an owner)
+    int32_t *owner;                 // [n + 1] rank -> node
+    int32_t *cand_count, *cand_off; // [n + 1], [n + 2] candidates per owner rank
+    int32_t *tmp_q, *tmp_order;     // [total] candidates in index order with their scan cell
+    int32_t *cand, *cand_rank;      // [total] candidates in getNodesWithinRadius order, their owner's rank
+    double *seg_start, *seg_end;    // [total][3] the walks candidate -> owner
+    const uint8_t *seg_ok, *seg_hit;
+    const int32_t *seg_unknown;
+    double unknown_limit;
+    int32_t *flag, *flag_off;       // [total], [total + 1] inserted candidates and their scan
+    int32_t *pairs;                 // [total][2] the inserted (p, q) in order
+};
+hipError_t fs_launch_ru_nodes(const FsRmUpdate &u, hipStream_t s);                     // keep rule, cell cap, robot pose -> xy, hdr
+hipError_t fs_launch_ru_owners(const FsRmUpdate &u, hipStream_t s);                    // closest, owners, candidate counts and offsets
+hipError_t fs_launch_ru_candidates(const FsRmUpdate &u, int32_t total, hipStream_t s); // the ordered lists and their segments
+hipError_t fs_launch_ru_insert(const FsRmUpdate &u, int32_t total, hipStream_t s);     // flags, scan, pairs
+
 // ---- key-frame anchors of the roadmap (fs_roadmap_kf.hip): mapDataCallback's anchoring, optimizeSHM's re-placement
 // and de-duplication
 #define FS_KF_RT 24                   // a key-frame slot: R [9] row-major, t [3], R^-1 [9], -R^-1 t [3] (float)

@@ -533,6 +533,19 @@ int fs_roadmap_rebuild(fs_ctx *ctx);
  * point's closest hash node linked both ways to the nodes within the radius it can connect to.  Every isConnectable of the call is
  * walked on the device in one batch, the insertions follow on the host in the reference's order.  xy [n][2].  No node: a no-op. */
 int fs_roadmap_connect(fs_ctx *ctx, int32_t n, const double *xy);
+/* UpdateRoadmapBT (ExplorationBT.cpp:247-257) in one call, decided on the device: addNodes(xy),
+ * addRobotPoseAsNode(robot_xy) if add_robot_pose, constructNewEdges(xy), constructNewEdgeRobotPose(robot_xy).  The roadmap afterwards
+ * equals, bit for bit (node list, key flags, adjacency in append order, pending key-frame queue), fs_roadmap_add_nodes(xy, 0);
+ * fs_roadmap_add_nodes(robot_xy, 1); fs_roadmap_connect(xy ++ robot_xy).  Outputs (each may be NULL): points of xy added as nodes,
+ * whether the robot pose was, undirected edges inserted.  Counters 1033-1035 (fs_get_counter): the call's isConnectable walks, its
+ * owners (distinct closest nodes, the only ones that build candidate lists) and the rounds of its keep rule.
+ * Non-finite input, a null pointer, nz > 1, more than 16384 points: FS_E_INVALID with NOTHING changed — every check comes before
+ * the first addition (the three-call sequence adds its nodes before fs_roadmap_connect refuses a 3-D grid).  A cell that comes to
+ * hold more than 20 nodes: FS_E_RANGE with the roadmap as the three calls leave it when they stop at the failing one — the nodes
+ * up to and including that one added, the robot pose not added if the list tripped, no edge built.  n == 0 without the robot pose
+ * on an empty roadmap: a no-op.  The roadmap generation is bumped once.  Two synchronisations (sizes, result). */
+int fs_roadmap_update(fs_ctx *ctx, int32_t n, const double *xy /* [n][2] */, const double robot_xy[2], int32_t add_robot_pose,
+                      int32_t *n_nodes_added, int32_t *robot_added, int64_t *n_edges_added);
 /* The roadmap, for tests and visualisation: node positions xy [n][2] in insertion order, key [n] (1: a key of roadmap_, what
  * getClosestNodeInRoadMap considers), the adjacency as CSR row_ptr [n + 1], col [n_edges] in append order.  Any pointer may be NULL
  * (call first with NULL arrays for the sizes). */
@@ -554,6 +567,20 @@ int fs_roadmap_plan(fs_ctx *ctx, const double robot_pose7[7], int32_t n, const d
  * (fs_set_roadmap_search); the path columns never visit the host. */
 int fs_get_frontier_costs_roadmap(fs_ctx *ctx, const double robot_pose7[7], int32_t n, const double *goal_xyz, const int32_t *frontier_size,
                   const uint8_t *blacklisted, double alpha, double beta, double max_vx, double max_wz, int with_fisher_information,
+                  fs_record *records, double *weighted_cost, double *arrival_utility, double *distance_utility, int32_t *order,
+                  double *path_length_m);
+/* The default planner's tick in one call: search -> roadmap update -> roadmap plan -> arrival (+ Fisher) -> U1 -> order.
+ * fs_get_frontier_costs_searched's arguments without allow_unknown and with add_robot_pose (fs_roadmap_update's): the search with the
+ * context's seed order (fs_set_frontier_seed_order), fs_roadmap_update on its goal points and the pose's xy — read from the goal column
+ * the search left on the device — then fs_get_frontier_costs_roadmap on the records under the context's roadmap search
+ * (fs_set_roadmap_search).  Same results, bit for bit, as fs_search_frontiers, fs_roadmap_update and fs_get_frontier_costs_roadmap in
+ * turn (the Fisher float sums excepted, as in fs_get_frontier_costs_searched).  More records than max_records: FS_E_INVALID with
+ * *n_frontiers set, the roadmap untouched.  FS_E_RANGE from the update: returned with *n_frontiers and the frontier records written,
+ * the roadmap as fs_roadmap_update leaves it, nothing ranked.  A robot off the map finds nothing; the update of an empty list runs. */
+int fs_get_frontier_costs_searched_roadmap(fs_ctx *ctx, const double robot_pose7[7], int32_t lethal_threshold, double max_frontier_distance,
+                  int32_t min_frontier_cluster_size, int32_t max_frontier_cluster_size, int32_t add_robot_pose,
+                  int32_t n_blacklist, const double *blacklist_xy, double alpha, double beta, double max_vx, double max_wz,
+                  int with_fisher_information, int32_t max_records, fs_frontier_record *frontiers, int32_t *n_frontiers,
                   fs_record *records, double *weighted_cost, double *arrival_utility, double *distance_utility, int32_t *order,
                   double *path_length_m);
 /* The routes behind fs_roadmap_plan's numbers: RoadmapPlanResult::path of getPlan (FrontierRoadmap.cpp:550-635,

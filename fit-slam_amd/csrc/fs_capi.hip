@@ -20,6 +20,7 @@
 #include <thread>
 #include <unordered_map>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 hipError_t fs_launch_rank(int32_t n, const fs_record *d_records, const uint8_t *d_black,
@@ -49,13 +50,32 @@ static void poison_device(void *p, size_t bytes)
 }
 #endif
 
+// Bytes the DevBuf / PinnedBuf objects of every context hold at this moment (fs_get_counter 1036): `ensure` adds what it allocated,
+// `release`, the destructor and a move take off what they free.  Process-wide like fs_alloc_generation, so a test can ask for
+// "a destroyed context gave everything back" exactly, on a device whose memory other processes use too.  Not in it: memory an
+// FS_POISON build has retired (it is no buffer's any more), rank_scratch and sort_scratch (raw pointers grown in fs_rank.hip /
+// fs_sort.hip).
+std::atomic<int64_t> buf_bytes_held{0};
+
+// A buffer owns its memory: destruction frees it, a move hands it over, a copy does not exist.
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t n)
     {
         if (n <= cap) return hipSuccess;
+        buf_bytes_held -= (int64_t)(cap * sizeof(T));
 #ifdef FS_POISON
         if (p) poison_device(p, cap * sizeof(T));                 // retired
 #else
@@ -65,7 +85,7 @@ struct DevBuf {
         size_t want = std::max<size_t>(n, 64);
         ++fs_alloc_generation;
         hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), want * sizeof(T));
-        if (e == hipSuccess) cap = want;
+        if (e == hipSuccess) { cap = want; buf_bytes_held += (int64_t)(want * sizeof(T)); }
 #ifdef FS_POISON
         if (e == hipSuccess) poison_device(p, want * sizeof(T));
 #endif
@@ -74,6 +94,7 @@ struct DevBuf {
     void release()
     {
         if (p) (void)hipFree(p);
+        buf_bytes_held -= (int64_t)(cap * sizeof(T));
         p = nullptr; cap = 0;
     }
 };
@@ -88,9 +109,20 @@ struct DevBuf {
 struct PinnedBuf {
     char *p = nullptr, *dev = nullptr;
     size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    PinnedBuf(PinnedBuf &&o) noexcept : p(o.p), dev(o.dev), cap(o.cap) { o.p = nullptr; o.dev = nullptr; o.cap = 0; }
+    PinnedBuf &operator=(PinnedBuf &&o) noexcept
+    {
+        if (this != &o) { release(); p = o.p; dev = o.dev; cap = o.cap; o.p = nullptr; o.dev = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~PinnedBuf() { release(); }
     hipError_t ensure(size_t bytes)
     {
         if (bytes <= cap) return hipSuccess;
+        buf_bytes_held -= (int64_t)cap;
 #ifdef FS_POISON
         if (p) { (void)hipDeviceSynchronize(); std::memset(p, 0xCD, cap); }      // retired (see DevBuf)
 #else
@@ -111,9 +143,11 @@ struct PinnedBuf {
             e = hipHostMalloc(reinterpret_cast<void **>(&p), want, hipHostMallocDefault);
             if (e != hipSuccess) { p = nullptr; return e; }
             cap = want;
+            buf_bytes_held += (int64_t)want;
             return hipSuccess;
         }
         cap = want;
+        buf_bytes_held += (int64_t)want;
         void *d = nullptr;
         if (hipHostGetDevicePointer(&d, p, 0) == hipSuccess) dev = static_cast<char *>(d);
         else (void)hipGetLastError();
@@ -122,6 +156,7 @@ struct PinnedBuf {
     void release()
     {
         if (p) (void)hipHostFree(p);
+        buf_bytes_held -= (int64_t)cap;
         p = nullptr; dev = nullptr; cap = 0;
     }
 };
@@ -659,6 +694,16 @@ struct PlanOutLayout {
     explicit PlanOutLayout(size_t n) : len(0), len_m(8 * n), head(16 * n), ach(24 * n), total(24 * n + ((n + 15) & ~(size_t)15)) {}
 };
 
+// ... from their host copy (the stream has drained) into the caller's four arrays
+void plan_columns_to_caller(const PinnedBuf &h_out, size_t n, double *path_length, double *path_length_m, double *path_heading, uint8_t *achievable)
+{
+    const PlanOutLayout O(n);
+    std::memcpy(path_length, h_out.p + O.len, 8 * n);
+    std::memcpy(path_length_m, h_out.p + O.len_m, 8 * n);
+    std::memcpy(path_heading, h_out.p + O.head, 8 * n);
+    std::memcpy(achievable, h_out.p + O.ach, n);
+}
+
 // Output block of fs_plan_paths_information in d_pi_out / h_pi_out: total, records | info_mean | info_min | first_unsafe
 struct PathInfoOutLayout {
     size_t hdr, mean, min, unsafe, total;
@@ -1087,61 +1132,14 @@ void fs_ctx_destroy(fs_ctx *c)
     for (auto &t : c->launches) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     for (auto &g : c->graphs) if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
-    c->d_out.release();
-    c->d_dir.release(); c->d_yawR.release(); c->d_cells.release(); c->d_cls.release(); c->d_cls_table.release(); c->d_cls_pool.release();
-    c->d_lx.release(); c->d_ly.release(); c->d_lz.release(); c->d_spheres.release(); c->d_counters.release();
-    c->d_table.release(); c->d_factor.release(); c->d_gtable.release();
-    c->d_kf_check.release(); c->d_kf_tri.release(); c->d_kf_off.release(); c->d_kf_flagged.release(); c->d_kf_cells.release();
-    c->d_kf_points.release(); c->d_kpx.release(); c->d_kpy.release(); c->d_kpz.release(); c->d_kf_gtable.release();
-    c->d_kf_counters.release();
-    c->d_goal.release(); c->d_yaw.release(); c->d_len.release(); c->d_head.release();
-    c->d_cost.release(); c->d_au.release(); c->d_du.release(); c->d_sums.release();
-    c->d_fsize.release(); c->d_arrival.release(); c->d_argmax.release(); c->d_status.release();
-    c->d_nvis.release(); c->d_nvox.release(); c->d_raycounts.release(); c->d_order.release(); c->d_err.release();
-    c->d_black.release(); c->d_achin.release(); c->d_ach.release();
-    c->d_info.release(); c->d_trace.release(); c->d_logdet.release(); c->d_fim21.release(); c->d_Rt.release();
-    c->d_overflow.release(); c->d_tested.release(); c->d_split_flags.release(); c->d_flagged.release(); c->d_records.release();
+    // (grown inside fs_rank.hip / fs_sort.hip: raw pointers, not buffers)
     if (c->rank_scratch) (void)hipFree(c->rank_scratch);
     if (c->sort_scratch) (void)hipFree(c->sort_scratch);
-    c->d_perm.release(); c->h_in.release(); c->h_out.release(); c->d_in.release(); c->h_gin.release(); c->d_gin.release(); c->h_fin.release(); c->h_win.release(); c->d_win.release();
-    c->d_cloud_raw.release(); c->d_cloud_perm.release(); c->d_cloud_bounds.release(); c->d_cloud_keys.release(); c->d_cloud_temp.release(); c->d_cloud_bbox.release();
-    c->d_seg_start.release(); c->d_seg_end.release(); c->d_tri.release(); c->d_seg_ok.release(); c->d_seg_hit.release();
-    c->d_mask.release(); c->d_brick_cells.release(); c->d_seg_traced.release(); c->d_seg_unknown.release();
-    c->d_seg_all.release(); c->d_brick_xyz.release(); c->d_bad.release(); c->d_count.release();
-    c->d_fc_parent_t.release(); c->d_fc_parent_f.release(); c->d_fc_aux.release(); c->d_fc_state.release(); c->d_fc_labels.release();
-    c->d_fc_queue.release(); c->d_fc_visited.release(); c->d_fc_clusters.release(); c->d_fc_sums.release();
-    c->d_fs_bcount.release(); c->d_fs_cidx.release(); c->d_fs_root.release(); c->d_fs_best_idx.release(); c->d_fs_csize.release();
-    c->d_fs_owner.release(); c->d_fs_key.release(); c->d_fs_pos.release(); c->d_fs_q.release(); c->d_fs_state.release(); c->d_fs_seeds.release();
-    c->d_fs_emit_comp.release(); c->d_fs_emit_seed.release(); c->d_fs_emit_base.release(); c->d_fs_rec_base.release(); c->d_fs_fsize.release();
-    c->d_fs_best_d2.release(); c->d_fs_sort.release(); c->d_fs_rec.release(); c->d_fs_every.release();
-    c->d_fs_goal.release(); c->d_fs_black_xy.release(); c->d_fs_black.release();
-    c->d_nav_cost.release(); c->d_nav_pot.release(); c->d_nav_flags.release(); c->d_nav_any.release(); c->d_nav_path.release();
-    c->d_nav_in.release(); c->d_nav_out.release(); c->h_nav_in.release(); c->h_nav_out.release();
-    c->d_pi_off.release(); c->d_pi_key.release(); c->d_pi_idx.release(); c->d_pi_rt.release(); c->d_pi_pose.release(); c->d_pi_val.release();
-    c->d_pi_temp.release(); c->d_pi_out.release(); c->h_pi_out.release();
-    c->d_rm_xy.release(); c->d_rm_d.release(); c->d_rm_key.release(); c->d_rm_cell_key.release(); c->d_rm_row.release(); c->d_rm_col.release();
-    c->d_rm_trow.release(); c->d_rm_tcol.release(); c->d_rm_tmp.release(); c->d_rm_cell_start.release(); c->d_rm_cell_nodes.release();
-    c->d_rm_cand_off.release(); c->d_rm_cand.release(); c->d_rm_hops.release(); c->d_rm_pred.release(); c->d_rm_word.release();
-    c->d_rm_in.release(); c->d_rm_out.release(); c->h_rm_in.release(); c->h_rm_out.release();
-    c->d_as_gnode.release(); c->d_as_mark.release(); c->d_as_qidx.release(); c->d_as_src.release(); c->d_as_dst.release();
-    c->d_as_status.release(); c->d_as_stats.release(); c->d_as_len.release(); c->d_as_pool.release(); c->h_as_io.release();
-    c->d_rt_chain_len.release(); c->d_rt_pool.release(); c->d_rt_idx.release(); c->d_rt_of.release(); c->d_rt_node.release();
-    c->d_rt_refined.release(); c->d_rt_chain_base.release(); c->d_rt_off.release(); c->d_rt_cursor.release(); c->d_rt_complete.release();
-    c->h_rt.release(); c->h_rt_list.release();
-    c->d_tour_d.release(); c->d_tour_hops.release(); c->d_tour_pred.release(); c->d_tour_word.release(); c->d_tour_work.release();
-    c->h_tour_out.release();
-    c->d_kf_rt.release(); c->d_kf_rec_p.release(); c->d_kf_pts.release(); c->d_kf_out.release(); c->d_kf_queue.release();
-    c->d_kf_rec_h.release(); c->d_kf_rec_ord.release(); c->d_kf_tab.release(); c->d_kf_work.release(); c->d_kf_cand.release();
-    c->d_kf_word.release(); c->d_kf_cell_key.release(); c->d_kf_hkey.release(); c->d_kf_state.release(); c->h_kf.release();
-    c->d_ru_xy.release(); c->d_ru_pts.release(); c->d_ru_key.release(); c->d_ru_rejected.release(); c->d_ru_conf.release();
-    c->d_ru_work.release(); c->d_ru_rank_of.release(); c->d_ru_cand.release(); c->h_ru.release();
-    c->d_rf_g.release(); c->d_rf_flags.release(); c->d_rf_any.release(); c->d_rf_in.release(); c->d_rf_scratch.release();
-    c->d_rf_out.release(); c->d_rf_pts.release(); c->h_rf_in.release(); c->h_rf_out.release(); c->h_rf_pts.release();
-    c->d_al_in.release(); c->d_al_work.release(); c->d_al_out.release(); c->d_al_stats.release(); c->h_al_in.release(); c->h_al_out.release();
-    c->d_fl_d.release(); c->d_fl_hops.release(); c->d_fl_pred.release(); c->d_fl_word.release(); c->d_fl_in.release(); c->d_fl_plan.release();
-    c->d_fl_out.release(); c->h_fl_in.release(); c->h_fl_out.release();
-    if (c->own_stream) (void)hipStreamDestroy(c->stream);
+    // every DevBuf / PinnedBuf member frees itself with the context; a stream of the context's own goes after them
+    const hipStream_t stream = c->stream;
+    const bool own_stream = c->own_stream;
     delete c;
+    if (own_stream) (void)hipStreamDestroy(stream);
 }
 
 const char *fs_last_error(const fs_ctx *c) { return c ? c->err.c_str() : "null context"; }
@@ -1552,6 +1550,41 @@ int search_results(fs_ctx *c, int32_t max_records, fs_frontier_record *records, 
     if ((size_t)stored > first || (every_xy && every > 0)) FS_HIP(c, hipStreamSynchronize(c->stream));
     *n_records = n;
     if (n_cells) *n_cells = state[FSS_CELLS];
+    return FS_OK;
+}
+
+// The list of fs_get_frontier_costs_searched / _searched_roadmap: the search writes the goal and size columns where the planner and
+// the scorer read them, the blacklist is matched there too (d_fs_black), and the found records come up — the count (which sizes
+// every launch that follows) with the first round, a list longer than that round holds at the price of a second.  *on_map = false:
+// the robot is off the map, nothing ran and *n stays as it is.  More than max_records: *n is set and the call refuses.
+int searched_list(fs_ctx *c, const double robot_pose7[7], int32_t lethal_threshold, double max_frontier_distance, int32_t min_size,
+                  int32_t max_size, int32_t n_blacklist, const double *blacklist_xy, int32_t max_records, bool *on_map, int32_t *n,
+                  std::vector<fs_frontier_record> &found)
+{
+    FsSearchArgs sa{};
+    int rc = search_enqueue(c, robot_pose7, lethal_threshold, max_frontier_distance, min_size, max_size, 0, nullptr, false, on_map, true, &sa);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (!*on_map) return FS_OK;
+    const size_t cells = (size_t)c->nx * c->ny;
+    FS_HIP(c, c->d_fs_black.ensure(cells));
+    if (n_blacklist > 0) {
+        FS_HIP(c, c->d_fs_black_xy.ensure(2 * (size_t)n_blacklist));
+        FS_HIP(c, hipMemcpyAsync(c->d_fs_black_xy.p, blacklist_xy, 16 * (size_t)n_blacklist, hipMemcpyHostToDevice, c->stream));
+    }
+    FS_HIP(c, fs_launch_search_blacklist(sa, c->d_fs_black_xy.p, n_blacklist, c->d_fs_black.p, c->stream));
+    std::vector<fs_frontier_record> first((size_t)std::min<int32_t>(max_records, 1024));
+    found.swap(first);
+    int32_t count = 0;
+    rc = search_results(c, (int32_t)found.size(), found.data(), &count, 0, nullptr, nullptr);
+    if (rc) return rc;
+    *n = count;
+    if (count > max_records) return fail(c, FS_E_INVALID, "%d frontiers found, room for %d: no partial ranking", count, max_records);
+    if ((size_t)count > found.size()) {
+        const size_t have = found.size();
+        found.resize((size_t)count);
+        FS_HIP(c, hipMemcpyAsync(found.data() + have, c->d_fs_rec.p + have, sizeof(fs_frontier_record) * ((size_t)count - have), hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+    }
     return FS_OK;
 }
 
@@ -2110,6 +2143,8 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
         *value = v;
         return FS_OK;
     }
+    // bytes the DevBuf / PinnedBuf objects hold (buf_bytes_held): of the whole process, not of this context alone
+    if (c && value && which == 1036) { *value = buf_bytes_held.load(); return FS_OK; }
     for (const auto &h : host)
         if (c && value && which == h.id) {
             *value = c->*h.v;
@@ -3237,10 +3272,7 @@ int plan_to_host(fs_ctx *c, const DevBuf<char> &d_out, PinnedBuf &h_out, int32_t
     FS_HIP(c, h_out.ensure(O.total));
     FS_HIP(c, hipMemcpyAsync(h_out.p, d_out.p, O.total, hipMemcpyDeviceToHost, c->stream));
     FS_HIP(c, hipStreamSynchronize(c->stream));
-    std::memcpy(path_length, h_out.p + O.len, 8 * nn);
-    std::memcpy(path_length_m, h_out.p + O.len_m, 8 * nn);
-    std::memcpy(path_heading, h_out.p + O.head, 8 * nn);
-    std::memcpy(achievable, h_out.p + O.ach, nn);
+    plan_columns_to_caller(h_out, nn, path_length, path_length_m, path_heading, achievable);
     return FS_OK;
 }
 
@@ -3266,6 +3298,53 @@ int rank_on_plan(fs_ctx *c, const DevBuf<char> &d_out, PinnedBuf &h_out, int32_t
         return rc;
     }
     if (path_length_m) std::memcpy(path_length_m, h_out.p + O.len_m, 8 * nn);
+    return FS_OK;
+}
+
+// The pose records of fs_plan_paths_information / fs_roadmap_routes (fs_pathinfo.hip: keys, sort, heads, records) for up to `bound`
+// way points or legs (`what` in the error text): the d_pi_* buffers are sized, `a` is pointed at them, the kernels are launched and
+// the header (total, distinct) is on its way to `hdr`.  Not synchronised; `stop` is the caller's return after a failed launch.
+template <class Stop>
+int pathinfo_prepare(fs_ctx *c, FsPathInfoArgs &a, int64_t bound, bool dump, const char *what, int64_t *hdr, Stop stop)
+{
+    const size_t room = (size_t)bound;
+    if (a.dedup) { FS_HIP(c, c->d_pi_key.ensure(2 * room)); }
+    FS_HIP(c, c->d_pi_idx.ensure(5 * room));
+    FS_HIP(c, c->d_pi_rt.ensure(12 * room));
+    if (dump) { FS_HIP(c, c->d_pi_pose.ensure(7 * room)); FS_HIP(c, c->d_pi_val.ensure(room)); }
+    a.bound = bound;
+    a.key_in = c->d_pi_key.p; a.key_out = c->d_pi_key.p + room;
+    a.wp_in = c->d_pi_idx.p; a.wp_out = a.wp_in + room; a.head = a.wp_out + room; a.rank = a.head + room; a.slot = a.rank + room;
+    a.rt = c->d_pi_rt.p;
+    a.pose7 = dump ? c->d_pi_pose.p : nullptr;
+    a.wp_info = dump ? c->d_pi_val.p : nullptr;
+    if (fs_launch_pathinfo_prepare(a, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "%s: launch failed", what));
+    FS_HIP(c, hipMemcpyAsync(hdr, a.hdr, 16, hipMemcpyDeviceToHost, c->stream));
+    return FS_OK;
+}
+
+// ... and their information (distinct > 0, known after the caller's synchronisation): fs_score_fim's launch sequence on the records;
+// a.info is where the finish kernel finds it.  What decides the size of the per-item scratch (maybe_split) comes before any pointer
+// into it.  A refused scratch returns as it is; every later failure goes through the caller's `stop`.
+template <class Stop>
+int pathinfo_score(fs_ctx *c, FsPathInfoArgs &a, int64_t distinct, Stop stop)
+{
+    int rc = ensure_candidate_scratch(c, (size_t)distinct, false);
+    if (rc) return rc;
+    FsFimArgs fa{};
+    if (const int rc_args = fill_fim_args(c, fa)) return rc_args;
+    fa.n = (int32_t)distinct;
+    fa.info_only = c->opt_special ? 1 : 0;
+    if (fa.info_only && fa.skip32 < 20) fa.skip32 = 20;        // (as fs_score_fim_begin)
+    rc = maybe_split(c, fa, (size_t)distinct, false);
+    if (rc) return stop(rc);
+    fa.Rt = c->d_pi_rt.p;
+    bind_fim_outputs(c, fa);
+    rc = run_fim_tier1(c, fa, nullptr, 0, fa.n << fa.split_shift);
+    if (rc) return stop(rc);
+    rc = run_fim_rest(c, fa);
+    if (rc) return stop(rc);
+    a.info = fa.info_ref;
     return FS_OK;
 }
 
@@ -3387,47 +3466,14 @@ int fs_plan_paths_information(fs_ctx *c, const double robot_pose7[7], int32_t al
         if (rc) return stop(rc);
         bind();
     }
-    const size_t room = (size_t)bound;
-    if (bound > 0) {
-        if (a.dedup) { FS_HIP(c, c->d_pi_key.ensure(2 * room)); }
-        FS_HIP(c, c->d_pi_idx.ensure(5 * room));
-        FS_HIP(c, c->d_pi_rt.ensure(12 * room));
-        if (dump) { FS_HIP(c, c->d_pi_pose.ensure(7 * room)); FS_HIP(c, c->d_pi_val.ensure(room)); }
-        a.bound = bound;
-        a.key_in = c->d_pi_key.p; a.key_out = c->d_pi_key.p + room;
-        a.wp_in = c->d_pi_idx.p; a.wp_out = a.wp_in + room; a.head = a.wp_out + room; a.rank = a.head + room; a.slot = a.rank + room;
-        a.rt = c->d_pi_rt.p;
-        a.pose7 = dump ? c->d_pi_pose.p : nullptr;
-        a.wp_info = dump ? c->d_pi_val.p : nullptr;
-        if (fs_launch_pathinfo_prepare(a, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "way points: launch failed"));
-        FS_HIP(c, hipMemcpyAsync(hdr, a.hdr, 16, hipMemcpyDeviceToHost, c->stream));
-    }
+    if (bound > 0 && (rc = pathinfo_prepare(c, a, bound, dump, "way points", hdr, stop))) return rc;
     // THE mid-call synchronisation: the worker's item count (and the room its per-item scratch needs) must be on the host
     FS_HIP(c, hipStreamSynchronize(c->stream));
     const int64_t total = bound > 0 ? hdr[0] : 0, distinct = bound > 0 ? hdr[1] : 0;
     c->pi_waypoints = total; c->pi_distinct = distinct;
     if (dump) *n_total = total;
     if (dump && total > max_waypoints) return fail(c, FS_E_RANGE, "%lld way points, room for %lld", (long long)total, (long long)max_waypoints);
-    if (distinct > 0) {
-        // fs_score_fim's launch sequence on the records: what decides the size of the per-item scratch (maybe_split) comes before
-        // any pointer into it
-        rc = ensure_candidate_scratch(c, (size_t)distinct, false);
-        if (rc) return rc;
-        FsFimArgs fa{};
-        if (const int rc_args = fill_fim_args(c, fa)) return rc_args;
-        fa.n = (int32_t)distinct;
-        fa.info_only = c->opt_special ? 1 : 0;
-        if (fa.info_only && fa.skip32 < 20) fa.skip32 = 20;        // (as fs_score_fim_begin)
-        rc = maybe_split(c, fa, (size_t)distinct, false);
-        if (rc) return stop(rc);
-        fa.Rt = c->d_pi_rt.p;
-        bind_fim_outputs(c, fa);
-        rc = run_fim_tier1(c, fa, nullptr, 0, fa.n << fa.split_shift);
-        if (rc) return stop(rc);
-        rc = run_fim_rest(c, fa);
-        if (rc) return stop(rc);
-        a.info = fa.info_ref;
-    }
+    if (distinct > 0 && (rc = pathinfo_score(c, a, distinct, stop))) return rc;
     if (fs_launch_pathinfo_finish(a, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "path information columns: launch failed"));
     FS_HIP(c, hipMemcpyAsync(c->h_pi_out.p + P.mean, c->d_pi_out.p + P.mean, P.total - P.mean, hipMemcpyDeviceToHost, c->stream));
     if (dump) {
@@ -3439,10 +3485,7 @@ int fs_plan_paths_information(fs_ctx *c, const double robot_pose7[7], int32_t al
     }
     FS_HIP(c, hipMemcpyAsync(n_waypoints, a.count, sizeof(int32_t) * nn, hipMemcpyDeviceToHost, c->stream));
     FS_HIP(c, hipStreamSynchronize(c->stream));
-    std::memcpy(path_length, c->h_nav_out.p + O.len, 8 * nn);
-    std::memcpy(path_length_m, c->h_nav_out.p + O.len_m, 8 * nn);
-    std::memcpy(path_heading, c->h_nav_out.p + O.head, 8 * nn);
-    std::memcpy(achievable, c->h_nav_out.p + O.ach, nn);
+    plan_columns_to_caller(c->h_nav_out, nn, path_length, path_length_m, path_heading, achievable);
     std::memcpy(info_mean, c->h_pi_out.p + P.mean, 8 * nn);
     std::memcpy(info_min, c->h_pi_out.p + P.min, 4 * nn);
     std::memcpy(first_unsafe, c->h_pi_out.p + P.unsafe, 4 * nn);
@@ -3486,35 +3529,13 @@ int fs_get_frontier_costs_searched(fs_ctx *c, const double robot_pose7[7], int32
     if (rc) return rc;
     rc = check_scoring_state(c, true, with_fisher_information != 0);
     if (rc) return rc;
-    // the search writes the goal and size columns where the planner and the scorer read them; the blacklist is matched there too
     bool on_map = false;
-    FsSearchArgs sa{};
-    rc = search_enqueue(c, robot_pose7, lethal_threshold, max_frontier_distance, min_frontier_cluster_size, max_frontier_cluster_size,
-                        0, nullptr, false, &on_map, true, &sa);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if (!on_map) return FS_OK;
-    const size_t cells = (size_t)c->nx * c->ny;
-    FS_HIP(c, c->d_fs_black.ensure(cells));
-    if (n_blacklist > 0) {
-        FS_HIP(c, c->d_fs_black_xy.ensure(2 * (size_t)n_blacklist));
-        FS_HIP(c, hipMemcpyAsync(c->d_fs_black_xy.p, blacklist_xy, 16 * (size_t)n_blacklist, hipMemcpyHostToDevice, c->stream));
-    }
-    FS_HIP(c, fs_launch_search_blacklist(sa, c->d_fs_black_xy.p, n_blacklist, c->d_fs_black.p, c->stream));
-    // the count (which sizes every launch below) and the records the caller receives; a list longer than the first round holds
-    // costs a second one
-    std::vector<fs_frontier_record> found((size_t)std::min<int32_t>(max_records, 1024));
-    int32_t n = 0;
-    rc = search_results(c, (int32_t)found.size(), found.data(), &n, 0, nullptr, nullptr);
+    std::vector<fs_frontier_record> found;
+    rc = searched_list(c, robot_pose7, lethal_threshold, max_frontier_distance, min_frontier_cluster_size, max_frontier_cluster_size,
+                       n_blacklist, blacklist_xy, max_records, &on_map, n_frontiers, found);
     if (rc) return rc;
-    *n_frontiers = n;
-    if (n > max_records) return fail(c, FS_E_INVALID, "%d frontiers found, room for %d: no partial ranking", n, max_records);
-    if (n == 0) return FS_OK;
-    if ((size_t)n > found.size()) {
-        const size_t have = found.size();
-        found.resize((size_t)n);
-        FS_HIP(c, hipMemcpyAsync(found.data() + have, c->d_fs_rec.p + have, sizeof(fs_frontier_record) * ((size_t)n - have), hipMemcpyDeviceToHost, c->stream));
-        FS_HIP(c, hipStreamSynchronize(c->stream));
-    }
+    const int32_t n = *n_frontiers;
+    if (n == 0) return FS_OK;                   // (a robot off the map among them)
     // setPlanForFrontier's heading is the host's libm by the planner's definition: computed from the records the
     // caller receives, the only column that goes up
     std::vector<double> heading((size_t)n);
@@ -3800,6 +3821,23 @@ int roadmap_astar_cols(fs_ctx *c)
     return FS_OK;
 }
 
+// The per-goal staging of a roadmap plan for one robot pose: the xy copy of the goals, getPlan's mode (0 not planned, 1 the robot
+// stands on the goal, 2 searched) and setPlanForFrontier's heading.  Returns whether any goal is searched (the plan needs a tree).
+bool rm_stage_goals(const double robot7[7], size_t n, const double *goal_xyz, const uint8_t *achievable_in, double *goal, uint8_t *mode,
+                    double *head)
+{
+    bool need_tree = false;
+    for (size_t i = 0; i < n; ++i) {
+        const double gx = goal_xyz[3 * i], gy = goal_xyz[3 * i + 1];
+        goal[2 * i] = gx; goal[2 * i + 1] = gy;
+        // getPlan's early return (FrontierRoadmap.cpp:548-554) comes before any search
+        mode[i] = (achievable_in && !achievable_in[i]) ? 0 : (robot7[0] == gx && robot7[1] == gy) ? 1 : 2;
+        head[i] = mode[i] ? nav_heading(robot7, gx, gy) : 0.0;
+        need_tree |= mode[i] == 2;
+    }
+    return need_tree;
+}
+
 // Start node, tree (cached or built), goals staged, the plan kernel: the four columns land in d_rm_out on the context's stream.
 // REFERENCE search: the A* queries instead of the tree (their stats in h_as_io: rm_astar_settle after the synchronisation).
 int roadmap_plan_enqueue(fs_ctx *c, const double robot7[7], int32_t n, const double *goal_xyz, const uint8_t *achievable_in)
@@ -3811,15 +3849,7 @@ int roadmap_plan_enqueue(fs_ctx *c, const double robot7[7], int32_t n, const dou
     FS_HIP(c, c->d_rm_out.ensure(O.total));
     double *goal = reinterpret_cast<double *>(c->h_rm_in.p + i_goal), *head = reinterpret_cast<double *>(c->h_rm_in.p + i_head);
     uint8_t *mode = reinterpret_cast<uint8_t *>(c->h_rm_in.p + i_mode);
-    bool need_tree = false;
-    for (size_t i = 0; i < nn; ++i) {
-        const double gx = goal_xyz[3 * i], gy = goal_xyz[3 * i + 1];
-        goal[2 * i] = gx; goal[2 * i + 1] = gy;
-        // getPlan's early return (FrontierRoadmap.cpp:548-554) comes before any search
-        mode[i] = (achievable_in && !achievable_in[i]) ? 0 : (robot7[0] == gx && robot7[1] == gy) ? 1 : 2;
-        head[i] = mode[i] ? nav_heading(robot7, gx, gy) : 0.0;
-        need_tree |= mode[i] == 2;
-    }
+    const bool need_tree = rm_stage_goals(robot7, nn, goal_xyz, achievable_in, goal, mode, head);
     const int32_t nodes = rm_nodes(c);
     const int32_t root = fs_rm_closest(c->rm_xy.data(), c->rm_key.data(), nodes, c->rm_cell, robot7[0], robot7[1]);
     const bool reference = c->rm_search == FS_ROADMAP_SEARCH_REFERENCE;
@@ -3864,9 +3894,7 @@ int kf_grow(fs_ctx *c, DevBuf<T> &b, size_t used, size_t need)
     FS_HIP(c, nb.ensure(std::max(need, 2 * b.cap)));
     if (used) FS_HIP(c, hipMemcpyAsync(nb.p, b.p, sizeof(T) * used, hipMemcpyDeviceToDevice, c->stream));
     FS_HIP(c, hipStreamSynchronize(c->stream));
-    b.release();
-    b.p = nb.p; b.cap = nb.cap;
-    nb.p = nullptr; nb.cap = 0;
+    b = std::move(nb);
     return FS_OK;
 }
 
@@ -4487,33 +4515,12 @@ int fs_get_frontier_costs_searched_roadmap(fs_ctx *c, const double robot_pose7[7
     rc = check_scoring_state(c, true, with_fisher_information != 0);
     if (rc) return rc;
     bool on_map = false;
-    FsSearchArgs sa{};
-    rc = search_enqueue(c, robot_pose7, lethal_threshold, max_frontier_distance, min_frontier_cluster_size, max_frontier_cluster_size,
-                        0, nullptr, false, &on_map, true, &sa);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
     std::vector<fs_frontier_record> found;
-    int32_t n = 0;
-    if (on_map) {
-        const size_t cells = (size_t)c->nx * c->ny;
-        FS_HIP(c, c->d_fs_black.ensure(cells));
-        if (n_blacklist > 0) {
-            FS_HIP(c, c->d_fs_black_xy.ensure(2 * (size_t)n_blacklist));
-            FS_HIP(c, hipMemcpyAsync(c->d_fs_black_xy.p, blacklist_xy, 16 * (size_t)n_blacklist, hipMemcpyHostToDevice, c->stream));
-        }
-        FS_HIP(c, fs_launch_search_blacklist(sa, c->d_fs_black_xy.p, n_blacklist, c->d_fs_black.p, c->stream));
-        found.resize((size_t)std::min<int32_t>(max_records, 1024));
-        rc = search_results(c, (int32_t)found.size(), found.data(), &n, 0, nullptr, nullptr);
-        if (rc) return rc;
-        *n_frontiers = n;
-        if (n > max_records) return fail(c, FS_E_INVALID, "%d frontiers found, room for %d: no partial ranking", n, max_records);
-        if ((size_t)n > found.size()) {
-            const size_t have = found.size();
-            found.resize((size_t)n);
-            FS_HIP(c, hipMemcpyAsync(found.data() + have, c->d_fs_rec.p + have, sizeof(fs_frontier_record) * ((size_t)n - have), hipMemcpyDeviceToHost, c->stream));
-            FS_HIP(c, hipStreamSynchronize(c->stream));
-        }
-        if (n > 0) std::memcpy(frontiers, found.data(), sizeof(fs_frontier_record) * (size_t)n);
-    }
+    rc = searched_list(c, robot_pose7, lethal_threshold, max_frontier_distance, min_frontier_cluster_size, max_frontier_cluster_size,
+                       n_blacklist, blacklist_xy, max_records, &on_map, n_frontiers, found);
+    if (rc) return rc;
+    const int32_t n = *n_frontiers;
+    if (n > 0) std::memcpy(frontiers, found.data(), sizeof(fs_frontier_record) * (size_t)n);
     // UpdateRoadmapBT on the searched list (a robot off the map found nothing: the update of an empty list)
     RmUpdateOut upd;
     rc = rm_update_core(c, n, c->d_fs_goal.p, 3, robot_pose7, add_robot_pose != 0, &upd);
@@ -4722,43 +4729,12 @@ int fs_roadmap_routes(fs_ctx *c, const double robot_pose7[7], int32_t n, const d
         a.temp = c->d_pi_temp.p; a.temp_bytes = c->d_pi_temp.cap;
         if (fs_launch_pathinfo_offsets(a, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "leg offsets: launch failed"));
         int64_t *hdr = reinterpret_cast<int64_t *>(c->h_pi_out.p + P.hdr);
-        if (leg_bound > 0) {
-            const size_t room = (size_t)leg_bound;
-            if (a.dedup) { FS_HIP(c, c->d_pi_key.ensure(2 * room)); }
-            FS_HIP(c, c->d_pi_idx.ensure(5 * room));
-            FS_HIP(c, c->d_pi_rt.ensure(12 * room));
-            if (dump_leg) { FS_HIP(c, c->d_pi_pose.ensure(7 * room)); FS_HIP(c, c->d_pi_val.ensure(room)); }
-            a.bound = leg_bound;
-            a.key_in = c->d_pi_key.p; a.key_out = c->d_pi_key.p + room;
-            a.wp_in = c->d_pi_idx.p; a.wp_out = a.wp_in + room; a.head = a.wp_out + room; a.rank = a.head + room; a.slot = a.rank + room;
-            a.rt = c->d_pi_rt.p;
-            a.pose7 = dump_leg ? c->d_pi_pose.p : nullptr;
-            a.wp_info = dump_leg ? c->d_pi_val.p : nullptr;
-            if (fs_launch_pathinfo_prepare(a, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "route legs: launch failed"));
-            FS_HIP(c, hipMemcpyAsync(hdr, a.hdr, 16, hipMemcpyDeviceToHost, c->stream));
-        }
+        if (leg_bound > 0 && (rc = pathinfo_prepare(c, a, leg_bound, dump_leg, "route legs", hdr, stop))) return rc;
         // the scoring launch is sized by the number of distinct poses
         FS_HIP(c, hipStreamSynchronize(c->stream));
         legs = leg_bound > 0 ? hdr[0] : 0; distinct = leg_bound > 0 ? hdr[1] : 0;
         c->rt_poses = distinct;
-        if (distinct > 0) {
-            rc = ensure_candidate_scratch(c, (size_t)distinct, false);
-            if (rc) return rc;
-            FsFimArgs fa{};
-            if (const int rc_args = fill_fim_args(c, fa)) return rc_args;
-            fa.n = (int32_t)distinct;
-            fa.info_only = c->opt_special ? 1 : 0;
-            if (fa.info_only && fa.skip32 < 20) fa.skip32 = 20;        // (as fs_score_fim_begin)
-            rc = maybe_split(c, fa, (size_t)distinct, false);
-            if (rc) return stop(rc);
-            fa.Rt = c->d_pi_rt.p;
-            bind_fim_outputs(c, fa);
-            rc = run_fim_tier1(c, fa, nullptr, 0, fa.n << fa.split_shift);
-            if (rc) return stop(rc);
-            rc = run_fim_rest(c, fa);
-            if (rc) return stop(rc);
-            a.info = fa.info_ref;
-        }
+        if (distinct > 0 && (rc = pathinfo_score(c, a, distinct, stop))) return rc;
         if (fs_launch_pathinfo_finish(a, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "route information columns: launch failed"));
         FS_HIP(c, hipMemcpyAsync(c->h_pi_out.p + P.mean, c->d_pi_out.p + P.mean, P.total - P.mean, hipMemcpyDeviceToHost, c->stream));
         if (dump_leg && legs > 0) {
@@ -4768,10 +4744,7 @@ int fs_roadmap_routes(fs_ctx *c, const double robot_pose7[7], int32_t n, const d
     }
     FS_HIP(c, hipStreamSynchronize(c->stream));
     // everything is on the host: the caller's arrays
-    std::memcpy(path_length, c->h_rm_out.p + O.len, 8 * nn);
-    std::memcpy(path_length_m, c->h_rm_out.p + O.len_m, 8 * nn);
-    std::memcpy(path_heading, c->h_rm_out.p + O.head, 8 * nn);
-    std::memcpy(achievable, c->h_rm_out.p + O.ach, nn);
+    plan_columns_to_caller(c->h_rm_out, nn, path_length, path_length_m, path_heading, achievable);
     std::memcpy(route_of, c->h_rt.p + h_of, 4 * nn);
     const int32_t *h_list_len = refine ? reinterpret_cast<const int32_t *>(c->h_rt.p + h_rlen) : h_route_len;
     if (nr > 0) {
@@ -4880,6 +4853,42 @@ void tour_unrank(int64_t rank, int k, int32_t *perm)
     }
 }
 
+// K shortest-path trees of the device roadmap (rm_device_graph has run), one per root, in batches of RM_TOUR_MAX_TREES and in the
+// caller's buffers: d / hops / pred [K][2][nodes] (the single-tree cache of rm_tree is neither read nor replaced), `word` of
+// max(PLAN_BATCH, K) words.  Up to tour_one_wg nodes a batch is one workgroup's loop per tree, not waited for: word[b] will hold the
+// rounds of tree b (negative: not settled) and the caller reads them with its results.  Above, a round per launch, polled (`what`
+// names the trees in poll_rounds' error); *rounds is then what the slowest batch took.  After its quiet round both buffers of a
+// tree hold it: buffer 0 is read.
+int rm_trees_enqueue(fs_ctx *c, const DevBuf<double> &d, const DevBuf<int32_t> &hops, const DevBuf<int32_t> &pred, const DevBuf<int32_t> &word,
+                     const int32_t *roots, int32_t K, const char *what, bool *polled, int64_t *rounds)
+{
+    const int32_t n = rm_nodes(c);
+    const int64_t max_rounds = 2 * (int64_t)n + 2;        // as rm_tree
+    *polled = n > c->tour_one_wg;
+    *rounds = 0;
+    for (int32_t k0 = 0; k0 < K; k0 += RM_TOUR_MAX_TREES) {
+        FsRmTreeBatch B{};
+        const size_t o = 2 * (size_t)n * (size_t)k0;
+        B.t = FsRmTree{n, -1, c->d_rm_xy.p, c->d_rm_trow.p, c->d_rm_tcol.p, {d.p + o, nullptr}, {hops.p + o, nullptr}, {pred.p + o, nullptr}};
+        B.k = std::min<int32_t>(RM_TOUR_MAX_TREES, K - k0);
+        for (int32_t b = 0; b < B.k; ++b) B.root[b] = roots[k0 + b];
+        FS_HIP(c, fs_launch_rm_batch_init(B, c->stream));
+        if (!*polled) {
+            FS_HIP(c, fs_launch_rm_batch_block(B, (int32_t)max_rounds, word.p + k0, c->stream));
+            continue;
+        }
+        const auto launch = [&](int64_t r0, int count) -> int {
+            for (int k = 0; k < count; ++k) FS_HIP(c, fs_launch_rm_batch_round(B, (int32_t)((r0 + k) & 1), word.p + k, c->stream));
+            return FS_OK;
+        };
+        int64_t batch_rounds = 0;
+        const int rc = poll_rounds(c, word.p, PLAN_BATCH, PLAN_BATCH, 1, max_rounds, what, max_rounds, launch, &batch_rounds);
+        if (rc) return rc;
+        *rounds = std::max(*rounds, batch_rounds);
+    }
+    return FS_OK;
+}
+
 // The trees of the batch (one per distinct source root), then the pair kernel and the tour search, all on the stream; the
 // one-workgroup route leaves everything to the caller's single synchronisation, the round-per-launch route polls its rounds.
 // Result, matrix and (one-workgroup route) the trees' rounds are copied to h_tour_out.
@@ -4896,27 +4905,11 @@ int tour_enqueue(fs_ctx *c, const FsRmPairArgs &pa_in, int32_t K, const int32_t 
         int rc = rm_device_graph(c);
         if (rc) return rc;
         FS_HIP(c, c->d_tour_d.ensure(2 * nn * K)); FS_HIP(c, c->d_tour_hops.ensure(2 * nn * K)); FS_HIP(c, c->d_tour_pred.ensure(2 * nn * K));
-        FsRmTreeBatch B{};
-        B.t = FsRmTree{n, -1, c->d_rm_xy.p, c->d_rm_trow.p, c->d_rm_tcol.p, {c->d_tour_d.p, nullptr}, {c->d_tour_hops.p, nullptr},
-                       {c->d_tour_pred.p, nullptr}};
-        B.k = K;
-        for (int32_t b = 0; b < K; ++b) B.root[b] = roots[b];
-        FS_HIP(c, fs_launch_rm_batch_init(B, c->stream));
-        const int64_t max_rounds = 2 * (int64_t)n + 2;        // as rm_tree
-        if (n <= c->tour_one_wg) {
-            FS_HIP(c, fs_launch_rm_batch_block(B, (int32_t)max_rounds, c->d_tour_word.p, c->stream));
+        rc = rm_trees_enqueue(c, c->d_tour_d, c->d_tour_hops, c->d_tour_pred, c->d_tour_word, roots, K, "the tour trees", polled, rounds_out);
+        if (rc) return rc;
+        if (!*polled)
             FS_HIP(c, hipMemcpyAsync(c->h_tour_out.p + kTourOffRounds, c->d_tour_word.p, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost,
                                      c->stream));
-        } else {
-            *polled = true;
-            const auto launch = [&](int64_t r0, int count) -> int {
-                for (int k = 0; k < count; ++k) FS_HIP(c, fs_launch_rm_batch_round(B, (int32_t)((r0 + k) & 1), c->d_tour_word.p + k, c->stream));
-                return FS_OK;
-            };
-            rc = poll_rounds(c, c->d_tour_word.p, PLAN_BATCH, PLAN_BATCH, 1, max_rounds, "the tour trees", max_rounds, launch, rounds_out);
-            if (rc) return rc;
-        }
-        // (after its quiet round both buffers of a tree hold it: buffer 0 is read)
         pa.d = c->d_tour_d.p; pa.pred = c->d_tour_pred.p;
     }
     pa.n_nodes = n; pa.xy = c->d_rm_xy.p;
@@ -5458,20 +5451,12 @@ int fs_fleet_allocate_roadmap(fs_ctx *c, int32_t n_robots, const double *robot_p
     std::memcpy(h + i_goal3, goal_xyz, 24 * nn);
     if (frontier_size) std::memcpy(h + i_fsize, frontier_size, 4 * nn); else std::memset(h + i_fsize, 0, 4 * nn);
     if (blacklisted) std::memcpy(h + i_black, blacklisted, nn); else std::memset(h + i_black, 0, nn);
-    for (size_t i = 0; i < nn; ++i) { goal2[2 * i] = goal_xyz[3 * i]; goal2[2 * i + 1] = goal_xyz[3 * i + 1]; }
-    // every robot's start node, modes and headings as roadmap_plan_enqueue takes them; a tree per distinct start node that a robot
-    // with a goal to search stands at
+    // every robot's start node, modes and headings as roadmap_plan_enqueue takes them (the xy copy of the goals is the same for
+    // every robot); a tree per distinct start node that a robot with a goal to search stands at
     std::vector<int32_t> root((size_t)R), tree((size_t)R, -1), roots;
     for (int32_t r = 0; r < R; ++r) {
         const double *pose = robot_pose7 + 7 * (size_t)r;
-        bool need_tree = false;
-        for (size_t i = 0; i < nn; ++i) {
-            const double gx = goal2[2 * i], gy = goal2[2 * i + 1];
-            const uint8_t m = (pose[0] == gx && pose[1] == gy) ? 1 : 2;
-            mode[(size_t)r * nn + i] = m;
-            head[(size_t)r * nn + i] = nav_heading(pose, gx, gy);
-            need_tree |= m == 2;
-        }
+        const bool need_tree = rm_stage_goals(pose, nn, goal_xyz, nullptr, goal2, mode + (size_t)r * nn, head + (size_t)r * nn);
         root[(size_t)r] = fs_rm_closest(c->rm_xy.data(), c->rm_key.data(), nodes, c->rm_cell, pose[0], pose[1]);
         if (reference || !need_tree || root[(size_t)r] < 0) continue;
         size_t b = 0;
@@ -5528,29 +5513,12 @@ int fs_fleet_allocate_roadmap(fs_ctx *c, int32_t n_robots, const double *robot_p
             FS_HIP(c, hipMemcpyAsync(d_ach + o, src + O.ach, nn, hipMemcpyDeviceToDevice, c->stream));
         }
     } else {
-        // the trees in batches of RM_TOUR_MAX_TREES, with the fleet's own buffers (the single-robot tree cache is neither read nor replaced)
-        const int64_t max_rounds = 2 * (int64_t)nodes + 2;        // as rm_tree
-        block_route = nodes <= c->tour_one_wg;
-        for (int32_t k0 = 0; k0 < K; k0 += RM_TOUR_MAX_TREES) {
-            FsRmTreeBatch B{};
-            const size_t o = 2 * nnodes * (size_t)k0;
-            B.t = FsRmTree{nodes, -1, c->d_rm_xy.p, c->d_rm_trow.p, c->d_rm_tcol.p, {c->d_fl_d.p + o, nullptr}, {c->d_fl_hops.p + o, nullptr},
-                           {c->d_fl_pred.p + o, nullptr}};
-            B.k = std::min<int32_t>(RM_TOUR_MAX_TREES, K - k0);
-            for (int32_t b = 0; b < B.k; ++b) B.root[b] = roots[(size_t)(k0 + b)];
-            FS_HIP(c, fs_launch_rm_batch_init(B, c->stream));
-            if (block_route) {
-                FS_HIP(c, fs_launch_rm_batch_block(B, (int32_t)max_rounds, c->d_fl_word.p + k0, c->stream));
-            } else {
-                const auto launch = [&](int64_t r0, int count) -> int {
-                    for (int k = 0; k < count; ++k) FS_HIP(c, fs_launch_rm_batch_round(B, (int32_t)((r0 + k) & 1), c->d_fl_word.p + k, c->stream));
-                    return FS_OK;
-                };
-                int64_t rounds = 0;
-                rc = poll_rounds(c, c->d_fl_word.p, PLAN_BATCH, PLAN_BATCH, 1, max_rounds, "the fleet's trees", max_rounds, launch, &rounds);
-                if (rc) return rc;
-            }
-        }
+        // the trees, with the fleet's own buffers (the single-robot tree cache is neither read nor replaced)
+        bool polled = false;
+        int64_t rounds = 0;
+        rc = rm_trees_enqueue(c, c->d_fl_d, c->d_fl_hops, c->d_fl_pred, c->d_fl_word, roots.data(), K, "the fleet's trees", &polled, &rounds);
+        if (rc) return rc;
+        block_route = !polled;
         FS_HIP(c, fs_launch_rm_fleet_plan(reinterpret_cast<const FsRmPlanArgs *>(din + i_desc), R, n, c->stream));
     }
     // ---- arrival information, once for the list (achievable_in = all), then every robot's U1 row and the solve where the rows lie

@@ -89,7 +89,10 @@ int  fs_set_option(fs_ctx *ctx, const char *key, double value);
  * the largest query of the last such call, 1023 = queries that took the global route (1021 and 1023 are reset by `reset`);
  * 1030 / 1031 / 1032 = augmentations (step 4), step-5 runs and step-3 primes of the last task allocation solve (the allocator
  * of fitslam_frontier.h; they stay on the device until asked for, so reading them waits for the context's stream; 1031 is at most
- * (R + 1) * (min(R, n) + 1)). */
+ * (R + 1) * (min(R, n) + 1)); 1036 = bytes of device and page-locked memory the buffers of EVERY context of the process hold at
+ * this moment (process-wide like the allocation generation, so "a destroyed context gave everything back" can be asked for exactly
+ * on a device that other processes use too; not in it: memory an FS_POISON build has retired and the two raw scratch blocks the
+ * ranking and the spatial sort grow for themselves). */
 int  fs_get_counter(fs_ctx *ctx, int which, int64_t *value, int reset);
 
 /* ---------------------------------------------------------------- self test */

@@ -1,6 +1,7 @@
 """fs_search_frontiers (FrontierSearch::searchFrom on the device, pieces and goal points included) against the
 oracle's restatement of the reference's search with the oracle's seeds, against the CPU restatement tests/frontier_ref with Nearest
-seeds, bit for bit; fs_get_frontier_costs_searched against fs_search_frontiers -> fs_get_frontier_costs_planned; the refusals."""
+seeds, bit for bit; fs_get_frontier_costs_searched against fs_search_frontiers -> fs_get_frontier_costs_planned (and, for a list
+longer than the first fetch round, the roadmap form against its three stages); the refusals."""
 import numpy as np
 import pytest
 
@@ -192,3 +193,74 @@ def test_python_buffers_grow_to_the_search(fs, scorer):
         assert small.tobytes() == full.tobytes() and ev.tobytes() == every.tobytes() and full.shape[0] > 2
     finally:
         sc.close()
+
+
+def _island_map(n=204, step=6):
+    """Free space with a 2 x 2 unknown island every `step` cells — one frontier component per island, (n / step)^2 of them — and
+    the robot in the middle.  0.3 m between islands: the roadmap update keeps every goal (closer than 0.25 m it drops them) and
+    fills no 1 m cell beyond its 20 nodes."""
+    cells = np.zeros((n, n), np.uint8)
+    for a in range(2):
+        for b in range(2):
+            cells[2 + a::step, 2 + b::step] = 255
+    origin = (-n * 0.05 / 2, -n * 0.05 / 2, 0.0)
+    return cells, origin, 0.05, (origin[0] + (n // 2 + 0.3) * 0.05, origin[1] + (n // 2 + 0.6) * 0.05)
+
+
+def _raw_searched(fs, sc, name, pose, max_size, cap):
+    """fs_get_frontier_costs_searched / _searched_roadmap as C sees them, into arrays filled with a pattern: (rc, n_frontiers, arrays)"""
+    import ctypes as C
+    P = fs.capi
+    out = dict(fr=np.full(cap, 0x5A, np.uint8).repeat(P.FRONTIER_RECORD_DTYPE.itemsize).view(P.FRONTIER_RECORD_DTYPE),
+               rec=np.full(cap, 0x5A, np.uint8).repeat(P.RECORD_DTYPE.itemsize).view(P.RECORD_DTYPE),
+               cost=np.full(cap, -7.0), order=np.full(cap, -7, np.int32))
+    before = {k: v.tobytes() for k, v in out.items()}
+    n = C.c_int32(-1)
+    p7 = (C.c_double * 7)(*[float(v) for v in pose])
+    rc = getattr(sc._L, name)(sc._h, C.byref(p7), 160, 50.0, 1, max_size, 0, 0, None, 0.25, 1.0, 0.5, 0.5, 0, cap, P._p(out["fr"]), C.byref(n),
+                              P._p(out["rec"]), P._p(out["cost"]), None, None, P._p(out["order"]), None)
+    return rc, n.value, all(out[k].tobytes() == before[k] for k in out)
+
+
+def test_searched_list_longer_than_one_fetch_round(fs, oracle):
+    """The one-call forms fetch the found records in a first round of at most 1 024 and the rest in a second: a list of 1 156
+    equals search -> plan -> costs record for record, on the grid planner and on the roadmap; one record short of room, both
+    refuse with the count and write nothing (the roadmap form before it touches the roadmap)."""
+    import dataclasses
+    cells, origin, res, pos = _island_map()
+    mx = 2
+    count = oracle.frontier_search(cells, origin[:2], res, pos, lethal_threshold=160, min_cluster=1, max_cluster=mx,
+                                   max_distance=50.0)["goals"].shape[0]
+    assert count == 34 * 34 > 1024
+    w = dataclasses.replace(fs.synth.make_workload("REF2D", n_cand=16, n_landmarks=2000), cells=cells[None], origin=origin, resolution=res)
+    pose = np.array([pos[0], pos[1], 0.0, 0.0, 0.0, 0.0, 1.0])
+    one, three = fs.FrontierScorer(device=0), fs.FrontierScorer(device=0)
+    try:
+        for sc in (one, three):
+            _setup_scoring(sc, w)
+        fr, _ = three.search_frontiers(pos, max_frontier_cluster_size=mx, want_every=False)
+        assert fr.shape[0] == count
+        goal = np.stack([fr["goal_x"], fr["goal_y"], np.zeros(count)], axis=1)
+
+        def same(got_fr, got, want, what):
+            assert got_fr.tobytes() == fr.tobytes(), what
+            for k in want:                                   # (no Fisher information: every column is exact)
+                assert got[k].tobytes() == want[k].tobytes(), (what, k)
+
+        # refused first, on contexts that have planned nothing yet: nothing is written, the roadmap stays empty
+        for name in ("fs_get_frontier_costs_searched", "fs_get_frontier_costs_searched_roadmap"):
+            rc, n, untouched = _raw_searched(fs, one, name, pose, mx, count - 1)
+            assert (rc, n, untouched) == (fs.capi.FS_E_INVALID, count, True), name
+            assert f"{count} frontiers found, room for {count - 1}: no partial ranking" in one._L.fs_last_error(one._h).decode()
+        assert one.roadmap_graph()["xy"].size == 0
+        want = three.get_frontier_costs_planned(pose, goal, frontier_size=fr["size"])
+        same(*one.get_frontier_costs_searched(pose, max_frontier_cluster_size=mx), want, "planned")
+        three.roadmap_update(goal[:, :2].copy(), pos)
+        got_fr, got = one.get_frontier_costs_searched_roadmap(pose, max_frontier_cluster_size=mx)
+        g1, g3 = one.roadmap_graph(), three.roadmap_graph()
+        for key in ("xy", "key", "row_ptr", "col"):
+            assert g1[key].tobytes() == g3[key].tobytes(), key
+        assert g1["xy"].size > 2 * 1024
+        same(got_fr, got, three.get_frontier_costs_roadmap(pose, goal, frontier_size=fr["size"]), "roadmap")
+    finally:
+        one.close(); three.close()

@@ -182,6 +182,68 @@ def test_fresh_multi_context_equals_a_warmed_single_one(fs):
         warm.close()
 
 
+def _one_call_of_every_family(fs, sc, w):
+    """Stages a small 2-D workload and makes one small call of every family of entry points: each grows buffers of its own."""
+    cells = w.cells[0]
+    free = np.argwhere(cells == 0)
+
+    def centre(k):
+        y, x = free[k % len(free)]
+        return (w.origin[0] + (x + 0.5) * w.resolution, w.origin[1] + (y + 0.5) * w.resolution)
+
+    sc.set_ray_params(**_params(w))
+    sc.upload_grid(w.cells, w.origin, w.resolution)
+    sc.upload_landmarks(w.landmarks)
+    sc.lookup_generate()
+    sc.set_arrival_limits(4000.0, sc.max_arrival()["min_gt"])      # (arrival / 4000 stays inside [0, 1] for every robot of the fleet call)
+    goals, n = w.goals, w.goals.shape[0]
+    pos = centre(len(free) // 2)
+    pose = np.array([pos[0], pos[1], 0.0, 0.0, 0.0, 0.0, 1.0])
+    rec = sc.score_candidates(goals, w.frontier_size, w.blacklisted)
+    sc.get_frontier_costs(goals, np.linspace(0.5, 5.0, n), np.linspace(0.0, 3.0, n), w.frontier_size, w.blacklisted, with_fim=True)
+    sc.score_fim(fs.synth.poses_from_yaw(goals, rec["yaw"]), info_only=True)
+    sc.search_frontiers(pos)
+    sc.plan_paths_information(pose, goals, want_waypoints=True)
+    sc.roadmap_add_nodes(np.array([centre(k * len(free) // 20) for k in range(20)]))
+    sc.roadmap_rebuild()
+    plan = sc.roadmap_plan(pose, goals)
+    sc.roadmap_routes(pose, goals, want_nodes=True, want_legs=True)
+    sc.roadmap_next_goal(pose, goals, plan["path_length_m"], plan["achievable"], fi_pose7=pose)
+    sc.refine_paths(np.repeat([pos], n, axis=0), goals[:, :2])
+    cost = 1.0 + np.arange(2.0 * n).reshape(2, n) % 5.0
+    sc.allocate_tasks(cost, distance=cost[::-1].copy(), method="minpos", want_rank=True)
+    other = centre(len(free) // 4)
+    sc.fleet_allocate_roadmap(np.array([pose, [other[0], other[1], 0.0, 0.0, 0.0, 0.0, 1.0]]), goals, w.frontier_size, w.blacklisted,
+                              want_matrix=True, want_records=True)
+
+
+def test_destroyed_context_gives_back_every_buffer(fs):
+    """Counter 1036 is the bytes the device and page-locked buffers of every context of the process hold.  With one context kept
+    alive, a second one that has served a call of every family holds more, and its destruction brings the figure back to what it
+    was EXACTLY: the buffers free themselves with the context, none is forgotten.  A second cycle peaks where the first did."""
+    import gc
+    gc.collect()             # (a scorer some earlier test dropped unclosed is destroyed now, not in the middle of the count)
+    w = fs.synth.make_small_2d(5, n=64, n_cand=8, n_landmarks=300)
+    keep = fs.FrontierScorer(0)
+    try:
+        keep.upload_grid(w.cells, w.origin, w.resolution)
+        held = keep.get_counter(1036)
+        assert held > 0
+        peaks = []
+        for cycle in range(2):
+            sc = fs.FrontierScorer(0)
+            try:
+                _one_call_of_every_family(fs, sc, w)
+                peaks.append(keep.get_counter(1036))
+            finally:
+                sc.close()
+            assert peaks[-1] > held, cycle
+            assert keep.get_counter(1036) == held, cycle
+        assert peaks[0] == peaks[1]
+    finally:
+        keep.close()
+
+
 def test_fresh_context_tests_under_the_poison_build():
     """The fresh-context tests once more, in a child process, against the FS_POISON development library (fs_capi.hip: a buffer that
     grows is retired instead of freed and both copies are filled with 0xCD — a pointer taken before the growth then fails every

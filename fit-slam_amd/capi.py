@@ -47,7 +47,11 @@ EXPORTED_SYMBOLS = [
     "fs_roadmap_routes",
     "fs_roadmap_update", "fs_get_frontier_costs_searched_roadmap",
     "fs_allocate_tasks", "fs_allocate_tasks_dev", "fs_fleet_allocate_roadmap",
+    "fs_keepout_add_fov", "fs_keepout_add_disc", "fs_keepout_clear", "fs_keepout_get", "fs_mark_lethal_fov", "fs_read_grid_region",
+    "fs_multi_keepout_add_fov", "fs_multi_keepout_add_disc", "fs_multi_keepout_clear", "fs_multi_mark_lethal_fov",
 ]
+FS_KEEPOUT_MAX_ZONES = 1024
+KEEPOUT_FOV, KEEPOUT_DISC = 0, 1
 
 RECORD_DTYPE = np.dtype([("arrival", "<i4"), ("argmax", "<i4"), ("yaw", "<f4"), ("info_ref", "<f4"),
                          ("trace", "<f4"), ("logdet", "<f4"), ("n_visible", "<i4"), ("flags", "<u4")])
@@ -212,6 +216,16 @@ def load_library(build: bool = True):
     L.fs_allocate_tasks.argtypes = [vp, i32, i32, vp, vp, i32, vp, C.POINTER(dbl), vp, vp]
     L.fs_allocate_tasks_dev.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]
     L.fs_fleet_allocate_roadmap.argtypes = [vp, i32, vp, i32, vp, vp, vp, dbl, dbl, dbl, dbl, i32, vp, C.POINTER(dbl), vp, vp, vp, vp, vp]
+    L.fs_keepout_add_fov.argtypes = [vp, dbl, dbl, dbl, dbl, C.POINTER(i32), C.POINTER(i64)]
+    L.fs_keepout_add_disc.argtypes = [vp, dbl, dbl, dbl, C.POINTER(i32), C.POINTER(i64)]
+    L.fs_keepout_clear.argtypes = [vp]
+    L.fs_keepout_get.argtypes = [vp, C.POINTER(i32), vp, vp, vp]
+    L.fs_mark_lethal_fov.argtypes = [vp, C.POINTER(dbl * 7), C.POINTER(dbl * 7), C.POINTER(i32), C.POINTER(i64)]
+    L.fs_read_grid_region.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, i64, i64]
+    L.fs_multi_keepout_add_fov.argtypes = [vp, dbl, dbl, dbl, dbl, C.POINTER(i32), C.POINTER(i64)]
+    L.fs_multi_keepout_add_disc.argtypes = [vp, dbl, dbl, dbl, C.POINTER(i32), C.POINTER(i64)]
+    L.fs_multi_keepout_clear.argtypes = [vp]
+    L.fs_multi_mark_lethal_fov.argtypes = [vp, C.POINTER(dbl * 7), C.POINTER(dbl * 7), C.POINTER(i32), C.POINTER(i64)]
     for name in EXPORTED_SYMBOLS:
         f = getattr(L, name)
         if name not in ("fs_ctx_destroy", "fs_last_error", "fs_multi_destroy", "fs_multi_last_error", "fs_multi_ctx"):
@@ -323,6 +337,57 @@ class FrontierScorer:
         numpy view into the caller's whole map with its strides (nothing packed on the Python side)"""
         ptr, sx, sy, sz, rs, ss, keep = _window_args(window, view)
         self._check(self._L.fs_update_grid_region(self._h, int(x0), int(y0), int(z0), sx, sy, sz, ptr, rs, ss))
+
+    def read_grid_region(self, x0=0, y0=0, z0=0, shape=None, out=None):
+        """fs_read_grid_region: the window [sz][sy][sx] of the staged grid from (x0, y0, z0) on, as a new array of `shape`
+        ((sy, sx) or (sz, sy, sx); default: the rest of the grid) — or written into `out`, which may be a numpy VIEW into a
+        larger array (contiguous along x): its strides are passed on."""
+        if out is None:
+            if shape is None:
+                nz, ny, nx = self._staged_shape()
+                shape = (nz - int(z0), ny - int(y0), nx - int(x0))
+            out = np.zeros(tuple(int(v) for v in shape), dtype=np.uint8)
+        if out.dtype != np.uint8 or not out.flags["WRITEABLE"]:
+            raise ValueError("out must be a writable uint8 array")
+        ptr, sx, sy, sz, rs, ss, keep = _window_args(out, True)
+        self._check(self._L.fs_read_grid_region(self._h, int(x0), int(y0), int(z0), sx, sy, sz, ptr, rs, ss))
+        return out
+
+    # -- keep-out zones (the costmap layer LethalMarker)
+    def keepout_add_fov(self, wx, wy, yaw, height_m=3.5):
+        """fs_keepout_add_fov (addNewMarkedAreaFOV): returns (zone id, distinct cells marked on the staged map)."""
+        zid, n = C.c_int32(), C.c_int64()
+        self._check(self._L.fs_keepout_add_fov(self._h, float(wx), float(wy), float(yaw), float(height_m), C.byref(zid), C.byref(n)))
+        return zid.value, n.value
+
+    def keepout_add_disc(self, wx, wy, radius_m=1.7):
+        """fs_keepout_add_disc (the older layer's addNewMarkedArea): returns (zone id, distinct cells)."""
+        zid, n = C.c_int32(), C.c_int64()
+        self._check(self._L.fs_keepout_add_disc(self._h, float(wx), float(wy), float(radius_m), C.byref(zid), C.byref(n)))
+        return zid.value, n.value
+
+    def keepout_clear(self):
+        """fs_keepout_clear: forgets the zones; cells already painted stay 253 until the map is staged again."""
+        self._check(self._L.fs_keepout_clear(self._h))
+
+    def keepout_get(self, want_mask=True):
+        """fs_keepout_get: (spec [n][5] = kind, wx, wy, yaw, size; n_cells [n]; union mask [ny][nx] or None)."""
+        spec = np.zeros((FS_KEEPOUT_MAX_ZONES, 5), dtype=np.float64)
+        cells = np.zeros(FS_KEEPOUT_MAX_ZONES, dtype=np.int64)
+        mask = None
+        if want_mask and self._grid_shape is not None:
+            mask = np.zeros(self._grid_shape[1:], dtype=np.uint8)
+        n = C.c_int32()
+        self._check(self._L.fs_keepout_get(self._h, C.byref(n), _p(spec), _p(cells), _p(mask)))
+        return spec[:n.value].copy(), cells[:n.value].copy(), mask
+
+    def mark_lethal_fov(self, robot_pose7):
+        """fs_mark_lethal_fov (MarkLethalFOV::tick): returns (blacklisted pose [7], zone id, distinct cells)."""
+        pose = (C.c_double * 7)(*[float(v) for v in robot_pose7])
+        black = (C.c_double * 7)()
+        zid, n = C.c_int32(), C.c_int64()
+        self._check(self._L.fs_mark_lethal_fov(self._h, C.byref(pose), C.byref(black), C.byref(zid), C.byref(n)))
+        return np.array(black[:], dtype=np.float64), zid.value, n.value
 
     def upload_grid_bricks(self, shape_zyx, origin, resolution, brick_xyz, brick_cells, default_value=255):
         nz, ny, nx = shape_zyx
@@ -1156,6 +1221,26 @@ class MultiScorer:
     def update_grid_region(self, x0, y0, z0, window, view=False):
         ptr, sx, sy, sz, rs, ss, keep = _window_args(window, view)
         self._check(self._L.fs_multi_update_grid_region(self._h, int(x0), int(y0), int(z0), sx, sy, sz, ptr, rs, ss))
+
+    def keepout_add_fov(self, wx, wy, yaw, height_m=3.5):
+        zid, n = C.c_int32(), C.c_int64()
+        self._check(self._L.fs_multi_keepout_add_fov(self._h, float(wx), float(wy), float(yaw), float(height_m), C.byref(zid), C.byref(n)))
+        return zid.value, n.value
+
+    def keepout_add_disc(self, wx, wy, radius_m=1.7):
+        zid, n = C.c_int32(), C.c_int64()
+        self._check(self._L.fs_multi_keepout_add_disc(self._h, float(wx), float(wy), float(radius_m), C.byref(zid), C.byref(n)))
+        return zid.value, n.value
+
+    def keepout_clear(self):
+        self._check(self._L.fs_multi_keepout_clear(self._h))
+
+    def mark_lethal_fov(self, robot_pose7):
+        pose = (C.c_double * 7)(*[float(v) for v in robot_pose7])
+        black = (C.c_double * 7)()
+        zid, n = C.c_int32(), C.c_int64()
+        self._check(self._L.fs_multi_mark_lethal_fov(self._h, C.byref(pose), C.byref(black), C.byref(zid), C.byref(n)))
+        return np.array(black[:], dtype=np.float64), zid.value, n.value
 
     def upload_landmarks(self, xyz):
         lm = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)

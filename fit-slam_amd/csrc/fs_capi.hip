@@ -3,6 +3,7 @@
 // table) and the launch sequences.  No CPU compute fallback exists: every scoring entry point
 // launches the HIP kernels of fs_raymarch.hip / fs_fim.hip / fs_rank.hip or fails.
 #include "fs_internal.h"
+#include "fs_keepout.h"
 #include "fs_median_sort.h"
 #include "fs_roadmap_astar.h"
 
@@ -176,6 +177,20 @@ struct GraphEntry {
     bool broken = false;         // capture failed once: this sequence stays on plain launches
 };
 
+// One keep-out zone as the layer stores it (zone_specs_, keepout_layer.hpp): the request, never its cells — those follow from
+// the staged map's geometry.  n_cells: distinct cells it marks on the map staged now.
+struct KoZone {
+    int32_t kind;                // FS_KO_FOV: size = height [m];  FS_KO_DISC: size = radius [m], yaw = 0
+    double wx, wy, yaw, size;
+    int64_t n_cells;
+};
+// the geometry a zone's cells depend on
+struct KoGeom {
+    int32_t nx, ny;
+    double ox, oy, res;
+    bool operator==(const KoGeom &o) const { return nx == o.nx && ny == o.ny && ox == o.ox && oy == o.oy && res == o.res; }
+};
+
 }  // namespace
 
 struct fs_ctx {
@@ -204,6 +219,15 @@ struct fs_ctx {
     int32_t nx = 0, ny = 0, nz = 0;
     double origin[3] = {0, 0, 0};
     double res = 0.0;
+
+    // keep-out zones (fs_keepout.hip): the stored requests; the union of their cells on the staged 2-D map, valid for ko_geom;
+    // the scratch image ONE zone is rasterised into (all zero between calls); ray table and per-zone cell counts
+    std::vector<KoZone> ko_zones;
+    bool ko_mask_valid = false;
+    KoGeom ko_geom{0, 0, 0.0, 0.0, 0.0};
+    DevBuf<uint8_t> d_ko_mask, d_ko_scratch;
+    DevBuf<int32_t> d_ko_rays;
+    DevBuf<unsigned long long> d_ko_counts;
 
     // landmarks
     bool have_lm = false;
@@ -1084,6 +1108,96 @@ int ensure_candidate_scratch(fs_ctx *c, size_t n, bool want_fim21)
     return FS_OK;
 }
 
+// ---------------------------------------------------------------- keep-out zones
+
+// addNewMarkedAreaFOV / addNewMarkedArea for one stored zone on a map of geometry g: its rays appended to `rays` (none when the
+// apex is off the map — the reference's early return, keepout_layer.cpp:205-206 — or the size in cells cannot be converted)
+void ko_zone_rays(const KoZone &z, const KoGeom &g, std::vector<fs_ko_ray> &rays)
+{
+    int32_t ax = 0, ay = 0;
+    uint32_t size_cells = 0;
+    if (!fs_ko_world_to_map(z.wx, z.wy, g.ox, g.oy, g.res, g.nx, g.ny, &ax, &ay)) return;
+    if (!fs_ko_size_in_cells(z.size, g.res, &size_cells)) return;
+    const size_t at = rays.size();
+    rays.resize(at + FS_KO_MAX_RAYS);
+    const int n = z.kind == FS_KO_FOV ? fs_ko_fov_rays(ax, ay, size_cells, z.yaw, g.nx, g.ny, &rays[at])
+                                      : fs_ko_disc_rays(ax, ay, size_cells, g.nx, g.ny, &rays[at]);
+    rays.resize(at + (size_t)n);
+}
+
+// Zones [first, end) rasterised on the 2-D grid of geometry g whose cells are in d_cells: each is marked into the scratch image
+// and folded — painted into the grid, counted, added to the union mask — on its bounding box; one wait for the counts at the
+// end.  A zone is folded on its own because its n_cells are ITS distinct cells, and zones overlap (the robot marks where it
+// keeps getting stuck).  box: the cells [x0, x1] x [y0, y1] written (x1 < x0: none).
+int ko_rasterise(fs_ctx *c, size_t first, const KoGeom &g, int32_t box[4])
+{
+    const size_t n = c->ko_zones.size() - first;
+    std::vector<fs_ko_ray> rays;
+    std::vector<size_t> start(n + 1, 0);
+    for (size_t k = 0; k < n; ++k) {
+        ko_zone_rays(c->ko_zones[first + k], g, rays);
+        start[k + 1] = rays.size();
+    }
+    box[0] = g.nx; box[1] = g.ny; box[2] = -1; box[3] = -1;
+    for (size_t k = 0; k < n; ++k) c->ko_zones[first + k].n_cells = 0;
+    if (rays.empty()) return FS_OK;
+    FS_HIP(c, c->d_ko_rays.ensure(rays.size() * 4));
+    FS_HIP(c, c->d_ko_counts.ensure(FS_KEEPOUT_MAX_ZONES));
+    FS_HIP(c, hipMemcpyAsync(c->d_ko_rays.p, rays.data(), rays.size() * sizeof(fs_ko_ray), hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, hipMemsetAsync(c->d_ko_counts.p, 0, n * sizeof(unsigned long long), c->stream));
+    for (size_t k = 0; k < n; ++k) {
+        if (start[k + 1] == start[k]) continue;
+        int32_t x0 = g.nx, y0 = g.ny, x1 = -1, y1 = -1;
+        for (size_t r = start[k]; r < start[k + 1]; ++r) {
+            x0 = std::min(x0, std::min(rays[r].ax, rays[r].ex)); x1 = std::max(x1, std::max(rays[r].ax, rays[r].ex));
+            y0 = std::min(y0, std::min(rays[r].ay, rays[r].ey)); y1 = std::max(y1, std::max(rays[r].ay, rays[r].ey));
+        }
+        FS_HIP(c, fs_launch_keepout_mark(c->d_ko_rays.p + 4 * start[k], (int64_t)(start[k + 1] - start[k]), c->d_ko_scratch.p, g.nx, g.ny, c->stream));
+        FS_HIP(c, fs_launch_keepout_fold(c->d_ko_scratch.p, c->d_ko_mask.p, c->d_cells.p, g.nx, g.ny, x0, y0, x1 - x0 + 1, y1 - y0 + 1,
+                                         c->d_ko_counts.p + k, c->stream));
+        box[0] = std::min(box[0], x0); box[1] = std::min(box[1], y0); box[2] = std::max(box[2], x1); box[3] = std::max(box[3], y1);
+    }
+    std::vector<unsigned long long> counts(n, 0);
+    FS_HIP(c, hipMemcpyAsync(counts.data(), c->d_ko_counts.p, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));              // (the ray table and the counts are this call's)
+    for (size_t k = 0; k < n; ++k) c->ko_zones[first + k].n_cells = (int64_t)counts[k];
+    return FS_OK;
+}
+
+// matchSize (keepout_layer.cpp:184-199): the cache is dropped and every stored zone rasterised again for geometry g.  The
+// reference's loop there calls addNewMarkedAreaFOV, which pushes onto zone_specs_ WHILE the loop iterates it — undefined
+// behaviour, and duplicate zones where it survives.  Not restated: one stored request stays one zone.
+int ko_rebuild(fs_ctx *c, const KoGeom &g, int32_t box[4])
+{
+    const size_t cells = (size_t)g.nx * (size_t)g.ny;
+    c->ko_mask_valid = false;
+    FS_HIP(c, c->d_ko_mask.ensure(cells)); FS_HIP(c, c->d_ko_scratch.ensure(cells));
+    FS_HIP(c, hipMemsetAsync(c->d_ko_mask.p, 0, cells, c->stream));
+    FS_HIP(c, hipMemsetAsync(c->d_ko_scratch.p, 0, cells, c->stream));
+    const int rc = ko_rasterise(c, 0, g, box);
+    if (rc) return rc;
+    c->ko_geom = g;
+    c->ko_mask_valid = true;
+    return FS_OK;
+}
+
+// The layer's cycle after a snapshot (fs_upload_grid, fs_upload_grid_bricks): the new cells are on the device, every zone is
+// painted into them — from the union mask when the geometry is the one it was cut for, else after matchSize.  A 3-D grid is
+// staged unmarked (the layer is a 2-D costmap's): the zones are kept and mark nothing.  Callers skip this with no zone stored.
+int ko_after_snapshot(fs_ctx *c, int32_t nx, int32_t ny, int32_t nz, const double origin_xyz[3], double resolution)
+{
+    if (nz != 1) {
+        c->ko_mask_valid = false;
+        for (KoZone &z : c->ko_zones) z.n_cells = 0;
+        return FS_OK;
+    }
+    const KoGeom g{nx, ny, origin_xyz[0], origin_xyz[1], resolution};
+    int32_t box[4];
+    if (!c->ko_mask_valid || !(c->ko_geom == g)) return ko_rebuild(c, g, box);
+    FS_HIP(c, fs_launch_keepout_apply(c->d_ko_mask.p, c->d_cells.p, nx, ny, 0, 0, nx, ny, nullptr, c->stream));
+    return FS_OK;
+}
+
 }  // namespace
 
 // ================================================================== C ABI
@@ -1280,6 +1394,10 @@ int fs_upload_grid(fs_ctx *c, const uint8_t *cells, int32_t nx, int32_t ny, int3
     ++c->grid_gen;
     FS_HIP(c, c->d_cells.ensure((size_t)total));
     FS_HIP(c, hipMemcpyAsync(c->d_cells.p, cells, (size_t)total, hipMemcpyHostToDevice, c->stream));
+    if (!c->ko_zones.empty()) {
+        const int rc = ko_after_snapshot(c, nx, ny, nz, origin_xyz, resolution);
+        if (rc) return rc;
+    }
     {
         const int rc = retile_grid(c, nx, ny, nz);
         if (rc) return rc;
@@ -1321,6 +1439,9 @@ int fs_update_grid_region(fs_ctx *c, int32_t x0, int32_t y0, int32_t z0, int32_t
             std::memcpy(c->h_win.p + ((size_t)z * sy + y) * sx, cells + (size_t)z * (size_t)slice_stride + (size_t)y * (size_t)row_stride, (size_t)sx);
     FS_HIP(c, hipMemcpyAsync(c->d_win.p, c->h_win.p, total, hipMemcpyHostToDevice, c->stream));
     FS_HIP(c, fs_launch_window_scatter(c->d_win.p, c->d_cells.p, c->nx, c->ny, x0, y0, z0, sx, sy, sz, c->stream));
+    // (the keep-out layer runs last in the cycle and paints its zones again: inside the window is all that changed)
+    if (!c->ko_zones.empty() && c->ko_mask_valid)
+        FS_HIP(c, fs_launch_keepout_apply(c->d_ko_mask.p, c->d_cells.p, c->nx, c->ny, x0, y0, sx, sy, nullptr, c->stream));
     if (c->have_cls) {
         const int b0[3] = {x0 >> 3, y0 >> 3, z0 >> 3};
         const int nb[3] = {((x0 + sx - 1) >> 3) - b0[0] + 1, ((y0 + sy - 1) >> 3) - b0[1] + 1, ((z0 + sz - 1) >> 3) - b0[2] + 1};
@@ -1362,6 +1483,10 @@ int fs_upload_grid_bricks(fs_ctx *c, int32_t nx, int32_t ny, int32_t nz, const d
         FS_HIP(c, hipStreamSynchronize(c->stream));
         if (d_bc.cap > ((size_t)64 << 20)) { d_bc.release(); d_xyz.release(); }   // a whole-map brick list (C5: 385 MB) is not worth keeping
         if (bad) { c->have_grid = false; return fail(c, FS_E_INVALID, "a brick lies outside the grid"); }
+    }
+    if (!c->ko_zones.empty()) {
+        const int rc = ko_after_snapshot(c, nx, ny, nz, origin_xyz, resolution);
+        if (rc) return rc;
     }
     {
         const int rc = retile_grid(c, nx, ny, nz);
@@ -5553,6 +5678,151 @@ int fs_fleet_allocate_roadmap(fs_ctx *c, int32_t n_robots, const double *robot_p
     if (weighted_cost) std::memcpy(weighted_cost, ho + o_cost, 8 * rn);
     if (path_length_m) std::memcpy(path_length_m, ho + o_lenm, 8 * rn);
     if (achievable) std::memcpy(achievable, ho + o_ach, rn);
+    return FS_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ keep-out zones (fs_keepout.hip)
+
+namespace {
+
+// A new zone: stored; on a staged 2-D grid rasterised, painted and counted on its bounding box, and the class image re-cut
+// for the bricks of that box.  Cached arrival limits stay (as for fs_update_grid_region: the fan does not depend on the cells).
+int ko_add(fs_ctx *c, int32_t kind, double wx, double wy, double yaw, double size_m, int32_t *zone_id, int64_t *n_cells)
+{
+    if (!c) return FS_E_INVALID;
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!std::isfinite(wx) || !std::isfinite(wy) || !std::isfinite(yaw) || !std::isfinite(size_m) || !(size_m >= 0.0))
+        return fail(c, FS_E_INVALID, "a keep-out zone needs a finite position and yaw and a finite size >= 0");
+    if (c->have_grid && c->nz != 1) return fail(c, FS_E_INVALID, "keep-out zones are defined on a 2-D costmap (nz == 1)");
+    uint32_t size_cells = 0;
+    if (c->have_grid && !fs_ko_size_in_cells(size_m, c->res, &size_cells))
+        return fail(c, FS_E_INVALID, "the zone's size is 2^31 cells or more (the reference's conversion to unsigned int is undefined)");
+    if (c->ko_zones.size() >= (size_t)FS_KEEPOUT_MAX_ZONES) return fail(c, FS_E_INVALID, "at most %d keep-out zones per context", FS_KEEPOUT_MAX_ZONES);
+    c->ko_zones.push_back(KoZone{kind, wx, wy, yaw, size_m, 0});
+    const size_t id = c->ko_zones.size() - 1;
+    if (c->have_grid) {
+        const KoGeom g{c->nx, c->ny, c->origin[0], c->origin[1], c->res};
+        int32_t box[4];
+        const int rc = c->ko_mask_valid ? ko_rasterise(c, id, g, box) : ko_rebuild(c, g, box);
+        if (rc) { c->ko_zones.pop_back(); c->ko_mask_valid = false; return rc; }
+        if (box[2] >= box[0]) {
+            if (c->have_cls) {
+                const int b0[3] = {box[0] >> 3, box[1] >> 3, 0};
+                const int nb[3] = {(box[2] >> 3) - b0[0] + 1, (box[3] >> 3) - b0[1] + 1, 1};
+                FS_HIP(c, fs_launch_classify_region(c->d_cells.p, c->d_cls.p, c->nx, c->ny, c->nz, c->cls_ranges[0], c->cls_ranges[1], c->cls_ranges[2],
+                                                    c->cls_ranges[3], b0, nb, c->stream));
+            }
+            c->have_sparse = false;
+            ++c->grid_gen;
+            ++c->epoch;
+        }
+    }
+    if (zone_id) *zone_id = (int32_t)id;
+    if (n_cells) *n_cells = c->ko_zones[id].n_cells;
+    return FS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fs_keepout_add_fov(fs_ctx *c, double wx, double wy, double yaw, double height_m, int32_t *zone_id, int64_t *n_cells)
+{
+    return ko_add(c, FS_KO_FOV, wx, wy, yaw, height_m, zone_id, n_cells);
+}
+
+int fs_keepout_add_disc(fs_ctx *c, double wx, double wy, double radius_m, int32_t *zone_id, int64_t *n_cells)
+{
+    return ko_add(c, FS_KO_DISC, wx, wy, 0.0, radius_m, zone_id, n_cells);
+}
+
+int fs_keepout_clear(fs_ctx *c)
+{
+    if (!c) return FS_E_INVALID;
+    c->ko_zones.clear();
+    c->ko_mask_valid = false;
+    return FS_OK;
+}
+
+int fs_keepout_get(fs_ctx *c, int32_t *n_zones, double *spec, int64_t *n_cells, uint8_t *mask)
+{
+    if (!c || !n_zones) return FS_E_INVALID;
+    FS_HIP(c, hipSetDevice(c->device));
+    *n_zones = (int32_t)c->ko_zones.size();
+    for (size_t k = 0; k < c->ko_zones.size(); ++k) {
+        const KoZone &z = c->ko_zones[k];
+        if (spec) { spec[5 * k] = (double)z.kind; spec[5 * k + 1] = z.wx; spec[5 * k + 2] = z.wy; spec[5 * k + 3] = z.yaw; spec[5 * k + 4] = z.size; }
+        if (n_cells) n_cells[k] = z.n_cells;
+    }
+    if (mask) {
+        if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+        const size_t cells = (size_t)c->nx * (size_t)c->ny;
+        if (c->ko_mask_valid) {
+            FS_HIP(c, hipMemcpyAsync(mask, c->d_ko_mask.p, cells, hipMemcpyDeviceToHost, c->stream));
+            FS_HIP(c, hipStreamSynchronize(c->stream));
+        } else {
+            std::memset(mask, 0, cells);
+        }
+    }
+    return FS_OK;
+}
+
+// MarkLethalFOV::tick (FisherInfoBTPlugin.cpp:148-182) with blacklistFrontier (:93-103); `float` as there
+int fs_mark_lethal_fov(fs_ctx *c, const double robot_pose7[7], double blacklist_pose7[7], int32_t *zone_id, int64_t *n_cells)
+{
+    if (!c || !robot_pose7) return FS_E_INVALID;
+    for (int i = 0; i < 7; ++i)
+        if (!std::isfinite(robot_pose7[i])) return fail(c, FS_E_INVALID, "the robot pose must be finite");
+    const double robotYaw = yaw_of_quaternion(robot_pose7 + 3);                                  // :158
+    if (!std::isfinite(robotYaw)) return fail(c, FS_E_INVALID, "the robot pose has no yaw (zero quaternion)");
+    const float blacklist_x = (float)(robot_pose7[0] + (2.5 * std::cos(robotYaw)));               // :159-160
+    const float blacklist_y = (float)(robot_pose7[1] + (2.5 * std::sin(robotYaw)));
+    const float blacklist_x_fov = (float)(robot_pose7[0] + (0.8 * std::cos(robotYaw)));           // :162-163
+    const float blacklist_y_fov = (float)(robot_pose7[1] + (0.8 * std::sin(robotYaw)));
+    // addNewMarkedAreaFOV(req->lethal_point.x, req->lethal_point.y, req->yaw, 3.5)  (keepout_layer.cpp:174)
+    const int rc = ko_add(c, FS_KO_FOV, (double)blacklist_x_fov, (double)blacklist_y_fov, robotYaw, 3.5, zone_id, n_cells);
+    if (rc) return rc;
+    if (blacklist_pose7) {
+        blacklist_pose7[0] = (double)blacklist_x + (1.7 * std::cos(robotYaw));                   // :96-98; the goal point's z is 0
+        blacklist_pose7[1] = (double)blacklist_y + (1.7 * std::sin(robotYaw));
+        blacklist_pose7[2] = 0.0;
+        // eulerToQuat(0, 0, robotYaw + M_PI): tf2's setRPY with roll = pitch = 0, then normalize() (GeometryUtils.hpp:49-61)
+        const double half = (robotYaw + M_PI) * 0.5, z = std::sin(half), w = std::cos(half);
+        const double inv = 1.0 / std::sqrt(z * z + w * w);
+        blacklist_pose7[3] = 0.0; blacklist_pose7[4] = 0.0; blacklist_pose7[5] = z * inv; blacklist_pose7[6] = w * inv;
+    }
+    return FS_OK;
+}
+
+// fs_update_grid_region's mirror: the window is gathered into a packed buffer on the device, copied to page-locked memory in
+// one transfer and laid out with the caller's strides
+int fs_read_grid_region(fs_ctx *c, int32_t x0, int32_t y0, int32_t z0, int32_t sx, int32_t sy, int32_t sz,
+                        uint8_t *cells, int64_t row_stride, int64_t slice_stride)
+{
+    if (!c) return FS_E_INVALID;
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (sx < 0 || sy < 0 || sz < 0) return fail(c, FS_E_INVALID, "negative window size");
+    if (x0 < 0 || y0 < 0 || z0 < 0 || (int64_t)x0 + sx > c->nx || (int64_t)y0 + sy > c->ny || (int64_t)z0 + sz > c->nz)
+        return fail(c, FS_E_INVALID, "window [%d,%lld) x [%d,%lld) x [%d,%lld) leaves the %d x %d x %d grid", x0, (long long)x0 + sx, y0, (long long)y0 + sy,
+                    z0, (long long)z0 + sz, c->nx, c->ny, c->nz);
+    if (sx == 0 || sy == 0 || sz == 0) return FS_OK;
+    if (!cells) return FS_E_INVALID;
+    if (row_stride == 0) row_stride = sx;
+    if (slice_stride == 0) slice_stride = row_stride * (int64_t)sy;
+    if (row_stride < sx || slice_stride < row_stride * (int64_t)(sy - 1) + sx) return fail(c, FS_E_INVALID, "window strides smaller than the window");
+    const size_t total = (size_t)sx * (size_t)sy * (size_t)sz;
+    FS_HIP(c, c->h_win.ensure(total));
+    FS_HIP(c, c->d_win.ensure(total));
+    FS_HIP(c, fs_launch_window_gather(c->d_cells.p, c->d_win.p, c->nx, c->ny, x0, y0, z0, sx, sy, sz, c->stream));
+    FS_HIP(c, hipMemcpyAsync(c->h_win.p, c->d_win.p, total, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    for (int32_t z = 0; z < sz; ++z)
+        for (int32_t y = 0; y < sy; ++y)
+            std::memcpy(cells + (size_t)z * (size_t)slice_stride + (size_t)y * (size_t)row_stride, c->h_win.p + ((size_t)z * sy + y) * sx, (size_t)sx);
+    if (c->h_win.cap > ((size_t)64 << 20)) { c->h_win.release(); c->d_win.release(); }   // (a window of map size: not worth keeping)
     return FS_OK;
 }
 

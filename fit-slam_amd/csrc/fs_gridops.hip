@@ -150,6 +150,16 @@ __global__ void fs_window_scatter_kernel(const uint8_t *__restrict__ win, uint8_
     }
 }
 
+// ... and back: the window at (x0, y0, z0) of the row-major image, packed [sz][sy][sx]
+__global__ void fs_window_gather_kernel(const uint8_t *__restrict__ grid, uint8_t *__restrict__ win, int nx, int ny,
+                                        int x0, int y0, int z0, int sx, int sy, long long total)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % sx), y = (int)((i / sx) % sy), z = (int)(i / ((long long)sx * sy));
+        win[i] = grid[((size_t)(z0 + z) * ny + (size_t)(y0 + y)) * nx + (size_t)(x0 + x)];
+    }
+}
+
 }  // namespace
 
 size_t fs_class_image_words(int nx, int ny, int nz)
@@ -185,7 +195,17 @@ hipError_t fs_launch_window_scatter(const uint8_t *d_window, uint8_t *d_grid, in
     return hipGetLastError();
 }
 
-hipError_t fs_launch_frontier_pair(int n, const float *lx, const float *ly, const float *lz, int m, const float *d_Rt,
+hipError_t fs_launch_window_gather(const uint8_t *d_grid, uint8_t *d_window, int nx, int ny, int x0, int y0, int z0,
+                                   int sx, int sy, int sz, hipStream_t s)
+{
+    const long long total = (long long)sx * sy * sz;
+    if (total <= 0) return hipSuccess;
+    const int blocks = (int)std::min<long long>((total + 255) / 256, 65535ll * 16);
+    hipLaunchKernelGGL(fs_window_gather_kernel, dim3(blocks), dim3(256), 0, s, d_grid, d_window, nx, ny, x0, y0, z0, sx, sy, total);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_frontier_pair(int n,const float *lx, const float *ly, const float *lz, int m, const float *d_Rt,
                                    const double *d_tri, float *d_out, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;

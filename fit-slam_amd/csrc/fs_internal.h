@@ -54,6 +54,20 @@ hipError_t fs_launch_classify_region(const uint8_t *d_cells, uint32_t *d_cls, in
                                      int trace_min, int trace_max, const int brick0[3], const int n_bricks[3], hipStream_t s);
 hipError_t fs_launch_window_scatter(const uint8_t *d_window, uint8_t *d_grid, int nx, int ny, int x0, int y0, int z0,
                                     int sx, int sy, int sz, hipStream_t s);
+// ... and its mirror: the window at (x0, y0, z0) of the row-major image, packed [sz][sy][sx] (fs_read_grid_region)
+hipError_t fs_launch_window_gather(const uint8_t *d_grid, uint8_t *d_window, int nx, int ny, int x0, int y0, int z0,
+                                   int sx, int sy, int sz, hipStream_t s);
+
+// keep-out zones (fs_keepout.hip).  mark: one lane per ray {ax, ay, ex, ey} of d_rays [n_rays][4], each walks
+// its line (fs_keepout.h) and stores 1 into d_image [ny][nx]; a ray with an end off the map is skipped.  apply: over the
+// rectangle [x0, x0+sx) x [y0, y0+sy) of a 2-D grid, cells[i] = src[i] ? 253 : cells[i]; d_count (may be NULL) += cells of src
+// in the rectangle.  fold = the same for ONE zone rasterised into the scratch image d_src: its cells also enter the union
+// mask d_mask and leave d_src, which is all zero again afterwards.
+hipError_t fs_launch_keepout_mark(const int32_t *d_rays, int64_t n_rays, uint8_t *d_image, int nx, int ny, hipStream_t s);
+hipError_t fs_launch_keepout_apply(const uint8_t *d_mask, uint8_t *d_cells, int nx, int ny, int x0, int y0, int sx, int sy,
+                                   unsigned long long *d_count, hipStream_t s);
+hipError_t fs_launch_keepout_fold(uint8_t *d_src, uint8_t *d_mask, uint8_t *d_cells, int nx, int ny, int x0, int y0, int sx, int sy,
+                                  unsigned long long *d_count, hipStream_t s);
 
 struct FsRayArgs {
     FsGridDev grid;

@@ -218,6 +218,36 @@ int fs_multi_update_grid_region(fs_multi *m, int32_t x0, int32_t y0, int32_t z0,
     return for_all_parallel(m, "fs_update_grid_region", [&](fs_ctx *c) { return fs_update_grid_region(c, x0, y0, z0, sx, sy, sz, cells, row_stride, slice_stride); });
 }
 
+int fs_multi_keepout_add_fov(fs_multi *m, double wx, double wy, double yaw, double height_m, int32_t *zone_id, int64_t *n_cells)
+{
+    // (every member stores the same list on the same map: member 0's answer is every member's)
+    return for_all_parallel(m, "fs_keepout_add_fov", [&](fs_ctx *c) {
+        const bool first = c == m->ctx[0];
+        return fs_keepout_add_fov(c, wx, wy, yaw, height_m, first ? zone_id : nullptr, first ? n_cells : nullptr);
+    });
+}
+
+int fs_multi_keepout_add_disc(fs_multi *m, double wx, double wy, double radius_m, int32_t *zone_id, int64_t *n_cells)
+{
+    return for_all_parallel(m, "fs_keepout_add_disc", [&](fs_ctx *c) {
+        const bool first = c == m->ctx[0];
+        return fs_keepout_add_disc(c, wx, wy, radius_m, first ? zone_id : nullptr, first ? n_cells : nullptr);
+    });
+}
+
+int fs_multi_keepout_clear(fs_multi *m)
+{
+    return for_all_parallel(m, "fs_keepout_clear", [&](fs_ctx *c) { return fs_keepout_clear(c); });
+}
+
+int fs_multi_mark_lethal_fov(fs_multi *m, const double robot_pose7[7], double blacklist_pose7[7], int32_t *zone_id, int64_t *n_cells)
+{
+    return for_all_parallel(m, "fs_mark_lethal_fov", [&](fs_ctx *c) {
+        const bool first = c == m->ctx[0];
+        return fs_mark_lethal_fov(c, robot_pose7, first ? blacklist_pose7 : nullptr, first ? zone_id : nullptr, first ? n_cells : nullptr);
+    });
+}
+
 int fs_multi_upload_landmarks(fs_multi *m, const float *xyz, int32_t n_landmarks)
 {
     if (!m || (n_landmarks > 0 && !xyz) || n_landmarks < 0) return FS_E_INVALID;

@@ -128,9 +128,12 @@ int fs_upload_grid_bricks(fs_ctx *ctx, int32_t nx, int32_t ny, int32_t nz, const
                           uint8_t default_value, int64_t n_bricks, const int32_t *brick_xyz, const uint8_t *brick_cells);
 
 /* A WINDOW of the staged map rewritten in place — what a costmap update cycle does to the master grid: every layer's
- * `updateCosts(master_grid, min_i, min_j, max_i, max_j)` writes only inside the cycle's bounds through `getCharMap()` (the
- * reference's own layers: DEP/src/nav2_plugins/lethal_marker.cpp:305-325, fit_slam2_nav2_plugins/plugins/keepout_layer.cpp:279-300;
- * the costmap is a rolling / bounded-update one, fit_slam2/params/active_slam_nav2_params.yaml:124).  The window is cells
+ * `updateCosts(master_grid, min_i, min_j, max_i, max_j)` writes inside the cycle's bounds through `getCharMap()` (the costmap
+ * is a rolling / bounded-update one, fit_slam2/params/active_slam_nav2_params.yaml:124) — with ONE exception among the
+ * reference's own layers: LethalMarker::updateCosts ignores min_i..max_j and writes every cell of every keep-out zone on every
+ * cycle (DEP/src/nav2_plugins/lethal_marker.cpp:305-325, fit_slam2_nav2_plugins/plugins/keepout_layer.cpp:279-300).  A zone
+ * outside the window is therefore on the host's master grid and not in the window: forward the zone itself (fs_keepout_add_fov
+ * below), and this call paints the stored zones again inside the window it wrote.  The window is cells
  * [x0, x0+sx) x [y0, y0+sy) x [z0, z0+sz) of the grid fs_upload_grid staged (same shape, origin and resolution: a map that
  * moved or was resized is a new snapshot).  `cells` points at the window's first cell, x fastest; row_stride / slice_stride are
  * the byte distances between its rows / z slices — pass `getCharMap() + y0 * size_x + x0` with row_stride = size_x to send a
@@ -140,6 +143,54 @@ int fs_upload_grid_bricks(fs_ctx *ctx, int32_t nx, int32_t ny, int32_t nz, const
  * map, bit for bit.  An empty window is a no-op; one that leaves the grid is refused (FS_E_INVALID), nothing written. */
 int fs_update_grid_region(fs_ctx *ctx, int32_t x0, int32_t y0, int32_t z0, int32_t sx, int32_t sy, int32_t sz,
                           const uint8_t *cells, int64_t row_stride, int64_t slice_stride);
+
+/* The window [x0, x0+sx) x [y0, y0+sy) x [z0, z0+sz) of the staged grid copied back to the host: the mirror of
+ * fs_update_grid_region (same window rules and strides; 2-D and 3-D grids).  What `getCharMap()` shows of the master grid after
+ * a cycle; nothing on the device changes. */
+int fs_read_grid_region(fs_ctx *ctx, int32_t x0, int32_t y0, int32_t z0, int32_t sx, int32_t sy, int32_t sz,
+                        uint8_t *cells, int64_t row_stride, int64_t slice_stride);
+
+/* ---------------------------------------------------------------- keep-out zones (costmap layer LethalMarker)
+ *
+ * Replaces the costmap layer fit_slam2_nav2_plugins::LethalMarker (fit_slam2_nav2_plugins/plugins/keepout_layer.cpp) on the
+ * staged 2-D grid (nz == 1).  The context stores every zone as its REQUEST (zone_specs_) and rasterises it exactly as the layer
+ * does: a fan of lines from the apex cell to 20 sampled base cells (getPointsInIsoscelesTriangle :74-126) or to 360 cells of a
+ * circle (getPointsInSemiCircle, DEP/src/nav2_plugins/lethal_marker.cpp:51-72), each walked with rayTraceGeneric (:13-41) —
+ * NOT a filled shape: the cells between the rays stay as they are.  Every cell of every zone holds cost 253 (markCells
+ * :212-218) after each staging call, as after each cycle of the layer (updateCosts :279-300): fs_upload_grid and
+ * fs_upload_grid_bricks paint all zones into the new snapshot, fs_update_grid_region paints them again inside its window.  A
+ * snapshot with another shape, origin or resolution re-rasterises the stored requests first (matchSize :184-199).
+ * Deviations, both deliberate: (1) matchSize's loop pushes onto zone_specs_ while iterating it (undefined behaviour, duplicate
+ * zones where it survives) — here one request stays one zone; (2) the reference's master grid is re-derived every cycle, the
+ * staged grid is not: fs_keepout_clear forgets the zones but CANNOT restore the cells they painted — stage the map again.
+ * With no zone stored, every staging call does exactly what it does without this layer.
+ *   - a zone added before any grid is staged is stored and painted by the first snapshot
+ *   - a zone whose apex is off the map is stored with *n_cells = 0 (worldToMap fails: the early return :205-206) and gets its
+ *     cells when a later snapshot contains the apex
+ *   - non-finite arguments, a negative size, or a size of 2^31 cells or more (the reference's conversion to `unsigned int` is
+ *     undefined) are refused with FS_E_INVALID, nothing stored; so is a new zone while a 3-D grid (nz > 1) is staged
+ *   - a 3-D snapshot with zones stored is staged unmarked: the zones are kept and report n_cells = 0
+ *   - at most FS_KEEPOUT_MAX_ZONES zones per context; one more is refused with FS_E_INVALID
+ * zone_id (index in the order of the requests) and n_cells (DISTINCT cells the zone marks on the staged map) may be NULL. */
+#define FS_KEEPOUT_MAX_ZONES 1024
+/* Replaces LethalMarker::addNewMarkedAreaFOV(center_wx, center_wy, angleYaw, height) (keepout_layer.cpp:201-210), the body of
+ * the `mark_lethal_zone` service (:171-176, which passes height 3.5). */
+int fs_keepout_add_fov(fs_ctx *ctx, double wx, double wy, double yaw, double height_m, int32_t *zone_id, int64_t *n_cells);
+/* Replaces LethalMarker::addNewMarkedArea(center_wx, center_wy, radius) of the older layer
+ * (DEP/src/nav2_plugins/lethal_marker.cpp:218-226; its service :193-198). */
+int fs_keepout_add_disc(fs_ctx *ctx, double wx, double wy, double radius_m, int32_t *zone_id, int64_t *n_cells);
+/* Forgets every zone (the reference has no counterpart short of re-creating the layer).  Cells already painted stay 253. */
+int fs_keepout_clear(fs_ctx *ctx);
+/* The layer's state: *n_zones; spec [n][5] = kind (0 FOV, 1 disc), wx, wy, yaw, size [m] (zone_specs_); n_cells [n]; mask
+ * [ny][nx] = 1 where any zone marks the staged map (the union of latest_cells_to_mark_index_; all 0 on a 3-D grid).  spec,
+ * n_cells and mask may be NULL; arrays of FS_KEEPOUT_MAX_ZONES entries always suffice. */
+int fs_keepout_get(fs_ctx *ctx, int32_t *n_zones, double *spec, int64_t *n_cells, uint8_t *mask);
+/* Replaces MarkLethalFOV::tick (fisher_information_plugins/src/fisher_information/FisherInfoBTPlugin.cpp:148-182) without the
+ * service round trip: yaw of robot_pose7 (x, y, z, qx, qy, qz, qw); a FOV zone of height 3.5 m with its apex 0.8 m ahead of the
+ * robot, the apex rounded to `float` as there (:162-163); blacklist_pose7 (may be NULL) = the pose blacklistFrontier (:93-103)
+ * appends to `posearray_blacklisted_region`: the point 2.5 m ahead (rounded to float, :159-160) moved 1.7 m further along the
+ * yaw, z = 0, orientation yaw + pi about Z.  Publishing it is the caller's job. */
+int fs_mark_lethal_fov(fs_ctx *ctx, const double robot_pose7[7], double blacklist_pose7[7], int32_t *zone_id, int64_t *n_cells);
 
 /* Frontier-cell predicate of FrontierSearch::isNewFrontierCell (DEP/src/FrontierSearch.cpp:218-249; isFree / isLethal /
  * isUnknown: DEP/include/.../FrontierSearch.hpp:129-142; frontierSearch/lethal_threshold 160) evaluated for every cell
@@ -357,6 +408,13 @@ int  fs_multi_set_ray_params(fs_multi *m, const fs_ray_params *p);
 int  fs_multi_upload_grid(fs_multi *m, const uint8_t *cells, int32_t nx, int32_t ny, int32_t nz, const double origin_xyz[3], double resolution);
 int  fs_multi_update_grid_region(fs_multi *m, int32_t x0, int32_t y0, int32_t z0, int32_t sx, int32_t sy, int32_t sz,
                                  const uint8_t *cells, int64_t row_stride, int64_t slice_stride);   /* the window on every device */
+/* the keep-out layer of every member (fs_keepout_add_fov / _add_disc / _clear, fs_mark_lethal_fov: the same request and the
+   same map on each, so the same cells; LethalMarker::addNewMarkedAreaFOV keepout_layer.cpp:201-210, addNewMarkedArea
+   lethal_marker.cpp:218-226, MarkLethalFOV::tick FisherInfoBTPlugin.cpp:148-182).  The outputs are member 0's. */
+int  fs_multi_keepout_add_fov(fs_multi *m, double wx, double wy, double yaw, double height_m, int32_t *zone_id, int64_t *n_cells);
+int  fs_multi_keepout_add_disc(fs_multi *m, double wx, double wy, double radius_m, int32_t *zone_id, int64_t *n_cells);
+int  fs_multi_keepout_clear(fs_multi *m);
+int  fs_multi_mark_lethal_fov(fs_multi *m, const double robot_pose7[7], double blacklist_pose7[7], int32_t *zone_id, int64_t *n_cells);
 int  fs_multi_upload_landmarks(fs_multi *m, const float *xyz, int32_t n_landmarks);
 int  fs_multi_lookup_generate(fs_multi *m, const float bounds[6]);
 int  fs_multi_lookup_load(fs_multi *m, const char *path);

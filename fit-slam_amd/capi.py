@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "fs_allocate_tasks", "fs_allocate_tasks_dev", "fs_fleet_allocate_roadmap",
     "fs_keepout_add_fov", "fs_keepout_add_disc", "fs_keepout_clear", "fs_keepout_get", "fs_mark_lethal_fov", "fs_read_grid_region",
     "fs_multi_keepout_add_fov", "fs_multi_keepout_add_disc", "fs_multi_keepout_clear", "fs_multi_mark_lethal_fov",
+    "fs_set_occlusion", "fs_get_occlusion", "fs_line_of_sight", "fs_multi_set_occlusion",
 ]
 FS_KEEPOUT_MAX_ZONES = 1024
 KEEPOUT_FOV, KEEPOUT_DISC = 0, 1
@@ -97,6 +98,10 @@ class RayParamsC(C.Structure):
 
 class FimParamsC(C.Structure):
     _fields_ = [("max_dist", C.c_double), ("max_angle", C.c_double)]
+
+
+class OcclusionParamsC(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("occ_min", C.c_int32), ("occ_max", C.c_int32), ("end_margin_m", C.c_double)]
 
 
 class FsError(RuntimeError):
@@ -152,6 +157,9 @@ def load_library(build: bool = True):
     L.fs_lookup_get_records.argtypes = [vp, vp]
     L.fs_lookup_query.argtypes = [vp, vp, C.POINTER(C.c_float)]
     L.fs_set_fim_params.argtypes = [vp, C.POINTER(FimParamsC)]
+    L.fs_set_occlusion.argtypes = [vp, C.POINTER(OcclusionParamsC)]
+    L.fs_get_occlusion.argtypes = [vp, C.POINTER(OcclusionParamsC)]
+    L.fs_line_of_sight.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.fs_score_fim.argtypes = [vp, i32] + [vp] * 7
     L.fs_information_frontier_pair.argtypes = [vp, i32, vp, vp, vp]
     L.fs_upload_keyframes.argtypes = [vp, i32, vp, vp, vp]
@@ -178,6 +186,7 @@ def load_library(build: bool = True):
     L.fs_multi_lookup_generate.argtypes = [vp, vp]
     L.fs_multi_lookup_load.argtypes = [vp, C.c_char_p]
     L.fs_multi_set_fim_params.argtypes = [vp, C.POINTER(FimParamsC)]
+    L.fs_multi_set_occlusion.argtypes = [vp, C.POINTER(OcclusionParamsC)]
     L.fs_multi_max_arrival.argtypes = [vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]
     L.fs_multi_score_arrival.argtypes = [vp, i32] + [vp] * 10
     L.fs_multi_score_candidates.argtypes = [vp, i32] + [vp] * 5
@@ -621,6 +630,29 @@ class FrontierScorer:
     def set_fim_params(self, max_dist=14.0, max_angle=1.0):
         p = FimParamsC(max_dist, max_angle)
         self._check(self._L.fs_set_fim_params(self._h, C.byref(p)))
+
+    def set_occlusion(self, enabled, occ=(254, 254), end_margin_m=0.3):
+        """fs_set_occlusion: with `enabled`, a landmark counts only if the line from the pose to it crosses no cell with a cost
+        in occ = (min, max) on the staged grid; the last 1 + int(end_margin_m / resolution) cells at the landmark's end are
+        not tested."""
+        p = OcclusionParamsC(1 if enabled else 0, int(occ[0]), int(occ[1]), float(end_margin_m))
+        self._check(self._L.fs_set_occlusion(self._h, C.byref(p)))
+
+    def get_occlusion(self):
+        p = OcclusionParamsC()
+        self._check(self._L.fs_get_occlusion(self._h, C.byref(p)))
+        return dict(enabled=bool(p.enabled), occ=(p.occ_min, p.occ_max), end_margin_m=p.end_margin_m)
+
+    def line_of_sight(self, from_xyz, to_xyz):
+        """fs_line_of_sight: the rule of set_occlusion (its range and margin, enabled or not) for pairs of points."""
+        a = np.ascontiguousarray(from_xyz, dtype=np.float64).reshape(-1, 3)
+        b = np.ascontiguousarray(to_xyz, dtype=np.float64).reshape(-1, 3)
+        if a.shape != b.shape:
+            raise ValueError("from_xyz and to_xyz must hold the same number of points")
+        n = a.shape[0]
+        ok = np.zeros(n, np.uint8); blocked = np.zeros(n, np.uint8); tested = np.zeros(n, np.int32)
+        self._check(self._L.fs_line_of_sight(self._h, n, _p(a), _p(b), _p(ok), _p(blocked), _p(tested)))
+        return dict(ok=ok, blocked=blocked, tested_cells=tested)
 
     def score_fim(self, pose7, want_fim=True, info_only=False):
         """info_only: what isPoseSafe itself needs — info_ref (and n_voxels); every other column is passed as NULL, which
@@ -1253,6 +1285,19 @@ class MultiScorer:
     def set_fim_params(self, max_dist=14.0, max_angle=1.0):
         p = FimParamsC(max_dist, max_angle)
         self._check(self._L.fs_multi_set_fim_params(self._h, C.byref(p)))
+
+    def set_occlusion(self, enabled, occ=(254, 254), end_margin_m=0.3):
+        """fs_multi_set_occlusion: FrontierScorer.set_occlusion on every member."""
+        p = OcclusionParamsC(1 if enabled else 0, int(occ[0]), int(occ[1]), float(end_margin_m))
+        self._check(self._L.fs_multi_set_occlusion(self._h, C.byref(p)))
+
+    def get_occlusion(self):
+        """member 0's settings (a broadcast keeps the members equal)"""
+        p = OcclusionParamsC()
+        rc = self._L.fs_get_occlusion(self.member(0), C.byref(p))
+        if rc != FS_OK:
+            raise FsError(rc, "fs_get_occlusion on member 0")
+        return dict(enabled=bool(p.enabled), occ=(p.occ_min, p.occ_max), end_margin_m=p.end_margin_m)
 
     def max_arrival(self):
         a, b, c = C.c_double(), C.c_double(), C.c_double()

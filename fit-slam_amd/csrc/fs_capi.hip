@@ -245,6 +245,8 @@ struct fs_ctx {
     // than one pass takes (tools/ref_visibility_probe.py, profiles/r04/ref_visibility_pass_margin.jsonl: 1.87 -> 1.69 ms)
     int opt_headroom = 28;
     DevBuf<unsigned long long> d_counters;
+    // fs_set_occlusion: landmarks count only in line of sight on the staged grid.  Off: no call comes near the code.
+    fs_occlusion_params occ{0, 254, 254, 0.3};
 
     // lookup table
     bool have_table = false;
@@ -2376,6 +2378,82 @@ int fs_set_fim_params(fs_ctx *c, const fs_fim_params *p)
     return FS_OK;
 }
 
+// The scoring route with fs_set_occlusion enabled, in place of run_fim_tier1 + run_fim_rest: no LDS tier, no pose
+// splitting (a.split_shift stays 0), no finish on the host — every pose goes through the HBM-tier worker with the line-of-sight
+// test in its visibility, then the finish kernel as usual.  The grid is the staged one AT THIS CALL: nothing is kept per landmark.
+static int occlusion_args(fs_ctx *c, FsFimArgs &a)
+{
+    if (!c->have_grid) return fail(c, FS_E_STATE, "occlusion is enabled (fs_set_occlusion) and fs_upload_grid has not been called");
+    a.occ_grid = grid_dev(c);
+    a.occ_min = c->occ.occ_min; a.occ_max = c->occ.occ_max;
+    // M = 1 + (unsigned)(end_margin_m / resolution); a walk has fewer than 2^31 visits, so a larger quotient tests nothing either way
+    const double q = c->occ.end_margin_m / c->res;
+    a.occ_margin = 1u + (q < 2147483647.0 ? (uint32_t)q : 2147483647u);
+    a.split_shift = 0; a.split_flags = nullptr; a.host_flag = nullptr;
+    return FS_OK;
+}
+
+static int run_fim_occluded(fs_ctx *c, FsFimArgs &a)
+{
+    a.cand_perm = nullptr; a.cand_lo = 0; a.cand_count = a.n;
+    {
+        ScopedTimer t(c, 2);
+        FS_HIP(c, fs_launch_fim_occluded(a, fs_ctx::kPool, c->stream));
+    }
+    FS_HIP(c, fs_launch_fim_finish(a, c->stream));
+    return FS_OK;
+}
+
+int fs_set_occlusion(fs_ctx *c, const fs_occlusion_params *p)
+{
+    if (!c) return FS_E_INVALID;
+    const fs_occlusion_params def{0, 254, 254, 0.3};
+    if (!p) p = &def;
+    if (p->occ_min < 0 || p->occ_max > 255 || p->occ_min > p->occ_max) return fail(c, FS_E_INVALID, "occ_min / occ_max must be costs 0..255 with occ_min <= occ_max");
+    if (!(p->end_margin_m >= 0.0) || !(p->end_margin_m < 1.0e6)) return fail(c, FS_E_INVALID, "end_margin_m must be finite, >= 0 and below 1e6 m");
+    c->occ = *p;
+    c->occ.enabled = p->enabled ? 1 : 0;
+    ++c->epoch;                                            // (captured launch sequences are taken again)
+    return FS_OK;
+}
+
+int fs_get_occlusion(const fs_ctx *c, fs_occlusion_params *p)
+{
+    if (!c || !p) return FS_E_INVALID;
+    *p = c->occ;
+    return FS_OK;
+}
+
+int fs_line_of_sight(fs_ctx *c, int32_t n, const double *from_xyz, const double *to_xyz, uint8_t *ok, uint8_t *blocked, int32_t *tested_cells)
+{
+    if (!c) return FS_E_INVALID;
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (n < 0 || (n > 0 && (!from_xyz || !to_xyz || !ok || !blocked))) return fail(c, FS_E_INVALID, "null pointer");
+    if (n == 0) return FS_OK;
+    // (the segment tracer's buffers: the same shapes, never in use at the same time)
+    DevBuf<double> &d_s = c->d_seg_start, &d_e = c->d_seg_end;
+    DevBuf<uint8_t> &d_ok = c->d_seg_ok, &d_hit = c->d_seg_hit;
+    DevBuf<int32_t> &d_all = c->d_seg_all;
+    FS_HIP(c, d_s.ensure((size_t)n * 3)); FS_HIP(c, d_e.ensure((size_t)n * 3));
+    FS_HIP(c, d_ok.ensure(n)); FS_HIP(c, d_hit.ensure(n)); FS_HIP(c, d_all.ensure(n));
+    FS_HIP(c, hipMemcpyAsync(d_s.p, from_xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, hipMemcpyAsync(d_e.p, to_xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    FsFimArgs fa{};
+    if (const int rc = occlusion_args(c, fa)) return rc;
+    FsLosArgs a{};
+    a.grid = fa.occ_grid;
+    a.n = n; a.from = d_s.p; a.to = d_e.p;
+    a.occ_min = fa.occ_min; a.occ_max = fa.occ_max; a.margin = fa.occ_margin;
+    a.ok = d_ok.p; a.blocked = d_hit.p; a.tested = d_all.p;
+    FS_HIP(c, fs_launch_los(a, c->stream));
+    FS_HIP(c, hipMemcpyAsync(ok, d_ok.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipMemcpyAsync(blocked, d_hit.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (tested_cells) FS_HIP(c, hipMemcpyAsync(tested_cells, d_all.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    return FS_OK;
+}
+
 // A call with few poses leaves most of the chip idle — ONE pose is one of 512 workgroup slots, and the reference's real call is one
 // pose per tick (FisherInfoBTPlugin.cpp:24-57): spread each pose over W = 2^shift workgroups by voxel slab (fs_fim.hip, SPLIT), as
 // long as all n * W items are resident at once and the cloud is big enough to be worth W workgroups' fixed cost (cull, table
@@ -2502,7 +2580,8 @@ int fs_score_fim_begin(fs_ctx *c, int32_t n, const double *pose7, float *info_re
     // scanned than the 13/32 the general worker caps its pass prediction at — C3, cone off: up to 0.5; an extra pass costs a
     // re-test of the landmarks, an overflow the HBM tier)
     if (a.info_only && a.skip32 < 20) a.skip32 = 20;
-    rc = maybe_split(c, a, nn, fim21 != nullptr);
+    const bool occluded = c->occ.enabled != 0;
+    rc = occluded ? occlusion_args(c, a) : maybe_split(c, a, nn, fim21 != nullptr);
     if (rc) return rc;
     struct Col { void *host; const void *dev; size_t bytes; };
     const Col cols[6] = {{info_ref, c->d_info.p, 4 * nn}, {fim21, c->d_fim21.p, 84 * nn}, {trace, c->d_trace.p, 4 * nn},
@@ -2546,10 +2625,14 @@ int fs_score_fim_begin(fs_ctx *c, int32_t n, const double *pose7, float *info_re
             a.sums = reinterpret_cast<double *>(c->h_fin.dev + 16);
             a.host_flag = reinterpret_cast<uint32_t *>(c->h_fin.dev);
         }
-        int r = run_fim_tier1(c, a, nullptr, 0, a.n << a.split_shift);      // (split: n * W work items)
-        if (r) return r;
-        if (host_finish) { c->fin_args = a; c->fin_active = true; return FS_OK; }
-        r = run_fim_rest(c, a);
+        int r;
+        if (occluded) r = run_fim_occluded(c, a);
+        else {
+            r = run_fim_tier1(c, a, nullptr, 0, a.n << a.split_shift);      // (split: n * W work items)
+            if (r) return r;
+            if (host_finish) { c->fin_args = a; c->fin_active = true; return FS_OK; }
+            r = run_fim_rest(c, a);
+        }
         if (r) return r;
         if (in_place) return FS_OK;
         size_t o = 0;
@@ -2776,7 +2859,8 @@ int fs_score_candidates_dev(fs_ctx *c, int32_t n, const double *d_goal_xyz, cons
     fa.n = n;
     fa.fim21 = nullptr;
     fa.yaw_only = (c->opt_special && c->yaw_exact) ? 1 : 0;   // the ray-march kernel copies the pose's rotation out of d_yawR
-    rc = maybe_split(c, fa, (size_t)n, false);                // a handful of frontiers: each pose over several workgroups
+    const bool occluded = c->occ.enabled != 0;
+    rc = occluded ? occlusion_args(c, fa) : maybe_split(c, fa, (size_t)n, false);   // a handful of frontiers: each pose over several workgroups
     if (rc) return rc;
     FsRayArgs ra{};
     if (const int rc_args = fill_ray_args(c, ra)) return rc_args;
@@ -2797,10 +2881,15 @@ int fs_score_candidates_dev(fs_ctx *c, int32_t n, const double *d_goal_xyz, cons
         ScopedTimer t(c, 0);
         FS_HIP(c, fs_launch_raymarch(ra, c->stream));
     }
+    // the finish kernel assembles the records (one launch less than a separate pack)
+    if (occluded) {
+        fa.records = d_records;
+        fa.rec_arrival = c->d_arrival.p; fa.rec_argmax = c->d_argmax.p; fa.rec_yaw = c->d_yaw.p; fa.rec_achievable = c->d_ach.p;
+        return run_fim_occluded(c, fa);
+    }
     // the FIM kernel visits the candidates in the same spatial order: neighbouring poses walk the same landmark chunks
     rc = run_fim_tier1(c, fa, ra.perm, 0, n << fa.split_shift);
     if (rc) return rc;
-    // the finish kernel assembles the records (one launch less than a separate pack)
     fa.records = d_records;
     fa.rec_arrival = c->d_arrival.p; fa.rec_argmax = c->d_argmax.p; fa.rec_yaw = c->d_yaw.p; fa.rec_achievable = c->d_ach.p;
     rc = run_fim_rest(c, fa);
@@ -3461,13 +3550,17 @@ int pathinfo_score(fs_ctx *c, FsPathInfoArgs &a, int64_t distinct, Stop stop)
     fa.n = (int32_t)distinct;
     fa.info_only = c->opt_special ? 1 : 0;
     if (fa.info_only && fa.skip32 < 20) fa.skip32 = 20;        // (as fs_score_fim_begin)
-    rc = maybe_split(c, fa, (size_t)distinct, false);
+    const bool occluded = c->occ.enabled != 0;
+    rc = occluded ? occlusion_args(c, fa) : maybe_split(c, fa, (size_t)distinct, false);
     if (rc) return stop(rc);
     fa.Rt = c->d_pi_rt.p;
     bind_fim_outputs(c, fa);
-    rc = run_fim_tier1(c, fa, nullptr, 0, fa.n << fa.split_shift);
-    if (rc) return stop(rc);
-    rc = run_fim_rest(c, fa);
+    if (occluded) rc = run_fim_occluded(c, fa);
+    else {
+        rc = run_fim_tier1(c, fa, nullptr, 0, fa.n << fa.split_shift);
+        if (rc) return stop(rc);
+        rc = run_fim_rest(c, fa);
+    }
     if (rc) return stop(rc);
     a.info = fa.info_ref;
     return FS_OK;

@@ -32,6 +32,7 @@
 // distinct voxels than the table takes is scored by the same workgroup in 2, 4 or 8 voxel-partitioned PASSES; only a
 // real overflow hands it to the table in HBM.  Scan + scatter-count has no dense contraction: no MFMA.
 #include "fs_internal.h"
+#include "fs_walk.h"        // line_of_sight: the occluded worker (OCCLUDED)
 
 #include <atomic>
 
@@ -367,10 +368,15 @@ enum { FS_CONE_OFF = 0, FS_CONE_NARROW = 1, FS_CONE_ANY = 2 };
 // The 6x6 block sums and the visible count follow the landmark: where they are taken at scoring time they are already partitioned
 // with the voxels; where they are taken at TEST time (cone off) the item that owns a landmark's CHUNK (chunk id mod W) takes them and
 // the other items skip that code — every visible landmark is in exactly one chunk.
-template <int THREADS, bool GLOBAL_TABLE, bool TABLE_FULL, int CONE, bool INFO_ONLY, bool YAW_ONLY, bool SPLIT = false>
+// OCCLUDED (fs_set_occlusion enabled; the HBM-tier worker only): a landmark that passes the predicate is visible only if the line
+// from the pose's translation to it — both float32, widened to double — is not blocked on FsFimArgs::occ_grid (fs_walk.h,
+// line_of_sight).  The test sits in front of the compaction queue, so everything downstream sees the smaller visible set and
+// nothing else changes; only lanes that passed the predicate walk, each at most max(nx, ny, nz) cells.
+template <int THREADS, bool GLOBAL_TABLE, bool TABLE_FULL, int CONE, bool INFO_ONLY, bool YAW_ONLY, bool SPLIT = false, bool OCCLUDED = false>
 __device__ __forceinline__ void fim_worker(const FsFimArgs &a, const FimWork work, uint32_t *lds, uint32_t *table, const int tier_bits)
 {
     static_assert(!SPLIT || (!GLOBAL_TABLE && TABLE_FULL && CONE != FS_CONE_ANY), "the split workers exist for the LDS tier, finite tables and the two common cone modes");
+    static_assert(!OCCLUDED || (GLOBAL_TABLE && CONE == FS_CONE_ANY && !INFO_ONLY && !YAW_ONLY && !SPLIT), "the line-of-sight test exists in the HBM-tier worker (one pass per pose: every landmark is walked once)");
     const int split_shift = SPLIT ? a.split_shift : 0;
     const int split_w_mask = (1 << split_shift) - 1;
     // item w of a split pose owns the voxels whose x index lies in [jlo, jhi): W contiguous slabs of the lattice along the camera's
@@ -801,7 +807,11 @@ __device__ __forceinline__ void fim_worker(const FsFimArgs &a, const FimWork wor
                     m3 = mine ? m3 : -1.0f;
                 }
                 else if (__builtin_expect(n_parts > 1, 0)) m3 = (voxel_part(a, true, px, n_parts) == part) ? m3 : -1.0f;   // wave-uniform branch (out of line: a taken branch costs a wave its instruction buffer); every lane evaluates
-                const bool vis = m3 >= 0.0f;
+                bool vis = m3 >= 0.0f;
+                if constexpr (OCCLUDED) {
+                    if (vis) vis = !line_of_sight(a.occ_grid, (double)t[0], (double)t[1], (double)t[2], (double)wx, (double)wy, (double)wz,
+                                                  a.occ_min, a.occ_max, a.occ_margin).blocked;
+                }
                 // ---- 3. compact
                 const unsigned long long m = __builtin_amdgcn_ballot_w64(vis);
                 if (m != 0ull) {
@@ -1155,6 +1165,29 @@ void fs_fim_tier3_kernel(const FsFimArgs a)
     fim_worker<THREADS, true, TABLE_FULL, FS_CONE_ANY, false, false>(a, work, fs_fim_lds, table, a.ghash_bits);
 }
 
+// The occluded route (fs_set_occlusion enabled): the same worker with the line-of-sight test in its visibility,
+// over EVERY pose of the call — fs_fim_occluded_init_kernel files them all into the HBM tier's work list, in list order, with
+// overflow[i] = 0: the finish kernel then learns no voxel ratio from them (scanned = 0), so the default route's pass prediction
+// is not steered by occluded calls.
+template <int THREADS, bool TABLE_FULL>
+__global__ __launch_bounds__(THREADS)
+void fs_fim_occluded_kernel(const FsFimArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t fs_fim_lds[];
+    const FimWork work{a.flagged, 0, (int)a.counters[2], a.counters + 9};
+    uint32_t *table = a.gtable + ((size_t)blockIdx.x << a.ghash_bits);
+    fim_worker<THREADS, true, TABLE_FULL, FS_CONE_ANY, false, false, false, true>(a, work, fs_fim_lds, table, a.ghash_bits);
+}
+
+__global__ void fs_fim_occluded_init_kernel(const FsFimArgs a)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= a.n) return;
+    a.flagged[i] = i;
+    a.overflow[i] = 0u;
+    if (i == 0) a.counters[2] = (unsigned long long)a.n;
+}
+
 template <int THREADS>
 size_t lds_bytes(int hash_bits, bool global_table, int n_chunks, int *n_groups, int mask_sets)
 {
@@ -1275,6 +1308,29 @@ hipError_t fs_launch_fim_overflow(const FsFimArgs &a0, int pool, hipStream_t s)
     FsFimArgs a = a0;
     a.ratio_slot = ratio_slot_of(a);
     return a.table_full ? launch_overflow<true>(a, pool, s) : launch_overflow<false>(a, pool, s);
+}
+
+hipError_t fs_launch_fim_occluded(const FsFimArgs &a0, int pool, hipStream_t s)
+{
+    if (a0.n <= 0) return hipSuccess;
+    if (!a0.occ_grid.cells || a0.split_shift != 0 || a0.split_flags) return hipErrorInvalidValue;
+    FsFimArgs a = a0;
+    a.ratio_slot = ratio_slot_of(a);
+    const int blocks = a.n < pool ? a.n : pool;
+    const size_t lds = lds_bytes<FS_HBM_THREADS>(0, true, a.n_chunks, &a.n_groups, 1);
+    hipLaunchKernelGGL(fs_fim_occluded_init_kernel, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (a.table_full) {
+        auto kernel = fs_fim_occluded_kernel<FS_HBM_THREADS, true>;
+        if ((e = allow_lds(kernel, lds)) != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(FS_HBM_THREADS), lds, s, a);
+    } else {
+        auto kernel = fs_fim_occluded_kernel<FS_HBM_THREADS, false>;
+        if ((e = allow_lds(kernel, lds)) != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(FS_HBM_THREADS), lds, s, a);
+    }
+    return hipGetLastError();
 }
 
 hipError_t fs_launch_fim_finish(const FsFimArgs &a0, hipStream_t s)

@@ -112,6 +112,17 @@ struct FsSegArgs {
     int32_t *traced, *unknown, *all;
 };
 hipError_t fs_launch_segments(const FsSegArgs &a, hipStream_t s);
+// ---- line of sight (fs_line_of_sight; the same rule inside the occluded FIM worker: fs_walk.h)
+struct FsLosArgs {
+    FsGridDev grid;
+    int32_t n;
+    const double *from, *to;        // [n][3]
+    int32_t occ_min, occ_max;       // costs that block
+    uint32_t margin;                // M = 1 + (unsigned)(end_margin_m / resolution): visits at the far end that are not tested
+    uint8_t *ok, *blocked;
+    int32_t *tested;                // or nullptr
+};
+hipError_t fs_launch_los(const FsLosArgs &a, hipStream_t s);
 hipError_t fs_launch_brick_scatter(int64_t n_bricks, const int32_t *d_coords, const uint8_t *d_cells, uint8_t *d_grid,
                                    int nx, int ny, int nz, int *d_bad, hipStream_t s);
 hipError_t fs_launch_frontier_pair(int n, const float *lx, const float *ly, const float *lz, int m, const float *d_Rt,
@@ -713,6 +724,11 @@ struct FsFimArgs {
     int32_t headroom;          // ... and, once a ratio has been learnt, headroom/32 of it (40 = 5/4) + 1/32 when that is smaller
     uint32_t *gtable;          // tier 3: HBM tables [pool][1 << ghash_bits]
     int32_t ghash_bits;
+    // occlusion (fs_set_occlusion; read by the occluded worker alone, at the end so that no other field moves): a
+    // landmark that passes the predicate is visible only if the line from the pose's translation to it is not blocked on `occ_grid`
+    int32_t occ_min, occ_max;
+    uint32_t occ_margin;       // M of the rule
+    FsGridDev occ_grid;
 };
 
 #define FS_COST_BINS   8192     // blocks of the sort's cost map (13 Morton bits)
@@ -745,6 +761,9 @@ hipError_t fs_launch_sort_candidates(int32_t n, const double *d_goal, const FsGr
 hipError_t fs_launch_fim(const FsFimArgs &a, hipStream_t s);
 bool fs_fim_can_split(const FsFimArgs &a);     // may split_shift be set for this call? (needs info_only, cone_mode, table_full filled in)
 hipError_t fs_launch_fim_overflow(const FsFimArgs &a, int pool, hipStream_t s);
+// the occluded route (fs_set_occlusion enabled): every pose filed into the HBM tier's work list, then the HBM-tier worker with
+// the line-of-sight test in its visibility; fs_launch_fim_finish follows as usual
+hipError_t fs_launch_fim_occluded(const FsFimArgs &a, int pool, hipStream_t s);
 hipError_t fs_launch_fim_finish(const FsFimArgs &a, hipStream_t s);
 hipError_t fs_launch_selftest(int32_t max_abs, double *d_sqrt, double *d_div, hipStream_t s);
 

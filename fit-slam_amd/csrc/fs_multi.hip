@@ -289,6 +289,11 @@ int fs_multi_set_fim_params(fs_multi *m, const fs_fim_params *p)
     return for_all(m, "fs_set_fim_params", [&](fs_ctx *c) { return fs_set_fim_params(c, p); });
 }
 
+int fs_multi_set_occlusion(fs_multi *m, const fs_occlusion_params *p)
+{
+    return for_all(m, "fs_set_occlusion", [&](fs_ctx *c) { return fs_set_occlusion(c, p); });
+}
+
 int fs_multi_max_arrival(fs_multi *m, double *max_value, double *max_gt, double *min_gt)
 {
     if (!m || m->ctx.empty()) return FS_E_INVALID;

@@ -14,6 +14,7 @@
 // byte per step.  Per-yaw sums live in LDS; the FOV window maximum and its first argmax are a
 // wave-shuffle reduction.  This is HBM/L2-bound byte gather: no MFMA.
 #include "fs_internal.h"
+#include "fs_walk.h"        // cell_quotient, world_to_map, sign_ref, minor_step, WalkLinear and its walk_init / walk_step / walk_cell / walk_visits
 
 #ifndef FS_RAY_WAVES
 #define FS_RAY_WAVES 4          // candidates per workgroup
@@ -27,51 +28,12 @@ namespace {
 __device__ __forceinline__ double std_min(double a, double b) { return (b < a) ? b : a; }   // std::min(a,b)
 __device__ __forceinline__ double std_max(double a, double b) { return (a < b) ? b : a; }   // std::max(a,b)
 
-// (unsigned)((w - origin) / resolution), the quotient of Costmap2D::worldToMap, without the fp64 division in the common
-// case.  Only the truncated quotient matters: t = a * (1 / res) lies within 4 ulp (< 1.5e-6 below 2^32) of the correctly
-// rounded a / res, so both truncate to the same cell unless t sits within 1e-5 of an integer — then, and for quotients
-// next to 2^32 or NaN, the division itself is evaluated (a few lanes in a million).  `q` is what the caller compares and
-// truncates: identical decisions to the division in every case.
-__device__ __forceinline__ double cell_quotient(double a, double res, double inv_res)
-{
-    const double t = a * inv_res;
-    const double fr = __builtin_amdgcn_fract(t);                       // t - floor(t), in [0, 1)
-    if (t < 4294967295.0 && fabs(fr - 0.5) < 0.5 - 1.0e-5) return t;
-    return a / res;
-}
-
-// nav2_costmap_2d::Costmap2D::worldToMap with a z axis. Quotients >= 2^32 are off-map.
-__device__ __forceinline__ bool world_to_map(const FsGridDev &g, double wx, double wy, double wz,
-                                             uint32_t &mx, uint32_t &my, uint32_t &mz)
-{
-    if (wx < g.ox || wy < g.oy || wz < g.oz) return false;
-    const double inv_res = 1.0 / g.res;                                // uniform: hoisted out of the ray loops
-    const double qx = cell_quotient(wx - g.ox, g.res, inv_res);
-    const double qy = cell_quotient(wy - g.oy, g.res, inv_res);
-    const double qz = cell_quotient(wz - g.oz, g.res, inv_res);
-    if (!(qx < 4294967296.0) || !(qy < 4294967296.0) || !(qz < 4294967296.0)) return false;
-    mx = (uint32_t)qx;
-    my = (uint32_t)qy;
-    mz = (uint32_t)qz;
-    return mx < (uint32_t)g.nx && my < (uint32_t)g.ny && mz < (uint32_t)g.nz;
-}
-
-__device__ __forceinline__ int sign_ref(int x) { return x > 0 ? 1 : -1; }   // Helpers.hpp:113-116
-
 // Two interchangeable walks over the same cell sequence (selected per launch, FsRayArgs::layout; DESIGN.md 4.1 holds the
 // measurements, including the five other formulations that were built, measured and removed):
 //
-// WalkLinear — the reference's own formulation on the dense row-major image: a linear offset, constant strides per
-// axis, bresenham2D's body (DEP/src/Helpers.cpp:21-27) with a second minor axis.  Cheapest in instructions; rows only give
-// x-major rays any cache-line reuse.  The winner for short rays (up to ~96 cells).
-struct WalkLinear {
-    uint32_t offset;
-    uint32_t abs_da, abs_db, abs_dc;
-    int err_b, err_c;
-    int off_a, off_b, off_c;
-    uint32_t end;            // min(max_length_steps, abs_da): loop visits, one more after the loop
-};
-
+// WalkLinear (fs_walk.h) — the reference's own formulation on the dense row-major image: a linear offset, constant strides per
+// axis.  Cheapest in instructions; the winner for short rays (up to ~96 cells).
+//
 // WalkClass — on the 2-bit class image (FsGridDev::cls: bricks of 8 x 8 x 8 cells = one 128-B cache line), which has no
 // constant strides.  The walk keeps the cell coordinates IN THE RAY'S OWN AXIS ORDER (a = major, b, c = minors): the major
 // coordinate steps unconditionally (the reference's `offset += offset_a`), the minors on their error terms exactly as
@@ -97,29 +59,6 @@ struct WalkClass {
 // (profiles/EXPERIMENTS.md holds the outcome).
 struct WalkSparse : WalkClass {};
 
-// one minor axis of a walk: e += |d_minor|; if (e >= |d_major|) { v += sign; e -= |d_major|; } in five instructions —
-// the subtraction's borrow IS the comparison (v_sub_co_u32), the smaller of e and e - |d_major| (unsigned wrap) is the new
-// error term.  (The compiler spends a sixth on a separate compare.)
-__device__ __forceinline__ void minor_step(uint32_t &v, int &e, uint32_t ad, uint32_t da, int sg)
-{
-    uint32_t t;
-    asm("v_add_u32 %[e], %[e], %[ad]\n\t"
-        "v_sub_co_u32 %[t], vcc, %[e], %[da]\n\t"
-        "v_min_u32 %[e], %[e], %[t]\n\t"
-        "v_cndmask_b32 %[t], %[sg], 0, vcc\n\t"
-        "v_add_u32 %[v], %[v], %[t]"
-        : [e] "+v"(e), [v] "+v"(v), [t] "=&v"(t)
-        : [ad] "v"(ad), [da] "v"(da), [sg] "v"(sg)
-        : "vcc");
-}
-
-__device__ __forceinline__ void walk_step(WalkLinear &w)
-{
-    w.offset += (uint32_t)w.off_a;
-    minor_step(w.offset, w.err_b, w.abs_db, w.abs_da, w.off_b);
-    minor_step(w.offset, w.err_c, w.abs_dc, w.abs_da, w.off_c);
-}
-
 __device__ __forceinline__ void walk_step(WalkClass &w)
 {
     w.a += (uint32_t)w.sga;
@@ -129,16 +68,6 @@ __device__ __forceinline__ void walk_step(WalkClass &w)
 
 __device__ __forceinline__ void walk_step(WalkSparse &w) { walk_step(static_cast<WalkClass &>(w)); }
 
-// The cell under the walk.  Both end points are on the map (worldToMap succeeded) and a Bresenham walk between two
-// cells never leaves their bounding box — each axis takes at most |d_axis| steps towards the end point — so every
-// visit, including the speculative ones (they stay within `visits`), is inside the grid.
-__device__ __forceinline__ int walk_cell(const FsGridDev &g, const WalkLinear &w)
-{
-#ifdef FS_RAY_BOUNDS   // development: verify the claim above on every visit instead of relying on it
-    if (w.offset >= (uint32_t)g.nx * (uint32_t)g.ny * (uint32_t)g.nz) { atomicMax(g.dbg, 1ull); return 256; }
-#endif
-    return (int)g.cells[w.offset];
-}
 // the class (0..3) of the cell under the walk
 __device__ __forceinline__ uint32_t walk_class(const FsGridDev &g, const WalkClass &w)
 {
@@ -171,54 +100,6 @@ __device__ __forceinline__ uint32_t walk_class(const FsGridDev &g, const WalkSpa
     const uint32_t B = (slot << 9) | (A & 511u);
     const uint32_t word = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(g.cls) + ((B >> 2) & ~3u));
     return __builtin_amdgcn_ubfe(word, A << 1, 2u);
-}
-
-// getTracedCells from the two map cells on (Helpers.cpp:46-94): `(unsigned)(scale * abs_da)` visits with
-// scale = min(1, max_length / hypot(d)).  Evaluated as the reference does (fp64 square root, division, product) only
-// where it could matter:
-//   * |d|^2 <= max_length^2 in integers (max_length a whole number): hypot(d) <= max_length, the quotient is >= 1 and the
-//     scale exactly 1;
-//   * otherwise s = |d_major| max_length / |d| in fp32 (v_rsq_f32; relative error < 1e-6) truncates like the fp64 chain
-//     (relative error 3e-16) unless it lies within 4e-6 s + 1e-6 of an integer — there the fp64 chain decides.
-__device__ __forceinline__ uint32_t walk_visits(int dx, int dy, int dz, uint32_t abs_da, double max_length)
-{
-    const long long d2 = (long long)dx * dx + (long long)dy * dy + (long long)dz * dz;
-    // (a whole number of cells below 2^26 — the arrival fan's case; fs_trace_segments may pass any double — squares exactly)
-    const bool whole = max_length < 67108864.0 && max_length == floor(max_length);
-    if (whole && d2 < (1ll << 52) && (double)d2 <= max_length * max_length) return abs_da;
-    if (d2 < (1ll << 24) && max_length < 16777216.0) {
-        const float s = ((float)abs_da * (float)max_length) * __builtin_amdgcn_rsqf((float)d2);
-        const float fr = s - floorf(s);
-        const float guard = 4.0e-6f * s + 1.0e-6f;
-        if (fr > guard && fr < 1.0f - guard) {
-            const uint32_t max_steps = (uint32_t)s;
-            return max_steps < abs_da ? max_steps : abs_da;
-        }
-    }
-    const double dist = sqrt((double)d2);          // == std::hypot(dx,dy) when dz == 0 (both correctly rounded)
-    const double q = max_length / dist;
-    const double scale = (dist == 0.0) ? 1.0 : ((q < 1.0) ? q : 1.0);       // std::min(1.0, max_length / dist)
-    const uint32_t max_steps = (uint32_t)(scale * (double)abs_da);
-    return max_steps < abs_da ? max_steps : abs_da;
-}
-
-__device__ __forceinline__ void walk_init(WalkLinear &w, const FsGridDev &g, uint32_t x0, uint32_t y0, uint32_t z0,
-                                          uint32_t x1, uint32_t y1, uint32_t z1, double max_length)
-{
-    const int dx = (int)(x1 - x0), dy = (int)(y1 - y0), dz = (int)(z1 - z0);
-    const uint32_t nx = (uint32_t)g.nx, ny = (uint32_t)g.ny;
-    w.offset = (z0 * ny + y0) * nx + x0;
-    const uint32_t adx = (uint32_t)abs(dx), ady = (uint32_t)abs(dy), adz = (uint32_t)abs(dz);
-    const int odx = sign_ref(dx), ody = sign_ref(dy) * (int)nx, odz = sign_ref(dz) * (int)(nx * ny);
-    if (adx >= ady && adx >= adz) {
-        w.abs_da = adx; w.abs_db = ady; w.abs_dc = adz; w.off_a = odx; w.off_b = ody; w.off_c = odz;
-    } else if (ady >= adz) {
-        w.abs_da = ady; w.abs_db = adx; w.abs_dc = adz; w.off_a = ody; w.off_b = odx; w.off_c = odz;
-    } else {
-        w.abs_da = adz; w.abs_db = adx; w.abs_dc = ady; w.off_a = odz; w.off_b = odx; w.off_c = ody;
-    }
-    w.err_b = w.err_c = (int)(w.abs_da / 2);
-    w.end = walk_visits(dx, dy, dz, w.abs_da, max_length);
 }
 
 __device__ __forceinline__ void walk_init(WalkClass &w, const FsGridDev &g, uint32_t x0, uint32_t y0, uint32_t z0,
@@ -564,6 +445,17 @@ __global__ void fs_segments_kernel(const FsSegArgs s)
     s.traced[i] = r.traced; s.unknown[i] = r.unknown; s.all[i] = r.all;
 }
 
+// fs_line_of_sight: the line-of-sight rule of fs_set_occlusion (fs_walk.h, line_of_sight) for caller-given pairs, one lane per pair
+__global__ void fs_los_kernel(const FsLosArgs s)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= s.n) return;
+    const LosResult r = line_of_sight(s.grid, s.from[3 * i], s.from[3 * i + 1], s.from[3 * i + 2], s.to[3 * i], s.to[3 * i + 1], s.to[3 * i + 2],
+                                      s.occ_min, s.occ_max, s.margin);
+    s.ok[i] = r.ok; s.blocked[i] = r.blocked;
+    if (s.tested) s.tested[i] = r.tested;
+}
+
 // FrontierRoadMap::refinePath (DEP/src/planners/FrontierRoadmap.cpp:657-714) on every route of fs_roadmap_routes,
 // one wave per route.  From the kept node P[kk] the reference tries P[kk + 1], P[kk + 2], ... in turn and stops at the first that
 // isConnectable (:716-737: walk ok, nothing in 253..254, unknown cells <= the limit) refuses; the last one it accepted is kept
@@ -646,6 +538,13 @@ hipError_t fs_launch_segments(const FsSegArgs &a, hipStream_t s)
     if (a.n <= 0) return hipSuccess;
     // (the segment visitor reports unknown cells separately from its ranges: it needs the costs, hence the byte image)
     hipLaunchKernelGGL(fs_segments_kernel<WalkLinear>, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_los(const FsLosArgs &a, hipStream_t s)
+{
+    if (a.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(fs_los_kernel, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -332,6 +332,34 @@ int fs_set_fim_params(fs_ctx *ctx, const fs_fim_params *p);
 int fs_score_fim(fs_ctx *ctx, int32_t n, const double *pose7, float *info_ref, float *fim21,
                  float *trace, float *logdet, int32_t *n_visible, int32_t *n_voxels);
 
+/* Landmarks count only in LINE OF SIGHT on the staged grid (SURVEY.md App. A.3's optional occlusion test; an extension, OFF by
+ * default — the reference counts a landmark behind a wall).  The rule, for a camera position s and a landmark w: the line is
+ * BLOCKED when getTracedCells(s, w) on the staged grid is ok (fs_trace_segments' walk, uncapped: scale 1, cell visits
+ * v = 0 .. end) and some visit with v + M <= end, M = 1 + (unsigned)(end_margin_m / resolution), has a cost in
+ * [occ_min, occ_max].  The start cell is tested; the last M visits, at the landmark's end, are not (a landmark sits ON a
+ * surface).  If either end is off the map nothing is tested and the line is not blocked.  On a 2-D grid (nz == 1) the walk is
+ * planar: both z coordinates are replaced by origin_z; on a 3-D grid it is the 3-D walk between the two points.
+ * With `enabled`, a landmark is visible from a pose if it passes fs_set_fim_params' predicate AND the line from the pose's
+ * float32 translation (getTransformFromPose's t) to the landmark's float32 position, both widened to double, is not blocked;
+ * voxel counts, crowding ranks, F, trace, log det, n_visible, n_voxels and the records follow from that visible set exactly as
+ * without it.  Applies to fs_score_fim, the Fisher columns of fs_score_candidates / fs_get_frontier_costs*, the way points of
+ * fs_plan_paths_information and the legs of fs_roadmap_routes.  The grid is read at call time: map updates and keep-out
+ * repaints take effect at once, nothing is cached per landmark.  Scoring with `enabled` and no grid staged: FS_E_STATE.
+ * occ_min / occ_max outside 0..255 or out of order, end_margin_m negative, not finite or >= 1e6: FS_E_INVALID, settings unchanged. */
+typedef struct fs_occlusion_params {
+    int32_t enabled;           /* 0 */
+    int32_t occ_min, occ_max;  /* 254, 254: LETHAL only — the keep-out layer's 253 zones are virtual and hide nothing */
+    double  end_margin_m;      /* 0.3 = the FI voxel step */
+} fs_occlusion_params;
+int fs_set_occlusion(fs_ctx *ctx, const fs_occlusion_params *p);   /* NULL: the defaults above */
+int fs_get_occlusion(const fs_ctx *ctx, fs_occlusion_params *p);
+/* The rule above (range and margin of fs_set_occlusion; `enabled` is not consulted) for n caller-given pairs.
+ *   from_xyz, to_xyz [n][3]
+ *   ok [n]            both ends on the map       blocked [n]  the line is blocked
+ *   tested_cells [n]  visits the rule covers: end + 1 - M, 0 when the line is shorter than M or not ok; or NULL */
+int fs_line_of_sight(fs_ctx *ctx, int32_t n, const double *from_xyz, const double *to_xyz,
+                     uint8_t *ok, uint8_t *blocked, int32_t *tested_cells);
+
 /* Replaces float computeInformationFrontierPair(std::vector<Point>& lndmrk_w, Pose& kf_pose_w, Pose& est_pose_w,
  * std::vector<Point2D>& FOVFrontierPair) (FIP/src/.../FisherInformationHelpers.cpp:125-143; isInside / onLeft:
  * FIP/include/.../FisherInformationHelpers.hpp:20-43) for a batch of (estimation pose, CCW triangle) pairs over the
@@ -419,6 +447,7 @@ int  fs_multi_upload_landmarks(fs_multi *m, const float *xyz, int32_t n_landmark
 int  fs_multi_lookup_generate(fs_multi *m, const float bounds[6]);
 int  fs_multi_lookup_load(fs_multi *m, const char *path);
 int  fs_multi_set_fim_params(fs_multi *m, const fs_fim_params *p);
+int  fs_multi_set_occlusion(fs_multi *m, const fs_occlusion_params *p);
 /* setMaxArrivalInformation once (member 0), the limits handed to every member */
 int  fs_multi_max_arrival(fs_multi *m, double *max_value, double *max_gt, double *min_gt);
 /* fs_score_arrival over all members (same arguments; every output array in list order) */

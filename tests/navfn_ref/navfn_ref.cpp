@@ -384,10 +384,11 @@ int nr_costs(const uint8_t *cells, int nx, int ny, int allow_unknown, uint8_t *c
 
 // One leg over n goals.  leg 0: converged (one field), 1: reference_astar (a field per goal).  Outputs [n]; limit [n] or NULL:
 // bit 0 the wave's cycle budget ran out, bit 1 a priority buffer refused a push (leg 1); bits 8.. why calcPath failed (both legs,
-// 1 out of bounds, 2 high potential, 3 zero gradient, 4 out of cycles).
-int nr_plan(const uint8_t *cells, int nx, int ny, double ox, double oy, double res, const double robot7[7], int allow_unknown, int leg,
-            int n, const double *goal_xyz, const uint8_t *achievable_in, double *path_length, double *path_length_m, double *path_heading,
-            uint8_t *achievable, int32_t *limit)
+// 1 out of bounds, 2 high potential, 3 zero gradient, 4 out of cycles).  path_x / path_y [n][path_stride] or NULL with
+// path_stride >= 4 * max(nx, ny): the points of every achievable goal's path as calcPath left them, path_length[i] of them.
+static int plan(const uint8_t *cells, int nx, int ny, double ox, double oy, double res, const double robot7[7], int allow_unknown, int leg,
+                int n, const double *goal_xyz, const uint8_t *achievable_in, double *path_length, double *path_length_m, double *path_heading,
+                uint8_t *achievable, int32_t *limit, float *path_x, float *path_y, int path_stride)
 {
     const double dmax = std::numeric_limits<double>::max();
     Map m;
@@ -397,6 +398,7 @@ int nr_plan(const uint8_t *cells, int nx, int ny, double ox, double oy, double r
     std::vector<float> field;
     if (leg == 0 && robot_on) { Stats st; converged_field(m, rx, ry, field, st); }
     const int max_cycles = 4 * std::max(nx, ny);
+    if (path_x && path_stride < max_cycles) return -1;
     std::vector<float> px((size_t)max_cycles), py((size_t)max_cycles);
     for (int i = 0; i < n; ++i) {
         path_length[i] = path_length_m[i] = path_heading[i] = dmax;
@@ -431,8 +433,27 @@ int nr_plan(const uint8_t *cells, int nx, int ny, double ox, double oy, double r
         path_length[i] = (double)len;
         path_length_m[i] = length_m(px.data(), py.data(), len, ox, oy, res);
         path_heading[i] = h;
+        if (path_x) memcpy(path_x + (size_t)i * path_stride, px.data(), (size_t)len * sizeof(float));
+        if (path_y) memcpy(path_y + (size_t)i * path_stride, py.data(), (size_t)len * sizeof(float));
     }
     return 0;
+}
+
+int nr_plan(const uint8_t *cells, int nx, int ny, double ox, double oy, double res, const double robot7[7], int allow_unknown, int leg,
+            int n, const double *goal_xyz, const uint8_t *achievable_in, double *path_length, double *path_length_m, double *path_heading,
+            uint8_t *achievable, int32_t *limit)
+{
+    return plan(cells, nx, ny, ox, oy, res, robot7, allow_unknown, leg, n, goal_xyz, achievable_in, path_length, path_length_m, path_heading,
+                achievable, limit, nullptr, nullptr, 0);
+}
+
+// nr_plan, and the path points of every leg as well (see plan above); -1 when path_stride is too small
+int nr_plan_points(const uint8_t *cells, int nx, int ny, double ox, double oy, double res, const double robot7[7], int allow_unknown, int leg,
+                   int n, const double *goal_xyz, const uint8_t *achievable_in, double *path_length, double *path_length_m,
+                   double *path_heading, uint8_t *achievable, int32_t *limit, float *path_x, float *path_y, int path_stride)
+{
+    return plan(cells, nx, ny, ox, oy, res, robot7, allow_unknown, leg, n, goal_xyz, achievable_in, path_length, path_length_m, path_heading,
+                achievable, limit, path_x, path_y, path_stride);
 }
 
 }  // extern "C"

@@ -26,6 +26,7 @@ def lib():
         L.nr_converged_field.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp]
         L.nr_costs.argtypes = [vp, ci, ci, ci, vp]
         L.nr_plan.argtypes = [vp, ci, ci, cd, cd, cd, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+        L.nr_plan_points.argtypes = L.nr_plan.argtypes + [vp, vp, ci]
         _lib = L
     return _lib
 
@@ -57,8 +58,9 @@ def costs(cells, allow_unknown=False):
     return out
 
 
-def plan(cells, origin, resolution, robot_pose7, goal_xyz, achievable_in=None, allow_unknown=False, leg=CONVERGED):
-    """The four columns of fs_plan_paths from one leg; leg REFERENCE_ASTAR also returns `limit` (bit 0 cycles, bit 1 buffer cap)."""
+def plan(cells, origin, resolution, robot_pose7, goal_xyz, achievable_in=None, allow_unknown=False, leg=CONVERGED, points=False):
+    """The four columns of fs_plan_paths from one leg; leg REFERENCE_ASTAR also returns `limit` (bit 0 cycles, bit 1 buffer cap).
+    points: also `pathx` / `pathy`, per goal the float32 path points as calcPath left them (empty where not achievable)."""
     c = _cells2d(cells)
     ny, nx = c.shape
     goal = np.ascontiguousarray(goal_xyz, dtype=np.float64).reshape(-1, 3)
@@ -68,9 +70,18 @@ def plan(cells, origin, resolution, robot_pose7, goal_xyz, achievable_in=None, a
     pl, plm, ph = np.zeros(n), np.zeros(n), np.zeros(n)
     ach = np.zeros(n, dtype=np.uint8)
     lim = np.zeros(n, dtype=np.int32)
-    lib().nr_plan(_p(c), nx, ny, float(origin[0]), float(origin[1]), float(resolution), _p(pose), 1 if allow_unknown else 0, int(leg), n,
-                  _p(goal), _p(ai), _p(pl), _p(plm), _p(ph), _p(ach), _p(lim))
-    return dict(path_length=pl, path_length_m=plm, path_heading=ph, achievable=ach, limit=lim)
+    args = (_p(c), nx, ny, float(origin[0]), float(origin[1]), float(resolution), _p(pose), 1 if allow_unknown else 0, int(leg), n,
+            _p(goal), _p(ai), _p(pl), _p(plm), _p(ph), _p(ach), _p(lim))
+    out = dict(path_length=pl, path_length_m=plm, path_heading=ph, achievable=ach, limit=lim)
+    if not points:
+        lib().nr_plan(*args)
+        return out
+    stride = 4 * max(nx, ny)
+    px, py = np.zeros((n, stride), dtype=np.float32), np.zeros((n, stride), dtype=np.float32)
+    assert lib().nr_plan_points(*args, _p(px), _p(py), stride) == 0
+    lens = [int(pl[i]) if ach[i] else 0 for i in range(n)]
+    out.update(pathx=[px[i, :k].copy() for i, k in enumerate(lens)], pathy=[py[i, :k].copy() for i, k in enumerate(lens)])
+    return out
 
 
 def cell_centre(origin, resolution, x, y):

@@ -1,6 +1,11 @@
 """Loader of tests/thetastar_ref/thetastar_ref.cpp, the CPU restatement of the any-angle leg refinement: the
 `field` leg (the definition the GPU is held to bit for bit) and the `reference` leg (the reference's Theta* search as it runs).
-Compiled by g++ -O2 -ffp-contract=off into a temporary directory on first use."""
+Compiled by g++ -O2 -ffp-contract=off into a temporary directory on first use.
+
+`vertices` lists every vertex of a leg once, start first.  The reference's generatePath returns one entry more: its backtrace pushes
+the last vertex (the goal) twice, and linearInterpolation runs over that list — which is why the interpolated poses end with the goal
+itself.  `poses` is computed from the list with the repeated goal, so it equals the reference's poses as they are; the reference's raw
+path is `vertices` plus `vertices[-1]` once more (tests/test_reference_built.py holds both to the reference's compiled Theta*)."""
 import ctypes as C
 import os
 import subprocess

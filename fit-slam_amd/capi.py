@@ -21,6 +21,8 @@ FS_SEEDS_NEAREST, FS_SEEDS_REFERENCE = 0, 1
 SEED_ORDERS = {"nearest": FS_SEEDS_NEAREST, "reference": FS_SEEDS_REFERENCE}
 FS_ROADMAP_SEARCH_TREE, FS_ROADMAP_SEARCH_REFERENCE = 0, 1
 ROADMAP_SEARCHES = {"tree": FS_ROADMAP_SEARCH_TREE, "reference": FS_ROADMAP_SEARCH_REFERENCE}
+FS_GRID_SEARCH_CONVERGED, FS_GRID_SEARCH_REFERENCE = 0, 1
+GRID_SEARCHES = {"converged": FS_GRID_SEARCH_CONVERGED, "reference": FS_GRID_SEARCH_REFERENCE}
 FS_ALLOC_HUNGARIAN, FS_ALLOC_MINPOS = 0, 1
 ALLOC_METHODS = {"hungarian": FS_ALLOC_HUNGARIAN, "minpos": FS_ALLOC_MINPOS}
 FS_ALLOC_MAX_ROBOTS, FS_ALLOC_MAX_TASKS = 64, 4096
@@ -44,7 +46,7 @@ EXPORTED_SYMBOLS = [
     "fs_get_frontier_costs_roadmap", "fs_roadmap_next_goal", "fs_refine_paths", "fs_refine_field",
     "fs_roadmap_set_keyframes", "fs_roadmap_optimize", "fs_roadmap_get_anchors",
     "fs_search_frontiers", "fs_get_frontier_costs_searched", "fs_set_frontier_seed_order", "fs_set_roadmap_search",
-    "fs_roadmap_routes",
+    "fs_roadmap_routes", "fs_set_grid_search", "fs_navfn_wave_potential",
     "fs_roadmap_update", "fs_get_frontier_costs_searched_roadmap",
     "fs_allocate_tasks", "fs_allocate_tasks_dev", "fs_fleet_allocate_roadmap",
     "fs_keepout_add_fov", "fs_keepout_add_disc", "fs_keepout_clear", "fs_keepout_get", "fs_mark_lethal_fov", "fs_read_grid_region",
@@ -220,6 +222,8 @@ def load_library(build: bool = True):
     L.fs_search_frontiers.argtypes = [vp, C.POINTER(dbl * 2), i32, dbl, i32, i32, i32, vp, i32, vp, C.POINTER(i32), i64, vp, C.POINTER(i64)]
     L.fs_set_frontier_seed_order.argtypes = [vp, i32]
     L.fs_set_roadmap_search.argtypes = [vp, i32]
+    L.fs_set_grid_search.argtypes = [vp, i32]
+    L.fs_navfn_wave_potential.argtypes = [vp, C.POINTER(dbl * 7), i32, C.POINTER(dbl * 3), vp, C.POINTER(i32)]
     L.fs_get_frontier_costs_searched.argtypes = [vp, C.POINTER(dbl * 7), i32, dbl, i32, i32, i32, i32, vp, dbl, dbl, dbl, dbl, C.c_int,
                                                  i32, vp, C.POINTER(i32), vp, vp, vp, vp, vp, vp]
     L.fs_allocate_tasks.argtypes = [vp, i32, i32, vp, vp, i32, vp, C.POINTER(dbl), vp, vp]
@@ -278,6 +282,7 @@ class FrontierScorer:
         self._grid_shape = None          # (nz, ny, nx) of the staged grid: what fs_navfn_potential writes
         self._seed_order = "nearest"     # the context's frontier seed order (fs_set_frontier_seed_order)
         self._roadmap_search = "tree"    # the context's roadmap search (fs_set_roadmap_search)
+        self._grid_search = "converged"  # the context's grid search (fs_set_grid_search)
         self.n_yaw = self.n_elev = self.window = 0
 
     # -- plumbing
@@ -751,8 +756,49 @@ class FrontierScorer:
                                                    alpha, beta, max_vx, max_wz, vp(d_cost), o(d_au), o(d_du), o(d_order), o(d_err)))
 
     # -- grid planner (the path columns)
-    def plan_paths(self, robot_pose7, goal_xyz, achievable_in=None, allow_unknown=False):
-        """setPlanForFrontier ("A*PlannerDistance") for every goal: one potential field from the robot, a descent per goal."""
+    def set_grid_search(self, name: str):
+        """How plan_paths, plan_paths_information, get_frontier_costs_planned and get_frontier_costs_searched plan on the grid
+        (fs_set_grid_search): "converged" (a fresh context's: one converged field per robot cell) or "reference" (the reference's
+        per-frontier A* wave, one per distinct goal cell, bit for bit)."""
+        if name not in GRID_SEARCHES:
+            raise FsError(FS_E_INVALID, f"unknown grid search {name!r} (converged | reference)")
+        self._check(self._L.fs_set_grid_search(self._h, GRID_SEARCHES[name]))
+        self._grid_search = name
+
+    @contextlib.contextmanager
+    def _grid_search_for_call(self, name):
+        """search= of one call: set for the call, the context's own setting restored afterwards"""
+        if name is None:
+            yield
+            return
+        prev = self._grid_search
+        self.set_grid_search(name)
+        try:
+            yield
+        finally:
+            self.set_grid_search(prev)
+
+    def navfn_wave_potential(self, robot_pose7, goal_xyz, allow_unknown=False):
+        """(field, limit): the field of ONE wave of the "reference" grid search, float32 [ny][nx] — the reference's potarr after
+        calcNavFnAstar from the robot cell, stopped at the goal's cell — and its limit bits (1: the cycle budget ran out, 2: a push was
+        dropped at the buffer cap).  Works whatever the grid search is."""
+        pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
+        g = np.asarray(goal_xyz, dtype=np.float64).reshape(-1)
+        goal = (C.c_double * 3)(float(g[0]), float(g[1]), float(g[2]) if g.shape[0] > 2 else 0.0)
+        if self._grid_shape is None:
+            raise FsError(FS_E_STATE, "no grid staged through this scorer (upload_grid / upload_grid_bricks)")
+        nz, ny, nx = self._grid_shape
+        if nz != 1:
+            raise FsError(FS_E_INVALID, "the grid planner is defined on a 2-D costmap (nz == 1)")
+        pot = np.zeros((ny, nx), dtype=np.float32)
+        limit = C.c_int32()
+        self._check(self._L.fs_navfn_wave_potential(self._h, C.byref(pose), 1 if allow_unknown else 0, C.byref(goal), _p(pot), C.byref(limit)))
+        return pot, limit.value
+
+    def plan_paths(self, robot_pose7, goal_xyz, achievable_in=None, allow_unknown=False, search=None):
+        """setPlanForFrontier ("A*PlannerDistance") for every goal, by the context's grid search (set_grid_search; search=
+        "converged" / "reference" for this call only): one potential field from the robot and a descent per goal, or the reference's
+        wave per distinct goal cell and the descent on it."""
         pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
         goal = np.ascontiguousarray(goal_xyz, dtype=np.float64).reshape(-1, 3)
         n = goal.shape[0]
@@ -761,12 +807,13 @@ class FrontierScorer:
             raise ValueError(f"achievable_in has {ai.shape[0]} entries for {n} goals")
         pl, plm, ph = np.zeros(n), np.zeros(n), np.zeros(n)
         ach = np.zeros(n, dtype=np.uint8)
-        self._check(self._L.fs_plan_paths(self._h, C.byref(pose), 1 if allow_unknown else 0, n, _p(goal), _p(ai), _p(pl), _p(plm), _p(ph), _p(ach)))
+        with self._grid_search_for_call(search):
+            self._check(self._L.fs_plan_paths(self._h, C.byref(pose), 1 if allow_unknown else 0, n, _p(goal), _p(ai), _p(pl), _p(plm), _p(ph), _p(ach)))
         return dict(path_length=pl, path_length_m=plm, path_heading=ph, achievable=ach)
 
     def plan_paths_information(self, robot_pose7, goal_xyz, achievable_in=None, allow_unknown=False, sample_distance=1.5, lookahead=10,
-                               fi_threshold=550.0, want_waypoints=False):
-        """plan_paths, and the Fisher information along every planned path: setPlanForFrontier's way points (one once more than
+                               fi_threshold=550.0, want_waypoints=False, search=None):
+        """plan_paths (search= as plan_paths'), and the Fisher information along every planned path: setPlanForFrontier's way points (one once more than
         int(sample_distance / resolution) path points have gone by, looking `lookahead` points ahead), isPoseSafe's scalar at each.
         Per frontier: n_waypoints, info_mean, info_min, first_unsafe (-1: every way point is above fi_threshold).
         want_waypoints: also waypoint_offset [n + 1], waypoint_pose7 [total][7] and waypoint_info [total], in list order."""
@@ -790,6 +837,10 @@ class FrontierScorer:
             return self._L.fs_plan_paths_information(self._h, C.byref(pose), 1 if allow_unknown else 0, n, _p(goal), _p(ai), C.byref(prm),
                                                      _p(pl), _p(plm), _p(ph), _p(ach), _p(nwp), _p(mean), _p(mn), _p(unsafe), room,
                                                      total, _p(off), _p(poses), _p(info))
+        with self._grid_search_for_call(search):
+            return self._plan_paths_information_call(call, out, n, want_waypoints)
+
+    def _plan_paths_information_call(self, call, out, n, want_waypoints):
         if not want_waypoints:
             self._check(call(0, None, None, None, None))
             return out
@@ -821,8 +872,9 @@ class FrontierScorer:
         return pot
 
     def get_frontier_costs_planned(self, robot_pose7, goal_xyz, frontier_size=None, blacklisted=None, allow_unknown=False,
-                                   with_fim=False, alpha=0.25, beta=1.0, max_vx=0.5, max_wz=0.5):
-        """get_frontier_costs with the path columns planned on the device in the same call (plan -> score -> rank)."""
+                                   with_fim=False, alpha=0.25, beta=1.0, max_vx=0.5, max_wz=0.5, search=None):
+        """get_frontier_costs with the path columns planned on the device in the same call (plan -> score -> rank); search= as
+        plan_paths'."""
         pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
         goal = np.ascontiguousarray(goal_xyz, dtype=np.float64).reshape(-1, 3)
         n = goal.shape[0]
@@ -830,9 +882,10 @@ class FrontierScorer:
         bl = None if blacklisted is None else np.ascontiguousarray(blacklisted, dtype=np.uint8)
         rec = np.zeros(n, dtype=RECORD_DTYPE)
         cost = np.zeros(n); au = np.zeros(n); du = np.zeros(n); order = np.zeros(n, dtype=np.int32); plm = np.zeros(n)
-        self._check(self._L.fs_get_frontier_costs_planned(self._h, C.byref(pose), 1 if allow_unknown else 0, n, _p(goal), _p(fs), _p(bl),
-                                                          alpha, beta, max_vx, max_wz, 1 if with_fim else 0, _p(rec), _p(cost), _p(au), _p(du),
-                                                          _p(order), _p(plm)))
+        with self._grid_search_for_call(search):
+            self._check(self._L.fs_get_frontier_costs_planned(self._h, C.byref(pose), 1 if allow_unknown else 0, n, _p(goal), _p(fs), _p(bl),
+                                                              alpha, beta, max_vx, max_wz, 1 if with_fim else 0, _p(rec), _p(cost), _p(au), _p(du),
+                                                              _p(order), _p(plm)))
         return dict(records=rec, weighted_cost=cost, arrival_utility=au, distance_utility=du, order=order, path_length_m=plm)
 
     # -- frontier roadmap (the reference's default planner, "RoadmapPlannerDistance")

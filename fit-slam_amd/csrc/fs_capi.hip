@@ -5,6 +5,7 @@
 #include "fs_internal.h"
 #include "fs_keepout.h"
 #include "fs_median_sort.h"
+#include "fs_navfn_wave.h"
 #include "fs_roadmap_astar.h"
 
 #include <algorithm>
@@ -376,6 +377,18 @@ struct fs_ctx {
     DevBuf<float> d_nav_path;         // [n][2][4 * max(nx, ny)] path points
     DevBuf<char> d_nav_in, d_nav_out; // goal cells | headings;  path length | length in m | heading | achievable
     PinnedBuf h_nav_in, h_nav_out;
+    // the REFERENCE grid search (fs_set_grid_search): one calcNavFnAstar wave per distinct goal cell (fs_navfn_wave.h), in batches
+    // of slots; nothing is kept across calls
+    int32_t nav_search = FS_GRID_SEARCH_CONVERGED;
+    int32_t nw_opt_slots = 0;                 // "navfn.wave_slots": 0 = as many as "navfn.wave_bytes" holds
+    int64_t nw_opt_bytes = (int64_t)1 << 30;  // "navfn.wave_bytes"
+    int32_t nw_opt_cap = 10000;               // "navfn.wave_cap": entries of each priority buffer (tests; the reference's 10 000)
+    int64_t nw_batches = 0;                   // slot batches of the last call (counter 1038)
+    DevBuf<float> d_nw_pot;           // [slots][ny][nx]
+    DevBuf<uint8_t> d_nw_pend;        // [slots][ny][nx]
+    DevBuf<int32_t> d_nw_buf;         // [slots][3][cap]
+    DevBuf<int32_t> d_nw_idx;         // stats [4] | wave cell [n] | frontier wave [n] | first [n] | wave limit [n] (NwIdxLayout)
+    PinnedBuf h_nw_idx;               // stats | wave cell | frontier wave, as the host form sends them
 
     // Fisher information along the planned paths (fs_pathinfo.hip)
     bool opt_pi_dedup = true;         // "pathinfo.dedup": one pose record per distinct (from cell, to cell) (0: one per way point)
@@ -2211,6 +2224,9 @@ int fs_set_option(fs_ctx *c, const char *key, double value)
     if (std::strcmp(key, "roadmap.tour_one_wg") == 0 && value >= 0 && value <= RM_TREE_ONE_WG) { c->tour_one_wg = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "roadmap.astar_lds_entries") == 0 && value >= 0 && value <= 2048) { c->astar_lds_entries = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "roadmap.dedup_one_wg") == 0 && value >= 0 && value <= FS_KF_DEDUP_ONE_WG) { c->kf_one_wg = (int32_t)value; return FS_OK; }
+    if (std::strcmp(key, "navfn.wave_slots") == 0 && value >= 0 && value <= 65535) { c->nw_opt_slots = (int32_t)value; return FS_OK; }
+    if (std::strcmp(key, "navfn.wave_bytes") == 0 && value >= 1 && value <= 1099511627776.0) { c->nw_opt_bytes = (int64_t)value; return FS_OK; }
+    if (std::strcmp(key, "navfn.wave_cap") == 0 && value >= 16 && value <= 10000) { c->nw_opt_cap = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "pathinfo.dedup") == 0) { c->opt_pi_dedup = value != 0.0; return FS_OK; }
     if (std::strcmp(key, "routes.dedup") == 0) { c->opt_rt_dedup = value != 0.0; return FS_OK; }
     if (std::strcmp(key, "routes.pool_nodes") == 0 && value >= 1 && value <= (double)(1 << 30)) { c->rt_pool_cap = (int64_t)value; return FS_OK; }
@@ -2257,7 +2273,21 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
         {1026, &fs_ctx::rt_routes, false}, {1027, &fs_ctx::rt_walks, false}, {1028, &fs_ctx::rt_poses, false}, {1029, &fs_ctx::rt_retries, true},
         // the per-tick update (fs_roadmap_update): walks, owners (distinct closest nodes) and keep-rule rounds of the last call
         {1033, &fs_ctx::ru_walks, false}, {1034, &fs_ctx::ru_owners, false}, {1035, &fs_ctx::ru_rounds, false},
+        // the REFERENCE grid search: slot batches of the last call
+        {1038, &fs_ctx::nw_batches, false},
     };
+    // ... its waves, the waves that ended on the cycle budget, the waves that dropped a push at the cap and the chunks run again, of
+    // the last call: they stay on the device until asked for
+    if (c && value && (which == 1037 || (which >= 1039 && which <= 1041))) {
+        FS_HIP(c, hipSetDevice(c->device));
+        *value = 0;
+        if (!c->d_nw_idx.p) return FS_OK;
+        int32_t v = 0;
+        FS_HIP(c, hipMemcpyAsync(&v, c->d_nw_idx.p + (which == 1037 ? 0 : which - 1038), sizeof v, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        *value = v;
+        return FS_OK;
+    }
     // the task allocator (fs_allocate_tasks, fs_allocate_tasks_dev, fs_fleet_allocate_roadmap): augmentations, step-5 runs and
     // step-3 primes of the last solve.  The solve leaves them on the device (the device form is not waited for): read here
     if (c && value && which >= 1030 && which <= 1032) {
@@ -3337,10 +3367,14 @@ double nav_heading(const double pose7[7], double gx, double gy)
     return h;
 }
 
+int navfn_wave_check(fs_ctx *c);
+
 int nav_check(fs_ctx *c, const double robot_pose7[7])
 {
     if (!robot_pose7) return fail(c, FS_E_INVALID, "null robot pose");
-    return grid2d_check(c, "the grid planner");
+    const int rc = grid2d_check(c, "the grid planner");
+    if (rc || c->nav_search != FS_GRID_SEARCH_REFERENCE) return rc;
+    return navfn_wave_check(c);
 }
 
 // The field for (robot cell, allow_unknown) on the staged grid: the cached one, or built now (synchronises the stream).
@@ -3406,8 +3440,8 @@ int navfn_ensure(fs_ctx *c, size_t nn)
     return FS_OK;
 }
 
-// The path kernel on `field` for the goal cells and headings in d_nav_in: the four columns land in d_nav_out.
-int navfn_paths(fs_ctx *c, const float *field, int32_t n, int32_t rx, int32_t ry)
+// The path kernel's arguments on `field` for the goal cells and headings in d_nav_in: the four columns land in d_nav_out.
+FsNavfnPathArgs navfn_path_args(fs_ctx *c, const float *field, int32_t n, int32_t rx, int32_t ry)
 {
     const NavInLayout I((size_t)n);
     const PlanOutLayout O((size_t)n);
@@ -3422,9 +3456,112 @@ int navfn_paths(fs_ctx *c, const float *field, int32_t n, int32_t rx, int32_t ry
     a.path_length_m = reinterpret_cast<double *>(c->d_nav_out.p + O.len_m);
     a.path_heading = reinterpret_cast<double *>(c->d_nav_out.p + O.head);
     a.achievable = reinterpret_cast<uint8_t *>(c->d_nav_out.p + O.ach);
+    return a;
+}
+
+// The path kernel on the one converged `field`.
+int navfn_paths(fs_ctx *c, const float *field, int32_t n, int32_t rx, int32_t ry)
+{
+    const FsNavfnPathArgs a = navfn_path_args(c, field, n, rx, ry);
     ScopedTimer t(c, 8);
     FS_HIP(c, fs_launch_navfn_paths(a, c->stream));
     return FS_OK;
+}
+
+// ---- the REFERENCE search (fs_set_grid_search): per distinct goal cell the calcNavFnAstar wave from the robot cell that stops at it
+// (fs_navfn_wave.h), one wavefront per wave, then calcPath on that wave's field.  The converged field and its cache are not touched.
+struct NwIdxLayout {
+    size_t stats, cell, wave, first, limit, total;       // in int32 words of d_nw_idx
+    explicit NwIdxLayout(size_t n) : stats(0), cell(4), wave(4 + n), first(4 + 2 * n), limit(4 + 3 * n), total(4 + 4 * n) {}
+};
+
+int navfn_wave_check(fs_ctx *c)
+{
+    if (c->nx > FS_NW_MAX_SIDE || c->ny > FS_NW_MAX_SIDE)
+        return fail(c, FS_E_INVALID, "the REFERENCE grid search takes maps of at most %d cells a side (this one: %d x %d)", FS_NW_MAX_SIDE, c->nx, c->ny);
+    return FS_OK;
+}
+
+// The slots for up to max_waves waves of a list of nn frontiers, the cost array, and the kernels' arguments.
+int navfn_wave_prepare(fs_ctx *c, int32_t rx, int32_t ry, int32_t allow, size_t nn, int64_t max_waves, FsNavfnWaveArgs &w)
+{
+    const size_t ns = (size_t)c->nx * (size_t)c->ny, cap = (size_t)c->nw_opt_cap;
+    const int64_t per_slot = (int64_t)(5 * ns + 12 * cap);
+    int64_t slots = c->nw_opt_slots > 0 ? c->nw_opt_slots : std::max<int64_t>(1, c->nw_opt_bytes / per_slot);
+    slots = std::min<int64_t>(std::min<int64_t>(slots, 65535), std::max<int64_t>(1, max_waves));
+    const NwIdxLayout L(nn);
+    FS_HIP(c, c->d_nav_cost.ensure(ns));
+    FS_HIP(c, c->d_nw_pot.ensure((size_t)slots * ns));
+    FS_HIP(c, c->d_nw_pend.ensure((size_t)slots * ns));
+    FS_HIP(c, c->d_nw_buf.ensure((size_t)slots * 3 * cap));
+    FS_HIP(c, c->d_nw_idx.ensure(L.total));
+    FS_HIP(c, fs_launch_navfn_costs(c->d_cells.p, c->nx, c->ny, allow ? 1 : 0, c->d_nav_cost.p, c->stream));
+    w = FsNavfnWaveArgs{};
+    w.cost = c->d_nav_cost.p; w.nx = c->nx; w.ny = c->ny; w.rx = rx; w.ry = ry;
+    w.cap = (int32_t)cap; w.slots = (int32_t)slots;
+    w.pot = c->d_nw_pot.p; w.pending = c->d_nw_pend.p; w.buf = c->d_nw_buf.p;
+    w.wave_cell = c->d_nw_idx.p + L.cell; w.frontier_wave = c->d_nw_idx.p + L.wave;
+    w.stats = c->d_nw_idx.p + L.stats; w.wave_limit = c->d_nw_idx.p + L.limit;
+    return FS_OK;
+}
+
+// Batch by batch, with no synchronisation in between: the fill, the waves, the descents of that batch's frontiers before the slots
+// are used again.  `waves` bounds the call's waves (the host form: their number); the descents of batch 0 also write the columns
+// of the frontiers without a wave, so they run even where there is none.
+int navfn_wave_batches(fs_ctx *c, const FsNavfnWaveArgs &w, int64_t waves, int32_t n, int32_t rx, int32_t ry)
+{
+    const FsNavfnPathArgs a = navfn_path_args(c, w.pot, n, rx, ry);
+    const int64_t batches = (waves + w.slots - 1) / w.slots;
+    c->nw_batches = batches;
+    for (int64_t b = 0; b < std::max<int64_t>(batches, 1); ++b) {
+        const int64_t base = b * w.slots;
+        if (b < batches) {
+            ScopedTimer t(c, 7);
+            FS_HIP(c, fs_launch_navfn_wave_batch(w, (int32_t)base, (int32_t)std::min<int64_t>(w.slots, waves - base), c->stream));
+        }
+        ScopedTimer t(c, 8);
+        FS_HIP(c, fs_launch_navfn_paths_wave(a, w, (int32_t)base, c->stream));
+    }
+    return FS_OK;
+}
+
+// navfn_plan_enqueue's tail under REFERENCE: cell [n] are the goal cells on the host (-1: not planned), d_nav_in is on its way.
+int navfn_wave_plan_host(fs_ctx *c, int32_t rx, int32_t ry, int32_t allow, int32_t n, const int32_t *cell)
+{
+    const size_t nn = (size_t)n;
+    std::vector<int32_t> distinct;
+    for (size_t i = 0; i < nn; ++i)
+        if (cell[i] >= 0) distinct.push_back(cell[i]);
+    std::sort(distinct.begin(), distinct.end());
+    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+    FsNavfnWaveArgs w;
+    const int rc = navfn_wave_prepare(c, rx, ry, allow, nn, (int64_t)distinct.size(), w);
+    if (rc) return rc;
+    const NwIdxLayout L(nn);
+    FS_HIP(c, c->h_nw_idx.ensure(4 * L.first));
+    int32_t *h = reinterpret_cast<int32_t *>(c->h_nw_idx.p);
+    h[0] = (int32_t)distinct.size(); h[1] = h[2] = h[3] = 0;
+    for (size_t k = 0; k < nn; ++k) h[L.cell + k] = k < distinct.size() ? distinct[k] : -1;
+    for (size_t i = 0; i < nn; ++i)
+        h[L.wave + i] = cell[i] < 0 ? -1 : (int32_t)(std::lower_bound(distinct.begin(), distinct.end(), cell[i]) - distinct.begin());
+    FS_HIP(c, hipMemcpyAsync(c->d_nw_idx.p, h, 4 * L.first, hipMemcpyHostToDevice, c->stream));
+    return navfn_wave_batches(c, w, (int64_t)distinct.size(), n, rx, ry);
+}
+
+// navfn_plan_enqueue_dev's tail under REFERENCE: the goal cells are in d_nav_in (-1: not planned) and the distinct ones are listed
+// on the device, so the host cuts batches for n waves and the kernels of a batch beyond the last wave return at once.
+int navfn_wave_plan_dev(fs_ctx *c, int32_t rx, int32_t ry, bool robot_on, int32_t allow, int32_t n)
+{
+    const size_t nn = (size_t)n;
+    FsNavfnWaveArgs w;
+    const int rc = navfn_wave_prepare(c, rx, ry, allow, nn, n, w);
+    if (rc) return rc;
+    const NwIdxLayout L(nn);
+    const NavInLayout I(nn);
+    FS_HIP(c, hipMemsetAsync(c->d_nw_idx.p, 0, 16, c->stream));
+    FS_HIP(c, fs_launch_navfn_wave_cells(reinterpret_cast<const int32_t *>(c->d_nav_in.p + I.cell), n, c->d_nw_idx.p + L.first, c->d_nw_idx.p + L.cell,
+                                         c->d_nw_idx.p + L.wave, c->d_nw_idx.p + L.stats, c->stream));
+    return navfn_wave_batches(c, w, robot_on ? n : 0, n, rx, ry);
 }
 
 // Goal cells and headings staged, the field (cached or built), the path kernel: the four columns land in d_nav_out on the
@@ -3447,6 +3584,10 @@ int navfn_plan_enqueue(fs_ctx *c, const double robot7[7], int32_t allow, int32_t
         head[i] = planned ? nav_heading(robot7, goal_xyz[3 * i], goal_xyz[3 * i + 1]) : 0.0;
         need_field |= planned;
     }
+    if (c->nav_search == FS_GRID_SEARCH_REFERENCE) {
+        FS_HIP(c, hipMemcpyAsync(c->d_nav_in.p, c->h_nav_in.p, I.total, hipMemcpyHostToDevice, c->stream));
+        return navfn_wave_plan_host(c, rx, ry, allow, n, cell);
+    }
     const float *field = nullptr;
     if (need_field) { rc = navfn_field(c, rx, ry, allow, &field); if (rc) return rc; }
     FS_HIP(c, hipMemcpyAsync(c->d_nav_in.p, c->h_nav_in.p, I.total, hipMemcpyHostToDevice, c->stream));
@@ -3464,12 +3605,14 @@ int navfn_plan_enqueue_dev(fs_ctx *c, const double robot7[7], int32_t allow, int
     if (rc) return rc;
     int32_t rx = 0, ry = 0;
     const bool robot_on = grid_world_to_map(c, robot7[0], robot7[1], rx, ry);
+    const bool reference = c->nav_search == FS_GRID_SEARCH_REFERENCE;
     const float *field = nullptr;
-    if (robot_on && n > 0) { rc = navfn_field(c, rx, ry, allow, &field); if (rc) return rc; }
+    if (!reference && robot_on && n > 0) { rc = navfn_field(c, rx, ry, allow, &field); if (rc) return rc; }
     std::memcpy(c->h_nav_in.p + I.head, h_heading, 8 * nn);
     FS_HIP(c, hipMemcpyAsync(c->d_nav_in.p + I.head, c->h_nav_in.p + I.head, 8 * nn, hipMemcpyHostToDevice, c->stream));
     FS_HIP(c, fs_launch_goal_cells(d_goal_xyz, n, c->nx, c->ny, c->origin[0], c->origin[1], c->res, robot_on ? 1 : 0,
                                    reinterpret_cast<int32_t *>(c->d_nav_in.p + I.cell), c->stream));
+    if (reference) return navfn_wave_plan_dev(c, rx, ry, robot_on, allow, n);
     return navfn_paths(c, field, n, rx, ry);
 }
 
@@ -3583,6 +3726,44 @@ int fs_navfn_potential(fs_ctx *c, const double robot_pose7[7], int32_t allow_unk
     if (rc) return rc;
     FS_HIP(c, hipMemcpyAsync(potential, field, sizeof(float) * (size_t)c->nx * (size_t)c->ny, hipMemcpyDeviceToHost, c->stream));
     FS_HIP(c, hipStreamSynchronize(c->stream));
+    return FS_OK;
+}
+
+int fs_set_grid_search(fs_ctx *c, int32_t search)
+{
+    if (!c) return FS_E_INVALID;
+    if (search != FS_GRID_SEARCH_CONVERGED && search != FS_GRID_SEARCH_REFERENCE) return fail(c, FS_E_INVALID, "unknown grid search %d", search);
+    c->nav_search = search;
+    return FS_OK;
+}
+
+int fs_navfn_wave_potential(fs_ctx *c, const double robot_pose7[7], int32_t allow_unknown, const double goal_xyz[3], float *potential, int32_t *limit)
+{
+    if (!c) return FS_E_INVALID;
+    if (!potential || !goal_xyz || !robot_pose7) return fail(c, FS_E_INVALID, "null pointer");
+    int rc = grid2d_check(c, "the grid planner");
+    if (rc) return rc;
+    rc = navfn_wave_check(c);
+    if (rc) return rc;
+    int32_t rx = 0, ry = 0, gx = 0, gy = 0;
+    if (!grid_world_to_map(c, robot_pose7[0], robot_pose7[1], rx, ry)) return fail(c, FS_E_INVALID, "the robot is off the costmap: no wave");
+    if (!grid_world_to_map(c, goal_xyz[0], goal_xyz[1], gx, gy)) return fail(c, FS_E_INVALID, "the goal is off the costmap: no wave");
+    FsNavfnWaveArgs w;
+    rc = navfn_wave_prepare(c, rx, ry, allow_unknown, 1, 1, w);
+    if (rc) return rc;
+    const NwIdxLayout L(1);
+    FS_HIP(c, c->h_nw_idx.ensure(4 * L.total));
+    int32_t *h = reinterpret_cast<int32_t *>(c->h_nw_idx.p);
+    h[0] = 1; h[1] = h[2] = h[3] = 0;
+    h[L.cell] = gy * c->nx + gx; h[L.wave] = 0;
+    const auto stop = [&](int code) { (void)hipStreamSynchronize(c->stream); return code; };
+    FS_HIP(c, hipMemcpyAsync(c->d_nw_idx.p, h, 4 * L.first, hipMemcpyHostToDevice, c->stream));
+    c->nw_batches = 1;
+    if (fs_launch_navfn_wave_batch(w, 0, 1, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "the wave: launch failed"));
+    FS_HIP(c, hipMemcpyAsync(potential, w.pot, sizeof(float) * (size_t)c->nx * (size_t)c->ny, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipMemcpyAsync(h + L.limit, w.wave_limit, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    if (limit) *limit = h[L.limit];
     return FS_OK;
 }
 

@@ -191,6 +191,27 @@ hipError_t fs_launch_navfn_init(float *d_a, float *d_b, int nx, int ny, int rx, 
 hipError_t fs_launch_navfn_round(const float *d_a, float *d_b, const uint8_t *d_cost, const uint32_t *d_prev, uint32_t *d_cur, int nx, int ny,
                                  int32_t *d_any, hipStream_t s);
 hipError_t fs_launch_navfn_paths(const FsNavfnPathArgs &a, hipStream_t s);
+// the REFERENCE grid search (fs_set_grid_search; fs_navfn_wave.h): one calcNavFnAstar wave per distinct goal cell, one wavefront per
+// wave, in batches of `slots` waves; the descents of a batch read their wave's slot
+struct FsNavfnWaveArgs {
+    const uint8_t *cost;       // [ny][nx] the planner's costs
+    int32_t nx, ny, rx, ry;
+    int32_t cap;               // entries of each priority buffer
+    int32_t slots;
+    float *pot;                // [slots][ny][nx]
+    uint8_t *pending;          // [slots][ny][nx]
+    int32_t *buf;              // [slots][3][cap]
+    const int32_t *wave_cell;      // [waves] the goal cell of every wave
+    const int32_t *frontier_wave;  // [n] the wave of every frontier, -1: none
+    int32_t *stats;            // [4] waves of the call; waves that ended on the cycle budget, that dropped a push, chunks run again
+    int32_t *wave_limit;       // [waves] FS_NW_LIMIT_* of every wave
+};
+// the distinct goal cells of d_cell [n] (-1: not planned) on the device: d_wave_cell, d_frontier_wave, d_stats[0]; d_first [n] scratch
+hipError_t fs_launch_navfn_wave_cells(const int32_t *d_cell, int32_t n, int32_t *d_first, int32_t *d_wave_cell, int32_t *d_frontier_wave,
+                                      int32_t *d_stats, hipStream_t s);
+// waves base .. base + count - 1 (count <= slots) on slots 0 .. count - 1: the fill, then the waves
+hipError_t fs_launch_navfn_wave_batch(const FsNavfnWaveArgs &w, int32_t base, int32_t count, hipStream_t s);
+hipError_t fs_launch_navfn_paths_wave(const FsNavfnPathArgs &a, const FsNavfnWaveArgs &w, int32_t base, hipStream_t s);
 
 // ---- any-angle leg refinement (fs_refine.hip): one converged fp64 cost field per start cell (all fields of a
 // call relaxed in the same launches, blockIdx.y = field), then one wave per leg: descent, Theta*'s parent rule, interpolation.

@@ -17,7 +17,12 @@
 //   * the field is done after a round in which no tile changed.  Both buffers then hold it.
 // Nothing depends on which workgroup runs when: a round reads only A and the flags of the round before.  No atomics.
 // tests/navfn_ref/navfn_ref.cpp performs exactly these steps on the CPU; the tests hold this file to it bit for bit.
+//
+// The REFERENCE search (fs_set_grid_search) does not use that field: per distinct goal cell it runs the reference's own partial wave
+// (NavFn::calcNavFnAstar, defined once in fs_navfn_wave.h), one wavefront per wave, and descends on that wave's field — the
+// kernels at the end of this file.
 #include "fs_internal.h"
+#include "fs_navfn_wave.h"
 
 #include <float.h>
 
@@ -63,19 +68,6 @@ __global__ void navfn_init_kernel(float *__restrict__ a, float *__restrict__ b, 
         b[k] = v;
     }
     if (k < tiles) flags_prev[k] = (k == robot_tile) ? kForce : 0u;
-}
-
-// updateCell's value from the four neighbours (double literals of the quadratic evaluated in double)
-__device__ __forceinline__ float cell_update(float l, float r, float u, float d, float hf)
-{
-    float tc = (l < r) ? l : r;
-    float ta = (u < d) ? u : d;
-    float dc = tc - ta;
-    if (dc < 0) { dc = -dc; ta = tc; }
-    if (dc >= hf) return ta + hf;
-    const float q = dc / hf;
-    const float v = (float)(-0.2301 * (double)q * (double)q + 0.5307 * (double)q + 0.7040);
-    return ta + hf * v;
 }
 
 // One round: workgroup t = one tile.  any[0] is raised (plain store of 1) when a tile changed.
@@ -130,7 +122,7 @@ __global__ __launch_bounds__(NAVFN_THREADS) void navfn_round_kernel(const float 
             const int l = slot[q];
             float p = S[l];
             if (upd[q]) {
-                const float pot = cell_update(S[l - 1], S[l + 1], S[l - NAVFN_W], S[l + NAVFN_W], hf[q]);
+                const float pot = fs_nw_cell_update(S[l - 1], S[l + 1], S[l - NAVFN_W], S[l + NAVFN_W], hf[q]);
                 if (pot < p) { p = pot; ch = 1; }
             }
             D[l] = p;
@@ -203,15 +195,14 @@ struct Field {
     }
 };
 
-__global__ void navfn_paths_kernel(FsNavfnPathArgs a)
+// calcPath from frontier f down `field` and the four columns (the points go to the frontier's scratch)
+__device__ __forceinline__ void navfn_descend(const FsNavfnPathArgs &a, int f, const float *__restrict__ field)
 {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= a.n) return;
     const double dmax = DBL_MAX;
     double len_pts = dmax, len_m = dmax, head = dmax;
     uint8_t ok = 0;
     const int32_t goal = a.goal_cell[f];
-    const Field F{a.pot, a.nx, (int64_t)a.nx * a.ny};
+    const Field F{field, a.nx, (int64_t)a.nx * a.ny};
     if (goal >= 0 && F.pot(goal) < kPotHigh) {
         float *px = a.scratch + (int64_t)f * 2 * a.max_cycles, *py = px + a.max_cycles;
         const int nx = a.nx;
@@ -289,6 +280,147 @@ __global__ void navfn_paths_kernel(FsNavfnPathArgs a)
     a.achievable[f] = ok;
 }
 
+__global__ void navfn_paths_kernel(FsNavfnPathArgs a)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= a.n) return;
+    navfn_descend(a, f, a.pot);
+}
+
+// ---------------------------------------------------------------- the REFERENCE search: one wave per distinct goal cell
+// (fs_navfn_wave.h holds the wave's definition; this is its walk in chunks of 64 entries, one per lane)
+
+// The distinct goal cells of a list whose cells lie in device memory.  first[f]: the lowest frontier with f's cell (-1: not planned).
+__global__ void navfn_wave_first_kernel(const int32_t *__restrict__ cell, int32_t n, int32_t *__restrict__ first)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    const int32_t c = cell[f];
+    int32_t g = -1;
+    if (c >= 0)
+        for (g = 0; g < f; ++g)
+            if (cell[g] == c) break;
+    first[f] = g;
+}
+
+// ... their waves in order of first appearance: frontier_wave[f], wave_cell[wave]; thread n counts them into stats[0]
+__global__ void navfn_wave_rank_kernel(const int32_t *__restrict__ cell, const int32_t *__restrict__ first, int32_t n,
+                                       int32_t *__restrict__ wave_cell, int32_t *__restrict__ frontier_wave, int32_t *__restrict__ stats)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f > n) return;
+    const int32_t upto = (f == n) ? n : first[f];
+    int32_t r = 0;
+    for (int32_t g = 0; g < upto; ++g) r += (first[g] == g) ? 1 : 0;
+    if (f == n) { stats[0] = r; return; }
+    frontier_wave[f] = (upto < 0) ? -1 : r;
+    if (upto == f) wave_cell[r] = cell[f];
+}
+
+// the slots of a batch: POT_HIGH, nothing pending (blockIdx.y = slot; slots beyond the list's last wave are left alone)
+__global__ void navfn_wave_fill_kernel(FsNavfnWaveArgs a, int32_t base)
+{
+    const int slot = blockIdx.y;
+    if (base + slot >= a.stats[0]) return;
+    const int64_t ns = (int64_t)a.nx * a.ny, k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= ns) return;
+    a.pot[slot * ns + k] = kPotHigh;
+    a.pending[slot * ns + k] = 0;
+}
+
+__device__ __forceinline__ int32_t uni(int32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// One workgroup of ONE wavefront per slot; wave `base + slot` of the call.  The wave's control state (fill counts, curT, limit, the
+// three buffer pointers) is held by every lane and computed from wave-uniform values only; lane k of a chunk owns entry k.
+// Lanes hand values to each other through global memory (potential, pending, buffers), and the compiler orders memory per lane
+// only: every phase that reads what another lane wrote in the phase before is separated from it by __syncthreads().  For a
+// workgroup of one wavefront that is a workgroup-scope release/acquire fence plus a barrier the wave passes at once; the lanes share
+// one CU's write-through L1, so workgroup scope is enough.  No atomic decides anything (the three statistics at the end are counted
+// with atomics and read by nobody on the device).  Every loop is bounded before it starts: cycles, cur_n, the bits of `todo`.
+__global__ __launch_bounds__(FS_NW_WIDTH) void navfn_wave_kernel(FsNavfnWaveArgs a, int32_t base)
+{
+    const int slot = blockIdx.x, lane = threadIdx.x;
+    const int32_t wid = base + slot;
+    if (wid >= a.stats[0]) return;
+    const int32_t nx = a.nx;
+    const int64_t ns = (int64_t)nx * a.ny;
+    const fs_nw_map m{a.cost, nx, a.ny};
+    const int32_t goal = a.wave_cell[wid];
+    fs_nw_wave w{};
+    w.pot = a.pot + slot * ns;
+    w.pending = a.pending + slot * ns;
+    w.cur = a.buf + (int64_t)slot * 3 * a.cap; w.next = w.cur + a.cap; w.over = w.next + a.cap;
+    w.cap = a.cap;
+    w.sx = goal % nx; w.sy = goal / nx;
+    w.hash = nullptr;
+    int32_t cycles = 0;
+    if (lane == 0) cycles = fs_nw_begin(m, w, a.rx, a.ry);
+    cycles = uni(cycles);
+    w.cur_n = uni(w.cur_n); w.next_n = 0; w.over_n = 0;
+    w.limit = uni(w.limit);
+    w.curT = __int_as_float(uni(__float_as_int(w.curT)));
+    __syncthreads();
+    int32_t cycle = 0, replays = 0;
+    for (; cycle < cycles; ++cycle) {
+        if (w.cur_n == 0 && w.next_n == 0) break;
+        for (int32_t i = lane; i < w.cur_n; i += FS_NW_WIDTH) w.pending[w.cur[i]] = 0;
+        __syncthreads();
+        for (int32_t at = 0; at < w.cur_n;) {
+            const int32_t cnt = min(FS_NW_WIDTH, w.cur_n - at);
+            // evaluate: every lane its entry, from memory
+            fs_nw_eval e;
+            e.cell = 0; e.p = 0.0f; e.bits = 0u;
+            e.pos[0] = e.pos[1] = e.pos[2] = e.pos[3] = 0;
+            if (lane < cnt) e = fs_nw_evaluate(m, w, w.cur[at + lane]);
+            // commit, in entry order, in wave-uniform code: entry j's bits and cell are broadcast, the appends and the cap are
+            // decided on the uniform fill counts, the later lanes react in registers
+            uint64_t todo = __ballot((e.bits & (FS_NW_STORE | FS_NW_CANDS)) != 0u);
+            uint64_t dep = 0;
+            while (todo) {
+                const int j = uni((int32_t)__builtin_ctzll(todo));
+                if (dep && (int)__builtin_ctzll(dep) <= j) break;
+                todo &= todo - 1;
+                const int32_t cell_j = __builtin_amdgcn_readlane(e.cell, j);
+                uint32_t bits_j = (uint32_t)__builtin_amdgcn_readlane((int32_t)e.bits, j);
+                int32_t pos[4] = {0, 0, 0, 0};
+                bits_j = fs_nw_commit_entry(w.next_n, w.over_n, w.limit, w.cap, bits_j, pos);
+                const bool mine = lane == j;
+                const uint32_t met = fs_nw_react(e.bits, e.cell, nx, cell_j, bits_j);
+                e.bits = mine ? bits_j : ((lane > j && lane < cnt) ? met : e.bits);
+                e.pos[0] = mine ? pos[0] : e.pos[0]; e.pos[1] = mine ? pos[1] : e.pos[1];
+                e.pos[2] = mine ? pos[2] : e.pos[2]; e.pos[3] = mine ? pos[3] : e.pos[3];
+                dep = __ballot((e.bits & FS_NW_DEP) != 0u);
+            }
+            // the prefix up to the first entry whose evaluation an earlier store made stale is final; the next chunk starts there
+            // (lane 0 is never stale: a chunk advances by at least one entry)
+            const int32_t done = dep ? min(cnt, (int32_t)__builtin_ctzll(dep)) : cnt;
+            if (lane < done) fs_nw_commit_write(w, nx, e);
+            if (done < cnt) ++replays;
+            at += done;
+            __syncthreads();
+        }
+        fs_nw_end_cycle(w);
+        if (w.pot[goal] < kPotHigh) break;
+    }
+    if (cycle >= cycles) w.limit |= FS_NW_LIMIT_CYCLES;
+    if (lane == 0) {
+        a.wave_limit[wid] = w.limit;
+        if (w.limit & FS_NW_LIMIT_CYCLES) atomicAdd(&a.stats[1], 1);
+        if (w.limit & FS_NW_LIMIT_CAP) atomicAdd(&a.stats[2], 1);
+        if (replays) atomicAdd(&a.stats[3], replays);
+    }
+}
+
+// the descents of a batch: every frontier whose wave ran in it, on its wave's slot; the frontiers without a wave with batch 0
+__global__ void navfn_paths_wave_kernel(FsNavfnPathArgs a, FsNavfnWaveArgs wv, int32_t base)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= a.n) return;
+    const int32_t wid = wv.frontier_wave[f];
+    if (wid < 0 ? base != 0 : (wid < base || wid >= base + wv.slots)) return;
+    navfn_descend(a, f, wid < 0 ? wv.pot : wv.pot + (int64_t)(wid - base) * a.nx * a.ny);
+}
+
 }  // namespace
 
 hipError_t fs_launch_navfn_costs(const uint8_t *d_cells, int nx, int ny, int allow_unknown, uint8_t *d_cost, hipStream_t s)
@@ -319,5 +451,29 @@ hipError_t fs_launch_navfn_paths(const FsNavfnPathArgs &a, hipStream_t s)
 {
     if (a.n <= 0) return hipSuccess;
     hipLaunchKernelGGL(navfn_paths_kernel, dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_navfn_wave_cells(const int32_t *d_cell, int32_t n, int32_t *d_first, int32_t *d_wave_cell, int32_t *d_frontier_wave,
+                                      int32_t *d_stats, hipStream_t s)
+{
+    if (n > 0) hipLaunchKernelGGL(navfn_wave_first_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, d_cell, n, d_first);
+    hipLaunchKernelGGL(navfn_wave_rank_kernel, dim3((unsigned)((n + 64) / 64)), dim3(64), 0, s, d_cell, d_first, n, d_wave_cell, d_frontier_wave, d_stats);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_navfn_wave_batch(const FsNavfnWaveArgs &w, int32_t base, int32_t count, hipStream_t s)
+{
+    if (count <= 0) return hipSuccess;
+    const int64_t ns = (int64_t)w.nx * w.ny;
+    hipLaunchKernelGGL(navfn_wave_fill_kernel, dim3((unsigned)((ns + 255) / 256), (unsigned)count), dim3(256), 0, s, w, base);
+    hipLaunchKernelGGL(navfn_wave_kernel, dim3((unsigned)count), dim3(FS_NW_WIDTH), 0, s, w, base);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_navfn_paths_wave(const FsNavfnPathArgs &a, const FsNavfnWaveArgs &w, int32_t base, hipStream_t s)
+{
+    if (a.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(navfn_paths_wave_kernel, dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, s, a, w, base);
     return hipGetLastError();
 }

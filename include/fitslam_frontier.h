@@ -535,12 +535,35 @@ int fs_rank_candidates_dev(fs_ctx *ctx, int32_t n, const fs_record *d_records, c
  * at the goal and drops pushes beyond 10 000 per buffer: per frontier, a partial field); it is kept per context for (grid,
  * robot cell, allow_unknown) — fs_upload_grid, fs_upload_grid_bricks and fs_update_grid_region drop it.  A frontier that is not
  * planned (achievable_in 0, robot or goal off the map, goal cell unreached, calcPath failed): achievable 0 and DBL_MAX in the
- * three columns.  nz > 1: FS_E_INVALID. */
+ * three columns.  nz > 1: FS_E_INVALID.
+ * Under FS_GRID_SEARCH_REFERENCE (fs_set_grid_search) every frontier is planned on the reference's own partial field instead: per
+ * distinct goal cell, the calcNavFnAstar wave from the robot cell that stops at that cell.  achievable is 1 when the robot and the
+ * goal are on the map, the wave reached the goal cell (potarr[goal] < POT_HIGH) and calcPath > 0 on that wave's field; the three
+ * path columns are defined exactly as above, on that path.  The converged field and its cache are neither used nor touched.  A map
+ * with a side above 4096 cells: FS_E_INVALID (the bound below which the wave's heuristic has been checked against libm's hypot). */
 int fs_plan_paths(fs_ctx *ctx, const double robot_pose7[7], int32_t allow_unknown, int32_t n, const double *goal_xyz,
                   const uint8_t *achievable_in, double *path_length, double *path_length_m, double *path_heading, uint8_t *achievable);
 /* the potential field fs_plan_paths descends, [ny][nx] float (NavFn::getPotArray): for tests and visualisation.  Robot off the
  * map: FS_E_INVALID */
 int fs_navfn_potential(fs_ctx *ctx, const double robot_pose7[7], int32_t allow_unknown, float *potential);
+/* How fs_plan_paths, fs_plan_paths_information, fs_get_frontier_costs_planned and fs_get_frontier_costs_searched plan on the grid, per
+ * context.  FS_GRID_SEARCH_CONVERGED (a fresh context's): ONE converged field per (grid, robot cell, allow_unknown), descended from
+ * every frontier.  FS_GRID_SEARCH_REFERENCE: the reference's per-frontier A* wave (NavFn::calcNavFnAstar: three priority buffers of
+ * 10 000 cells, the curT / priInc thresholds, the stop at the frontier cell, max(nx * ny / 20, nx + ny) cycles) once per distinct
+ * goal cell, one wavefront per wave on the device, and calcPath on that wave's field — the reference's columns bit for bit
+ * (DESIGN.md 4.9 records where the converged field differs).  Any other value: FS_E_INVALID, the setting unchanged.
+ * fs_set_option: "navfn.wave_slots" (0: as many waves side by side as "navfn.wave_bytes", default 1 GiB, holds; a positive value is
+ * the slot count itself) — results are identical for every slot count —, "navfn.wave_cap" (16..10 000, default 10 000: the
+ * capacity of each priority buffer; for tests, only the default is the reference's). */
+#define FS_GRID_SEARCH_CONVERGED 0
+#define FS_GRID_SEARCH_REFERENCE 1
+int fs_set_grid_search(fs_ctx *ctx, int32_t search);
+/* The field of ONE wave of the REFERENCE grid search, [ny][nx] float: NavFn::getPotArray after calcNavFnAstar from the robot cell
+ * with the wave stopped at the goal's cell.  For tests and visualisation; works whatever the context's grid search is.  limit (may
+ * be NULL): bit 0 the cycle budget ran out, bit 1 a push was dropped at the buffer cap.  Robot or goal off the map, nz > 1, a side
+ * above 4096 cells: FS_E_INVALID. */
+int fs_navfn_wave_potential(fs_ctx *ctx, const double robot_pose7[7], int32_t allow_unknown, const double goal_xyz[3], float *potential,
+                            int32_t *limit);
 /* fs_get_frontier_costs with the path columns planned on the device: plan -> arrival (+ Fisher) -> U1 -> order, one call; the
  * planner's achievability feeds achievable_in; path_length_m [n] or NULL.  Same results, bit for bit, as fs_plan_paths followed by
  * fs_get_frontier_costs on its columns; the path columns never visit the host in between. */

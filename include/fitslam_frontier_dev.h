@@ -92,7 +92,11 @@ int  fs_set_option(fs_ctx *ctx, const char *key, double value);
  * (R + 1) * (min(R, n) + 1)); 1036 = bytes of device and page-locked memory the buffers of EVERY context of the process hold at
  * this moment (process-wide like the allocation generation, so "a destroyed context gave everything back" can be asked for exactly
  * on a device that other processes use too; not in it: memory an FS_POISON build has retired and the two raw scratch blocks the
- * ranking and the spatial sort grow for themselves). */
+ * ranking and the spatial sort grow for themselves);
+ * 1037 .. 1041 = the REFERENCE grid search (fs_set_grid_search) in the last call that planned under it: 1037 = waves run (its distinct
+ * goal cells), 1038 = slot batches, 1039 = waves that ended on the cycle budget, 1040 = waves that dropped a push at the buffer cap,
+ * 1041 = chunks of 64 entries that had to be run again from a stale entry on (1037 and 1039-1041 stay on the device until asked
+ * for; all five are 0 on a context that never left FS_GRID_SEARCH_CONVERGED and never called fs_navfn_wave_potential). */
 int  fs_get_counter(fs_ctx *ctx, int which, int64_t *value, int reset);
 
 /* ---------------------------------------------------------------- self test */

@@ -23,6 +23,8 @@ FS_ROADMAP_SEARCH_TREE, FS_ROADMAP_SEARCH_REFERENCE = 0, 1
 ROADMAP_SEARCHES = {"tree": FS_ROADMAP_SEARCH_TREE, "reference": FS_ROADMAP_SEARCH_REFERENCE}
 FS_GRID_SEARCH_CONVERGED, FS_GRID_SEARCH_REFERENCE = 0, 1
 GRID_SEARCHES = {"converged": FS_GRID_SEARCH_CONVERGED, "reference": FS_GRID_SEARCH_REFERENCE}
+FS_REFINE_SEARCH_FIELD, FS_REFINE_SEARCH_REFERENCE = 0, 1
+REFINE_SEARCHES = {"field": FS_REFINE_SEARCH_FIELD, "reference": FS_REFINE_SEARCH_REFERENCE}
 FS_ALLOC_HUNGARIAN, FS_ALLOC_MINPOS = 0, 1
 ALLOC_METHODS = {"hungarian": FS_ALLOC_HUNGARIAN, "minpos": FS_ALLOC_MINPOS}
 FS_ALLOC_MAX_ROBOTS, FS_ALLOC_MAX_TASKS = 64, 4096
@@ -46,7 +48,7 @@ EXPORTED_SYMBOLS = [
     "fs_get_frontier_costs_roadmap", "fs_roadmap_next_goal", "fs_refine_paths", "fs_refine_field",
     "fs_roadmap_set_keyframes", "fs_roadmap_optimize", "fs_roadmap_get_anchors",
     "fs_search_frontiers", "fs_get_frontier_costs_searched", "fs_set_frontier_seed_order", "fs_set_roadmap_search",
-    "fs_roadmap_routes", "fs_set_grid_search", "fs_navfn_wave_potential",
+    "fs_roadmap_routes", "fs_set_grid_search", "fs_navfn_wave_potential", "fs_set_refine_search",
     "fs_roadmap_update", "fs_get_frontier_costs_searched_roadmap",
     "fs_allocate_tasks", "fs_allocate_tasks_dev", "fs_fleet_allocate_roadmap",
     "fs_keepout_add_fov", "fs_keepout_add_disc", "fs_keepout_clear", "fs_keepout_get", "fs_mark_lethal_fov", "fs_read_grid_region",
@@ -223,6 +225,7 @@ def load_library(build: bool = True):
     L.fs_set_frontier_seed_order.argtypes = [vp, i32]
     L.fs_set_roadmap_search.argtypes = [vp, i32]
     L.fs_set_grid_search.argtypes = [vp, i32]
+    L.fs_set_refine_search.argtypes = [vp, i32]
     L.fs_navfn_wave_potential.argtypes = [vp, C.POINTER(dbl * 7), i32, C.POINTER(dbl * 3), vp, C.POINTER(i32)]
     L.fs_get_frontier_costs_searched.argtypes = [vp, C.POINTER(dbl * 7), i32, dbl, i32, i32, i32, i32, vp, dbl, dbl, dbl, dbl, C.c_int,
                                                  i32, vp, C.POINTER(i32), vp, vp, vp, vp, vp, vp]
@@ -283,6 +286,7 @@ class FrontierScorer:
         self._seed_order = "nearest"     # the context's frontier seed order (fs_set_frontier_seed_order)
         self._roadmap_search = "tree"    # the context's roadmap search (fs_set_roadmap_search)
         self._grid_search = "converged"  # the context's grid search (fs_set_grid_search)
+        self._refine_search = "field"    # the context's refine search (fs_set_refine_search)
         self.n_yaw = self.n_elev = self.window = 0
 
     # -- plumbing
@@ -1174,11 +1178,34 @@ class FrontierScorer:
         return out
 
     # -- leg refinement (computePathBetweenPointsThetaStar: the path the robot drives)
-    def refine_paths(self, starts, goals, allow_unknown=True, w_euc=1.0, w_traversal=2.0, corners=8):
-        """computePathBetweenPointsThetaStar for every leg starts[i] -> goals[i] ([n][2] world; extra columns ignored): one cost
-        field per distinct start cell, a descent and Theta*'s parent rule per leg.  dict(status [n] (0 path, 1 start off the map,
-        2 goal off the map, 3 start unsafe, 4 goal unsafe, 5 no path), cost [n], vertices (a [V][2] array per leg, start first),
-        poses (a [N][2] array per leg: the interpolated path the reference publishes))."""
+    def set_refine_search(self, name: str):
+        """How refine_paths and refine_tour plan a leg (fs_set_refine_search): "field" (a fresh context's: a converged cost field per
+        start cell, a descent, Theta*'s parent rule along it) or "reference" (the reference's own Theta* search, one wavefront per
+        distinct leg: its status — 5 also where its loop drops the entry popped last —, vertices and poses bit for bit)."""
+        if name not in REFINE_SEARCHES:
+            raise FsError(FS_E_INVALID, f"unknown refine search {name!r} (field | reference)")
+        self._check(self._L.fs_set_refine_search(self._h, REFINE_SEARCHES[name]))
+        self._refine_search = name
+
+    @contextlib.contextmanager
+    def _refine_search_for_call(self, name):
+        """search= of one call: set for the call, the context's own setting restored afterwards"""
+        if name is None:
+            yield
+            return
+        prev = self._refine_search
+        self.set_refine_search(name)
+        try:
+            yield
+        finally:
+            self.set_refine_search(prev)
+
+    def refine_paths(self, starts, goals, allow_unknown=True, w_euc=1.0, w_traversal=2.0, corners=8, search=None):
+        """computePathBetweenPointsThetaStar for every leg starts[i] -> goals[i] ([n][2] world; extra columns ignored), by the
+        context's refine search (set_refine_search; search= "field" / "reference" for this call only): one cost field per distinct
+        start cell, a descent and Theta*'s parent rule per leg, or the reference's own search per distinct leg.  dict(status [n]
+        (0 path, 1 start off the map, 2 goal off the map, 3 start unsafe, 4 goal unsafe, 5 no path), cost [n], vertices (a [V][2]
+        array per leg, start first), poses (a [N][2] array per leg: the interpolated path the reference publishes))."""
         def pts(a):
             a = np.asarray(a, dtype=np.float64)
             a = a.reshape(-1, a.shape[-1]) if a.ndim else a.reshape(-1, 2)
@@ -1190,10 +1217,11 @@ class FrontierScorer:
         st = np.zeros(n, dtype=np.int32); cost = np.zeros(n)
         nv = np.zeros(n, dtype=np.int32); npz = np.zeros(n, dtype=np.int32)
         args = (1 if allow_unknown else 0, float(w_euc), float(w_traversal), int(corners))
-        # size first (the fields are cached, so the second call only repeats the legs)
-        self._check(self._L.fs_refine_paths(self._h, n, _p(s), _p(g), *args, _p(st), _p(cost), _p(nv), None, _p(npz), None))
-        vert = np.zeros((int(nv.sum()), 2)); pose = np.zeros((int(npz.sum()), 2))
-        self._check(self._L.fs_refine_paths(self._h, n, _p(s), _p(g), *args, _p(st), _p(cost), _p(nv), _p(vert), _p(npz), _p(pose)))
+        with self._refine_search_for_call(search):
+            # size first (the fields are cached, so the second call only repeats the legs; "reference" searches twice)
+            self._check(self._L.fs_refine_paths(self._h, n, _p(s), _p(g), *args, _p(st), _p(cost), _p(nv), None, _p(npz), None))
+            vert = np.zeros((int(nv.sum()), 2)); pose = np.zeros((int(npz.sum()), 2))
+            self._check(self._L.fs_refine_paths(self._h, n, _p(s), _p(g), *args, _p(st), _p(cost), _p(nv), _p(vert), _p(npz), _p(pose)))
         vo, po = np.concatenate([[0], np.cumsum(nv)]), np.concatenate([[0], np.cumsum(npz)])
         return dict(status=st, cost=cost, n_vertices=nv, n_poses=npz,
                     vertices=[vert[vo[i]:vo[i + 1]] for i in range(n)], poses=[pose[po[i]:po[i + 1]] for i in range(n)])
@@ -1212,10 +1240,10 @@ class FrontierScorer:
                                             int(corners), _p(out)))
         return out
 
-    def refine_tour(self, robot_pose7, goal_xyz, tour):
+    def refine_tour(self, robot_pose7, goal_xyz, tour, search=None):
         """getNextGoal's published plan for a roadmap_next_goal result: the legs robot -> goal[tour[0]] -> goal[tour[1]] -> ...,
         planned as computePathBetweenPointsThetaStar(..., true) does.  refine_paths' dict plus `path`: the poses of the legs that
-        found a path, back to back (what FullPathOptimizer accumulates into its plan)."""
+        found a path, back to back (what FullPathOptimizer accumulates into its plan).  search= as refine_paths'."""
         robot = np.asarray(robot_pose7, dtype=np.float64).reshape(7)[:2]
         goal = np.asarray(goal_xyz, dtype=np.float64).reshape(-1, 3)[:, :2]
         idx = np.asarray(tour["tour"] if isinstance(tour, dict) else tour, dtype=np.int64).reshape(-1)
@@ -1223,7 +1251,7 @@ class FrontierScorer:
             return dict(status=np.zeros(0, np.int32), cost=np.zeros(0), n_vertices=np.zeros(0, np.int32), n_poses=np.zeros(0, np.int32),
                         vertices=[], poses=[], path=np.zeros((0, 2)))
         pts = np.vstack([robot[None], goal[idx]])
-        out = self.refine_paths(pts[:-1], pts[1:])
+        out = self.refine_paths(pts[:-1], pts[1:], search=search)
         ok = [p for p, s in zip(out["poses"], out["status"]) if s == 0]
         out["path"] = np.vstack(ok) if ok else np.zeros((0, 2))
         return out

@@ -7,6 +7,7 @@
 #include "fs_median_sort.h"
 #include "fs_navfn_wave.h"
 #include "fs_roadmap_astar.h"
+#include "fs_thetastar.h"
 
 #include <algorithm>
 #include <atomic>
@@ -504,6 +505,18 @@ struct fs_ctx {
     DevBuf<int32_t> d_rf_any, d_rf_in, d_rf_scratch;   // rounds x fields words | legs' inputs | chain, parents, vertex cells
     DevBuf<char> d_rf_out, d_rf_pts;          // per-leg columns | vertex and pose slots (when the page-locked buffer is not mapped)
     PinnedBuf h_rf_in, h_rf_out, h_rf_pts;
+    // the REFERENCE refine search (fs_set_refine_search): the reference's Theta* search per distinct (start cell, goal cell)
+    // (fs_thetastar.h), in batches of slots; nothing is kept across calls but the hypot table of the grid's shape
+    int32_t rf_search = FS_REFINE_SEARCH_FIELD;
+    int32_t rs_opt_slots = 0;                 // "refine.search_slots": 0 = as many as "refine.search_bytes" holds
+    int64_t rs_opt_bytes = (int64_t)1 << 30;  // "refine.search_bytes"
+    int64_t rs_searches = 0, rs_batches = 0, rs_pops = 0, rs_walks = 0, rs_max_heap = 0;   // counters 1042-1046, of the last call
+    int32_t rs_vtx_cap = 256;
+    int32_t rs_hyp_nx = 0, rs_hyp_ny = 0;     // the shape d_rs_hyp was filled for
+    DevBuf<double> d_rs_hyp;          // [nx][ny] std::hypot of cell differences, by this host's libm
+    DevBuf<char> d_rs_slab;           // [slots][slot bytes]
+    DevBuf<char> d_rs_io;             // search cells | per-search columns | vertex cells (RsLayout)
+    PinnedBuf h_rs_io;
 
     // task allocation (fs_allocate.hip).  d_al_work: the working copy | MinPos' matrix | MinPos' P; d_al_out: the
     // packed result (AllocOut); d_al_stats: status and counters 1030-1032 of the last solve (read when fs_get_counter asks).
@@ -2227,6 +2240,8 @@ int fs_set_option(fs_ctx *c, const char *key, double value)
     if (std::strcmp(key, "navfn.wave_slots") == 0 && value >= 0 && value <= 65535) { c->nw_opt_slots = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "navfn.wave_bytes") == 0 && value >= 1 && value <= 1099511627776.0) { c->nw_opt_bytes = (int64_t)value; return FS_OK; }
     if (std::strcmp(key, "navfn.wave_cap") == 0 && value >= 16 && value <= 10000) { c->nw_opt_cap = (int32_t)value; return FS_OK; }
+    if (std::strcmp(key, "refine.search_slots") == 0 && value >= 0 && value <= 65535) { c->rs_opt_slots = (int32_t)value; return FS_OK; }
+    if (std::strcmp(key, "refine.search_bytes") == 0 && value >= 1 && value <= 1099511627776.0) { c->rs_opt_bytes = (int64_t)value; return FS_OK; }
     if (std::strcmp(key, "pathinfo.dedup") == 0) { c->opt_pi_dedup = value != 0.0; return FS_OK; }
     if (std::strcmp(key, "routes.dedup") == 0) { c->opt_rt_dedup = value != 0.0; return FS_OK; }
     if (std::strcmp(key, "routes.pool_nodes") == 0 && value >= 1 && value <= (double)(1 << 30)) { c->rt_pool_cap = (int64_t)value; return FS_OK; }
@@ -2275,6 +2290,9 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
         {1033, &fs_ctx::ru_walks, false}, {1034, &fs_ctx::ru_owners, false}, {1035, &fs_ctx::ru_rounds, false},
         // the REFERENCE grid search: slot batches of the last call
         {1038, &fs_ctx::nw_batches, false},
+        // the REFERENCE refine search, of the last call under it: searches, slot batches, nodes popped, line-of-sight walks, largest heap
+        {1042, &fs_ctx::rs_searches, false}, {1043, &fs_ctx::rs_batches, false}, {1044, &fs_ctx::rs_pops, false},
+        {1045, &fs_ctx::rs_walks, false}, {1046, &fs_ctx::rs_max_heap, false},
     };
     // ... its waves, the waves that ended on the cycle budget, the waves that dropped a push at the cap and the chunks run again, of
     // the last call: they stay on the device until asked for
@@ -5570,9 +5588,136 @@ struct RfOutLayout {
                                      total(walks + 8 * n) {}
 };
 
+// ---- the REFERENCE search (fs_set_refine_search): ThetaStar::generatePath itself per distinct (start cell, goal cell), one wavefront
+// per search in batches of slots, one synchronisation, then backtrace's list through linearInterpolation on the host (std::hypot of
+// world differences: fs_thetastar.h).  The fields, their cache and counters 1011-1013 are not touched.
+struct RsLayout {
+    size_t in, st, nv, mh, cost, pops, walks, vtx, total;      // byte offsets in d_rs_io / h_rs_io
+    RsLayout(size_t n, size_t vcap) : in(0), st(8 * n), nv(12 * n), mh(16 * n), cost((20 * n + 7) & ~(size_t)7), pops(cost + 8 * n),
+                                      walks(pops + 8 * n), vtx(walks + 8 * n), total(vtx + 4 * n * vcap) {}
+};
+
+int rs_check(fs_ctx *c)
+{
+    if (c->nx > FS_THETA_MAX_SIDE || c->ny > FS_THETA_MAX_SIDE)
+        return fail(c, FS_E_INVALID, "the REFERENCE refine search takes maps of at most %d cells a side (this one: %d x %d)", FS_THETA_MAX_SIDE, c->nx, c->ny);
+    return FS_OK;
+}
+
+int rs_refine_paths(fs_ctx *c, int32_t n, const double *start_xy, const double *goal_xy, int32_t allow, double w_euc, double w_trav,
+                    int32_t corners, int32_t *status, double *cost, int32_t *n_vertices, double *vertex_xy, int32_t *n_poses, double *pose_xy)
+{
+    int rc = rs_check(c);
+    if (rc) return rc;
+    const size_t nn = (size_t)n;
+    const int nx = c->nx, ny = c->ny;
+    const size_t ns = (size_t)nx * (size_t)ny;
+    // refusals before any search (worldToMap of start, then goal); the distinct (start cell, goal cell) in order of first appearance
+    std::vector<int32_t> pre(nn, 0), of(nn, -1), cellsv;
+    std::map<std::pair<int32_t, int32_t>, int32_t> seen;
+    for (size_t i = 0; i < nn; ++i) {
+        int32_t sx = 0, sy = 0, gx = 0, gy = 0;
+        if (!grid_world_to_map(c, start_xy[2 * i], start_xy[2 * i + 1], sx, sy)) { pre[i] = FS_REFINE_START_OFF_MAP; continue; }
+        if (!grid_world_to_map(c, goal_xy[2 * i], goal_xy[2 * i + 1], gx, gy)) { pre[i] = FS_REFINE_GOAL_OFF_MAP; continue; }
+        const std::pair<int32_t, int32_t> key(sy * nx + sx, gy * nx + gx);
+        auto it = seen.find(key);
+        if (it == seen.end()) { it = seen.emplace(key, (int32_t)(cellsv.size() / 2)).first; cellsv.push_back(key.first); cellsv.push_back(key.second); }
+        of[i] = it->second;
+    }
+    const size_t S = cellsv.size() / 2;
+    c->rs_searches = (int64_t)S; c->rs_batches = 0; c->rs_pops = 0; c->rs_walks = 0; c->rs_max_heap = 0;
+    if (S > 0) {
+        // the table of this grid shape, by the libm this process runs on
+        if (c->rs_hyp_nx != nx || c->rs_hyp_ny != ny || !c->d_rs_hyp.p) {
+            std::vector<double> hyp(ns);
+            fs_theta_fill_table(hyp.data(), nx, ny);
+            c->rs_hyp_nx = c->rs_hyp_ny = 0;
+            FS_HIP(c, c->d_rs_hyp.ensure(ns));
+            FS_HIP(c, hipMemcpyAsync(c->d_rs_hyp.p, hyp.data(), 8 * ns, hipMemcpyHostToDevice, c->stream));
+            FS_HIP(c, hipStreamSynchronize(c->stream));       // (hyp is pageable and leaves scope)
+            c->rs_hyp_nx = nx; c->rs_hyp_ny = ny;
+        }
+        const int64_t per_slot = fs_refine_search_slot_bytes((int64_t)ns);
+        int64_t slots = c->rs_opt_slots > 0 ? c->rs_opt_slots : std::max<int64_t>(1, c->rs_opt_bytes / per_slot);
+        slots = std::min<int64_t>(std::min<int64_t>(slots, 65535), (int64_t)S);
+        FS_HIP(c, c->d_rs_slab.ensure((size_t)slots * (size_t)per_slot));
+        for (int attempt = 0;; ++attempt) {
+            const size_t vcap = (size_t)c->rs_vtx_cap;
+            const RsLayout L(S, vcap);
+            FS_HIP(c, c->d_rs_io.ensure(L.total)); FS_HIP(c, c->h_rs_io.ensure(L.total));
+            std::memcpy(c->h_rs_io.p + L.in, cellsv.data(), 8 * S);
+            FS_HIP(c, hipMemcpyAsync(c->d_rs_io.p + L.in, c->h_rs_io.p + L.in, 8 * S, hipMemcpyHostToDevice, c->stream));
+            FsRefineSearchArgs a{};
+            a.cells = c->d_cells.p; a.nx = nx; a.ny = ny; a.allow = allow ? 1 : 0; a.corners = corners; a.w_euc = w_euc; a.w_trav = w_trav;
+            a.hyp = c->d_rs_hyp.p; a.slab = c->d_rs_slab.p; a.slot_bytes = per_slot;
+            char *o = c->d_rs_io.p;
+            a.search_in = reinterpret_cast<const int32_t *>(o + L.in);
+            a.vtx_cap = (int32_t)vcap; a.vtx = reinterpret_cast<int32_t *>(o + L.vtx);
+            a.status = reinterpret_cast<int32_t *>(o + L.st); a.n_vertices = reinterpret_cast<int32_t *>(o + L.nv);
+            a.max_heap = reinterpret_cast<int32_t *>(o + L.mh); a.cost = reinterpret_cast<double *>(o + L.cost);
+            a.pops = reinterpret_cast<int64_t *>(o + L.pops); a.walks = reinterpret_cast<int64_t *>(o + L.walks);
+            c->rs_batches = ((int64_t)S + slots - 1) / slots;
+            for (int64_t base = 0; base < (int64_t)S; base += slots)
+                FS_HIP(c, fs_launch_refine_search_batch(a, (int32_t)base, (int32_t)std::min<int64_t>(slots, (int64_t)S - base), c->stream));
+            FS_HIP(c, hipMemcpyAsync(c->h_rs_io.p + L.st, c->d_rs_io.p + L.st, L.total - L.st, hipMemcpyDeviceToHost, c->stream));
+            FS_HIP(c, hipStreamSynchronize(c->stream));
+            const int32_t *nv = reinterpret_cast<const int32_t *>(c->h_rs_io.p + L.nv);
+            int32_t most = 0;
+            for (size_t k = 0; k < S; ++k) most = std::max(most, nv[k]);
+            if (most <= (int32_t)vcap) break;
+            if (attempt >= 1) return fail(c, FS_E_HIP, "vertex scratch did not settle");
+            c->rs_vtx_cap = most;                             // (a parent chain longer than the scratch: grown, the searches run again)
+        }
+    }
+    const RsLayout L(S, (size_t)c->rs_vtx_cap);
+    const char *h = c->h_rs_io.p;
+    for (size_t k = 0; k < S; ++k) {
+        c->rs_pops += reinterpret_cast<const int64_t *>(h + L.pops)[k];
+        c->rs_walks += reinterpret_cast<const int64_t *>(h + L.walks)[k];
+        c->rs_max_heap = std::max<int64_t>(c->rs_max_heap, reinterpret_cast<const int32_t *>(h + L.mh)[k]);
+    }
+    // per distinct search: the vertices' world points and the published poses, once
+    std::vector<std::vector<double>> vx(S), vy(S), px(S), py(S);
+    std::vector<char> done(S, 0);
+    size_t vo = 0, po = 0;
+    for (size_t i = 0; i < nn; ++i) {
+        if (pre[i]) { status[i] = pre[i]; cost[i] = std::numeric_limits<double>::max(); n_vertices[i] = 0; n_poses[i] = 0; continue; }
+        const size_t k = (size_t)of[i];
+        status[i] = reinterpret_cast<const int32_t *>(h + L.st)[k];
+        cost[i] = reinterpret_cast<const double *>(h + L.cost)[k];
+        if (status[i] == FS_REFINE_OK && !done[k]) {
+            const int32_t nv = reinterpret_cast<const int32_t *>(h + L.nv)[k];
+            const int32_t *v = reinterpret_cast<const int32_t *>(h + L.vtx) + k * (size_t)c->rs_vtx_cap;
+            vx[k].resize((size_t)nv); vy[k].resize((size_t)nv);
+            for (int32_t j = 0; j < nv; ++j) {
+                vx[k][(size_t)j] = fs_theta_map_to_world(c->origin[0], c->res, v[j] % nx);
+                vy[k][(size_t)j] = fs_theta_map_to_world(c->origin[1], c->res, v[j] / nx);
+            }
+            fs_theta_interpolate(vx[k].data(), vy[k].data(), (size_t)nv, c->res, px[k], py[k]);
+            done[k] = 1;
+        }
+        n_vertices[i] = (int32_t)vx[k].size();
+        n_poses[i] = (int32_t)px[k].size();
+        if (status[i] != FS_REFINE_OK) { n_vertices[i] = 0; n_poses[i] = 0; }
+        for (int32_t j = 0; vertex_xy && j < n_vertices[i]; ++j) { vertex_xy[2 * (vo + j)] = vx[k][(size_t)j]; vertex_xy[2 * (vo + j) + 1] = vy[k][(size_t)j]; }
+        for (int32_t j = 0; pose_xy && j < n_poses[i]; ++j) { pose_xy[2 * (po + j)] = px[k][(size_t)j]; pose_xy[2 * (po + j) + 1] = py[k][(size_t)j]; }
+        vo += (size_t)n_vertices[i];
+        po += (size_t)n_poses[i];
+    }
+    return FS_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int fs_set_refine_search(fs_ctx *c, int32_t search)
+{
+    if (!c) return FS_E_INVALID;
+    if (search != FS_REFINE_SEARCH_FIELD && search != FS_REFINE_SEARCH_REFERENCE) return fail(c, FS_E_INVALID, "unknown refine search %d", search);
+    c->rf_search = search;
+    return FS_OK;
+}
 
 int fs_refine_field(fs_ctx *c, const double start_xy[2], int32_t allow_unknown, double w_euc, double w_traversal, int32_t corners, double *g)
 {
@@ -5602,6 +5747,8 @@ int fs_refine_paths(fs_ctx *c, int32_t n, const double *start_xy, const double *
     int rc = rf_check(c, w_euc, w_traversal, corners);
     if (rc) return rc;
     if (n == 0) return FS_OK;
+    if (c->rf_search == FS_REFINE_SEARCH_REFERENCE)
+        return rs_refine_paths(c, n, start_xy, goal_xy, allow_unknown, w_euc, w_traversal, corners, status, cost, n_vertices, vertex_xy, n_poses, pose_xy);
     const size_t nn = (size_t)n;
     const int nx = c->nx, ny = c->ny, M = c->rf_max_fields;
     fs_ctx::RfKey base;

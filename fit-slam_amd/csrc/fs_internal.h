@@ -258,6 +258,31 @@ struct FsRefineLegArgs {
 hipError_t fs_launch_refine_init(const FsRefineFieldArgs &a, uint32_t *d_flags_prev, hipStream_t s);
 hipError_t fs_launch_refine_round(const FsRefineFieldArgs &a, const uint32_t *d_prev, uint32_t *d_cur, int32_t *d_any, hipStream_t s);
 hipError_t fs_launch_refine_legs(const FsRefineLegArgs &a, int32_t n_blocks, hipStream_t s);
+// the REFERENCE refine search (fs_set_refine_search; fs_thetastar.h): the reference's Theta* search once per distinct (start cell,
+// goal cell), one wavefront per search, in batches of `slots` searches; a slot holds one search's cell map, heap and records
+struct FsRefineSearchArgs {
+    const uint8_t *cells;
+    int32_t nx, ny;
+    int32_t allow, corners;
+    double w_euc, w_trav;
+    const double *hyp;         // [nx][ny] the host libm's hypot of cell differences
+    char *slab;                // [slots][slot_bytes]
+    int64_t slot_bytes;
+    const int32_t *search_in;  // [searches][2]: start cell, goal cell
+    int32_t vtx_cap;
+    int32_t *vtx;              // [searches][vtx_cap] the vertex cells, start first
+    int32_t *status, *n_vertices, *max_heap;   // [searches]
+    double *cost;              // [searches] the goal record's g
+    int64_t *pops, *walks;     // [searches]
+};
+// bytes of one slot for ns cells, every array 8-byte aligned (the kernel cuts a slot the same way)
+__host__ __device__ inline int64_t fs_rs_up8(int64_t v) { return (v + 7) & ~(int64_t)7; }
+__host__ __device__ inline int64_t fs_refine_search_slot_bytes(int64_t ns)
+{
+    return fs_rs_up8(4 * ns) + fs_rs_up8(4 * (ns + 1)) + fs_rs_up8(4 * ns) + 3 * 8 * ns + fs_rs_up8(4 * ns) + fs_rs_up8(ns);
+}
+// searches base .. base + count - 1 (count <= slots) on slots 0 .. count - 1: the cell maps cleared, then the searches
+hipError_t fs_launch_refine_search_batch(const FsRefineSearchArgs &a, int32_t base, int32_t count, hipStream_t s);
 
 // ---- frontier roadmap (fs_roadmap.hip): FrontierRoadMap's spatial hash and roadmap_ on the device
 // FrontierRoadMap::getGridCell: floor(x / grid_cell_size), truncated to int

@@ -19,7 +19,15 @@
 // parent, walked by all 64 lanes: Bresenham's position at step k is closed-form and the sum is an exact int64), the vertices, and
 // backtrace + linearInterpolation.  tests/thetastar_ref/thetastar_ref.cpp restates all of it; the tests hold this file to it bit
 // for bit.
+//
+// The REFERENCE search (fs_set_refine_search): the reference's Theta* search itself, stated once in fs_thetastar.h.  One wavefront per
+// search; a slot of global memory holds its cell map, heap and records.  The search is serial: every lane runs the header's steps
+// with the same values (wave-uniform code, ordinary stores), and the wave's width is spent inside a step — resetParent's walk puts
+// iteration k on lane k mod 64, gathers the terms in LDS and adds them in walk order (an ordered fold, not a tree); setNeighbors
+// evaluates the moves on lanes 0..corners-1 and commits them one by one in moves[] order.  No hypot is computed here: the host's
+// table is read (fs_thetastar.h).
 #include "fs_internal.h"
+#include "fs_thetastar.h"
 
 #include <float.h>
 
@@ -346,6 +354,100 @@ __global__ __launch_bounds__(64) void rf_legs_kernel(FsRefineLegArgs a)
     }
 }
 
+// ---------------------------------------------------------------- the REFERENCE search, one wave each
+
+__device__ __forceinline__ fs_theta_mem rs_slot(const FsRefineSearchArgs &a, int32_t slot)
+{
+    const int64_t ns = (int64_t)a.nx * a.ny;
+    char *p = a.slab + (int64_t)slot * a.slot_bytes;
+    fs_theta_mem m;
+    m.at = reinterpret_cast<int32_t *>(p); p += fs_rs_up8(4 * ns);
+    m.heap = reinterpret_cast<int32_t *>(p); p += fs_rs_up8(4 * (ns + 1));
+    m.cell = reinterpret_cast<int32_t *>(p); p += fs_rs_up8(4 * ns);
+    m.g = reinterpret_cast<double *>(p); p += 8 * ns;
+    m.h = reinterpret_cast<double *>(p); p += 8 * ns;
+    m.f = reinterpret_cast<double *>(p); p += 8 * ns;
+    m.parent = reinterpret_cast<int32_t *>(p); p += fs_rs_up8(4 * ns);
+    m.queued = reinterpret_cast<uint8_t *>(p);
+    return m;
+}
+
+// blockIdx.y = slot: no cell has a record
+__global__ void rs_fill_kernel(FsRefineSearchArgs a)
+{
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, ns = (int64_t)a.nx * a.ny;
+    if (k < ns) rs_slot(a, (int32_t)blockIdx.y).at[k] = -1;
+}
+
+__global__ __launch_bounds__(64) void rs_search_kernel(FsRefineSearchArgs a, int32_t base)
+{
+    __shared__ double s_term[128];
+    __shared__ int s_cnt[64];
+    const int lane = threadIdx.x;
+    const int64_t k = (int64_t)base + blockIdx.x;
+    const fs_theta_mem m = rs_slot(a, (int32_t)blockIdx.x);
+    const fs_theta_map M{a.cells, a.nx, a.ny, a.allow, a.corners, a.w_euc, a.w_trav, a.w_euc < 1.0 ? a.w_euc : 1.0, a.hyp};
+    const int32_t src = a.search_in[2 * k], goal = a.search_in[2 * k + 1];
+    int status = FS_REFINE_NO_PATH;
+    double cost = kInf;
+    int32_t nv = 0;
+    fs_theta_state S{};
+    if (!fs_theta_safe(a.cells[src], a.allow)) status = FS_REFINE_START_UNSAFE;
+    else if (!fs_theta_safe(a.cells[goal], a.allow)) status = FS_REFINE_GOAL_UNSAFE;
+    else {
+        fs_theta_begin(M, m, S, src % a.nx, src / a.nx, goal % a.nx, goal / a.nx);
+        bool found = false;
+        while (S.hsize > 0) {
+            if (fs_theta_is_goal(M, m, S)) { found = true; break; }
+            int x0, y0, x1, y1;
+            const int32_t gp = fs_theta_reset_cells(M, m, S, x0, y0, x1, y1);
+            // losCheck: 64 iterations at a time, each lane's terms and verdict, then the terms added in walk order
+            const int n = fs_theta_walk_len(x0, y0, x1, y1);
+            bool ok = true;
+            double los = 0;
+            for (int k0 = 0; k0 < n; k0 += 64) {
+                double t[2] = {0.0, 0.0};
+                const int cnt = k0 + lane < n ? fs_theta_walk_iter(M, x0, y0, x1, y1, k0 + lane, t) : 0;
+                if (__any(cnt < 0)) { ok = false; break; }
+                s_term[2 * lane] = t[0]; s_term[2 * lane + 1] = t[1]; s_cnt[lane] = cnt;
+                __syncthreads();
+                const int act = n - k0 < 64 ? n - k0 : 64;
+                for (int l = 0; l < act; ++l) {
+                    const int c = s_cnt[l];
+                    if (c > 0) los += s_term[2 * l];
+                    if (c > 1) los += s_term[2 * l + 1];
+                }
+                __syncthreads();
+            }
+            fs_theta_reset_parent(M, m, S, gp, ok, los, x0, y0, x1, y1);
+            // setNeighbors: evaluated across lanes, committed in moves[] order
+            const double g = m.g[S.cur];
+            int32_t cell = 0;
+            double gc = 0, hc = 0, fc = 0;
+            const bool valid = lane < a.corners && fs_theta_neighbor(M, S, x0, y0, g, lane, cell, gc, hc, fc);
+            const unsigned long long mask = __ballot(valid);
+            for (int i = 0; i < a.corners; ++i) {
+                if (!((mask >> i) & 1ull)) continue;
+                fs_theta_commit(m, S, __shfl(cell, i, 64), __shfl(gc, i, 64), __shfl(hc, i, 64), __shfl(fc, i, 64));
+            }
+            fs_theta_next(m, S);
+        }
+        if (found) {
+            status = FS_REFINE_OK;
+            cost = m.g[S.cur];
+            nv = fs_theta_backtrace(m, S.cur, a.vtx + k * a.vtx_cap, a.vtx_cap);
+        }
+    }
+    if (lane == 0) {
+        a.status[k] = status;
+        a.cost[k] = cost;
+        a.n_vertices[k] = nv;
+        a.max_heap[k] = S.max_heap;
+        a.pops[k] = S.pops;
+        a.walks[k] = S.walks;
+    }
+}
+
 }  // namespace
 
 hipError_t fs_launch_refine_init(const FsRefineFieldArgs &a, uint32_t *d_flags_prev, hipStream_t s)
@@ -365,5 +467,14 @@ hipError_t fs_launch_refine_legs(const FsRefineLegArgs &a, int32_t n_blocks, hip
 {
     if (n_blocks <= 0) return hipSuccess;
     hipLaunchKernelGGL(rf_legs_kernel, dim3((unsigned)n_blocks), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t fs_launch_refine_search_batch(const FsRefineSearchArgs &a, int32_t base, int32_t count, hipStream_t s)
+{
+    if (count <= 0) return hipSuccess;
+    const int64_t ns = (int64_t)a.nx * a.ny;
+    hipLaunchKernelGGL(rs_fill_kernel, dim3((unsigned)((ns + 255) / 256), (unsigned)count), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(rs_search_kernel, dim3((unsigned)count), dim3(64), 0, s, a, base);
     return hipGetLastError();
 }

@@ -809,8 +809,26 @@ int fs_roadmap_next_goal(fs_ctx *ctx, const double robot_pose7[7], int32_t n, co
 int fs_refine_paths(fs_ctx *ctx, int32_t n, const double *start_xy, const double *goal_xy, int32_t allow_unknown, double w_euc,
                     double w_traversal, int32_t corners, int32_t *status, double *cost, int32_t *n_vertices, double *vertex_xy,
                     int32_t *n_poses, double *pose_xy);
+/* How fs_refine_paths plans a leg, per context.  FS_REFINE_SEARCH_FIELD (a fresh context's): the restatement above.
+ * FS_REFINE_SEARCH_REFERENCE: the reference's own search, ThetaStar::generatePath as it runs — a binary heap of
+ * nodes whose f is rewritten in place and never re-sifted, popped in libstdc++'s exact order; resetParent with the fp64 left fold of
+ * the line-of-sight terms; the strict f test of setNeighbors; and the loop that never examines the entry it popped last, so a leg
+ * whose search ends that way (every one-cell corridor) has status 5 here where the FIELD search finds a path.  One wavefront per
+ * distinct (start cell, goal cell) of the call.  fs_refine_paths keeps its signature: status as above; cost = the goal record's g;
+ * vertex_xy = the parent chain at cell centres, start first, the goal once; pose_xy = backtrace + linearInterpolation as the
+ * reference publishes them, interpolated by the host library with std::hypot.  status, vertices and poses equal the reference's
+ * compiled planner bit for bit, cost equals the CPU restatement (tests/thetastar_ref).  Every hypot of the search is read from a
+ * table the host library fills with its own libm per grid shape (8 B per cell).  One deviation: a line-of-sight cell off the map is
+ * unsafe (the reference reads outside its array for a straight walk along row or column 0).  Nothing is cached across calls; the
+ * fields of the FIELD search and fs_refine_field are untouched.  A side above 4096 cells: FS_E_INVALID.  One synchronisation (one
+ * more in the first call on a grid shape, for the table).  Any other value: FS_E_INVALID, the setting unchanged.
+ * fs_set_option: "refine.search_slots" (0: as many searches side by side as "refine.search_bytes", default 1 GiB, holds, at about
+ * 45 B per cell each; a positive value is the slot count itself) — results are identical for every slot count. */
+#define FS_REFINE_SEARCH_FIELD 0
+#define FS_REFINE_SEARCH_REFERENCE 1
+int fs_set_refine_search(fs_ctx *ctx, int32_t search);
 /* the cost field fs_refine_paths descends from start_xy, [ny][nx] double (DBL_MAX where not reached; everywhere for an unsafe start):
- * for tests and visualisation.  Start off the map: FS_E_INVALID */
+ * for tests and visualisation; the same whatever fs_set_refine_search says.  Start off the map: FS_E_INVALID */
 int fs_refine_field(fs_ctx *ctx, const double start_xy[2], int32_t allow_unknown, double w_euc, double w_traversal, int32_t corners,
                     double *g);
 

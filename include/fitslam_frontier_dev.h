@@ -96,7 +96,11 @@ int  fs_set_option(fs_ctx *ctx, const char *key, double value);
  * 1037 .. 1041 = the REFERENCE grid search (fs_set_grid_search) in the last call that planned under it: 1037 = waves run (its distinct
  * goal cells), 1038 = slot batches, 1039 = waves that ended on the cycle budget, 1040 = waves that dropped a push at the buffer cap,
  * 1041 = chunks of 64 entries that had to be run again from a stale entry on (1037 and 1039-1041 stay on the device until asked
- * for; all five are 0 on a context that never left FS_GRID_SEARCH_CONVERGED and never called fs_navfn_wave_potential). */
+ * for; all five are 0 on a context that never left FS_GRID_SEARCH_CONVERGED and never called fs_navfn_wave_potential);
+ * 1042 .. 1046 = the REFERENCE refine search (fs_set_refine_search) in the last fs_refine_paths under it: 1042 = searches run (its
+ * distinct (start cell, goal cell) pairs on the map), 1043 = slot batches, 1044 = nodes popped, summed over the searches, 1045 =
+ * line-of-sight walks (one per expanded node), summed, 1046 = the largest heap of any search (all five 0 on a context that never
+ * refined under FS_REFINE_SEARCH_REFERENCE). */
 int  fs_get_counter(fs_ctx *ctx, int which, int64_t *value, int reset);
 
 /* ---------------------------------------------------------------- self test */

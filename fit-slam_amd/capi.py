@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = [
     "fs_keepout_add_fov", "fs_keepout_add_disc", "fs_keepout_clear", "fs_keepout_get", "fs_mark_lethal_fov", "fs_read_grid_region",
     "fs_multi_keepout_add_fov", "fs_multi_keepout_add_disc", "fs_multi_keepout_clear", "fs_multi_mark_lethal_fov",
     "fs_set_occlusion", "fs_get_occlusion", "fs_line_of_sight", "fs_multi_set_occlusion",
+    "fs_landmarks_in_view",
 ]
 FS_KEEPOUT_MAX_ZONES = 1024
 KEEPOUT_FOV, KEEPOUT_DISC = 0, 1
@@ -106,6 +107,15 @@ class FimParamsC(C.Structure):
 
 class OcclusionParamsC(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("occ_min", C.c_int32), ("occ_max", C.c_int32), ("end_margin_m", C.c_double)]
+
+
+class ViewLandmarkC(C.Structure):
+    _fields_ = [("index", C.c_int32), ("p_camera", C.c_float * 3), ("table_value", C.c_float)]
+
+
+# fs_view_landmark: one entry of fs_landmarks_in_view
+VIEW_DTYPE = np.dtype([("index", "<i4"), ("p_camera", "<f4", (3,)), ("table_value", "<f4")])
+assert VIEW_DTYPE.itemsize == C.sizeof(ViewLandmarkC) == 20
 
 
 class FsError(RuntimeError):
@@ -165,6 +175,7 @@ def load_library(build: bool = True):
     L.fs_get_occlusion.argtypes = [vp, C.POINTER(OcclusionParamsC)]
     L.fs_line_of_sight.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.fs_score_fim.argtypes = [vp, i32] + [vp] * 7
+    L.fs_landmarks_in_view.argtypes = [vp, i32, vp, i64, vp, vp]
     L.fs_information_frontier_pair.argtypes = [vp, i32, vp, vp, vp]
     L.fs_upload_keyframes.argtypes = [vp, i32, vp, vp, vp]
     L.fs_information_for_pose.argtypes = [vp, i32, vp, C.POINTER(KeyframeParamsC), vp, vp, vp]
@@ -678,6 +689,22 @@ class FrontierScorer:
         nvis = np.zeros(n, dtype=np.int32); nvox = np.zeros(n, dtype=np.int32)
         self._check(self._L.fs_score_fim(self._h, n, _p(ps), _p(info), _p(fim21), _p(trace), _p(logdet), _p(nvis), _p(nvox)))
         return dict(info_ref=info, fim21=fim21, trace=trace, logdet=logdet, n_visible=nvis, n_voxels=nvox)
+
+    def landmarks_in_view(self, pose7, max_total=None):
+        """fs_landmarks_in_view: (offsets [n + 1] int64, entries VIEW_DTYPE) — the landmarks score_fim counts in n_visible, per pose
+        in ascending upload index; pose i's entries are entries[offsets[i]:offsets[i + 1]].  max_total None: the count-only form,
+        then a fill of exactly offsets[n] entries.  An integer is passed straight through: `entries` is the stored prefix,
+        min(offsets[n], max_total) long, and offsets still holds the true counts."""
+        ps = np.ascontiguousarray(pose7, dtype=np.float64).reshape(-1, 7)
+        n = ps.shape[0]
+        off = np.zeros(n + 1, dtype=np.int64)
+        if max_total is None:
+            self._check(self._L.fs_landmarks_in_view(self._h, n, _p(ps), 0, _p(off), None))
+            max_total = int(off[n])
+        max_total = int(max_total)
+        out = np.zeros(max_total, dtype=VIEW_DTYPE)
+        self._check(self._L.fs_landmarks_in_view(self._h, n, _p(ps), max_total, _p(off), _p(out) if max_total > 0 else None))
+        return off, out[:min(int(off[n]), max_total)]
 
     def information_frontier_pair(self, est_pose7, triangles_xy):
         ps = np.ascontiguousarray(est_pose7, dtype=np.float64).reshape(-1, 7)

@@ -350,6 +350,15 @@ struct fs_ctx {
     DevBuf<uint64_t> d_cloud_keys;
     DevBuf<uint32_t> d_cloud_bbox;
     DevBuf<char> d_cloud_temp;
+    // fs_landmarks_in_view (fs_view.hip).  Kept with the staged cloud by both ordering routes and refreshed by every
+    // upload: d_view_perm [n_chunks * 64] = the landmark's position in the uploaded array per staged slot (-1: a sentinel),
+    // d_view_inv [m] = the slot per position (-1: unusable).  The rest is the call's scratch.
+    DevBuf<int32_t> d_view_perm, d_view_inv, d_view_counts;
+    DevBuf<float> d_view_Rt;
+    DevBuf<uint32_t> d_view_mask;
+    DevBuf<int64_t> d_view_off;
+    DevBuf<fs_view_landmark> d_view_out;
+    int32_t opt_view_round = 0;    // "view.round_poses": poses per round; 0 = as many as FS_VIEW_MASK_BYTES of mask words hold
     bool opt_sort = true;
     bool opt_sort_reverse = false; // development: blocks in reverse Morton order (order-sensitivity measurements)
     bool opt_costmap = true;       // the spatial sort puts the blocks that were expensive in the previous call first ("sort.costmap")
@@ -2089,9 +2098,11 @@ void fs_stage_landmarks(const float *xyz, int32_t m, FsStagedCloud &out)
     // coordinate beyond 1e17 m: rotated into a camera frame it can overflow fp32 to +-inf, and an invisible landmark's terms are
     // removed by a factor q = 0, which inf * 0 = NaN defeats (NaN in the 6x6 sums of every pose with a general rotation).  Nothing
     // that far out is within any range fs_set_fim_params accepts (max_dist < 1e9 m).
+    out.perm.assign(mp, -1);                                      // (sentinels: the padding and the unusable points' slots)
     for (int32_t i = 0; i < n_finite; ++i) {
         const float *p = xyz + 3 * (size_t)order[i];
         x[i] = p[0]; y[i] = p[1]; z[i] = p[2];
+        out.perm[i] = order[i];
     }
     for (int32_t ch = 0; ch < n_chunks; ++ch) {
         double blo[3] = {1e300, 1e300, 1e300}, bhi[3] = {-1e300, -1e300, -1e300};
@@ -2127,12 +2138,16 @@ int fs_upload_staged_landmarks(fs_ctx *c, const FsStagedCloud &st)
     const int32_t m = st.m, n_chunks = st.n_chunks;
     const size_t mp = (size_t)n_chunks * FS_CHUNK;
     const std::vector<float> &x = st.x, &y = st.y, &z = st.z, &sph = st.sph;
+    if (st.perm.size() != mp) return fail(c, FS_E_INVALID, "staged cloud without its permutation");
     FS_HIP(c, c->d_lx.ensure(mp)); FS_HIP(c, c->d_ly.ensure(mp)); FS_HIP(c, c->d_lz.ensure(mp));
     FS_HIP(c, c->d_spheres.ensure(sph.size()));
     FS_HIP(c, hipMemcpyAsync(c->d_lx.p, x.data(), sizeof(float) * mp, hipMemcpyHostToDevice, c->stream));
     FS_HIP(c, hipMemcpyAsync(c->d_ly.p, y.data(), sizeof(float) * mp, hipMemcpyHostToDevice, c->stream));
     FS_HIP(c, hipMemcpyAsync(c->d_lz.p, z.data(), sizeof(float) * mp, hipMemcpyHostToDevice, c->stream));
     FS_HIP(c, hipMemcpyAsync(c->d_spheres.p, sph.data(), sizeof(float) * sph.size(), hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, c->d_view_perm.ensure(mp)); FS_HIP(c, c->d_view_inv.ensure((size_t)std::max(m, 1)));
+    FS_HIP(c, hipMemcpyAsync(c->d_view_perm.p, st.perm.data(), sizeof(int32_t) * mp, hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, fs_view_keep_perm(nullptr, 0, (int32_t)mp, m, c->d_view_perm.p, c->d_view_inv.p, c->stream));
     FS_HIP(c, hipStreamSynchronize(c->stream));
     c->m = m; c->n_chunks = n_chunks;
     reset_voxel_ratio(c);
@@ -2147,6 +2162,8 @@ int fs_upload_staged_landmarks(fs_ctx *c, const FsStagedCloud &st)
 }
 
 #define FS_CLOUD_DEVICE_FROM 4096
+#define FS_VIEW_MASK_BYTES ((size_t)64 << 20)   // fs_landmarks_in_view: the mask words of one round of poses (12.5 KB per pose at 100 k landmarks)
+#define FS_VIEW_MAX_ROUND 65536                 // ... and the poses of a round at most, whatever the cloud's size
 bool fs_ctx_cloud_on_device(const fs_ctx *c, int32_t m) { return c && (c->opt_cloud_order == 2 || (c->opt_cloud_order == 1 && m >= FS_CLOUD_DEVICE_FROM)); }
 
 // "cloud.order" 1: the raw cloud goes up as it is and the device puts it into k-d leaf order (fs_cloud.hip) — the host only finds
@@ -2189,6 +2206,9 @@ static int upload_landmarks_device_order(fs_ctx *c, const float *xyz, int32_t m)
     FS_HIP(c, fs_cloud_order_device(c->d_cloud_raw.p, n_usable, c->d_cloud_bounds.p, level_off, level_nodes, level_largest, perm_a, perm_b, c->d_cloud_keys.p,
                                     c->d_cloud_keys.p + std::max(n_usable, 1), c->d_cloud_temp.p, temp_bytes, c->d_cloud_bbox.p, c->stream, &perm));
     FS_HIP(c, fs_cloud_finish(c->d_cloud_raw.p, perm, n_usable, n_chunks, c->d_lx.p, c->d_ly.p, c->d_lz.p, c->d_spheres.p, c->stream));
+    // the order is kept (the scratch above may be released): fs_landmarks_in_view names landmarks by their place in `xyz`
+    FS_HIP(c, c->d_view_perm.ensure(mp)); FS_HIP(c, c->d_view_inv.ensure((size_t)std::max(m, 1)));
+    FS_HIP(c, fs_view_keep_perm(perm, n_usable, (int32_t)mp, m, c->d_view_perm.p, c->d_view_inv.p, c->stream));
     FS_HIP(c, hipStreamSynchronize(c->stream));                  // (the caller's cloud and the vectors above are read until here)
     if (c->d_cloud_raw.cap > ((size_t)16 << 20)) { c->d_cloud_raw.release(); c->d_cloud_perm.release(); c->d_cloud_keys.release(); c->d_cloud_temp.release(); }
     c->m = m; c->n_chunks = n_chunks;
@@ -2242,6 +2262,7 @@ int fs_set_option(fs_ctx *c, const char *key, double value)
     if (std::strcmp(key, "navfn.wave_cap") == 0 && value >= 16 && value <= 10000) { c->nw_opt_cap = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "refine.search_slots") == 0 && value >= 0 && value <= 65535) { c->rs_opt_slots = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "refine.search_bytes") == 0 && value >= 1 && value <= 1099511627776.0) { c->rs_opt_bytes = (int64_t)value; return FS_OK; }
+    if (std::strcmp(key, "view.round_poses") == 0 && value >= 0 && value <= FS_VIEW_MAX_ROUND) { c->opt_view_round = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "pathinfo.dedup") == 0) { c->opt_pi_dedup = value != 0.0; return FS_OK; }
     if (std::strcmp(key, "routes.dedup") == 0) { c->opt_rt_dedup = value != 0.0; return FS_OK; }
     if (std::strcmp(key, "routes.pool_nodes") == 0 && value >= 1 && value <= (double)(1 << 30)) { c->rt_pool_cap = (int64_t)value; return FS_OK; }
@@ -2751,6 +2772,85 @@ int fs_score_fim(fs_ctx *c, int32_t n, const double *pose7, float *info_ref, flo
     const int rc = fs_score_fim_begin(c, n, pose7, info_ref, fim21, trace, logdet, n_visible, n_voxels);
     if (rc) return rc;
     return fs_score_fim_end(c);
+}
+
+// The landmarks in view of each pose.  Two passes at most, one synchronisation each.  Pass 1 marks, counts and
+// scans round by round (a round's masks are the scratch of the next) and brings `offsets` back — the caller's count-only form
+// ends there, and so does a call with nothing to store.  Pass 2 emits: a call of ONE round (every call within FS_VIEW_MASK_BYTES)
+// still holds its masks; a call of several marks each round again, only the rounds that have entries below max_total.
+int fs_landmarks_in_view(fs_ctx *c, int32_t n, const double *pose7, int64_t max_total, int64_t *offsets, fs_view_landmark *out)
+{
+    if (!c) return FS_E_INVALID;
+    if (n < 0 || max_total < 0 || (n > 0 && (!pose7 || !offsets)) || (max_total > 0 && !out)) return fail(c, FS_E_INVALID, "null pointer or negative size");
+    FS_HIP(c, hipSetDevice(c->device));
+    int rc = check_scoring_state(c, false, true);
+    if (rc) return rc;
+    FsFimArgs fa{};
+    if (const int rc_args = fill_fim_args(c, fa)) return rc_args;
+    const bool occluded = c->occ.enabled != 0;
+    if (occluded) { rc = occlusion_args(c, fa); if (rc) return rc; }
+    if (n == 0) { if (offsets) offsets[0] = 0; return FS_OK; }
+    const size_t nn = (size_t)n;
+    std::vector<float> Rt(nn * 12);
+    for (int32_t i = 0; i < n; ++i) pose_to_rt(pose7 + 7 * (size_t)i, &Rt[12 * (size_t)i]);
+    // (as fs_score_fim: the sphere cull needs R orthonormal — a non-unit quaternion switches the call to the brute-force scan)
+    for (int32_t i = 0; i < n && fa.cull; ++i) {
+        const double *q = pose7 + 7 * (size_t)i + 3;
+        const double nq = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+        if (!(std::fabs(nq - 1.0) <= 1.0e-4)) fa.cull = 0;
+    }
+    const int32_t words = std::max(1, (c->m + 31) / 32);
+    int64_t per_round = c->opt_view_round > 0 ? c->opt_view_round
+                                              : std::max<int64_t>(1, std::min<int64_t>(FS_VIEW_MAX_ROUND, (int64_t)(FS_VIEW_MASK_BYTES / (sizeof(uint32_t) * (size_t)words))));
+    per_round = std::min<int64_t>(per_round, n);
+    const int64_t rounds = ((int64_t)n + per_round - 1) / per_round;
+    FS_HIP(c, c->d_view_Rt.ensure(nn * 12)); FS_HIP(c, c->d_view_off.ensure(nn + 1));
+    FS_HIP(c, c->d_view_mask.ensure((size_t)per_round * (size_t)words)); FS_HIP(c, c->d_view_counts.ensure((size_t)per_round));
+    FsViewArgs a{};
+    a.lx = c->d_lx.p; a.ly = c->d_ly.p; a.lz = c->d_lz.p; a.spheres = c->d_spheres.p;
+    a.n_chunks = c->n_chunks; a.m = c->m;
+    a.perm = c->d_view_perm.p; a.inv = c->d_view_inv.p;
+    a.Rt = c->d_view_Rt.p;
+    a.words = words; a.mask = c->d_view_mask.p; a.counts = c->d_view_counts.p;
+    // a single pose is the reference's real call: fewer chunks per wave until the round fills the chip's wave slots
+    a.group = 64;
+    while (a.group > 4 && per_round * ((c->n_chunks + a.group - 1) / a.group) < 2048) a.group >>= 1;
+    a.cull = fa.cull; a.max_dist_f = fa.max_dist_f;
+    a.maxd2 = fa.maxd2; a.cos2 = fa.cos2; a.cone_mode = fa.cone_mode;
+    a.table = fa.table; a.jx0 = fa.jx0; a.jy0 = fa.jy0; a.jz0 = fa.jz0; a.tx = fa.tx; a.ty = fa.ty; a.tz = fa.tz; a.inv_step = fa.inv_step;
+    a.occluded = occluded ? 1 : 0;
+    if (occluded) { a.occ_min = fa.occ_min; a.occ_max = fa.occ_max; a.occ_margin = fa.occ_margin; a.occ_grid = fa.occ_grid; }
+    a.offsets = c->d_view_off.p; a.max_total = 0; a.out = nullptr;
+    auto mark_round = [&](int64_t r) -> int {
+        a.pose_lo = (int32_t)(r * per_round);
+        a.n_round = (int32_t)std::min<int64_t>(per_round, (int64_t)n - r * per_round);
+        FS_HIP(c, hipMemsetAsync(c->d_view_mask.p, 0, sizeof(uint32_t) * (size_t)a.n_round * (size_t)words, c->stream));
+        FS_HIP(c, fs_launch_view_mark(a, c->stream));
+        return FS_OK;
+    };
+    FS_HIP(c, hipMemcpyAsync(c->d_view_Rt.p, Rt.data(), sizeof(float) * 12 * nn, hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, hipMemsetAsync(c->d_view_off.p, 0, sizeof(int64_t), c->stream));
+    for (int64_t r = 0; r < rounds; ++r) {
+        rc = mark_round(r);
+        if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+        FS_HIP(c, fs_launch_view_count(a, c->stream));
+    }
+    FS_HIP(c, hipMemcpyAsync(offsets, c->d_view_off.p, sizeof(int64_t) * (nn + 1), hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    const int64_t stored = std::min<int64_t>(offsets[n], max_total);
+    if (!out || stored <= 0) return FS_OK;
+    FS_HIP(c, c->d_view_out.ensure((size_t)stored));
+    a.max_total = stored; a.out = c->d_view_out.p;
+    for (int64_t r = 0; r < rounds; ++r) {
+        if (offsets[r * per_round] >= stored) break;              // (ascending: nothing of this round or a later one is stored)
+        if (rounds > 1) { rc = mark_round(r); if (rc) { (void)hipStreamSynchronize(c->stream); return rc; } }
+        else { a.pose_lo = 0; a.n_round = n; }
+        FS_HIP(c, fs_launch_view_emit(a, c->stream));
+    }
+    FS_HIP(c, hipMemcpyAsync(out, c->d_view_out.p, sizeof(fs_view_landmark) * (size_t)stored, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->d_view_out.cap * sizeof(fs_view_landmark) > ((size_t)64 << 20)) c->d_view_out.release();   // (a large list is not kept between calls)
+    return FS_OK;
 }
 
 int fs_information_frontier_pair(fs_ctx *c, int32_t n, const double *est_pose7, const double *triangle_xy, float *information)

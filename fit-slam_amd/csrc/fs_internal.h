@@ -674,6 +674,7 @@ struct FsStagedCloud {
     int32_t m = 0, n_chunks = 0;
     std::vector<float> x, y, z;     // SoA in k-d leaf order, padded to whole chunks with far-away sentinels
     std::vector<float> sph;         // [n_chunks][4] bounding spheres (cx, cy, cz, r + safety margin)
+    std::vector<int32_t> perm;      // per staged slot: the landmark's position in the uploaded array, -1 for a sentinel (fs_landmarks_in_view)
 };
 void fs_stage_landmarks(const float *xyz, int32_t m, FsStagedCloud &out);
 int fs_upload_staged_landmarks(fs_ctx *c, const FsStagedCloud &st);
@@ -690,6 +691,39 @@ hipError_t fs_cloud_order_device(const float *d_raw, int32_t n_usable, const int
 size_t fs_cloud_top_bbox_words();   // scratch of the top levels' bounding boxes (d_top_bbox; nullptr: one workgroup per node at every level)
 hipError_t fs_cloud_finish(const float *d_raw, const int32_t *d_perm, int32_t n_usable, int32_t n_chunks, float *d_lx, float *d_ly, float *d_lz,
                            float *d_spheres, hipStream_t s);
+
+// ---- landmarks in view of each pose (fs_landmarks_in_view; fs_view.hip)
+// The cloud's permutation, kept by both ordering routes: keep[slot] = the landmark's position in the uploaded array (-1 for a
+// sentinel: padding, unusable landmarks), inv[position] = its slot (-1: unusable).  d_src: the first n_usable slots' positions as
+// the device route left them, or nullptr when `keep` has been uploaded whole (the host route).
+hipError_t fs_view_keep_perm(const int32_t *d_src, int32_t n_usable, int32_t padded, int32_t m, int32_t *d_keep, int32_t *d_inv, hipStream_t s);
+struct FsViewArgs {
+    const float *lx, *ly, *lz, *spheres;   // the staged cloud, as FsFimArgs
+    int32_t n_chunks, m;
+    const int32_t *perm, *inv;             // fs_view_keep_perm's keep [n_chunks * 64] and inv [m]
+    const float *Rt;                       // [n][12] pose records of the whole call
+    int32_t pose_lo, n_round;              // this round's poses: pose_lo .. pose_lo + n_round - 1
+    int32_t words;                         // mask words per pose: ceil(m / 32)
+    uint32_t *mask;                        // [n_round][words], bit i of a pose: landmark i is in view
+    int32_t *counts;                       // [n_round]
+    int32_t group;                         // chunks per wave of the mark kernel (a power of two, 4 .. 64)
+    int32_t cull;                          // 0: every chunk is tested
+    float max_dist_f;                      // culling reach (FsFimArgs::max_dist_f)
+    float maxd2, cos2;                     // the predicate (FsFimArgs' fields)
+    int32_t cone_mode;
+    const float *table;                    // dense lookup table (FsFimArgs' fields)
+    int32_t jx0, jy0, jz0, tx, ty, tz;
+    double inv_step;
+    int32_t occluded, occ_min, occ_max;    // fs_set_occlusion (FsFimArgs' fields); occ_grid is read only when occluded
+    uint32_t occ_margin;
+    FsGridDev occ_grid;
+    int64_t *offsets;                      // [n + 1] CSR row pointer over the true counts
+    int64_t max_total;                     // entries `out` holds
+    fs_view_landmark *out;
+};
+hipError_t fs_launch_view_mark(const FsViewArgs &a, hipStream_t s);      // mask of the round's poses (zeroed by the caller)
+hipError_t fs_launch_view_count(const FsViewArgs &a, hipStream_t s);     // counts, then offsets[pose_lo + 1 ..] from offsets[pose_lo]
+hipError_t fs_launch_view_emit(const FsViewArgs &a, hipStream_t s);      // the entries below max_total
 
 // ---- FIM kernel arguments ---------------------------------------------------------------------
 struct FsFimArgs {

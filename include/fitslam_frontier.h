@@ -360,6 +360,33 @@ int fs_get_occlusion(const fs_ctx *ctx, fs_occlusion_params *p);
 int fs_line_of_sight(fs_ctx *ctx, int32_t n, const double *from_xyz, const double *to_xyz,
                      uint8_t *ok, uint8_t *blocked, int32_t *tested_cells);
 
+/* Which landmarks each pose sees.  Stands in for the GetLandmarksInView round trip of isPoseSafe
+ * (FIP/src/fisher_information/FisherInfoManager.cpp:52-88): the reference sends the pose to the SLAM process and gets `map_points`
+ * back in the pose's frame; here the cloud is the one fs_upload_landmarks staged and the answer is a list per pose.
+ * Pose i's landmarks are exactly the set fs_score_fim counts in n_visible[i] under the context's settings at call time:
+ * fs_set_fim_params' predicate and, with fs_set_occlusion enabled, the line of sight on the staged grid.  A landmark that misses
+ * the lookup table's box is listed (table_value NaN) — it counts in n_visible; a non-finite or far-away landmark keeps its
+ * place in 0 .. m-1 and is never listed.
+ *   pose7    [n][7]      as fs_score_fim; turned into R, t the same way (getTransformFromPose)
+ *   offsets  [n + 1]     CSR row pointer over the TRUE counts: offsets[0] = 0, offsets[i + 1] - offsets[i] = pose i's count,
+ *                        whatever max_total is
+ *   out      [max_total] entry k of pose i is stored at out[offsets[i] + k] iff that position is < max_total; nothing at or
+ *                        beyond max_total is written.  Within a pose the entries are in ascending `index`.
+ * out == NULL with max_total == 0 is the count-only form.  offsets[n] > max_total is not an error: the caller reads it and calls
+ * again.  The entries of a pose in list order, fed to the reference's loop (:85-97 — voxel key, pointCount, factor, NaN
+ * skipped), reproduce info_ref and n_voxels; they are also the points of the `fim_pointcloud` publisher (:15,101-107).
+ * The output is a function of the inputs alone: not of the staged order of the cloud ("cloud.order"), not of call history.
+ * NULL ctx, n < 0, max_total < 0, offsets == NULL (or pose7 == NULL) with n > 0, out == NULL with max_total > 0: FS_E_INVALID,
+ * nothing written.  No cloud, no lookup table, or occlusion enabled and no grid: FS_E_STATE.  n == 0: FS_OK, offsets[0] = 0.
+ * Synchronises once (count-only, or nothing to store) or twice.  No fs_multi_* form: call it on fs_multi_ctx(m, 0). */
+typedef struct fs_view_landmark {
+    int32_t index;        /* position of the landmark in the array fs_upload_landmarks was given (0 .. m-1) */
+    float   p_camera[3];  /* the landmark in the pose's frame: what map_points[].position carries (:85-88) */
+    float   table_value;  /* getInformationFromLookup(Eigen::Vector3f&) at p_camera: plain table value, NaN on a miss */
+} fs_view_landmark;       /* 20 bytes */
+int fs_landmarks_in_view(fs_ctx *ctx, int32_t n, const double *pose7, int64_t max_total, int64_t *offsets /* [n + 1] */,
+                         fs_view_landmark *out /* [max_total] or NULL */);
+
 /* Replaces float computeInformationFrontierPair(std::vector<Point>& lndmrk_w, Pose& kf_pose_w, Pose& est_pose_w,
  * std::vector<Point2D>& FOVFrontierPair) (FIP/src/.../FisherInformationHelpers.cpp:125-143; isInside / onLeft:
  * FIP/include/.../FisherInformationHelpers.hpp:20-43) for a batch of (estimation pose, CCW triangle) pairs over the

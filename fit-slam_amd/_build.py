@@ -56,15 +56,23 @@ if os.environ.get("FS_RAY_UNROLL"):       # speculative cell loads in flight per
     DEV_FLAGS.append("-DFS_RAY_UNROLL=" + os.environ["FS_RAY_UNROLL"])
 if os.environ.get("FS_RAY_WAVES"):        # fans (waves) per workgroup of the ray-march kernel (default 4)
     DEV_FLAGS.append("-DFS_RAY_WAVES=" + os.environ["FS_RAY_WAVES"])
-if os.environ.get("FS_FIM_SCHEDULE"):     # per-candidate start / duration / workgroup of the persistent FIM grid (tools/fim_schedule.py)
+if os.environ.get("FS_RAY_ABLATE_DISC"):  # TIMING ONLY: the ray-march kernel without its footprint-disc scan — `achievable` is wrong by construction; tools/ray_disc_probe.py is its one user
+    DEV_FLAGS.append("-DFS_RAY_ABLATE_DISC")
+if os.environ.get("FS_FIM_SCHEDULE"):    # per-candidate start / duration / workgroup of the persistent FIM grid (tools/fim_schedule.py)
     DEV_FLAGS.append("-DFS_FIM_SCHEDULE")
 if os.environ.get("FS_EXTRA_FLAGS"):      # anything else an experiment wants to define (A/B variants inside the sources)
     DEV_FLAGS += os.environ["FS_EXTRA_FLAGS"].split()
     RESOURCE_LIMITS = {} if os.environ.get("FS_NO_LIMITS") else RESOURCE_LIMITS
+def dev_library(dev_flags) -> str:
+    """Where the development build with exactly these flags lives (a process that holds two builds asks for the other one's file:
+    tools/ray_disc_probe.py)."""
+    import hashlib
+    return os.path.join(CSRC, "libfitslam_frontier_dev" + hashlib.sha1(" ".join(dev_flags).encode()).hexdigest()[:8] + ".so")
+
+
 SUFFIX = ""
 if DEV_FLAGS:
-    import hashlib
-    SUFFIX = "_dev" + hashlib.sha1(" ".join(DEV_FLAGS).encode()).hexdigest()[:8]
+    SUFFIX = os.path.basename(dev_library(DEV_FLAGS))[len("libfitslam_frontier"):-len(".so")]
     HIPCC_FLAGS = HIPCC_FLAGS + ["-DFS_DEV"] + DEV_FLAGS
 LIB = os.path.join(CSRC, f"libfitslam_frontier{SUFFIX}.so")
 RESOURCES = os.path.join(CSRC, f"kernel_resources{SUFFIX}.json")

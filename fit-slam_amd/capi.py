@@ -127,14 +127,18 @@ class FsError(RuntimeError):
 _lib = None
 
 
-def load_library(build: bool = True):
-    """Load (building first if needed) the HIP library.  Raises if it is missing: no CPU fallback."""
+def load_library(build: bool = True, path: str | None = None):
+    """Load (building first if needed) the HIP library.  Raises if it is missing: no CPU fallback.
+    `path`: load THAT build of the library instead, next to the process's own and never in its place (an A/B probe holds two
+    builds in one process and hands one to FrontierScorer(library=...)); nothing is built for it."""
     global _lib
-    if _lib is not None:
+    other = path is not None
+    if not other and _lib is not None:
         return _lib
-    path = _build.LIB
-    if build and _build.needs_build():
-        path = _build.build()
+    if not other:
+        path = _build.LIB
+        if build and _build.needs_build():
+            path = _build.build()
     if not os.path.exists(path):
         raise FsError(FS_E_NO_DEVICE, f"{path} is missing and could not be built; there is no CPU fallback")
     L = C.CDLL(path)
@@ -257,7 +261,8 @@ def load_library(build: bool = True):
         f = getattr(L, name)
         if name not in ("fs_ctx_destroy", "fs_last_error", "fs_multi_destroy", "fs_multi_last_error", "fs_multi_ctx"):
             f.restype = C.c_int
-    _lib = L
+    if not other:
+        _lib = L
     return L
 
 
@@ -285,8 +290,8 @@ class FrontierScorer:
     """One scoring context = one GPU + one HIP stream.  Mirrors the call order of the reference:
     construct (parameters) -> grid snapshot -> max-arrival calibration -> score."""
 
-    def __init__(self, device: int = 0, stream: int | None = None):
-        self._L = load_library()
+    def __init__(self, device: int = 0, stream: int | None = None, library=None):
+        self._L = library if library is not None else load_library()
         h = C.c_void_p()
         rc = self._L.fs_ctx_create(int(device), C.c_void_p(stream) if stream else None, C.byref(h))
         if rc != FS_OK:

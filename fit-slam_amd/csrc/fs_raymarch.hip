@@ -262,6 +262,39 @@ __device__ __forceinline__ void wave_lds_fence()
     __builtin_amdgcn_wave_barrier();
 }
 
+// The robot-footprint disc (isRobotFootprintInLethal, DEP/src/Helpers.cpp:135-155) in the start cell's z slice: the cells of the
+// side x side square within the radius, 64 per pass of the wave.  It is the one part of the kernel that reads the row-major byte
+// image behind a class walk — lines the fan has not touched, cold in L2 — so the passes go in groups of FS_RAY_DISC_GROUP
+// independent loads, and what does not depend on the pass is worked out once per wave.  (Issuing the loads in front of the
+// fan's rounds instead, to be folded in behind them, was built and measured: slower on C3 and on REF2D — DESIGN.md 4.1.)
+#ifndef FS_RAY_DISC_GROUP
+#define FS_RAY_DISC_GROUP 2     // independent loads per group (1, 2, 4 measured: profiles/r06/ray_disc.json)
+#endif
+struct Disc {
+    const uint8_t *slice;       // the start cell's z slice of the byte image (the scan needs the cost itself: 254)
+    double r2;                  // radius^2 as the reference forms it: fp64 product of the fp64 radius
+    float inv_side;
+    int ri, side, cells;        // (int)radius, 2 ri + 1, side^2
+    uint32_t nx, ny, x0, y0;    // grid extent, start cell
+};
+
+// The cost of cell t of the disc's scan order (row-major over the square); `in`: t is a cell of the square, within the radius
+// and on the grid (off-grid cells are not lethal).  Every lane loads — the others the start cell, which is on the grid, and
+// their `in` discards it: a load under a per-lane condition sits in a block of its own, where the compiler waits for it on the
+// spot, and a group of them arrives one after the other.
+__device__ __forceinline__ uint32_t disc_cell(const Disc &d, int t, bool &in)
+{
+    // t / side and t % side without the integer division: the float quotient is within one of the true row for
+    // t < 2^22 (side <= 2048; larger discs divide), and one step on the remainder makes it exact
+    int row = d.side <= 2048 ? (int)(((float)t + 0.5f) * d.inv_side) : t / d.side;
+    int col = t - row * d.side;
+    if (col < 0) { --row; col += d.side; } else if (col >= d.side) { ++row; col -= d.side; }
+    const int dx = row - d.ri, dy = col - d.ri;
+    const uint32_t x = d.x0 + (uint32_t)dx, y = d.y0 + (uint32_t)dy;
+    in = t < d.cells && (double)(dx * dx + dy * dy) <= d.r2 && x < d.nx && y < d.ny;
+    return d.slice[(size_t)(in ? y : d.y0) * (size_t)d.nx + (in ? x : d.x0)];
+}
+
 #ifdef FS_RAY_WAVES_PER_EU
 #define FS_RAY_OCCUPANCY __attribute__((amdgpu_waves_per_eu(FS_RAY_WAVES_PER_EU)))
 #else
@@ -290,10 +323,15 @@ void fs_raymarch_kernel(const FsRayArgs a)
 
     bool black = false;
     double sx = 0, sy = 0, sz = 0;
+    int fsize_v = 0;
     if (active) {
         black = a.blacklisted && a.blacklisted[c];
         sx = a.goal[3 * c]; sy = a.goal[3 * c + 1]; sz = a.goal[3 * c + 2];
+        if (a.frontier_size) fsize_v = a.frontier_size[c];
     }
+    // (read here, with the candidate's other columns, and not behind the fan, where nothing would hide the load; the size is the
+    // same in every lane: as a scalar it costs the fan no vector register and the scan's skip is one scalar branch)
+    const int fsize = __builtin_amdgcn_readfirstlane(fsize_v);
     bool fail = false;
     uint32_t sxm = 0, sym = 0, szm = 0;
     const bool start_ok = active && world_to_map(a.grid, sx, sy, sz, sxm, sym, szm);
@@ -339,30 +377,34 @@ void fs_raymarch_kernel(const FsRayArgs a)
         return;
     }
 
-    // footprint disc, DEP/src/Helpers.cpp:135-155 in the candidate's z slice; off-grid cells are not lethal
-    const int ri = (int)a.footprint_radius;
-    const int side = 2 * ri + 1;
-    bool lethal = false;
-    auto scan_disc = [&](auto cell_at) {
-        const float inv_side = 1.0f / (float)side;
-        for (int t = lane; t < side * side; t += 64) {
-            // t / side and t % side without the integer division: the float quotient is within one of the true row for
-            // t < 2^22 (side <= 2048; larger discs divide), and one step on the remainder makes it exact
-            int row = side <= 2048 ? (int)(((float)t + 0.5f) * inv_side) : t / side;
-            int col = t - row * side;
-            if (col < 0) { --row; col += side; } else if (col >= side) { ++row; col -= side; }
-            const int dx = row - ri, dy = col - ri;
-            if ((double)(dx * dx + dy * dy) <= a.footprint_radius * a.footprint_radius) {
-                const uint32_t x = sxm + (uint32_t)dx, y = sym + (uint32_t)dy;
-                if (x < (uint32_t)a.grid.nx && y < (uint32_t)a.grid.ny && cell_at(x, y) == 254) lethal = true;
-            }
+    // The footprint verdict is read in one place, `lethal && frontier_size < 10` (CostCalculator.cpp:77-82): a larger frontier
+    // skips the scan altogether.  (No frontier sizes: 0, the scan runs.)
+#ifdef FS_RAY_ABLATE_DISC    // timing only (tools/ray_disc_probe.py): no scan at all, `achievable` is wrong by construction
+    const bool scan = false;
+    (void)fsize;
+#else
+    const bool scan = (double)fsize < 10.0;
+#endif
+    if (scan) {
+        Disc disc;
+        disc.ri = (int)a.footprint_radius;
+        disc.side = 2 * disc.ri + 1;
+        disc.cells = disc.side * disc.side;
+        disc.inv_side = 1.0f / (float)disc.side;
+        disc.r2 = a.footprint_radius * a.footprint_radius;
+        disc.slice = a.grid.cells + (size_t)szm * (size_t)a.grid.ny * (size_t)a.grid.nx;
+        disc.nx = (uint32_t)a.grid.nx; disc.ny = (uint32_t)a.grid.ny; disc.x0 = sxm; disc.y0 = sym;
+        bool lethal = false;
+        for (int t0 = 0; t0 < disc.cells; t0 += 64 * FS_RAY_DISC_GROUP) {
+            uint32_t dv[FS_RAY_DISC_GROUP];
+            bool in[FS_RAY_DISC_GROUP];
+#pragma unroll
+            for (int u = 0; u < FS_RAY_DISC_GROUP; ++u) dv[u] = disc_cell(disc, t0 + 64 * u + lane, in[u]);
+#pragma unroll
+            for (int u = 0; u < FS_RAY_DISC_GROUP; ++u) lethal = lethal || (in[u] && dv[u] == 254u);
         }
-    };
-    const uint8_t *slice = a.grid.cells + (size_t)szm * (size_t)a.grid.ny * (size_t)a.grid.nx;       // (needs the cost itself: 254)
-    scan_disc([&](uint32_t x, uint32_t y) -> int { return slice[(size_t)y * (size_t)a.grid.nx + x]; });
-    lethal = __any(lethal);
-    const int fsize = a.frontier_size ? a.frontier_size[c] : 0;
-    if (lethal && (double)fsize < 10.0) ach = 0;           // CostCalculator.cpp:77-82
+        if (__any(lethal)) ach = 0;
+    }
 
     // FOV window, no wrap-around, first maximum (CostCalculator.cpp:87-107)
     const int k = a.window;

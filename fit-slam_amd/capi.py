@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = [
     "fs_multi_keepout_add_fov", "fs_multi_keepout_add_disc", "fs_multi_keepout_clear", "fs_multi_mark_lethal_fov",
     "fs_set_occlusion", "fs_get_occlusion", "fs_line_of_sight", "fs_multi_set_occlusion",
     "fs_landmarks_in_view",
+    "fs_upload_world", "fs_sense", "fs_goals_mapped", "fs_grid_census",
 ]
 FS_KEEPOUT_MAX_ZONES = 1024
 KEEPOUT_FOV, KEEPOUT_DISC = 0, 1
@@ -180,6 +181,10 @@ def load_library(build: bool = True, path: str | None = None):
     L.fs_line_of_sight.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.fs_score_fim.argtypes = [vp, i32] + [vp] * 7
     L.fs_landmarks_in_view.argtypes = [vp, i32, vp, i64, vp, vp]
+    L.fs_upload_world.argtypes = [vp, vp, i32, i32, i32]
+    L.fs_sense.argtypes = [vp, i32, vp, vp, C.POINTER(RayParamsC), vp, vp, vp, C.POINTER(i64), C.POINTER(i64), vp]
+    L.fs_goals_mapped.argtypes = [vp, i32, vp, vp]
+    L.fs_grid_census.argtypes = [vp, vp]
     L.fs_information_frontier_pair.argtypes = [vp, i32, vp, vp, vp]
     L.fs_upload_keyframes.argtypes = [vp, i32, vp, vp, vp]
     L.fs_information_for_pose.argtypes = [vp, i32, vp, C.POINTER(KeyframeParamsC), vp, vp, vp]
@@ -355,6 +360,7 @@ class FrontierScorer:
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self._L.fs_ray_fan_shape(self._h, C.byref(a), C.byref(b), C.byref(c)))
         self.n_yaw, self.n_elev, self.window = a.value, b.value, c.value
+        self._delta_theta, self._camera_fov = float(delta_theta), float(camera_fov)
 
     def upload_grid(self, cells: np.ndarray, origin, resolution: float):
         c = np.ascontiguousarray(cells, dtype=np.uint8)
@@ -710,6 +716,62 @@ class FrontierScorer:
         out = np.zeros(max_total, dtype=VIEW_DTYPE)
         self._check(self._L.fs_landmarks_in_view(self._h, n, _p(ps), max_total, _p(off), _p(out) if max_total > 0 else None))
         return off, out[:min(int(off[n]), max_total)]
+
+    # -- the sensor sweep on a ground-truth world (this project's own extension)
+    def upload_world(self, cells):
+        """fs_upload_world: the ground truth behind the staged grid, of its shape ([nz][ny][nx] or [ny][nx]); None releases it."""
+        if cells is None:
+            self._check(self._L.fs_upload_world(self._h, None, 0, 0, 0))
+            return
+        c = np.ascontiguousarray(cells, dtype=np.uint8)
+        if c.ndim == 2:
+            c = c[None]
+        nz, ny, nx = c.shape
+        self._check(self._L.fs_upload_world(self._h, _p(c), nx, ny, nz))
+
+    def sense(self, origins, first_ray=None, sensor=None, rays=False):
+        """fs_sense: one sweep of the arrival fan from each of origins [n][3] through the world; what it sees is copied into the staged
+        grid on the device.  first_ray [n]: -1 = all yaw rays, else the FOV window starting there (`argmax` of the scoring calls);
+        None = all rays for every pose.  sensor: a dict of set_ray_params' keyword arguments for a fan of its own (None: the
+        context's).  Returns a dict: status [n], seen_unknown [n], ray_unknown [n][n_elev][n_yaw] (rays=True, else None), n_seen,
+        n_revealed, window (x0, y0, z0, sx, sy, sz)."""
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        n = o.shape[0]
+        fr = None if first_ray is None else np.ascontiguousarray(first_ray, dtype=np.int32).reshape(-1)
+        if fr is not None and fr.shape[0] != n:
+            raise ValueError("first_ray must hold one entry per pose")
+        sp, n_elev, n_yaw = None, self.n_elev, self.n_yaw
+        if sensor is not None:
+            sp = _ray_params_c(**sensor)
+            n_elev, n_yaw = sp.n_elev, fan_n_yaw(sp.delta_theta, sp.n_rays)
+        ru = np.zeros((n, n_elev, n_yaw), dtype=np.int32) if rays else None
+        seen = np.zeros(n, dtype=np.int32); status = np.zeros(n, dtype=np.int32)
+        n_seen, n_rev = C.c_int64(), C.c_int64()
+        win = np.zeros(6, dtype=np.int32)
+        self._check(self._L.fs_sense(self._h, n, _p(o), _p(fr), None if sp is None else C.byref(sp), _p(ru), _p(seen), _p(status),
+                                     C.byref(n_seen), C.byref(n_rev), _p(win)))
+        return dict(status=status, seen_unknown=seen, ray_unknown=ru, n_seen=n_seen.value, n_revealed=n_rev.value,
+                    window=tuple(int(v) for v in win))
+
+    def goals_mapped(self, goals):
+        """fs_goals_mapped: surroundingCellsMapped (what CheckIfGoalMapped asks) for goals [n][3] on the staged 2-D grid -> uint8 [n]."""
+        g = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros(g.shape[0], dtype=np.uint8)
+        self._check(self._L.fs_goals_mapped(self._h, g.shape[0], _p(g), _p(out)))
+        return out
+
+    def grid_census(self):
+        """fs_grid_census: cells of the staged grid that are known (!= 255), unknown (== 255), lethal (== 254), free (== 0)."""
+        v = np.zeros(4, dtype=np.int64)
+        self._check(self._L.fs_grid_census(self._h, _p(v)))
+        return dict(known=int(v[0]), unknown=int(v[1]), lethal=int(v[2]), free=int(v[3]))
+
+    def first_ray_for_yaw(self, yaw):
+        """The window start i whose pose yaw i * delta_theta + camera_fov / 2 (DEP/src/CostCalculator.cpp:119) is nearest to `yaw`,
+        in [0, n_yaw - window]: what sense() takes as first_ray for a camera looking that way."""
+        if not self.n_yaw:
+            raise FsError(FS_E_STATE, "no ray parameters set (set_ray_params)")
+        return first_ray_for_yaw(yaw, self._delta_theta, self._camera_fov, self.n_yaw)
 
     def information_frontier_pair(self, est_pose7, triangles_xy):
         ps = np.ascontiguousarray(est_pose7, dtype=np.float64).reshape(-1, 7)
@@ -1306,6 +1368,30 @@ def _ray_params_c(max_camera_depth=2.0, delta_theta=0.10, camera_fov=1.04, robot
     for i in range(4):
         p.polygon[i] = float(polygon[i])
     return p
+
+
+def fan_n_yaw(delta_theta, n_rays=0):
+    """Yaw rays of a fan: n_rays, or the reference's loop `theta <= 2 * pi` over the accumulated theta (DEP/src/CostCalculator.cpp:36)."""
+    if n_rays > 0:
+        return int(n_rays)
+    import math
+    n, t = 0, 0.0
+    while t <= 2 * math.pi and n <= 4096:
+        n += 1
+        t += delta_theta
+    return n
+
+
+def first_ray_for_yaw(yaw, delta_theta, camera_fov, n_yaw):
+    """The window start i in [0, n_yaw - window], window = (int)(camera_fov / delta_theta), whose pose yaw
+    i * delta_theta + camera_fov / 2 (DEP/src/CostCalculator.cpp:119) is nearest to `yaw` (the first of equally near ones)."""
+    window = int(camera_fov / delta_theta)
+    best, best_d = 0, None
+    for i in range(n_yaw - window + 1):
+        d = abs((i * delta_theta) + (camera_fov / 2) - yaw)
+        if best_d is None or d < best_d:
+            best, best_d = i, d
+    return best
 
 
 def shard_bounds(n: int, n_shards: int, shard: int):

@@ -231,6 +231,18 @@ struct fs_ctx {
     DevBuf<int32_t> d_ko_rays;
     DevBuf<unsigned long long> d_ko_counts;
 
+    // the sensor sweep (fs_sense.hip): the ground-truth world, of the staged grid's shape; the mark image of seen
+    // cells (all zero between calls — sense_mark_clean says it is known to be); the direction table of the last non-NULL `sensor`
+    // (sense_dir: its host copy, what a new one is compared with); the call's inputs and results (d_sense_out: box [6] | status [n]
+    // | seen_unknown [n]; d_sense_counts [4]: the merge's seen / revealed cells, the census)
+    bool have_world = false;
+    DevBuf<uint8_t> d_world, d_sense_mark, d_sense_mapped;
+    bool sense_mark_clean = false;
+    std::vector<double> sense_dir;
+    DevBuf<double> d_sense_dir, d_sense_origin;
+    DevBuf<int32_t> d_sense_first, d_sense_rays, d_sense_out;
+    DevBuf<unsigned long long> d_sense_counts;
+
     // landmarks
     bool have_lm = false;
     int32_t m = 0, n_chunks = 0;
@@ -1020,6 +1032,19 @@ int check_scoring_state(fs_ctx *c, bool need_rays, bool need_fim)
     return FS_OK;
 }
 
+// The end point clamp of CostCalculator.cpp:47-48 folded into one interval per axis, b = lo_x, hi_x, lo_y, hi_y, lo_z, hi_z:
+// max(poly_min, origin), min(poly_max, origin + sizeInMeters), getSizeInMeters = (size - 1 + 0.5) * resolution
+void ray_clamp_bounds(const fs_ctx *c, const fs_ray_params &p, double b[6])
+{
+    const double smx = (c->nx - 1 + 0.5) * c->res, smy = (c->ny - 1 + 0.5) * c->res, smz = (c->nz - 1 + 0.5) * c->res;
+    b[0] = std_max(p.polygon[0], c->origin[0]);
+    b[1] = std_min(p.polygon[2], c->origin[0] + smx);
+    b[2] = std_max(p.polygon[1], c->origin[1]);
+    b[3] = std_min(p.polygon[3], c->origin[1] + smy);
+    b[4] = c->origin[2];
+    b[5] = c->origin[2] + smz;
+}
+
 int fill_ray_args(fs_ctx *c, FsRayArgs &a, bool class_ok = true)
 {
     const fs_ray_params &p = c->rp;
@@ -1053,18 +1078,57 @@ int fill_ray_args(fs_ctx *c, FsRayArgs &a, bool class_ok = true)
     }
     a.obst_min = p.obst_min; a.obst_max = p.obst_max; a.trace_min = p.trace_min; a.trace_max = p.trace_max;
     a.clamp = 1;
-    // CostCalculator.cpp:47-48, getSizeInMeters = (size - 1 + 0.5) * resolution
-    const double smx = (c->nx - 1 + 0.5) * c->res, smy = (c->ny - 1 + 0.5) * c->res, smz = (c->nz - 1 + 0.5) * c->res;
-    a.lo_x = std_max(p.polygon[0], c->origin[0]);
-    a.hi_x = std_min(p.polygon[2], c->origin[0] + smx);
-    a.lo_y = std_max(p.polygon[1], c->origin[1]);
-    a.hi_y = std_min(p.polygon[3], c->origin[1] + smy);
-    a.lo_z = c->origin[2];
-    a.hi_z = c->origin[2] + smz;
+    double b[6];
+    ray_clamp_bounds(c, p, b);
+    a.lo_x = b[0]; a.hi_x = b[1]; a.lo_y = b[2]; a.hi_y = b[3]; a.lo_z = b[4]; a.hi_z = b[5];
     a.footprint_radius = std::ceil(p.robot_radius / c->res);               // CostCalculator.cpp:77
     a.delta_theta = p.delta_theta;
     a.half_fov = p.camera_fov / 2;
     a.min_gt = c->min_gt;
+    return FS_OK;
+}
+
+// What fs_set_ray_params admits, and the fan it stands for: n_yaw accumulated thetas, the FOV window k, the direction table
+// dir[(e * n_yaw + i) * 3] (FsRayArgs::dir) and the thetas themselves.  Shared with fs_sense's `sensor`.
+int ray_fan_build(fs_ctx *c, const fs_ray_params *p, std::vector<double> &dir, int &n_yaw, int &k)
+{
+    if (!(p->delta_theta > 0.0) || !(p->max_camera_depth > 0.0) || !(p->camera_fov > 0.0))
+        return fail(c, FS_E_INVALID, "max_camera_depth, delta_theta and camera_fov must be positive");
+    if (p->n_elev < 1 || p->n_elev > FS_MAX_ELEV) return fail(c, FS_E_INVALID, "n_elev must be in [1,%d]", FS_MAX_ELEV);
+    if (!std::isfinite(p->delta_theta) || !std::isfinite(p->max_camera_depth) || !std::isfinite(p->camera_fov) || !std::isfinite(p->robot_radius) ||
+        !(p->robot_radius >= 0.0))
+        return fail(c, FS_E_INVALID, "max_camera_depth, delta_theta, camera_fov and robot_radius must be finite (robot_radius >= 0)");
+    for (int e = 0; e < p->n_elev; ++e)
+        if (!std::isfinite(p->elev[e])) return fail(c, FS_E_INVALID, "elevation angles must be finite");
+    for (int j = 0; j < 4; ++j)
+        if (p->polygon[j] != p->polygon[j]) return fail(c, FS_E_INVALID, "polygon bounds must not be NaN");      // (+-DBL_MAX / +-inf = no clamp)
+    // DEP/src/CostCalculator.cpp:36 — accumulated theta, `theta <= 2*pi`
+    std::vector<double> theta;
+    if (p->n_rays > 0) {
+        double t = 0;
+        for (int i = 0; i < p->n_rays; ++i) { theta.push_back(t); t += p->delta_theta; }
+    } else {
+        for (double t = 0; t <= (2 * M_PI); t += p->delta_theta) {
+            theta.push_back(t);
+            if (theta.size() > 4096) break;
+        }
+    }
+    n_yaw = (int)theta.size();
+    k = static_cast<int>(p->camera_fov / p->delta_theta);                    // :87
+    if (n_yaw > 4096) return fail(c, FS_E_INVALID, "more than 4096 yaw rays");
+    if (k < 1 || n_yaw < k)
+        return fail(c, FS_E_INVALID, "fewer yaw rays (%d) than the FOV window (%d): the reference would build a negative-size vector (CostCalculator.cpp:90)", n_yaw, k);
+    dir.assign((size_t)n_yaw * p->n_elev * 3, 0.0);
+    for (int e = 0; e < p->n_elev; ++e) {
+        const double d_h = p->max_camera_depth * std::cos(p->elev[e]);
+        const double d_z = p->max_camera_depth * std::sin(p->elev[e]);
+        for (int i = 0; i < n_yaw; ++i) {
+            double *d = &dir[((size_t)e * n_yaw + i) * 3];
+            d[0] = d_h * std::cos(theta[i]);                                 // :42
+            d[1] = d_h * std::sin(theta[i]);                                 // :43
+            d[2] = d_z;
+        }
+    }
     return FS_OK;
 }
 
@@ -1235,6 +1299,15 @@ int ko_after_snapshot(fs_ctx *c, int32_t nx, int32_t ny, int32_t nz, const doubl
     return FS_OK;
 }
 
+// the ground-truth world and the mark image of its shape leave the context (the stream has drained)
+void drop_world(fs_ctx *c)
+{
+    c->d_world.release();
+    c->d_sense_mark.release();
+    c->have_world = false;
+    c->sense_mark_clean = false;
+}
+
 }  // namespace
 
 // ================================================================== C ABI
@@ -1340,42 +1413,11 @@ int fs_set_ray_params(fs_ctx *c, const fs_ray_params *p)
 {
     if (!c || !p) return FS_E_INVALID;
     FS_HIP(c, hipSetDevice(c->device));
-    if (!(p->delta_theta > 0.0) || !(p->max_camera_depth > 0.0) || !(p->camera_fov > 0.0))
-        return fail(c, FS_E_INVALID, "max_camera_depth, delta_theta and camera_fov must be positive");
-    if (p->n_elev < 1 || p->n_elev > FS_MAX_ELEV) return fail(c, FS_E_INVALID, "n_elev must be in [1,%d]", FS_MAX_ELEV);
-    if (!std::isfinite(p->delta_theta) || !std::isfinite(p->max_camera_depth) || !std::isfinite(p->camera_fov) || !std::isfinite(p->robot_radius) ||
-        !(p->robot_radius >= 0.0))
-        return fail(c, FS_E_INVALID, "max_camera_depth, delta_theta, camera_fov and robot_radius must be finite (robot_radius >= 0)");
-    for (int e = 0; e < p->n_elev; ++e)
-        if (!std::isfinite(p->elev[e])) return fail(c, FS_E_INVALID, "elevation angles must be finite");
-    for (int k = 0; k < 4; ++k)
-        if (p->polygon[k] != p->polygon[k]) return fail(c, FS_E_INVALID, "polygon bounds must not be NaN");      // (+-DBL_MAX / +-inf = no clamp)
-    // DEP/src/CostCalculator.cpp:36 — accumulated theta, `theta <= 2*pi`
-    std::vector<double> theta;
-    if (p->n_rays > 0) {
-        double t = 0;
-        for (int i = 0; i < p->n_rays; ++i) { theta.push_back(t); t += p->delta_theta; }
-    } else {
-        for (double t = 0; t <= (2 * M_PI); t += p->delta_theta) {
-            theta.push_back(t);
-            if (theta.size() > 4096) break;
-        }
-    }
-    const int n_yaw = (int)theta.size();
-    const int k = static_cast<int>(p->camera_fov / p->delta_theta);          // :87
-    if (n_yaw > 4096) return fail(c, FS_E_INVALID, "more than 4096 yaw rays");
-    if (k < 1 || n_yaw < k)
-        return fail(c, FS_E_INVALID, "fewer yaw rays (%d) than the FOV window (%d): the reference would build a negative-size vector (CostCalculator.cpp:90)", n_yaw, k);
-    std::vector<double> dir((size_t)n_yaw * p->n_elev * 3);
-    for (int e = 0; e < p->n_elev; ++e) {
-        const double d_h = p->max_camera_depth * std::cos(p->elev[e]);
-        const double d_z = p->max_camera_depth * std::sin(p->elev[e]);
-        for (int i = 0; i < n_yaw; ++i) {
-            double *d = &dir[((size_t)e * n_yaw + i) * 3];
-            d[0] = d_h * std::cos(theta[i]);                                 // :42
-            d[1] = d_h * std::sin(theta[i]);                                 // :43
-            d[2] = d_z;
-        }
+    std::vector<double> dir;
+    int n_yaw = 0, k = 0;
+    {
+        const int rc = ray_fan_build(c, p, dir, n_yaw, k);
+        if (rc) return rc;
     }
     // rotation of the pose (goal, best yaw) for every possible argmax: orientationAroundZAxis(yaw)
     // (setRPY(0,0,yaw)) -> Quaternionf -> rotation matrix, as isPoseSafe(Point,Point) + getTransformFromPose
@@ -1440,6 +1482,7 @@ int fs_upload_grid(fs_ctx *c, const uint8_t *cells, int32_t nx, int32_t ny, int3
         if (rc) return rc;
     }
     FS_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->have_world && (nx != c->nx || ny != c->ny || nz != c->nz)) drop_world(c);   // (the world is of the staged grid's shape)
     c->nx = nx; c->ny = ny; c->nz = nz;
     c->origin[0] = origin_xyz[0]; c->origin[1] = origin_xyz[1]; c->origin[2] = origin_xyz[2];
     c->res = resolution;
@@ -1530,6 +1573,7 @@ int fs_upload_grid_bricks(fs_ctx *c, int32_t nx, int32_t ny, int32_t nz, const d
         if (rc) return rc;
     }
     FS_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->have_world && (nx != c->nx || ny != c->ny || nz != c->nz)) drop_world(c);   // (the world is of the staged grid's shape)
     c->nx = nx; c->ny = ny; c->nz = nz;
     c->origin[0] = origin_xyz[0]; c->origin[1] = origin_xyz[1]; c->origin[2] = origin_xyz[2];
     c->res = resolution;
@@ -1560,6 +1604,169 @@ int fs_frontier_cells(fs_ctx *c, int32_t lethal_threshold, uint8_t *mask, int64_
     FS_HIP(c, hipStreamSynchronize(c->stream));
     *count = (int64_t)n;
     if (d_mask.cap > ((size_t)64 << 20)) d_mask.release();       // a whole-map mask (128 MB at 512^3, 1 GiB at 1024^3) is not worth keeping between ticks
+    return FS_OK;
+}
+
+// ------------------------------------------------------------------ sensor sweep on a ground-truth world
+
+int fs_upload_world(fs_ctx *c, const uint8_t *cells, int32_t nx, int32_t ny, int32_t nz)
+{
+    if (!c) return FS_E_INVALID;
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (!cells) {
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        drop_world(c);
+        return FS_OK;
+    }
+    if (nx != c->nx || ny != c->ny || nz != c->nz)
+        return fail(c, FS_E_INVALID, "the world is %d x %d x %d, the staged grid %d x %d x %d", nx, ny, nz, c->nx, c->ny, c->nz);
+    const size_t total = (size_t)nx * (size_t)ny * (size_t)nz;
+    c->have_world = false;
+    FS_HIP(c, c->d_world.ensure(total));
+    FS_HIP(c, hipMemcpyAsync(c->d_world.p, cells, total, hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    c->have_world = true;
+    return FS_OK;
+}
+
+int fs_sense(fs_ctx *c, int32_t n, const double *origin_xyz, const int32_t *first_ray, const fs_ray_params *sensor, int32_t *ray_unknown,
+             int32_t *seen_unknown, int32_t *status, int64_t *n_seen, int64_t *n_revealed, int32_t window[6])
+{
+    if (!c || n < 0 || (n > 0 && (!origin_xyz || !seen_unknown || !status))) return FS_E_INVALID;
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (!c->have_world) return fail(c, FS_E_STATE, "fs_upload_world has not been called");
+    if (!sensor && !c->have_ray) return fail(c, FS_E_STATE, "fs_set_ray_params has not been called and no sensor is given");
+    FsSenseArgs a{};
+    const fs_ray_params &p = sensor ? *sensor : c->rp;
+    if (sensor) {
+        // the same host code as fs_set_ray_params'; the table goes to the device only when it is not the one already there
+        std::vector<double> dir;
+        int n_yaw = 0, k = 0;
+        const int rc = ray_fan_build(c, sensor, dir, n_yaw, k);
+        if (rc) return rc;
+        if (dir != c->sense_dir) {
+            c->sense_dir.clear();
+            FS_HIP(c, c->d_sense_dir.ensure(dir.size()));
+            FS_HIP(c, hipMemcpyAsync(c->d_sense_dir.p, dir.data(), dir.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            FS_HIP(c, hipStreamSynchronize(c->stream));
+            c->sense_dir.swap(dir);
+        }
+        a.dir = c->d_sense_dir.p;
+        a.n_yaw = n_yaw; a.n_elev = sensor->n_elev; a.window = k;
+    } else {
+        a.dir = c->d_dir.p;
+        a.n_yaw = c->n_yaw; a.n_elev = c->n_elev; a.window = c->window;
+    }
+    if (first_ray)
+        for (int32_t i = 0; i < n; ++i)
+            if (first_ray[i] < -1 || first_ray[i] > a.n_yaw - a.window)
+                return fail(c, FS_E_INVALID, "first_ray[%d] = %d is outside [-1, %d]", i, first_ray[i], a.n_yaw - a.window);
+    if (n_seen) *n_seen = 0;
+    if (n_revealed) *n_revealed = 0;
+    if (window) std::fill(window, window + 6, 0);
+    if (n == 0) return FS_OK;
+
+    a.world = grid_dev(c);
+    a.world.cells = c->d_world.p;
+    a.world.cls = nullptr;
+    a.staged = c->d_cells.p;
+    a.max_length = (unsigned int)(p.max_camera_depth / c->res);             // CostCalculator.cpp:28
+    a.obst_min = p.obst_min; a.obst_max = p.obst_max; a.trace_min = p.trace_min; a.trace_max = p.trace_max;
+    {
+        double b[6];
+        ray_clamp_bounds(c, p, b);
+        a.lo_x = b[0]; a.hi_x = b[1]; a.lo_y = b[2]; a.hi_y = b[3]; a.lo_z = b[4]; a.hi_z = b[5];
+    }
+    const size_t total = (size_t)c->nx * (size_t)c->ny * (size_t)c->nz, n_rays = (size_t)a.n_yaw * (size_t)a.n_elev;
+    {   // the mark image: allocated and zeroed once per grid shape, all zero again after every merge
+        const bool grown = c->d_sense_mark.cap < total;
+        FS_HIP(c, c->d_sense_mark.ensure(total));
+        if (grown || !c->sense_mark_clean) FS_HIP(c, hipMemsetAsync(c->d_sense_mark.p, 0, c->d_sense_mark.cap, c->stream));
+        c->sense_mark_clean = false;
+    }
+    const size_t un = (size_t)n;
+    FS_HIP(c, c->d_sense_origin.ensure(3 * un)); FS_HIP(c, c->d_sense_out.ensure(6 + 2 * un)); FS_HIP(c, c->d_sense_counts.ensure(4));
+    if (first_ray) FS_HIP(c, c->d_sense_first.ensure(un));
+    if (ray_unknown) FS_HIP(c, c->d_sense_rays.ensure(un * n_rays));
+    const int32_t box0[6] = {c->nx, c->ny, c->nz, -1, -1, -1};
+    FS_HIP(c, hipMemcpyAsync(c->d_sense_origin.p, origin_xyz, 3 * un * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (first_ray) FS_HIP(c, hipMemcpyAsync(c->d_sense_first.p, first_ray, un * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, hipMemcpyAsync(c->d_sense_out.p, box0, sizeof box0, hipMemcpyHostToDevice, c->stream));
+    a.n = n;
+    a.origin = c->d_sense_origin.p;
+    a.first_ray = first_ray ? c->d_sense_first.p : nullptr;
+    a.mark = c->d_sense_mark.p;
+    a.ray_unknown = ray_unknown ? c->d_sense_rays.p : nullptr;
+    a.box = c->d_sense_out.p;
+    a.status = c->d_sense_out.p + 6;
+    a.seen_unknown = c->d_sense_out.p + 6 + un;
+    FS_HIP(c, fs_launch_sense(a, c->stream));
+    std::vector<int32_t> out(6 + 2 * un);
+    FS_HIP(c, hipMemcpyAsync(out.data(), c->d_sense_out.p, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (ray_unknown) FS_HIP(c, hipMemcpyAsync(ray_unknown, c->d_sense_rays.p, un * n_rays * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));                  // (the one wait between the two kernels: status, box, counts per pose)
+    std::copy(out.begin() + 6, out.begin() + 6 + n, status);
+    std::copy(out.begin() + 6 + n, out.end(), seen_unknown);
+    if (out[3] < out[0]) {                                       // no pose on the map: nothing was marked, nothing changes
+        c->sense_mark_clean = true;
+        return FS_OK;
+    }
+    const int32_t x0 = out[0], y0 = out[1], z0 = out[2], sx = out[3] - out[0] + 1, sy = out[4] - out[1] + 1, sz = out[5] - out[2] + 1;
+    if (x0 < 0 || y0 < 0 || z0 < 0 || sy < 1 || sz < 1 || out[3] >= c->nx || out[4] >= c->ny || out[5] >= c->nz)
+        return fail(c, FS_E_HIP, "fs_sense: the seen cells' box [%d,%d] x [%d,%d] x [%d,%d] leaves the grid", out[0], out[3], out[1], out[4], out[2], out[5]);
+    // from here on: what fs_update_grid_region does for the window
+    ++c->grid_gen;
+    FS_HIP(c, hipMemsetAsync(c->d_sense_counts.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    FS_HIP(c, fs_launch_sense_merge(c->d_world.p, c->d_cells.p, c->d_sense_mark.p, c->nx, c->ny, x0, y0, z0, sx, sy, sz, c->d_sense_counts.p, c->stream));
+    if (!c->ko_zones.empty() && c->ko_mask_valid)
+        FS_HIP(c, fs_launch_keepout_apply(c->d_ko_mask.p, c->d_cells.p, c->nx, c->ny, x0, y0, sx, sy, nullptr, c->stream));
+    if (c->have_cls) {
+        const int b0[3] = {x0 >> 3, y0 >> 3, z0 >> 3};
+        const int nb[3] = {((x0 + sx - 1) >> 3) - b0[0] + 1, ((y0 + sy - 1) >> 3) - b0[1] + 1, ((z0 + sz - 1) >> 3) - b0[2] + 1};
+        FS_HIP(c, fs_launch_classify_region(c->d_cells.p, c->d_cls.p, c->nx, c->ny, c->nz, c->cls_ranges[0], c->cls_ranges[1], c->cls_ranges[2],
+                                            c->cls_ranges[3], b0, nb, c->stream));
+    }
+    c->have_sparse = false;
+    unsigned long long counts[2] = {0ull, 0ull};
+    FS_HIP(c, hipMemcpyAsync(counts, c->d_sense_counts.p, sizeof counts, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));                  // (the counts are the merge's)
+    c->sense_mark_clean = true;
+    ++c->epoch;
+    if (n_seen) *n_seen = (int64_t)counts[0];
+    if (n_revealed) *n_revealed = (int64_t)counts[1];
+    if (window) { window[0] = x0; window[1] = y0; window[2] = z0; window[3] = sx; window[4] = sy; window[5] = sz; }
+    return FS_OK;
+}
+
+int fs_goals_mapped(fs_ctx *c, int32_t n, const double *goal_xyz, uint8_t *mapped)
+{
+    if (!c || n < 0 || (n > 0 && (!goal_xyz || !mapped))) return FS_E_INVALID;
+    const int rc = grid2d_check(c, "fs_goals_mapped");
+    if (rc) return rc;
+    if (n == 0) return FS_OK;
+    const size_t un = (size_t)n;
+    FS_HIP(c, c->d_sense_origin.ensure(3 * un)); FS_HIP(c, c->d_sense_mapped.ensure(un));
+    FS_HIP(c, hipMemcpyAsync(c->d_sense_origin.p, goal_xyz, 3 * un * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, fs_launch_goals_mapped(c->d_cells.p, c->nx, c->ny, c->origin[0], c->origin[1], c->res, n, c->d_sense_origin.p, c->d_sense_mapped.p, c->stream));
+    FS_HIP(c, hipMemcpyAsync(mapped, c->d_sense_mapped.p, un, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    return FS_OK;
+}
+
+int fs_grid_census(fs_ctx *c, int64_t counts[4])
+{
+    if (!c || !counts) return FS_E_INVALID;
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    unsigned long long v[4] = {0ull, 0ull, 0ull, 0ull};
+    FS_HIP(c, c->d_sense_counts.ensure(4));
+    FS_HIP(c, hipMemsetAsync(c->d_sense_counts.p, 0, sizeof v, c->stream));
+    FS_HIP(c, fs_launch_grid_census(c->d_cells.p, (size_t)c->nx * (size_t)c->ny * (size_t)c->nz, c->d_sense_counts.p, c->stream));
+    FS_HIP(c, hipMemcpyAsync(v, c->d_sense_counts.p, sizeof v, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 4; ++k) counts[k] = (int64_t)v[k];
     return FS_OK;
 }
 

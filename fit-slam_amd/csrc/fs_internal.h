@@ -725,6 +725,36 @@ hipError_t fs_launch_view_mark(const FsViewArgs &a, hipStream_t s);      // mask
 hipError_t fs_launch_view_count(const FsViewArgs &a, hipStream_t s);     // counts, then offsets[pose_lo + 1 ..] from offsets[pose_lo]
 hipError_t fs_launch_view_emit(const FsViewArgs &a, hipStream_t s);      // the entries below max_total
 
+// ---- sensor sweep on a ground-truth world (fs_sense; fs_sense.hip)
+// sense: one wavefront per pose walks the pose's used rays through `world` (an FsGridDev whose cells are the world's), stores 1
+// into mark [nz][ny][nx] at every seen cell, counts the staged-unknown visits per ray and folds the seen cells' bounding box into
+// box [6] = min x, y, z, max x, y, z (preset to nx, ny, nz, -1, -1, -1).  merge: over the window, staged = world where the mark is
+// set, counts [2] += seen cells, revealed cells (255 before, not 255 in the world); the marks are cleared.
+struct FsSenseArgs {
+    FsGridDev world;
+    const uint8_t *staged;     // the staged grid, same shape
+    const double *dir;         // the fan's direction table, as FsRayArgs::dir
+    int32_t n_yaw, n_elev, window;
+    uint32_t max_length;
+    int32_t obst_min, obst_max, trace_min, trace_max;
+    double lo_x, hi_x, lo_y, hi_y, lo_z, hi_z;   // the folded clamp bounds, as FsRayArgs'
+    int32_t n;
+    const double *origin;      // [n][3]
+    const int32_t *first_ray;  // [n] or nullptr: -1 = all n_yaw rays, else the window from there (checked on the host)
+    uint8_t *mark;
+    int32_t *ray_unknown;      // [n][n_elev][n_yaw] or nullptr
+    int32_t *seen_unknown, *status;   // [n]
+    int32_t *box;              // [6]
+};
+hipError_t fs_launch_sense(const FsSenseArgs &a, hipStream_t s);
+hipError_t fs_launch_sense_merge(const uint8_t *d_world, uint8_t *d_staged, uint8_t *d_mark, int nx, int ny, int x0, int y0, int z0,
+                                 int sx, int sy, int sz, unsigned long long *d_counts, hipStream_t s);
+// surroundingCellsMapped (Helpers.cpp:98-133) of d_goal [n][3] on the 2-D grid, one lane per goal
+hipError_t fs_launch_goals_mapped(const uint8_t *d_cells, int nx, int ny, double ox, double oy, double res, int32_t n, const double *d_goal,
+                                  uint8_t *d_mapped, hipStream_t s);
+// d_counts [4] += cells != 255, == 255, == 254, == 0
+hipError_t fs_launch_grid_census(const uint8_t *d_cells, size_t total, unsigned long long *d_counts, hipStream_t s);
+
 // ---- FIM kernel arguments ---------------------------------------------------------------------
 struct FsFimArgs {
     // landmarks: SoA in k-d leaf order, n_chunks chunks of 64 (the tail padded with far-away sentinels),

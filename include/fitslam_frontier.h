@@ -919,6 +919,58 @@ int fs_fleet_allocate_roadmap(fs_ctx *ctx, int32_t n_robots, const double *robot
                   int32_t method, int32_t *assignment, double *total_cost, double *assigned_cost, fs_record *records,
                   double *weighted_cost, double *path_length_m, uint8_t *achievable);
 
+/* ---------------------------------------------------------------- sensor sweep on a ground-truth world (closed loop)
+ *
+ * THIS PROJECT'S OWN EXTENSION.  The reference's map comes from its depth camera and the traversability mapper, both outside the
+ * vendored tree; it closes the exploration loop only in simulation and measures it with comparision_scripts/
+ * explored_map_counter.cpp (known cells per second).  Here the arrival fan (DEP/src/CostCalculator.cpp:23-121) — the reference's
+ * PREDICTION of what a camera at a goal would reveal — is walked through a ground-truth WORLD grid instead, and what it sees is
+ * copied into the staged map on the device: a map update that never crosses the bus, and the first check of `arrival` against
+ * what is actually seen. */
+
+/* The ground truth: same costs, shape, origin and resolution as the staged grid; dense in HBM next to it (the 2^32-cell limit
+ * applies).  No grid staged: FS_E_STATE.  A shape other than the staged grid's: FS_E_INVALID, nothing changed.  cells == NULL
+ * releases it.  A later fs_upload_grid / fs_upload_grid_bricks with ANOTHER shape drops it, the same shape keeps it;
+ * fs_update_grid_region never touches it. */
+int fs_upload_world(fs_ctx *ctx, const uint8_t *cells, int32_t nx, int32_t ny, int32_t nz);
+
+/* One sweep from each of n poses.  The fan is exactly the arrival fan of `sensor` (validated as fs_set_ray_params validates; its
+ * direction table is cached in the context until a different one arrives) or, sensor == NULL, of the context's ray parameters:
+ * accumulated theta, end point sx + depth cos(e) cos(theta) clamped as fs_score_arrival clamps it, max_length =
+ * (unsigned)(depth / resolution), getTracedCells' walk with its end + 1 visits.  Fields used: max_camera_depth, delta_theta,
+ * camera_fov, n_rays, n_elev, elev, obst_*, trace_*, polygon.
+ *   rays of pose p   first_ray[p] == -1, or first_ray == NULL: all n_yaw rays (a lidar); otherwise the window =
+ *                    (int)(camera_fov / delta_theta) rays starting there — what `argmax` of the scoring calls names.  A value
+ *                    outside [-1, n_yaw - window]: FS_E_INVALID, nothing written.
+ *   per used ray     visits go in order through the WORLD.  Every visited cell is seen; the first visited cell whose world cost
+ *                    lies in [obst_min, obst_max] is seen too (the camera sees the wall's face) and ends the ray.
+ *                    ray_unknown [n][n_elev][n_yaw] (may be NULL) = the visits BEFORE that blocking visit whose STAGED cost
+ *                    before the call lies in [trace_min, trace_max]; unused rays get 0.  seen_unknown [p] = the sum over the
+ *                    pose's used rays: the figure to hold against `arrival`.
+ *   off the map      a pose whose own worldToMap fails, or any of whose USED rays' end points fails, sees nothing at all, as the
+ *                    arrival fan aborts (CostCalculator.cpp:50-55): status FS_STATUS_OFF_MAP, counts 0.  Every other pose:
+ *                    FS_STATUS_OK.
+ * After all poses: staged[cell] = world[cell] for every cell seen by any pose, no other cell changes; *n_seen = distinct seen
+ * cells; *n_revealed = those that were 255 before and whose world cost is not 255; window = x0 y0 z0 sx sy sz, the bounding box
+ * of the seen cells (sizes 0 when nothing was seen).  n_seen, n_revealed, window, ray_unknown may be NULL.  The context then does
+ * what fs_update_grid_region does for that window: stored keep-out zones are painted again inside it, derived images are re-cut
+ * for the bricks it touches, cached arrival limits stay.  Every figure is an integer that does not depend on the order the
+ * device works in.  n == 0, or nothing seen: a no-op that returns FS_OK.  No world staged: FS_E_STATE.  2-D and 3-D grids. */
+int fs_sense(fs_ctx *ctx, int32_t n, const double *origin_xyz /* [n][3] */, const int32_t *first_ray /* [n] or NULL */,
+             const fs_ray_params *sensor /* NULL: the context's ray parameters */,
+             int32_t *ray_unknown /* [n][n_elev][n_yaw] or NULL */, int32_t *seen_unknown /* [n] */, int32_t *status /* [n] */,
+             int64_t *n_seen, int64_t *n_revealed, int32_t window[6] /* x0 y0 z0 sx sy sz, may be NULL */);
+
+/* Replaces CheckIfGoalMapped -> surroundingCellsMapped (DEP/src/Helpers.cpp:98-133) for a batch of goals on the staged 2-D grid
+ * (nz == 1).  mapped [i], in this order: goal off the map -> 0; its cell is 254 -> 1; three or more of its nhood8 cells are
+ * 254 -> 1; otherwise 0 if any cell of nhood20 (nhood4 plus the nhood8 of each of those, clipped at the map's edges as
+ * Helpers.cpp:186-275 clips them; the cell itself is among them) is 255, else 1. */
+int fs_goals_mapped(fs_ctx *ctx, int32_t n, const double *goal_xyz /* [n][3] */, uint8_t *mapped /* [n] */);
+
+/* The explored-cell counter's figure (comparision_scripts/explored_map_counter.cpp) on the staged grid: counts = cells known
+ * (!= 255; OccupancyGrid -1 corresponds to 255), unknown (== 255), lethal (== 254), free (== 0). */
+int fs_grid_census(fs_ctx *ctx, int64_t counts[4] /* known (!= 255), unknown (== 255), lethal (== 254), free (== 0) */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "fs_set_occlusion", "fs_get_occlusion", "fs_line_of_sight", "fs_multi_set_occlusion",
     "fs_landmarks_in_view",
     "fs_upload_world", "fs_sense", "fs_goals_mapped", "fs_grid_census",
+    "fs_upload_world_landmarks", "fs_sense_landmarks", "fs_world_landmarks_get", "fs_staged_cloud_get",
 ]
 FS_KEEPOUT_MAX_ZONES = 1024
 KEEPOUT_FOV, KEEPOUT_DISC = 0, 1
@@ -108,6 +109,14 @@ class FimParamsC(C.Structure):
 
 class OcclusionParamsC(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("occ_min", C.c_int32), ("occ_max", C.c_int32), ("end_margin_m", C.c_double)]
+
+
+class LandmarkSensorC(C.Structure):
+    _fields_ = [("max_dist", C.c_double), ("max_angle", C.c_double), ("line_of_sight", C.c_int32), ("min_views", C.c_int32),
+                ("occ_min", C.c_int32), ("occ_max", C.c_int32), ("end_margin_m", C.c_double)]
+
+
+assert C.sizeof(LandmarkSensorC) == 40
 
 
 class ViewLandmarkC(C.Structure):
@@ -185,6 +194,10 @@ def load_library(build: bool = True, path: str | None = None):
     L.fs_sense.argtypes = [vp, i32, vp, vp, C.POINTER(RayParamsC), vp, vp, vp, C.POINTER(i64), C.POINTER(i64), vp]
     L.fs_goals_mapped.argtypes = [vp, i32, vp, vp]
     L.fs_grid_census.argtypes = [vp, vp]
+    L.fs_upload_world_landmarks.argtypes = [vp, vp, i32, vp]
+    L.fs_sense_landmarks.argtypes = [vp, i32, vp, C.POINTER(LandmarkSensorC), vp, C.POINTER(i32), C.POINTER(i32)]
+    L.fs_world_landmarks_get.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), vp, vp]
+    L.fs_staged_cloud_get.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), vp, vp, vp]
     L.fs_information_frontier_pair.argtypes = [vp, i32, vp, vp, vp]
     L.fs_upload_keyframes.argtypes = [vp, i32, vp, vp, vp]
     L.fs_information_for_pose.argtypes = [vp, i32, vp, C.POINTER(KeyframeParamsC), vp, vp, vp]
@@ -717,6 +730,17 @@ class FrontierScorer:
         self._check(self._L.fs_landmarks_in_view(self._h, n, _p(ps), max_total, _p(off), _p(out) if max_total > 0 else None))
         return off, out[:min(int(off[n]), max_total)]
 
+    def staged_cloud(self):
+        """fs_staged_cloud_get: the staged cloud as the kernels read it — a dict with m, n_chunks,
+        soa [3][n_chunks * 64] (x, y, z in k-d leaf order, sentinels in the padding), spheres [n_chunks][4], perm [n_chunks * 64]."""
+        m, nc = C.c_int32(), C.c_int32()
+        self._check(self._L.fs_staged_cloud_get(self._h, C.byref(m), C.byref(nc), None, None, None))
+        soa = np.zeros((3, nc.value * 64), dtype=np.float32)
+        sph = np.zeros((nc.value, 4), dtype=np.float32)
+        perm = np.zeros(nc.value * 64, dtype=np.int32)
+        self._check(self._L.fs_staged_cloud_get(self._h, C.byref(m), C.byref(nc), _p(soa), _p(sph), _p(perm)))
+        return dict(m=m.value, n_chunks=nc.value, soa=soa, spheres=sph, perm=perm)
+
     # -- the sensor sweep on a ground-truth world (this project's own extension; DESIGN.md 4.22)
     def upload_world(self, cells):
         """fs_upload_world: the ground truth behind the staged grid, of its shape ([nz][ny][nx] or [ny][nx]); None releases it."""
@@ -772,6 +796,53 @@ class FrontierScorer:
         if not self.n_yaw:
             raise FsError(FS_E_STATE, "no ray parameters set (set_ray_params)")
         return first_ray_for_yaw(yaw, self._delta_theta, self._camera_fov, self.n_yaw)
+
+    # -- the landmark sensor on a ground-truth cloud (this project's own extension)
+    def upload_world_landmarks(self, xyz, known=None):
+        """fs_upload_world_landmarks: the ground-truth cloud [m_world][3] behind the staged one; known [m_world] marks landmarks
+        discovered from the start.  Afterwards the staged cloud is the known set.  xyz None releases the world cloud and leaves
+        the staged cloud alone."""
+        if xyz is None:
+            self._check(self._L.fs_upload_world_landmarks(self._h, None, 0, None))
+            return
+        lm = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        m = lm.shape[0]
+        kn = None
+        if known is not None:
+            kn = np.ascontiguousarray(np.asarray(known).reshape(-1) != 0, dtype=np.uint8)
+            if kn.shape[0] != m:
+                raise ValueError("known must hold one entry per world landmark")
+        buf = lm if m > 0 else np.zeros((1, 3), dtype=np.float32)        # (an empty world is xyz != NULL with m_world == 0)
+        self._check(self._L.fs_upload_world_landmarks(self._h, _p(buf), m, _p(kn) if m > 0 else None))
+
+    def sense_landmarks(self, pose7, sensor=None):
+        """fs_sense_landmarks: one sweep of the world cloud from each of pose7 [n][7]; what the poses see is counted, what reaches
+        min_views sightings is discovered, and the staged cloud becomes the discovered set on the device.  sensor: None (the
+        context's volume and occlusion settings) or a dict with max_dist, max_angle and optionally line_of_sight (default 1),
+        min_views (1), occ ((254, 254)), end_margin_m (0.3).  Returns a dict: n_in_view [n], n_new, n_discovered."""
+        ps = np.ascontiguousarray(pose7, dtype=np.float64).reshape(-1, 7)
+        n = ps.shape[0]
+        sp = None
+        if sensor is not None:
+            occ = sensor.get("occ", (254, 254))
+            sp = LandmarkSensorC(float(sensor["max_dist"]), float(sensor["max_angle"]), int(sensor.get("line_of_sight", 1)),
+                                 int(sensor.get("min_views", 1)), int(occ[0]), int(occ[1]), float(sensor.get("end_margin_m", 0.3)))
+        niv = np.zeros(n, dtype=np.int32)
+        n_new, n_disc = C.c_int32(), C.c_int32()
+        self._check(self._L.fs_sense_landmarks(self._h, n, _p(ps), None if sp is None else C.byref(sp), _p(niv), C.byref(n_new),
+                                               C.byref(n_disc)))
+        return dict(n_in_view=niv, n_new=n_new.value, n_discovered=n_disc.value)
+
+    def world_landmarks(self, views=True):
+        """fs_world_landmarks_get: a dict with m_world, n_discovered, world_index [n_discovered] (ascending; entry r is the landmark
+        landmarks_in_view calls r while the staged cloud is the discovered set) and views [m_world] (None with views=False)."""
+        m, nd = C.c_int32(), C.c_int32()
+        self._check(self._L.fs_world_landmarks_get(self._h, C.byref(m), C.byref(nd), None, None))
+        idx = np.zeros(nd.value, dtype=np.int32)
+        v = np.zeros(m.value, dtype=np.int32) if views else None
+        self._check(self._L.fs_world_landmarks_get(self._h, C.byref(m), C.byref(nd), _p(idx) if nd.value > 0 else None,
+                                                   _p(v) if views and m.value > 0 else None))
+        return dict(m_world=m.value, n_discovered=nd.value, world_index=idx, views=v)
 
     def information_frontier_pair(self, est_pose7, triangles_xy):
         ps = np.ascontiguousarray(est_pose7, dtype=np.float64).reshape(-1, 7)

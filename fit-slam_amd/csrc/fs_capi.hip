@@ -243,6 +243,18 @@ struct fs_ctx {
     DevBuf<int32_t> d_sense_first, d_sense_rays, d_sense_out;
     DevBuf<unsigned long long> d_sense_counts;
 
+    // the landmark sensor (fs_sense_landmarks.hip): the ground-truth cloud as raw xyz [wl_m][3], in a k-d leaf order
+    // of its own (SoA padded to wl_chunks chunks, spheres, d_wl_perm: the world index per slot) and with one sighting counter and
+    // one `discovered` flag per landmark; wl_discovered: how many flags are set; wl_staged: the staged cloud IS the discovered set
+    // (cleared by every other route that stages a cloud).  d_wl_out: totals [3] (new, discovered, discovered and usable) |
+    // n_in_view [n]; d_wl_blocks: per block of 256 landmarks the counts [2] and, behind them, their exclusive sums.
+    bool have_wl = false, wl_staged = false;
+    int32_t wl_m = 0, wl_chunks = 0, wl_discovered = 0;
+    DevBuf<float> d_wl_raw, d_wl_lx, d_wl_ly, d_wl_lz, d_wl_spheres, d_wl_Rt;
+    DevBuf<int32_t> d_wl_perm, d_wl_inv, d_wl_out, d_wl_blocks;
+    DevBuf<uint32_t> d_wl_views;
+    DevBuf<uint8_t> d_wl_flag;
+
     // landmarks
     bool have_lm = false;
     int32_t m = 0, n_chunks = 0;
@@ -1132,6 +1144,25 @@ int ray_fan_build(fs_ctx *c, const fs_ray_params *p, std::vector<double> &dir, i
     return FS_OK;
 }
 
+// A visibility volume as the kernels take it (FsFimArgs' fields of the same names): the range and the culling reach, the cone of
+// the exact predicate and the slightly wider one of the chunk culling.  Shared by fs_set_fim_params' volume and a landmark sensor's.
+void fim_volume(double max_dist, double max_angle, float &maxd2, float &max_dist_f, float &cos2, int32_t &cone_mode, float &cos_a, float &sin_a)
+{
+    maxd2 = (float)(max_dist * max_dist);
+    max_dist_f = (float)max_dist * 1.0001f + 1.0e-3f;              // culling reach, rounded outwards
+    if (max_angle >= M_PI) {
+        cone_mode = 0; cos2 = 0.0f; cos_a = -1.0f; sin_a = 0.0f;
+    } else {
+        const float cs = (float)std::cos(max_angle);
+        cos2 = cs * cs;
+        cone_mode = (cs >= 0.0f) ? 1 : 2;
+        // chunk culling uses a slightly wider cone (alpha + 1e-3 rad) than the exact per-landmark predicate
+        cos_a = (float)std::cos(max_angle + 1.0e-3);
+        sin_a = (float)std::sin(max_angle + 1.0e-3);
+        if (max_angle + 1.0e-3 >= M_PI / 2) cone_mode = (cone_mode == 1) ? 3 : 2;   // 3: exact predicate of mode 1, no cone culling
+    }
+}
+
 int fill_fim_args(fs_ctx *c, FsFimArgs &a)
 {
     a.lx = c->d_lx.p; a.ly = c->d_ly.p; a.lz = c->d_lz.p;
@@ -1146,8 +1177,7 @@ int fill_fim_args(fs_ctx *c, FsFimArgs &a)
     a.factor = c->d_factor.p;
     a.fac1 = c->fac[1]; a.fac2 = c->fac[2]; a.fac3 = c->fac[3]; a.fac4 = c->fac[4];
     a.table_full = c->table_full ? 1 : 0;
-    a.maxd2 = (float)(c->fp.max_dist * c->fp.max_dist);
-    a.max_dist_f = (float)c->fp.max_dist * 1.0001f + 1.0e-3f;      // culling reach, rounded outwards
+    fim_volume(c->fp.max_dist, c->fp.max_angle, a.maxd2, a.max_dist_f, a.cos2, a.cone_mode, a.cos_a, a.sin_a);
     a.far_lattice = !((double)a.max_dist_f * a.inv_step < 1000.0) ? 1 : 0;   // (NaN / inf / huge ranges: exact path for every landmark)
     {   // fl32(p * fl32(1/step)) is within |r| * 2^-23 of the double product the reference rounds (one rounding of the factor, one of
         // the product); twice that at the largest |r| a scored landmark can have, plus an absolute cushion, is the band around a
@@ -1155,17 +1185,6 @@ int fill_fim_args(fs_ctx *c, FsFimArgs &a)
         const double r_max = std::max(1.0, (double)a.max_dist_f * a.inv_step);
         const double band = 2.0 * r_max * 1.1920929e-7 + 1.0e-6;
         a.key_thr = a.far_lattice ? 0.0f : (float)(0.5 - band);
-    }
-    if (c->fp.max_angle >= M_PI) {
-        a.cone_mode = 0; a.cos2 = 0.0f; a.cos_a = -1.0f; a.sin_a = 0.0f;
-    } else {
-        const float cs = (float)std::cos(c->fp.max_angle);
-        a.cos2 = cs * cs;
-        a.cone_mode = (cs >= 0.0f) ? 1 : 2;
-        // chunk culling uses a slightly wider cone (alpha + 1e-3 rad) than the exact per-landmark predicate
-        a.cos_a = (float)std::cos(c->fp.max_angle + 1.0e-3);
-        a.sin_a = (float)std::sin(c->fp.max_angle + 1.0e-3);
-        if (c->fp.max_angle + 1.0e-3 >= M_PI / 2) a.cone_mode = (a.cone_mode == 1) ? 3 : 2;   // 3: exact predicate of mode 1, no cone culling
     }
     // LDS tier: 2^14 slots (64 KiB, two 512-thread workgroups per CU) or fewer for small clouds; crowded poses are
     // scored in passes; the HBM tier behind it takes what still overflows
@@ -2337,6 +2356,8 @@ void fs_stage_landmarks(const float *xyz, int32_t m, FsStagedCloud &out)
     out.m = m; out.n_chunks = n_chunks;
 }
 
+static int staged_cloud_done(fs_ctx *c, int32_t m, int32_t n_chunks);
+
 // Device half: four copies and the HBM-tier tables.
 int fs_upload_staged_landmarks(fs_ctx *c, const FsStagedCloud &st)
 {
@@ -2356,16 +2377,7 @@ int fs_upload_staged_landmarks(fs_ctx *c, const FsStagedCloud &st)
     FS_HIP(c, hipMemcpyAsync(c->d_view_perm.p, st.perm.data(), sizeof(int32_t) * mp, hipMemcpyHostToDevice, c->stream));
     FS_HIP(c, fs_view_keep_perm(nullptr, 0, (int32_t)mp, m, c->d_view_perm.p, c->d_view_inv.p, c->stream));
     FS_HIP(c, hipStreamSynchronize(c->stream));
-    c->m = m; c->n_chunks = n_chunks;
-    reset_voxel_ratio(c);
-    // HBM hash tables for tier 3: one per pool workgroup, 2x the landmark count
-    int gb = 12;
-    while ((1ll << gb) < 2ll * std::max(m, 1)) ++gb;
-    c->ghash_bits = gb;
-    FS_HIP(c, c->d_gtable.ensure((size_t)fs_ctx::kPool << gb));
-    c->have_lm = true;
-    ++c->epoch;
-    return FS_OK;
+    return staged_cloud_done(c, m, n_chunks);
 }
 
 #define FS_CLOUD_DEVICE_FROM 4096
@@ -2373,51 +2385,10 @@ int fs_upload_staged_landmarks(fs_ctx *c, const FsStagedCloud &st)
 #define FS_VIEW_MAX_ROUND 65536                 // ... and the poses of a round at most, whatever the cloud's size
 bool fs_ctx_cloud_on_device(const fs_ctx *c, int32_t m) { return c && (c->opt_cloud_order == 2 || (c->opt_cloud_order == 1 && m >= FS_CLOUD_DEVICE_FROM)); }
 
-// "cloud.order" 1: the raw cloud goes up as it is and the device puts it into k-d leaf order (fs_cloud.hip) — the host only finds
-// out how many landmarks are usable (the level layout depends on that number) and which, if any, are not.
-static int upload_landmarks_device_order(fs_ctx *c, const float *xyz, int32_t m)
+// every route that stages a cloud ends here: sizes, the learnt voxel ratio, the HBM tier's hash tables (one per pool workgroup, 2x the
+// landmark count).  The cloud is then NOT the landmark sensor's discovered set unless fs_sense_landmarks says so afterwards.
+static int staged_cloud_done(fs_ctx *c, int32_t m, int32_t n_chunks)
 {
-    FS_HIP(c, hipSetDevice(c->device));
-    auto ok = [&](int32_t i) {                                    // as fs_stage_landmarks: finite and within 1e17 m (fabsf of a NaN compares false)
-        const float *p = xyz + 3 * (size_t)i;
-        return std::fabs(p[0]) <= 1.0e17f && std::fabs(p[1]) <= 1.0e17f && std::fabs(p[2]) <= 1.0e17f;
-    };
-    int32_t n_usable = 0;
-    for (int32_t i = 0; i < m; ++i) n_usable += ok(i) ? 1 : 0;
-    std::vector<int32_t> usable;                                  // the usable landmarks in input order — only when some are not (rare)
-    if (n_usable != m) {
-        usable.reserve((size_t)n_usable);
-        for (int32_t i = 0; i < m; ++i) if (ok(i)) usable.push_back(i);
-    }
-    const bool all_usable = n_usable == m;
-    c->have_lm = false;                                          // (until the new cloud is whole: an error on the way leaves no cloud, not half of one)
-    const int32_t n_chunks = std::max<int32_t>(1, (m + FS_CHUNK - 1) / FS_CHUNK);
-    const size_t mp = (size_t)n_chunks * FS_CHUNK;
-    std::vector<int32_t> bounds, level_off, level_nodes, level_largest;
-    fs_cloud_levels(n_usable, bounds, level_off, level_nodes, level_largest);
-    const size_t temp_bytes = fs_cloud_sort_temp_bytes(n_usable, c->stream);
-    FS_HIP(c, c->d_lx.ensure(mp)); FS_HIP(c, c->d_ly.ensure(mp)); FS_HIP(c, c->d_lz.ensure(mp));
-    FS_HIP(c, c->d_spheres.ensure((size_t)n_chunks * 4));
-    FS_HIP(c, c->d_cloud_raw.ensure(3 * (size_t)std::max(m, 1)));
-    FS_HIP(c, c->d_cloud_perm.ensure(2 * (size_t)std::max(n_usable, 1)));
-    FS_HIP(c, c->d_cloud_keys.ensure(2 * (size_t)std::max(n_usable, 1)));
-    FS_HIP(c, c->d_cloud_bounds.ensure(std::max<size_t>(bounds.size(), 1)));
-    FS_HIP(c, c->d_cloud_temp.ensure(std::max<size_t>(temp_bytes, 256)));
-    FS_HIP(c, c->d_cloud_bbox.ensure(fs_cloud_top_bbox_words()));
-    if (m > 0) FS_HIP(c, hipMemcpyAsync(c->d_cloud_raw.p, xyz, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, c->stream));
-    if (!bounds.empty()) FS_HIP(c, hipMemcpyAsync(c->d_cloud_bounds.p, bounds.data(), sizeof(int32_t) * bounds.size(), hipMemcpyHostToDevice, c->stream));
-    int32_t *perm_a = c->d_cloud_perm.p, *perm_b = perm_a + std::max(n_usable, 1);
-    if (all_usable) FS_HIP(c, fs_cloud_iota(perm_a, n_usable, c->stream));
-    else if (n_usable > 0) FS_HIP(c, hipMemcpyAsync(perm_a, usable.data(), sizeof(int32_t) * (size_t)n_usable, hipMemcpyHostToDevice, c->stream));
-    int32_t *perm = perm_a;
-    FS_HIP(c, fs_cloud_order_device(c->d_cloud_raw.p, n_usable, c->d_cloud_bounds.p, level_off, level_nodes, level_largest, perm_a, perm_b, c->d_cloud_keys.p,
-                                    c->d_cloud_keys.p + std::max(n_usable, 1), c->d_cloud_temp.p, temp_bytes, c->d_cloud_bbox.p, c->stream, &perm));
-    FS_HIP(c, fs_cloud_finish(c->d_cloud_raw.p, perm, n_usable, n_chunks, c->d_lx.p, c->d_ly.p, c->d_lz.p, c->d_spheres.p, c->stream));
-    // the order is kept (the scratch above may be released): fs_landmarks_in_view names landmarks by their place in `xyz`
-    FS_HIP(c, c->d_view_perm.ensure(mp)); FS_HIP(c, c->d_view_inv.ensure((size_t)std::max(m, 1)));
-    FS_HIP(c, fs_view_keep_perm(perm, n_usable, (int32_t)mp, m, c->d_view_perm.p, c->d_view_inv.p, c->stream));
-    FS_HIP(c, hipStreamSynchronize(c->stream));                  // (the caller's cloud and the vectors above are read until here)
-    if (c->d_cloud_raw.cap > ((size_t)16 << 20)) { c->d_cloud_raw.release(); c->d_cloud_perm.release(); c->d_cloud_keys.release(); c->d_cloud_temp.release(); }
     c->m = m; c->n_chunks = n_chunks;
     reset_voxel_ratio(c);
     int gb = 12;
@@ -2425,8 +2396,94 @@ static int upload_landmarks_device_order(fs_ctx *c, const float *xyz, int32_t m)
     c->ghash_bits = gb;
     FS_HIP(c, c->d_gtable.ensure((size_t)fs_ctx::kPool << gb));
     c->have_lm = true;
+    c->wl_staged = false;
     ++c->epoch;
     return FS_OK;
+}
+
+// where an ordered cloud goes: the staged cloud's arrays (fs_upload_landmarks, fs_sense_landmarks) or the world cloud's
+struct CloudDest {
+    DevBuf<float> &lx, &ly, &lz, &spheres;
+    DevBuf<int32_t> &perm, &inv;
+};
+
+// The device ordering (fs_cloud.hip) of a cloud whose raw xyz [m][3] is on the device — or on its way there on the context's stream:
+// `start` is called with the first permutation buffer once the scratch is allocated and enqueues whatever fills d_raw and the
+// n_usable usable landmarks' positions in ascending order.  The level layout is a function of n_usable alone, so that number is all
+// the host has to know.  Ends with the stream drained: what `start` reads on the host may go afterwards.
+static int order_cloud_on_device(fs_ctx *c, const float *d_raw, int32_t m, int32_t n_usable, const std::function<int(int32_t *)> &start,
+                                 const CloudDest &d, int32_t &n_chunks_out)
+{
+    const int32_t n_chunks = std::max<int32_t>(1, (m + FS_CHUNK - 1) / FS_CHUNK);
+    const size_t mp = (size_t)n_chunks * FS_CHUNK;
+    std::vector<int32_t> bounds, level_off, level_nodes, level_largest;
+    fs_cloud_levels(n_usable, bounds, level_off, level_nodes, level_largest);
+    const size_t temp_bytes = fs_cloud_sort_temp_bytes(n_usable, c->stream);
+    FS_HIP(c, d.lx.ensure(mp)); FS_HIP(c, d.ly.ensure(mp)); FS_HIP(c, d.lz.ensure(mp));
+    FS_HIP(c, d.spheres.ensure((size_t)n_chunks * 4));
+    FS_HIP(c, c->d_cloud_perm.ensure(2 * (size_t)std::max(n_usable, 1)));
+    FS_HIP(c, c->d_cloud_keys.ensure(2 * (size_t)std::max(n_usable, 1)));
+    FS_HIP(c, c->d_cloud_bounds.ensure(std::max<size_t>(bounds.size(), 1)));
+    FS_HIP(c, c->d_cloud_temp.ensure(std::max<size_t>(temp_bytes, 256)));
+    FS_HIP(c, c->d_cloud_bbox.ensure(fs_cloud_top_bbox_words()));
+    int32_t *perm_a = c->d_cloud_perm.p, *perm_b = perm_a + std::max(n_usable, 1);
+    if (const int rc = start(perm_a)) return rc;
+    if (!bounds.empty()) FS_HIP(c, hipMemcpyAsync(c->d_cloud_bounds.p, bounds.data(), sizeof(int32_t) * bounds.size(), hipMemcpyHostToDevice, c->stream));
+    int32_t *perm = perm_a;
+    FS_HIP(c, fs_cloud_order_device(d_raw, n_usable, c->d_cloud_bounds.p, level_off, level_nodes, level_largest, perm_a, perm_b, c->d_cloud_keys.p,
+                                    c->d_cloud_keys.p + std::max(n_usable, 1), c->d_cloud_temp.p, temp_bytes, c->d_cloud_bbox.p, c->stream, &perm));
+    FS_HIP(c, fs_cloud_finish(d_raw, perm, n_usable, n_chunks, d.lx.p, d.ly.p, d.lz.p, d.spheres.p, c->stream));
+    // the order is kept (the scratch above may be released): fs_landmarks_in_view names landmarks by their place in the array
+    FS_HIP(c, d.perm.ensure(mp)); FS_HIP(c, d.inv.ensure((size_t)std::max(m, 1)));
+    FS_HIP(c, fs_view_keep_perm(perm, n_usable, (int32_t)mp, m, d.perm.p, d.inv.p, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));                  // (the caller's cloud and the vectors above are read until here)
+    if (c->d_cloud_raw.cap > ((size_t)16 << 20)) { c->d_cloud_raw.release(); c->d_cloud_perm.release(); c->d_cloud_keys.release(); c->d_cloud_temp.release(); }
+    n_chunks_out = n_chunks;
+    return FS_OK;
+}
+
+// the usable landmarks of a host cloud (as fs_stage_landmarks: finite and within 1e17 m; fabsf of a NaN compares false): how many,
+// and — only when some are not (rare) — which, in input order
+static int32_t usable_landmarks(const float *xyz, int32_t m, std::vector<int32_t> &usable)
+{
+    auto ok = [&](int32_t i) {
+        const float *p = xyz + 3 * (size_t)i;
+        return std::fabs(p[0]) <= 1.0e17f && std::fabs(p[1]) <= 1.0e17f && std::fabs(p[2]) <= 1.0e17f;
+    };
+    int32_t n_usable = 0;
+    for (int32_t i = 0; i < m; ++i) n_usable += ok(i) ? 1 : 0;
+    usable.clear();
+    if (n_usable != m) {
+        usable.reserve((size_t)n_usable);
+        for (int32_t i = 0; i < m; ++i) if (ok(i)) usable.push_back(i);
+    }
+    return n_usable;
+}
+
+// a host cloud goes up as it is into d_raw and is put into k-d leaf order there: the host only finds out how many landmarks are
+// usable and which, if any, are not
+static int order_host_cloud_on_device(fs_ctx *c, const float *xyz, int32_t m, float *d_raw, const CloudDest &d, int32_t &n_chunks)
+{
+    std::vector<int32_t> usable;
+    const int32_t n_usable = usable_landmarks(xyz, m, usable);
+    return order_cloud_on_device(c, d_raw, m, n_usable, [&](int32_t *perm_a) -> int {
+        if (m > 0) FS_HIP(c, hipMemcpyAsync(d_raw, xyz, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, c->stream));
+        if (n_usable == m) FS_HIP(c, fs_cloud_iota(perm_a, n_usable, c->stream));
+        else if (n_usable > 0) FS_HIP(c, hipMemcpyAsync(perm_a, usable.data(), sizeof(int32_t) * (size_t)n_usable, hipMemcpyHostToDevice, c->stream));
+        return FS_OK;
+    }, d, n_chunks);
+}
+
+// "cloud.order" 1 / 2: fs_upload_landmarks on the device route
+static int upload_landmarks_device_order(fs_ctx *c, const float *xyz, int32_t m)
+{
+    FS_HIP(c, hipSetDevice(c->device));
+    c->have_lm = false;                                          // (until the new cloud is whole: an error on the way leaves no cloud, not half of one)
+    FS_HIP(c, c->d_cloud_raw.ensure(3 * (size_t)std::max(m, 1)));
+    int32_t n_chunks = 0;
+    const CloudDest staged{c->d_lx, c->d_ly, c->d_lz, c->d_spheres, c->d_view_perm, c->d_view_inv};
+    if (const int rc = order_host_cloud_on_device(c, xyz, m, c->d_cloud_raw.p, staged, n_chunks)) return rc;
+    return staged_cloud_done(c, m, n_chunks);
 }
 
 extern "C" {
@@ -3057,6 +3114,195 @@ int fs_landmarks_in_view(fs_ctx *c, int32_t n, const double *pose7, int64_t max_
     FS_HIP(c, hipMemcpyAsync(out, c->d_view_out.p, sizeof(fs_view_landmark) * (size_t)stored, hipMemcpyDeviceToHost, c->stream));
     FS_HIP(c, hipStreamSynchronize(c->stream));
     if (c->d_view_out.cap * sizeof(fs_view_landmark) > ((size_t)64 << 20)) c->d_view_out.release();   // (a large list is not kept between calls)
+    return FS_OK;
+}
+
+// ------------------------------------------------------------------ landmark sensor on a ground-truth cloud
+
+}  // extern "C"
+
+// flags from counters, the per-block counts and their offsets: enqueued; d_wl_out [0..2] then holds new / discovered / usable
+static int wl_enqueue_flags(fs_ctx *c, uint32_t min_views)
+{
+    const size_t n_blocks = ((size_t)std::max(c->wl_m, 1) + 255) / 256;
+    FS_HIP(c, c->d_wl_blocks.ensure(4 * n_blocks));
+    FS_HIP(c, hipMemsetAsync(c->d_wl_out.p, 0, 3 * sizeof(int32_t), c->stream));
+    FS_HIP(c, fs_launch_landmark_flags(c->d_wl_raw.p, c->d_wl_views.p, c->d_wl_flag.p, c->wl_m, min_views, c->d_wl_blocks.p,
+                                       c->d_wl_blocks.p + 2 * n_blocks, c->d_wl_out.p, c->stream));
+    return FS_OK;
+}
+
+// The staged cloud becomes the discovered set (n_disc landmarks, n_usable of them usable — the counts wl_enqueue_flags left): the
+// compaction in ascending world index, then the body fs_upload_landmarks' device route runs.
+static int wl_restage(fs_ctx *c, int32_t n_disc, int32_t n_usable)
+{
+    const size_t n_blocks = ((size_t)std::max(c->wl_m, 1) + 255) / 256;
+    c->have_lm = false;                                          // (until the new cloud is whole)
+    FS_HIP(c, c->d_cloud_raw.ensure(3 * (size_t)std::max(n_disc, 1)));
+    int32_t n_chunks = 0;
+    const CloudDest staged{c->d_lx, c->d_ly, c->d_lz, c->d_spheres, c->d_view_perm, c->d_view_inv};
+    const int rc = order_cloud_on_device(c, c->d_cloud_raw.p, n_disc, n_usable, [&](int32_t *perm_a) -> int {
+        FS_HIP(c, fs_launch_landmark_scatter(c->d_wl_raw.p, c->d_wl_flag.p, c->wl_m, c->d_wl_blocks.p + 2 * n_blocks, n_disc, n_usable,
+                                             c->d_cloud_raw.p, perm_a, c->stream));
+        return FS_OK;
+    }, staged, n_chunks);
+    if (rc) return rc;
+    if (const int rc2 = staged_cloud_done(c, n_disc, n_chunks)) return rc2;
+    c->wl_discovered = n_disc;
+    c->wl_staged = true;
+    return FS_OK;
+}
+
+static void drop_world_landmarks(fs_ctx *c)
+{
+    c->have_wl = false; c->wl_staged = false;
+    c->wl_m = c->wl_chunks = c->wl_discovered = 0;
+    c->d_wl_raw.release(); c->d_wl_lx.release(); c->d_wl_ly.release(); c->d_wl_lz.release(); c->d_wl_spheres.release();
+    c->d_wl_perm.release(); c->d_wl_inv.release(); c->d_wl_views.release(); c->d_wl_flag.release(); c->d_wl_blocks.release();
+}
+
+extern "C" {
+
+int fs_upload_world_landmarks(fs_ctx *c, const float *xyz, int32_t m_world, const uint8_t *known)
+{
+    if (!c || m_world < 0 || (m_world > 0 && !xyz)) return FS_E_INVALID;
+    if (m_world > 2000000) return fail(c, FS_E_INVALID, "at most 2,000,000 landmarks per world cloud");
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!xyz) {                                                  // (m_world == 0) released; the staged cloud stays as it is
+        FS_HIP(c, hipStreamSynchronize(c->stream));
+        drop_world_landmarks(c);
+        return FS_OK;
+    }
+    const size_t mw = (size_t)std::max(m_world, 1);
+    c->have_wl = false; c->wl_staged = false;                    // (until the new world cloud is whole)
+    FS_HIP(c, c->d_wl_raw.ensure(3 * mw)); FS_HIP(c, c->d_wl_views.ensure(mw)); FS_HIP(c, c->d_wl_flag.ensure(mw));
+    FS_HIP(c, c->d_wl_out.ensure(4));
+    std::vector<uint8_t> flag((size_t)m_world, 0);
+    if (known) for (int32_t i = 0; i < m_world; ++i) flag[(size_t)i] = known[i] ? 1 : 0;
+    FS_HIP(c, hipMemsetAsync(c->d_wl_views.p, 0, sizeof(uint32_t) * mw, c->stream));
+    if (m_world > 0) FS_HIP(c, hipMemcpyAsync(c->d_wl_flag.p, flag.data(), (size_t)m_world, hipMemcpyHostToDevice, c->stream));
+    const CloudDest world{c->d_wl_lx, c->d_wl_ly, c->d_wl_lz, c->d_wl_spheres, c->d_wl_perm, c->d_wl_inv};
+    int32_t n_chunks = 0;
+    if (const int rc = order_host_cloud_on_device(c, xyz, m_world, c->d_wl_raw.p, world, n_chunks)) return rc;
+    c->wl_m = m_world; c->wl_chunks = n_chunks; c->wl_discovered = 0;
+    c->have_wl = true;
+    // the staged cloud becomes the known set: no counter reaches UINT32_MAX, so the flags are counted and nothing is new
+    if (const int rc = wl_enqueue_flags(c, 0xFFFFFFFFu)) return rc;
+    int32_t totals[3] = {0, 0, 0};
+    FS_HIP(c, hipMemcpyAsync(totals, c->d_wl_out.p, sizeof totals, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    return wl_restage(c, totals[1], totals[2]);
+}
+
+int fs_sense_landmarks(fs_ctx *c, int32_t n, const double *pose7, const fs_landmark_sensor *sensor, int32_t *n_in_view, int32_t *n_new,
+                       int32_t *n_discovered)
+{
+    if (!c || n < 0 || (n > 0 && !pose7)) return FS_E_INVALID;
+    fs_landmark_sensor s;
+    if (sensor) s = *sensor;
+    else s = fs_landmark_sensor{c->fp.max_dist, c->fp.max_angle, c->have_world ? 1 : 0, 1, c->occ.occ_min, c->occ.occ_max, c->occ.end_margin_m};
+    if (!(s.max_dist > 0.0) || !(s.max_angle > 0.0)) return fail(c, FS_E_INVALID, "sensor: max_dist and max_angle must be positive");
+    if (!(s.max_dist < 1.0e9)) return fail(c, FS_E_INVALID, "sensor: max_dist must be below 1e9 m");
+    if (s.line_of_sight != 0 && s.line_of_sight != 1) return fail(c, FS_E_INVALID, "sensor: line_of_sight must be 0 or 1");
+    if (s.min_views < 1) return fail(c, FS_E_INVALID, "sensor: min_views must be at least 1");
+    if (s.occ_min < 0 || s.occ_max > 255 || s.occ_min > s.occ_max) return fail(c, FS_E_INVALID, "sensor: occ_min / occ_max must be costs 0..255 with occ_min <= occ_max");
+    if (!(s.end_margin_m >= 0.0) || !(s.end_margin_m < 1.0e6)) return fail(c, FS_E_INVALID, "sensor: end_margin_m must be finite, >= 0 and below 1e6 m");
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!c->have_wl) return fail(c, FS_E_STATE, "fs_upload_world_landmarks has not been called");
+    if (s.line_of_sight && (!c->have_grid || !c->have_world)) return fail(c, FS_E_STATE, "line_of_sight needs a world grid (fs_upload_world)");
+    if (n == 0) {                                                // nothing changes; the counts are the world cloud's as it stands
+        if (n_new) *n_new = 0;
+        if (n_discovered) *n_discovered = c->wl_discovered;
+        return FS_OK;
+    }
+
+    const size_t nn = (size_t)n;
+    FsLandmarkSenseArgs a{};
+    float cos_a, sin_a;
+    fim_volume(s.max_dist, s.max_angle, a.maxd2, a.max_dist_f, a.cos2, a.cone_mode, cos_a, sin_a);
+    std::vector<float> Rt(nn * 12);
+    for (int32_t i = 0; i < n; ++i) pose_to_rt(pose7 + 7 * (size_t)i, &Rt[12 * (size_t)i]);
+    // (as fs_score_fim: the sphere cull needs R orthonormal — a non-unit quaternion switches the call to the brute-force scan)
+    a.cull = c->opt_cull ? 1 : 0;
+    for (int32_t i = 0; i < n && a.cull; ++i) {
+        const double *q = pose7 + 7 * (size_t)i + 3;
+        const double nq = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+        if (!(std::fabs(nq - 1.0) <= 1.0e-4)) a.cull = 0;
+    }
+    a.lx = c->d_wl_lx.p; a.ly = c->d_wl_ly.p; a.lz = c->d_wl_lz.p; a.spheres = c->d_wl_spheres.p; a.perm = c->d_wl_perm.p;
+    a.n_chunks = c->wl_chunks; a.m_world = c->wl_m;
+    a.n = n;
+    // a single pose is the common call: fewer chunks per wave until the call fills the chip's wave slots (fs_landmarks_in_view's rule)
+    a.group = 64;
+    while (a.group > 4 && (int64_t)n * ((c->wl_chunks + a.group - 1) / a.group) < 2048) a.group >>= 1;
+    a.los = s.line_of_sight;
+    if (a.los) {
+        a.world = grid_dev(c);
+        a.world.cells = c->d_world.p;
+        a.world.cls = nullptr;
+        a.occ_min = s.occ_min; a.occ_max = s.occ_max;
+        // M = 1 + (unsigned)(end_margin_m / resolution), as occlusion_args
+        const double q = s.end_margin_m / c->res;
+        a.occ_margin = 1u + (q < 2147483647.0 ? (uint32_t)q : 2147483647u);
+    }
+    FS_HIP(c, c->d_wl_Rt.ensure(nn * 12)); FS_HIP(c, c->d_wl_out.ensure(3 + nn));
+    a.Rt = c->d_wl_Rt.p; a.views = c->d_wl_views.p; a.n_in_view = c->d_wl_out.p + 3;
+    FS_HIP(c, hipMemcpyAsync(c->d_wl_Rt.p, Rt.data(), sizeof(float) * 12 * nn, hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, hipMemsetAsync(c->d_wl_out.p + 3, 0, sizeof(int32_t) * nn, c->stream));
+    FS_HIP(c, fs_launch_sense_landmarks(a, c->stream));
+    if (const int rc = wl_enqueue_flags(c, (uint32_t)s.min_views)) { (void)hipStreamSynchronize(c->stream); return rc; }
+    std::vector<int32_t> out(3 + nn);
+    FS_HIP(c, hipMemcpyAsync(out.data(), c->d_wl_out.p, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));                  // (the one wait: the level layout depends on the discovered count)
+    if (out[1] < 0 || out[1] > c->wl_m || out[2] < 0 || out[2] > out[1])
+        return fail(c, FS_E_HIP, "fs_sense_landmarks: %d discovered, %d usable of %d world landmarks", out[1], out[2], c->wl_m);
+    c->wl_discovered = out[1];
+    if (out[0] > 0 || !c->wl_staged)
+        if (const int rc = wl_restage(c, out[1], out[2])) return rc;
+    if (n_in_view) std::copy(out.begin() + 3, out.end(), n_in_view);
+    if (n_new) *n_new = out[0];
+    if (n_discovered) *n_discovered = out[1];
+    return FS_OK;
+}
+
+int fs_world_landmarks_get(fs_ctx *c, int32_t *m_world, int32_t *n_discovered, int32_t *world_index, int32_t *views)
+{
+    if (!c) return FS_E_INVALID;
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!c->have_wl) return fail(c, FS_E_STATE, "fs_upload_world_landmarks has not been called");
+    const size_t mw = (size_t)c->wl_m;
+    std::vector<uint8_t> flag;
+    if (world_index && mw > 0) {
+        flag.resize(mw);
+        FS_HIP(c, hipMemcpyAsync(flag.data(), c->d_wl_flag.p, mw, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (views && mw > 0) FS_HIP(c, hipMemcpyAsync(views, c->d_wl_views.p, sizeof(uint32_t) * mw, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    if (world_index) {
+        int32_t r = 0;
+        for (size_t i = 0; i < flag.size() && r < c->wl_discovered; ++i) if (flag[i]) world_index[r++] = (int32_t)i;
+    }
+    if (m_world) *m_world = c->wl_m;
+    if (n_discovered) *n_discovered = c->wl_discovered;
+    return FS_OK;
+}
+
+int fs_staged_cloud_get(fs_ctx *c, int32_t *m, int32_t *n_chunks, float *soa, float *spheres, int32_t *perm)
+{
+    if (!c) return FS_E_INVALID;
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!c->have_lm) return fail(c, FS_E_STATE, "fs_upload_landmarks has not been called");
+    const size_t mp = (size_t)c->n_chunks * FS_CHUNK;
+    if (soa) {
+        FS_HIP(c, hipMemcpyAsync(soa, c->d_lx.p, sizeof(float) * mp, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipMemcpyAsync(soa + mp, c->d_ly.p, sizeof(float) * mp, hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(c, hipMemcpyAsync(soa + 2 * mp, c->d_lz.p, sizeof(float) * mp, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (spheres) FS_HIP(c, hipMemcpyAsync(spheres, c->d_spheres.p, sizeof(float) * 4 * (size_t)c->n_chunks, hipMemcpyDeviceToHost, c->stream));
+    if (perm) FS_HIP(c, hipMemcpyAsync(perm, c->d_view_perm.p, sizeof(int32_t) * mp, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    if (m) *m = c->m;
+    if (n_chunks) *n_chunks = c->n_chunks;
     return FS_OK;
 }
 

@@ -755,6 +755,36 @@ hipError_t fs_launch_goals_mapped(const uint8_t *d_cells, int nx, int ny, double
 // d_counts [4] += cells != 255, == 255, == 254, == 0
 hipError_t fs_launch_grid_census(const uint8_t *d_cells, size_t total, unsigned long long *d_counts, hipStream_t s);
 
+// ---- landmark sensor on a ground-truth cloud (fs_sense_landmarks; fs_sense_landmarks.hip)
+// sweep: one wavefront per (pose, group of chunks) of the WORLD cloud; a landmark a pose sees gets views[world index] += 1, the
+// pose n_in_view[pose] += 1 (both zero-based sums: the caller clears n_in_view, views carry on from earlier calls).
+struct FsLandmarkSenseArgs {
+    const float *lx, *ly, *lz, *spheres;   // the world cloud in its own k-d leaf order, as FsFimArgs' staged one
+    const int32_t *perm;                   // [n_chunks * 64]: the world index per slot, -1 for a sentinel
+    int32_t n_chunks, m_world;
+    const float *Rt;                       // [n][12]
+    int32_t n;
+    int32_t group;                         // chunks per wave (a power of two, 4 .. 64)
+    int32_t cull;                          // 0: every chunk is tested
+    float max_dist_f;                      // culling reach (FsFimArgs::max_dist_f)
+    float maxd2, cos2;                     // the predicate (FsFimArgs' fields)
+    int32_t cone_mode;
+    int32_t los, occ_min, occ_max;         // line of sight through `world` (read only when los)
+    uint32_t occ_margin;
+    FsGridDev world;                       // the WORLD grid
+    uint32_t *views;                       // [m_world]
+    int32_t *n_in_view;                    // [n]
+};
+hipError_t fs_launch_sense_landmarks(const FsLandmarkSenseArgs &a, hipStream_t s);
+// flags: views >= min_views sets flag for good; d_totals [3] += newly discovered, discovered, discovered and usable;
+// d_block_counts / d_block_off [2 * ceil(m_world / 256)]: the last two per block of 256 landmarks and their exclusive sums.
+hipError_t fs_launch_landmark_flags(const float *d_raw, const uint32_t *d_views, uint8_t *d_flag, int32_t m_world, uint32_t min_views,
+                                    int32_t *d_block_counts, int32_t *d_block_off, int32_t *d_totals, hipStream_t s);
+// scatter: the discovered landmarks' raw xyz in ascending world index -> d_raw_out [n_disc][3]; the ranks of the usable ones,
+// ascending -> d_usable_out [n_usable] (what fs_cloud_order_device starts from)
+hipError_t fs_launch_landmark_scatter(const float *d_raw, const uint8_t *d_flag, int32_t m_world, const int32_t *d_block_off, int32_t n_disc,
+                                      int32_t n_usable, float *d_raw_out, int32_t *d_usable_out, hipStream_t s);
+
 // ---- FIM kernel arguments ---------------------------------------------------------------------
 struct FsFimArgs {
     // landmarks: SoA in k-d leaf order, n_chunks chunks of 64 (the tail padded with far-away sentinels),

@@ -971,6 +971,76 @@ int fs_goals_mapped(fs_ctx *ctx, int32_t n, const double *goal_xyz /* [n][3] */,
  * (!= 255; OccupancyGrid -1 corresponds to 255), unknown (== 255), lethal (== 254), free (== 0). */
 int fs_grid_census(fs_ctx *ctx, int64_t counts[4] /* known (!= 255), unknown (== 255), lethal (== 254), free (== 0) */);
 
+/* ---------------------------------------------------------------- landmark sensor on a ground-truth cloud (closed loop)
+ *
+ * THIS PROJECT'S OWN EXTENSION, the other half of fs_sense.  In the reference the map points behind every Fisher-information
+ * figure come from the ORB-SLAM3 wrapper (GetLandmarksInView, FIP/src/fisher_information/FisherInfoManager.cpp:52-88), which is
+ * outside the vendored tree.  Here a ground-truth WORLD cloud lives in HBM beside the world grid, the poses the robot visits see
+ * parts of it, and the staged cloud — what fs_score_fim, fs_score_candidates and fs_landmarks_in_view read — is the part seen
+ * so far, put into its order on the device, never crossing the bus. */
+
+/* The world cloud: up to 2 000 000 points (fs_upload_landmarks' limit; more: FS_E_INVALID), kept on the device as raw xyz, in a
+ * k-d leaf order of its own with one bounding sphere per 64-landmark chunk, and with one uint32 sighting counter (0) and one
+ * `discovered` flag per landmark.  known [i] != 0 marks landmark i discovered from the start; NULL: none.  After the call the
+ * staged cloud is exactly the known set, possibly empty, staged as described under fs_sense_landmarks.  A non-finite world
+ * landmark, or one beyond 1e17 m (fs_upload_landmarks' usability test), keeps its index and is never seen.  xyz == NULL with
+ * m_world == 0 releases the world cloud and leaves the staged cloud alone; xyz != NULL with m_world == 0 stages an empty world.
+ * Needs neither a grid nor a lookup table.  NULL context, m_world < 0, xyz == NULL with m_world > 0: FS_E_INVALID. */
+int fs_upload_world_landmarks(fs_ctx *ctx, const float *xyz /* [m_world][3] */, int32_t m_world,
+                              const uint8_t *known /* [m_world] or NULL */);
+
+typedef struct fs_landmark_sensor {
+    double  max_dist, max_angle;   /* validated as fs_set_fim_params validates them */
+    int32_t line_of_sight;         /* 0: predicate only; 1: also the line of sight through the WORLD grid */
+    int32_t min_views;             /* >= 1: sightings (all calls together) before a landmark counts as discovered */
+    int32_t occ_min, occ_max;      /* as fs_occlusion_params */
+    double  end_margin_m;
+} fs_landmark_sensor;
+
+/* One sweep of the world cloud from each of n poses.  Pose p SEES world landmark i when
+ *   - the visibility predicate of fs_set_fim_params accepts it under the sensor's volume: the same getTransformFromPose
+ *     conversion of pose7, the same fp32 transform and comparison as fs_score_fim and fs_landmarks_in_view, and
+ *   - with line_of_sight == 1, the line from the pose's float32 translation to the landmark's float32 position, both widened to
+ *     double, is not blocked on the WORLD grid (fs_upload_world) under the rule of fs_set_occlusion, word for word: the uncapped
+ *     walk, the start cell tested, the last 1 + (unsigned)(end_margin_m / resolution) cells at the landmark's end left out, an
+ *     end off the map tests nothing, planar on nz == 1.
+ * Every sighting adds 1 to the landmark's counter (modulo 2^32); identical poses count separately.  A landmark becomes
+ * discovered when its counter reaches min_views and stays discovered for good.  n_in_view [p] (may be NULL) = landmarks pose p
+ * sees, discovered before or not; *n_new (may be NULL) = landmarks that became discovered in this call; *n_discovered (may be
+ * NULL) = the total afterwards.  Every figure is an integer sum that does not depend on the order the device works in; there is
+ * no "who discovered it".
+ *   sensor == NULL   fs_set_fim_params' volume, min_views 1, range and margin of fs_set_occlusion (its `enabled` is not
+ *                    consulted), line_of_sight 1 if a world grid is staged, else 0.
+ *   restaging        After the sweep the staged cloud is rebuilt — on the device — if anything became discovered or if the staged
+ *                    cloud is not currently the discovered set (fs_upload_landmarks was called in between: that call leaves the
+ *                    world cloud, counters and flags alone).  The discovered landmarks' raw xyz are compacted in ascending world
+ *                    index and staged as fs_upload_landmarks stages that array under "cloud.order" 2, whatever the option says
+ *                    and however small the set; an empty set is staged as fs_upload_landmarks(ctx, NULL, 0) stages it.  The
+ *                    only host traffic is the poses in, the counts out and one read-back of the discovered count.  Afterwards
+ *                    "upload index" in fs_landmarks_in_view means rank in the discovered set; fs_world_landmarks_get maps rank
+ *                    to world index.
+ * FS_E_INVALID, nothing changed or written: NULL context, n < 0, pose7 == NULL with n > 0, an invalid sensor (volume, min_views
+ * < 1, line_of_sight other than 0 / 1, cost range or margin as fs_set_occlusion refuses them).  FS_E_STATE, nothing changed or
+ * written: no world cloud staged; line_of_sight == 1 with no world grid staged (also after fs_upload_grid of another shape has
+ * dropped it).  n == 0 returns FS_OK and changes nothing (*n_new = 0, *n_discovered = the total as it stands). */
+int fs_sense_landmarks(fs_ctx *ctx, int32_t n, const double *pose7 /* [n][7] */,
+                       const fs_landmark_sensor *sensor /* NULL: see above */,
+                       int32_t *n_in_view /* [n] or NULL */, int32_t *n_new /* or NULL */, int32_t *n_discovered /* or NULL */);
+
+/* The state of the world cloud: its size, the number of discovered landmarks, their world indices in ascending order (entry r is
+ * the landmark fs_landmarks_in_view calls r while the staged cloud is the discovered set) and every landmark's sighting counter.
+ * Each pointer may be NULL.  No world cloud staged: FS_E_STATE. */
+int fs_world_landmarks_get(fs_ctx *ctx, int32_t *m_world, int32_t *n_discovered,
+                           int32_t *world_index /* [n_discovered] ascending, or NULL */,
+                           int32_t *views /* [m_world] or NULL */);
+
+/* The staged landmark cloud as the kernels read it: m landmarks in n_chunks chunks of 64; soa [3][n_chunks * 64] = x, y, z in k-d
+ * leaf order with the far-away sentinels in the padding; spheres [n_chunks][4]; perm [n_chunks * 64] = the landmark's position in the
+ * staged array per slot, -1 for a sentinel.  Every pointer may be NULL (call once for the sizes).  A read-back like
+ * fs_read_grid_region: what two routes that claim to stage the same cloud (fs_upload_landmarks with the device ordering,
+ * fs_sense_landmarks) are held to, byte for byte — the Fisher float sums are not bit-stable from call to call even on one cloud.  No cloud staged: FS_E_STATE. */
+int fs_staged_cloud_get(fs_ctx *ctx, int32_t *m, int32_t *n_chunks, float *soa, float *spheres, int32_t *perm);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,10 +55,12 @@ EXPORTED_SYMBOLS = [
     "fs_multi_keepout_add_fov", "fs_multi_keepout_add_disc", "fs_multi_keepout_clear", "fs_multi_mark_lethal_fov",
     "fs_set_occlusion", "fs_get_occlusion", "fs_line_of_sight", "fs_multi_set_occlusion",
     "fs_landmarks_in_view",
-    "fs_upload_world", "fs_sense", "fs_goals_mapped", "fs_grid_census",
+    "fs_upload_world", "fs_sense", "fs_goals_mapped", "fs_grid_census", "fs_drive",
     "fs_upload_world_landmarks", "fs_sense_landmarks", "fs_world_landmarks_get", "fs_staged_cloud_get",
 ]
 FS_KEEPOUT_MAX_ZONES = 1024
+FS_DRIVE_ARRIVED, FS_DRIVE_BLOCKED, FS_DRIVE_COLLIDED, FS_DRIVE_OFF_MAP, FS_DRIVE_MAPPED = 0, 1, 2, 3, 4
+FS_DRIVE_MAX_STATIONS, FS_DRIVE_MAX_ROBOTS = 2048, 4096
 KEEPOUT_FOV, KEEPOUT_DISC = 0, 1
 
 RECORD_DTYPE = np.dtype([("arrival", "<i4"), ("argmax", "<i4"), ("yaw", "<f4"), ("info_ref", "<f4"),
@@ -117,6 +119,13 @@ class LandmarkSensorC(C.Structure):
 
 
 assert C.sizeof(LandmarkSensorC) == 40
+
+
+class DriveParamsC(C.Structure):
+    _fields_ = [("block_min", C.c_int32), ("block_max", C.c_int32), ("stop_when_mapped", C.c_int32)]
+
+
+assert C.sizeof(DriveParamsC) == 12
 
 
 class ViewLandmarkC(C.Structure):
@@ -194,6 +203,7 @@ def load_library(build: bool = True, path: str | None = None):
     L.fs_sense.argtypes = [vp, i32, vp, vp, C.POINTER(RayParamsC), vp, vp, vp, C.POINTER(i64), C.POINTER(i64), vp]
     L.fs_goals_mapped.argtypes = [vp, i32, vp, vp]
     L.fs_grid_census.argtypes = [vp, vp]
+    L.fs_drive.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(RayParamsC), C.POINTER(DriveParamsC), vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), vp]
     L.fs_upload_world_landmarks.argtypes = [vp, vp, i32, vp]
     L.fs_sense_landmarks.argtypes = [vp, i32, vp, C.POINTER(LandmarkSensorC), vp, C.POINTER(i32), C.POINTER(i32)]
     L.fs_world_landmarks_get.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), vp, vp]
@@ -789,6 +799,41 @@ class FrontierScorer:
         v = np.zeros(4, dtype=np.int64)
         self._check(self._L.fs_grid_census(self._h, _p(v)))
         return dict(known=int(v[0]), unknown=int(v[1]), lethal=int(v[2]), free=int(v[3]))
+
+    def drive(self, stations, goals, first_ray=None, sensor=None, block=(253, 254), stop_when_mapped=True):
+        """fs_drive: robot r drives stations[r] ([n_r][3], n_r >= 1) through the world, sensing at every station,
+        and stops at a cost in `block` on the staged map (FS_DRIVE_BLOCKED), at one only the world holds (COLLIDED), off the map
+        (OFF_MAP), when goals[r] is mapped (MAPPED, with stop_when_mapped) or out of stations (ARRIVED) — one call and one wait for
+        all robots and stations.  first_ray: None (every station sweeps all rays) or one [n_r] array per robot, as sense()'s;
+        sensor: as sense()'s.  Returns a dict: status [R], reached [R], station_status and seen_unknown (a list of [n_r] arrays;
+        -1 and 0 for stations never reached), n_seen, n_revealed, window (x0, y0, z0, sx, sy, sz)."""
+        st = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3) for a in stations]
+        R = len(st)
+        g = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
+        if g.shape[0] != R:
+            raise ValueError("goals must hold one entry per robot")
+        ns = np.array([a.shape[0] for a in st], dtype=np.int32)
+        T = int(ns.sum())
+        xyz = np.ascontiguousarray(np.concatenate(st, axis=0)) if R else np.zeros((0, 3))
+        fr = None
+        if first_ray is not None:
+            if len(first_ray) != R:
+                raise ValueError("first_ray must hold one array per robot")
+            parts = [np.asarray(f, dtype=np.int32).reshape(-1) for f in first_ray]
+            if any(f.shape[0] != n for f, n in zip(parts, ns)):
+                raise ValueError("first_ray must hold one entry per station")
+            fr = np.ascontiguousarray(np.concatenate(parts)) if R else np.zeros(0, dtype=np.int32)
+        sp = None if sensor is None else _ray_params_c(**sensor)
+        dp = DriveParamsC(int(block[0]), int(block[1]), 1 if stop_when_mapped else 0)
+        status = np.zeros(R, dtype=np.int32); reached = np.zeros(R, dtype=np.int32)
+        sst = np.zeros(T, dtype=np.int32); seen = np.zeros(T, dtype=np.int32)
+        n_seen, n_rev = C.c_int64(), C.c_int64()
+        win = np.zeros(6, dtype=np.int32)
+        self._check(self._L.fs_drive(self._h, R, _p(xyz), _p(ns), _p(fr), _p(g), None if sp is None else C.byref(sp), C.byref(dp),
+                                     _p(status), _p(reached), _p(sst), _p(seen), C.byref(n_seen), C.byref(n_rev), _p(win)))
+        cut = np.cumsum(ns)[:-1] if R else []
+        return dict(status=status, reached=reached, station_status=np.split(sst, cut) if R else [], seen_unknown=np.split(seen, cut) if R else [],
+                    n_seen=n_seen.value, n_revealed=n_rev.value, window=tuple(int(v) for v in win))
 
     def first_ray_for_yaw(self, yaw):
         """The window start i whose pose yaw i * delta_theta + camera_fov / 2 (DEP/src/CostCalculator.cpp:119) is nearest to `yaw`,
@@ -1463,6 +1508,43 @@ def first_ray_for_yaw(yaw, delta_theta, camera_fov, n_yaw):
         if best_d is None or d < best_d:
             best, best_d = i, d
     return best
+
+
+def stations_along(poses_xy, spacing_m, look=10, delta_theta=0.10, camera_fov=1.04, n_rays=0, z=0.0):
+    """Stations for FrontierScorer.drive from a pose list [N][2] (refine_paths' `poses`): the first pose, then every pose at which
+    the way driven since the last station reaches spacing_m, and always the last pose.  Each station looks along the path: its
+    first_ray is first_ray_for_yaw — for the fan of delta_theta, camera_fov, n_rays (set_ray_params' arguments and defaults) — of the
+    direction from it to the pose `look` entries ahead (the last pose when there are fewer; the last station keeps the station's
+    before it, a lone station gets window 0).  Host only, numpy.  Returns (stations [n][3] with z in the third column,
+    first_ray [n] int32, index [n]: the pose each station is)."""
+    import math
+    n_yaw = fan_n_yaw(delta_theta, n_rays)
+    p = np.asarray(poses_xy, dtype=np.float64)
+    p = p.reshape(-1, p.shape[-1])[:, :2] if p.size else p.reshape(0, 2)
+    n = p.shape[0]
+    if n == 0:
+        return np.zeros((0, 3)), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64)
+    keep, since = [0], 0.0
+    for i in range(1, n):
+        since += math.hypot(p[i, 0] - p[i - 1, 0], p[i, 1] - p[i - 1, 1])
+        if since >= spacing_m:
+            keep.append(i)
+            since = 0.0
+    if keep[-1] != n - 1:
+        keep.append(n - 1)
+    first = np.zeros(len(keep), dtype=np.int32)
+    for j, i in enumerate(keep):
+        a = min(i + int(look), n - 1)
+        dx, dy = p[a, 0] - p[i, 0], p[a, 1] - p[i, 1]
+        if dx == 0.0 and dy == 0.0:
+            first[j] = first[j - 1] if j else 0
+            continue
+        yaw = math.atan2(dy, dx)
+        first[j] = first_ray_for_yaw(yaw if yaw >= 0.0 else yaw + 2 * math.pi, delta_theta, camera_fov, n_yaw)
+    st = np.zeros((len(keep), 3))
+    st[:, :2] = p[keep]
+    st[:, 2] = z
+    return st, first, np.asarray(keep, dtype=np.int64)
 
 
 def shard_bounds(n: int, n_shards: int, shard: int):

@@ -242,6 +242,9 @@ struct fs_ctx {
     DevBuf<double> d_sense_dir, d_sense_origin;
     DevBuf<int32_t> d_sense_first, d_sense_rays, d_sense_out;
     DevBuf<unsigned long long> d_sense_counts;
+    // the drive (fs_drive.hip): stations and goals; one int32 block of inputs, presets and results (see fs_drive)
+    DevBuf<double> d_drive_xyz;
+    DevBuf<int32_t> d_drive_i32;
 
     // the landmark sensor (fs_sense_landmarks.hip): the ground-truth cloud as raw xyz [wl_m][3], in a k-d leaf order
     // of its own (SoA padded to wl_chunks chunks, spheres, d_wl_perm: the world index per slot) and with one sighting counter and
@@ -1318,6 +1321,56 @@ int ko_after_snapshot(fs_ctx *c, int32_t nx, int32_t ny, int32_t nz, const doubl
     return FS_OK;
 }
 
+// fs_sense's and fs_drive's fan: `sensor`'s (validated and built by the same host code as fs_set_ray_params'; the table goes to the
+// device only when it is not the one already there) or, sensor == NULL, the context's
+int sense_fan_setup(fs_ctx *c, const fs_ray_params *sensor, FsSenseArgs &a)
+{
+    if (sensor) {
+        std::vector<double> dir;
+        int n_yaw = 0, k = 0;
+        const int rc = ray_fan_build(c, sensor, dir, n_yaw, k);
+        if (rc) return rc;
+        if (dir != c->sense_dir) {
+            c->sense_dir.clear();
+            FS_HIP(c, c->d_sense_dir.ensure(dir.size()));
+            FS_HIP(c, hipMemcpyAsync(c->d_sense_dir.p, dir.data(), dir.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            FS_HIP(c, hipStreamSynchronize(c->stream));
+            c->sense_dir.swap(dir);
+        }
+        a.dir = c->d_sense_dir.p;
+        a.n_yaw = n_yaw; a.n_elev = sensor->n_elev; a.window = k;
+    } else {
+        a.dir = c->d_dir.p;
+        a.n_yaw = c->n_yaw; a.n_elev = c->n_elev; a.window = c->window;
+    }
+    return FS_OK;
+}
+
+// the world, the staged grid, the walk's cap, the visitor's ranges and the clamp bounds of a sweep with ray parameters p
+void sense_world_setup(const fs_ctx *c, const fs_ray_params &p, FsSenseArgs &a)
+{
+    a.world = grid_dev(c);
+    a.world.cells = c->d_world.p;
+    a.world.cls = nullptr;
+    a.staged = c->d_cells.p;
+    a.max_length = (unsigned int)(p.max_camera_depth / c->res);             // CostCalculator.cpp:28
+    a.obst_min = p.obst_min; a.obst_max = p.obst_max; a.trace_min = p.trace_min; a.trace_max = p.trace_max;
+    double b[6];
+    ray_clamp_bounds(c, p, b);
+    a.lo_x = b[0]; a.hi_x = b[1]; a.lo_y = b[2]; a.hi_y = b[3]; a.lo_z = b[4]; a.hi_z = b[5];
+}
+
+// the mark image: allocated and zeroed once per grid shape, all zero again after every merge
+int sense_mark_ready(fs_ctx *c)
+{
+    const size_t total = (size_t)c->nx * (size_t)c->ny * (size_t)c->nz;
+    const bool grown = c->d_sense_mark.cap < total;
+    FS_HIP(c, c->d_sense_mark.ensure(total));
+    if (grown || !c->sense_mark_clean) FS_HIP(c, hipMemsetAsync(c->d_sense_mark.p, 0, c->d_sense_mark.cap, c->stream));
+    c->sense_mark_clean = false;
+    return FS_OK;
+}
+
 // the ground-truth world and the mark image of its shape leave the context (the stream has drained)
 void drop_world(fs_ctx *c)
 {
@@ -1659,24 +1712,9 @@ int fs_sense(fs_ctx *c, int32_t n, const double *origin_xyz, const int32_t *firs
     if (!sensor && !c->have_ray) return fail(c, FS_E_STATE, "fs_set_ray_params has not been called and no sensor is given");
     FsSenseArgs a{};
     const fs_ray_params &p = sensor ? *sensor : c->rp;
-    if (sensor) {
-        // the same host code as fs_set_ray_params'; the table goes to the device only when it is not the one already there
-        std::vector<double> dir;
-        int n_yaw = 0, k = 0;
-        const int rc = ray_fan_build(c, sensor, dir, n_yaw, k);
+    {
+        const int rc = sense_fan_setup(c, sensor, a);
         if (rc) return rc;
-        if (dir != c->sense_dir) {
-            c->sense_dir.clear();
-            FS_HIP(c, c->d_sense_dir.ensure(dir.size()));
-            FS_HIP(c, hipMemcpyAsync(c->d_sense_dir.p, dir.data(), dir.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-            FS_HIP(c, hipStreamSynchronize(c->stream));
-            c->sense_dir.swap(dir);
-        }
-        a.dir = c->d_sense_dir.p;
-        a.n_yaw = n_yaw; a.n_elev = sensor->n_elev; a.window = k;
-    } else {
-        a.dir = c->d_dir.p;
-        a.n_yaw = c->n_yaw; a.n_elev = c->n_elev; a.window = c->window;
     }
     if (first_ray)
         for (int32_t i = 0; i < n; ++i)
@@ -1687,23 +1725,11 @@ int fs_sense(fs_ctx *c, int32_t n, const double *origin_xyz, const int32_t *firs
     if (window) std::fill(window, window + 6, 0);
     if (n == 0) return FS_OK;
 
-    a.world = grid_dev(c);
-    a.world.cells = c->d_world.p;
-    a.world.cls = nullptr;
-    a.staged = c->d_cells.p;
-    a.max_length = (unsigned int)(p.max_camera_depth / c->res);             // CostCalculator.cpp:28
-    a.obst_min = p.obst_min; a.obst_max = p.obst_max; a.trace_min = p.trace_min; a.trace_max = p.trace_max;
+    sense_world_setup(c, p, a);
+    const size_t n_rays = (size_t)a.n_yaw * (size_t)a.n_elev;
     {
-        double b[6];
-        ray_clamp_bounds(c, p, b);
-        a.lo_x = b[0]; a.hi_x = b[1]; a.lo_y = b[2]; a.hi_y = b[3]; a.lo_z = b[4]; a.hi_z = b[5];
-    }
-    const size_t total = (size_t)c->nx * (size_t)c->ny * (size_t)c->nz, n_rays = (size_t)a.n_yaw * (size_t)a.n_elev;
-    {   // the mark image: allocated and zeroed once per grid shape, all zero again after every merge
-        const bool grown = c->d_sense_mark.cap < total;
-        FS_HIP(c, c->d_sense_mark.ensure(total));
-        if (grown || !c->sense_mark_clean) FS_HIP(c, hipMemsetAsync(c->d_sense_mark.p, 0, c->d_sense_mark.cap, c->stream));
-        c->sense_mark_clean = false;
+        const int rc = sense_mark_ready(c);
+        if (rc) return rc;
     }
     const size_t un = (size_t)n;
     FS_HIP(c, c->d_sense_origin.ensure(3 * un)); FS_HIP(c, c->d_sense_out.ensure(6 + 2 * un)); FS_HIP(c, c->d_sense_counts.ensure(4));
@@ -1771,6 +1797,163 @@ int fs_goals_mapped(fs_ctx *c, int32_t n, const double *goal_xyz, uint8_t *mappe
     FS_HIP(c, fs_launch_goals_mapped(c->d_cells.p, c->nx, c->ny, c->origin[0], c->origin[1], c->res, n, c->d_sense_origin.p, c->d_sense_mapped.p, c->stream));
     FS_HIP(c, hipMemcpyAsync(mapped, c->d_sense_mapped.p, un, hipMemcpyDeviceToHost, c->stream));
     FS_HIP(c, hipStreamSynchronize(c->stream));
+    return FS_OK;
+}
+
+// The drive: every step's launches go onto the stream back to back, the stop decisions stay on the device, and
+// the one wait at the end reads every output.  d_drive_i32, T = all stations: n_stations [R] | first station [R] | state [R][2] |
+// union box [4] | station_status [T] | seen_unknown [T] | station boxes [T][4] | first_ray [T]; the part from `state` up to the
+// boxes is what comes back.
+int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32_t *n_stations, const int32_t *first_ray, const double *goal_xyz,
+             const fs_ray_params *sensor, const fs_drive_params *params, int32_t *status, int32_t *reached, int32_t *station_status,
+             int32_t *seen_unknown, int64_t *n_seen, int64_t *n_revealed, int32_t window[6])
+{
+    if (!c || n_robots < 0 || (n_robots > 0 && (!station_xyz || !n_stations || !goal_xyz || !status || !reached || !station_status || !seen_unknown)))
+        return FS_E_INVALID;
+    FS_HIP(c, hipSetDevice(c->device));
+    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (!c->have_world) return fail(c, FS_E_STATE, "fs_upload_world has not been called");
+    if (!sensor && !c->have_ray) return fail(c, FS_E_STATE, "fs_set_ray_params has not been called and no sensor is given");
+    if (c->nz != 1) return fail(c, FS_E_INVALID, "fs_drive is defined on a 2-D costmap (nz == 1)");
+    if (n_robots > FS_DRIVE_MAX_ROBOTS) return fail(c, FS_E_INVALID, "%d robots, at most %d", n_robots, FS_DRIVE_MAX_ROBOTS);
+    const size_t R = (size_t)n_robots;
+    size_t T = 0;
+    int32_t K = 0;
+    for (size_t r = 0; r < R; ++r) {
+        if (n_stations[r] < 1) return fail(c, FS_E_INVALID, "n_stations[%zu] = %d: every robot needs a station", r, n_stations[r]);
+        if (n_stations[r] > FS_DRIVE_MAX_STATIONS) return fail(c, FS_E_INVALID, "n_stations[%zu] = %d, at most %d", r, n_stations[r], FS_DRIVE_MAX_STATIONS);
+        T += (size_t)n_stations[r];
+        K = std::max(K, n_stations[r]);
+    }
+    const fs_drive_params dp = params ? *params : fs_drive_params{253, 254, 1};
+    FsDriveArgs a{};
+    const fs_ray_params &p = sensor ? *sensor : c->rp;
+    {
+        const int rc = sense_fan_setup(c, sensor, a.sense);
+        if (rc) return rc;
+    }
+    if (first_ray)
+        for (size_t i = 0; i < T; ++i)
+            if (first_ray[i] < -1 || first_ray[i] > a.sense.n_yaw - a.sense.window)
+                return fail(c, FS_E_INVALID, "first_ray[%zu] = %d is outside [-1, %d]", i, first_ray[i], a.sense.n_yaw - a.sense.window);
+    if (n_seen) *n_seen = 0;
+    if (n_revealed) *n_revealed = 0;
+    if (window) std::fill(window, window + 6, 0);
+    if (R == 0) return FS_OK;
+
+    sense_world_setup(c, p, a.sense);
+    {
+        const int rc = sense_mark_ready(c);
+        if (rc) return rc;
+    }
+    // what a station can touch: its cell +- the fan's reach (an end point lies within depth of the pose, so its cell within
+    // max_length + 2 of the pose's), clipped; empty for a station off the map.  It sizes the merge launch and says where the
+    // keep-out zones are painted again — over more cells than the sweep saw, which repeats what is already painted there.
+    const int32_t reach = (int32_t)std::min<unsigned int>(a.sense.max_length, (unsigned int)(c->nx + c->ny)) + 3;
+    struct Win { int32_t x0, y0, x1, y1; };
+    std::vector<int32_t> off(R);
+    std::vector<Win> cons(T);
+    {
+        size_t t = 0;
+        for (size_t r = 0; r < R; ++r) {
+            off[r] = (int32_t)t;
+            for (int32_t k = 0; k < n_stations[r]; ++k, ++t) {
+                int32_t mx = 0, my = 0;
+                if (grid_world_to_map(c, station_xyz[3 * t], station_xyz[3 * t + 1], mx, my))
+                    cons[t] = Win{std::max(mx - reach, 0), std::max(my - reach, 0), std::min(mx + reach, c->nx - 1), std::min(my + reach, c->ny - 1)};
+                else
+                    cons[t] = Win{c->nx, c->ny, -1, -1};
+            }
+        }
+    }
+    const size_t o_n = 0, o_off = R, o_state = 2 * R, o_union = 4 * R, o_status = 4 * R + 4, o_seen = o_status + T, o_box = o_seen + T,
+                 o_first = o_box + 4 * T, n_i32 = o_first + (first_ray ? T : 0), n_back = o_box - o_state;
+    std::vector<int32_t> h(n_i32);
+    for (size_t r = 0; r < R; ++r) {
+        h[o_n + r] = n_stations[r]; h[o_off + r] = off[r];
+        h[o_state + 2 * r] = FS_DRIVE_DRIVING; h[o_state + 2 * r + 1] = 0;
+    }
+    h[o_union] = c->nx; h[o_union + 1] = c->ny; h[o_union + 2] = -1; h[o_union + 3] = -1;
+    for (size_t t = 0; t < T; ++t) {
+        h[o_status + t] = -1; h[o_seen + t] = 0;
+        h[o_box + 4 * t] = c->nx; h[o_box + 4 * t + 1] = c->ny; h[o_box + 4 * t + 2] = -1; h[o_box + 4 * t + 3] = -1;
+    }
+    if (first_ray) std::copy(first_ray, first_ray + T, h.begin() + (std::ptrdiff_t)o_first);
+    std::vector<double> xyz(3 * (T + R));
+    std::copy(station_xyz, station_xyz + 3 * T, xyz.begin());
+    std::copy(goal_xyz, goal_xyz + 3 * R, xyz.begin() + (std::ptrdiff_t)(3 * T));
+    FS_HIP(c, c->d_drive_xyz.ensure(xyz.size())); FS_HIP(c, c->d_drive_i32.ensure(n_i32)); FS_HIP(c, c->d_sense_counts.ensure(4));
+    FS_HIP(c, hipMemcpyAsync(c->d_drive_xyz.p, xyz.data(), xyz.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, hipMemcpyAsync(c->d_drive_i32.p, h.data(), n_i32 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, hipMemsetAsync(c->d_sense_counts.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    int32_t *const d = c->d_drive_i32.p;
+    a.sense.n = (int32_t)T;
+    a.sense.origin = c->d_drive_xyz.p;
+    a.sense.first_ray = first_ray ? d + o_first : nullptr;
+    a.sense.mark = c->d_sense_mark.p;
+    a.sense.ray_unknown = nullptr;
+    a.sense.box = nullptr;
+    a.sense.status = d + o_status;
+    a.sense.seen_unknown = d + o_seen;
+    a.staged = grid_dev(c);
+    a.staged.cls = nullptr;
+    a.n_robots = n_robots;
+    a.n_stations = d + o_n; a.station_off = d + o_off;
+    a.goal = c->d_drive_xyz.p + 3 * T;
+    a.block_min = dp.block_min; a.block_max = dp.block_max;
+    a.move_max_length = (double)c->nx + (double)c->ny;
+    a.state = d + o_state; a.station_box = d + o_box; a.union_box = d + o_union;
+    a.counts = c->d_sense_counts.p;
+
+    ++c->grid_gen;
+    const bool paint = !c->ko_zones.empty() && c->ko_mask_valid;
+    Win all{c->nx, c->ny, -1, -1};
+    for (int32_t k = 0; k < K; ++k) {
+        Win w{c->nx, c->ny, -1, -1};
+        unsigned long long most = 0;
+        for (size_t r = 0; r < R; ++r) {
+            if (k >= n_stations[r]) continue;
+            const Win &s = cons[(size_t)off[r] + (size_t)k];
+            if (s.x1 < s.x0) continue;
+            w = Win{std::min(w.x0, s.x0), std::min(w.y0, s.y0), std::max(w.x1, s.x1), std::max(w.y1, s.y1)};
+            most = std::max(most, (unsigned long long)(s.x1 - s.x0 + 1) * (unsigned long long)(s.y1 - s.y0 + 1));
+        }
+        a.step = k;
+        FS_HIP(c, fs_launch_drive_step(a, c->stream));
+        if (w.x1 >= w.x0) {
+            FS_HIP(c, fs_launch_drive_merge(a, (unsigned)((most + 255ull) / 256ull), c->stream));
+            if (paint)
+                FS_HIP(c, fs_launch_keepout_apply(c->d_ko_mask.p, c->d_cells.p, c->nx, c->ny, w.x0, w.y0, w.x1 - w.x0 + 1, w.y1 - w.y0 + 1, nullptr, c->stream));
+            all = Win{std::min(all.x0, w.x0), std::min(all.y0, w.y0), std::max(all.x1, w.x1), std::max(all.y1, w.y1)};
+        }
+        if (dp.stop_when_mapped) FS_HIP(c, fs_launch_drive_goal(a, c->stream));
+    }
+    // from here on: what fs_update_grid_region does, once, for everything the drive can have touched
+    if (c->have_cls && all.x1 >= all.x0) {
+        const int b0[3] = {all.x0 >> 3, all.y0 >> 3, 0};
+        const int nb[3] = {(all.x1 >> 3) - b0[0] + 1, (all.y1 >> 3) - b0[1] + 1, 1};
+        FS_HIP(c, fs_launch_classify_region(c->d_cells.p, c->d_cls.p, c->nx, c->ny, c->nz, c->cls_ranges[0], c->cls_ranges[1], c->cls_ranges[2],
+                                            c->cls_ranges[3], b0, nb, c->stream));
+    }
+    c->have_sparse = false;
+    std::vector<int32_t> back(n_back);
+    unsigned long long counts[2] = {0ull, 0ull};
+    FS_HIP(c, hipMemcpyAsync(back.data(), d + o_state, n_back * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipMemcpyAsync(counts, c->d_sense_counts.p, sizeof counts, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));                  // (the one wait of the call)
+    c->sense_mark_clean = true;
+    ++c->epoch;
+    for (size_t r = 0; r < R; ++r) {
+        const int32_t st = back[2 * r];
+        status[r] = st == FS_DRIVE_DRIVING ? FS_DRIVE_ARRIVED : st;           // still driving after the last step: out of stations
+        reached[r] = back[2 * r + 1];
+    }
+    const int32_t *ub = back.data() + (o_union - o_state);
+    std::copy(back.begin() + (std::ptrdiff_t)(o_status - o_state), back.begin() + (std::ptrdiff_t)(o_seen - o_state), station_status);
+    std::copy(back.begin() + (std::ptrdiff_t)(o_seen - o_state), back.end(), seen_unknown);
+    if (n_seen) *n_seen = (int64_t)counts[0];
+    if (n_revealed) *n_revealed = (int64_t)counts[1];
+    if (window && ub[2] >= ub[0]) { window[0] = ub[0]; window[1] = ub[1]; window[2] = 0; window[3] = ub[2] - ub[0] + 1; window[4] = ub[3] - ub[1] + 1; window[5] = 1; }
     return FS_OK;
 }
 

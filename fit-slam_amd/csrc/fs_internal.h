@@ -755,6 +755,37 @@ hipError_t fs_launch_goals_mapped(const uint8_t *d_cells, int nx, int ny, double
 // d_counts [4] += cells != 255, == 255, == 254, == 0
 hipError_t fs_launch_grid_census(const uint8_t *d_cells, size_t total, unsigned long long *d_counts, hipStream_t s);
 
+// ---- driving station lists through the world (fs_drive; fs_drive.hip)
+// One step k of all robots is three or four launches on one stream, none of which waits for anything but its predecessor:
+//   step   — one wavefront per robot still FS_DRIVE_DRIVING: out of stations -> ARRIVED; k >= 1: the move station k - 1 -> k on the
+//            staged map and the world (OFF_MAP / BLOCKED / COLLIDED, else reached = k); then the sweep from station k as
+//            fs_sense_kernel does it, the seen cells' box into station_box [station][4] = min x, y, max x, y (preset nx, ny, -1, -1)
+//            and into union_box [4]
+//   merge  — blockIdx.y = robot, over that robot's box of this step: as fs_sense_merge_kernel; a cell in several robots' boxes
+//            belongs to the lowest robot whose box holds it
+//   (fs_launch_keepout_apply over the step's window, by the caller, when zones are stored)
+//   goal   — one lane per robot still driving: surroundingCellsMapped of its goal -> MAPPED
+#define FS_DRIVE_DRIVING (-1)      // state[2 r] while robot r drives; the FS_DRIVE_* codes of the header once it has stopped
+struct FsDriveArgs {
+    FsSenseArgs sense;             // the fan and the world as fs_sense fills them; origin = station_xyz [total][3], first_ray [total] or
+                                   // nullptr, status / seen_unknown [total] (preset -1 / 0); n, ray_unknown and box are not used
+    FsGridDev staged;              // the staged grid, for the move
+    int32_t n_robots, step;
+    const int32_t *n_stations;     // [R]
+    const int32_t *station_off;    // [R] first station of each robot
+    const double *goal;            // [R][3]
+    int32_t block_min, block_max;
+    double move_max_length;        // nx + ny: never cuts a segment
+    int32_t *state;                // [R][2] status, reached (preset FS_DRIVE_DRIVING, 0)
+    int32_t *station_box;          // [total][4]
+    int32_t *union_box;            // [4] preset nx, ny, -1, -1
+    unsigned long long *counts;    // [2] += seen, revealed
+};
+hipError_t fs_launch_drive_step(const FsDriveArgs &a, hipStream_t s);
+// merge_blocks: blocks per robot (the caller sizes them by the largest window a robot can touch in this step)
+hipError_t fs_launch_drive_merge(const FsDriveArgs &a, unsigned merge_blocks, hipStream_t s);
+hipError_t fs_launch_drive_goal(const FsDriveArgs &a, hipStream_t s);
+
 // ---- landmark sensor on a ground-truth cloud (fs_sense_landmarks; fs_sense_landmarks.hip)
 // sweep: one wavefront per (pose, group of chunks) of the WORLD cloud; a landmark a pose sees gets views[world index] += 1, the
 // pose n_in_view[pose] += 1 (both zero-based sums: the caller clears n_in_view, views carry on from earlier calls).

@@ -971,6 +971,57 @@ int fs_goals_mapped(fs_ctx *ctx, int32_t n, const double *goal_xyz /* [n][3] */,
  * (!= 255; OccupancyGrid -1 corresponds to 255), unknown (== 255), lethal (== 254), free (== 0). */
 int fs_grid_census(fs_ctx *ctx, int64_t counts[4] /* known (!= 255), unknown (== 255), lethal (== 254), free (== 0) */);
 
+/* ---------------------------------------------------------------- driving through the world (closed loop)
+ *
+ * THIS PROJECT'S OWN EXTENSION, built on fs_sense.  In the reference the robot is driven by its controller server, its map grows
+ * from the depth camera while it drives, and CheckIfGoalMapped ends a goal in mid-drive; none of that is in the vendored tree.
+ * Here n_robots robots drive their lists of STATIONS (poses cut from a planned path) through the world, sensing at every station
+ * and stopping on their own, with every decision taken on the device: one call, one wait, however many stations.
+ *
+ * Robot r has n_stations[r] >= 1 stations, station_xyz holds the robots' lists back to back, first_ray (may be NULL) one entry
+ * per station with fs_sense's meaning and validation.  Steps k = 0 .. max n_stations - 1; all robots still driving move in
+ * lockstep, and every step's moves see the staged map as step k - 1 of ALL robots left it:
+ *   1 move (k >= 1)  a robot without a station k stops, FS_DRIVE_ARRIVED.  Otherwise the segment station k - 1 -> station k is
+ *                    walked as fs_trace_segments walks it, uncapped (max_length_cells = nx + ny), and in this order: a
+ *                    worldToMap failure stops the robot FS_DRIVE_OFF_MAP; any visited STAGED cost in [block_min, block_max]
+ *                    (stored keep-out zones are painted there) FS_DRIVE_BLOCKED; otherwise any visited WORLD cost in that range
+ *                    FS_DRIVE_COLLIDED — it drove into something it had not seen; otherwise reached[r] = k.  A stopped robot
+ *                    stays at station reached[r] and does nothing more.
+ *   2 sense          the robots still driving sweep from their station k exactly as ONE fs_sense call over those poses would
+ *                    (counts against the staged map before this step's merge): station_status = FS_STATUS_OK / FS_STATUS_OFF_MAP,
+ *                    seen_unknown as fs_sense's.  A station that sees nothing does not stop the robot.
+ *   3 merge          as fs_sense: staged = world on the cells seen in this step, stored keep-out zones painted again.
+ *   4 goal           with stop_when_mapped, a robot whose goal fs_goals_mapped now calls mapped stops, FS_DRIVE_MAPPED.
+ * A robot still driving after the last step has run out of stations: FS_DRIVE_ARRIVED.
+ * status, reached [n_robots]; station_status, seen_unknown one entry per station: -1 and 0 for a station never reached (station
+ * 0 always is).  *n_seen = the sum over the steps of the step's distinct seen cells, *n_revealed likewise — both equal the sums of
+ * the equivalent fs_sense calls; window = the bounding box of everything seen (sizes 0: nothing).  These three may be NULL.
+ * Every figure is an integer sum, minimum or maximum and depends neither on the order of the robots nor on the device's.
+ * At the end the context does once what fs_update_grid_region does, for a window that holds everything the drive touched.
+ * Decided before anything is written: no grid, no world, no ray parameters (and no sensor): FS_E_STATE; nz > 1, a first_ray
+ * outside [-1, n_yaw - window], n_stations[r] < 1 or > FS_DRIVE_MAX_STATIONS, n_robots > FS_DRIVE_MAX_ROBOTS: FS_E_INVALID.
+ * n_robots == 0: a no-op.  params == NULL: block 253..254 (isConnectable's visitor), stop_when_mapped 1.  Landmarks are not
+ * sensed on the way: run fs_sense_landmarks on the reached stations afterwards. */
+#define FS_DRIVE_ARRIVED  0   /* out of stations */
+#define FS_DRIVE_BLOCKED  1   /* the staged map shows something in the block range on the next segment */
+#define FS_DRIVE_COLLIDED 2   /* only the world does */
+#define FS_DRIVE_OFF_MAP  3   /* an end of the next segment is off the map */
+#define FS_DRIVE_MAPPED   4   /* the goal is mapped (stop_when_mapped) */
+#define FS_DRIVE_MAX_STATIONS 2048
+#define FS_DRIVE_MAX_ROBOTS   4096
+
+typedef struct fs_drive_params {
+    int32_t block_min, block_max;  /* the costs that stop a move */
+    int32_t stop_when_mapped;
+} fs_drive_params;
+
+int fs_drive(fs_ctx *ctx, int32_t n_robots, const double *station_xyz /* [sum n_stations][3] */, const int32_t *n_stations /* [n_robots] */,
+             const int32_t *first_ray /* [sum n_stations] or NULL */, const double *goal_xyz /* [n_robots][3] */,
+             const fs_ray_params *sensor /* NULL: the context's ray parameters */, const fs_drive_params *params /* NULL: the defaults */,
+             int32_t *status /* [n_robots] */, int32_t *reached /* [n_robots] */, int32_t *station_status /* [sum n_stations] */,
+             int32_t *seen_unknown /* [sum n_stations] */, int64_t *n_seen, int64_t *n_revealed,
+             int32_t window[6] /* x0 y0 z0 sx sy sz, may be NULL */);
+
 /* ---------------------------------------------------------------- landmark sensor on a ground-truth cloud (closed loop)
  *
  * THIS PROJECT'S OWN EXTENSION, the other half of fs_sense.  In the reference the map points behind every Fisher-information

@@ -489,23 +489,33 @@ class FrontierScorer:
     def set_frontier_seed_order(self, order: str):
         """The seeds of search_frontiers without seeds and of get_frontier_costs_searched (fs_set_frontier_seed_order):
         "nearest" (a fresh context's) or "reference" (the reference's outer search decides seeds and list order)."""
-        if order not in SEED_ORDERS:
-            raise FsError(FS_E_INVALID, f"unknown frontier seed order {order!r} (nearest | reference)")
-        self._check(self._L.fs_set_frontier_seed_order(self._h, SEED_ORDERS[order]))
-        self._seed_order = order
+        self._set_mode("_seed_order", order)
+
+    # the context's named modes, by the attribute that remembers the setting: (names, C setter, what an error calls it)
+    _MODES = {"_seed_order": (SEED_ORDERS, "fs_set_frontier_seed_order", "frontier seed order"),
+              "_grid_search": (GRID_SEARCHES, "fs_set_grid_search", "grid search"),
+              "_roadmap_search": (ROADMAP_SEARCHES, "fs_set_roadmap_search", "roadmap search"),
+              "_refine_search": (REFINE_SEARCHES, "fs_set_refine_search", "refine search")}
+
+    def _set_mode(self, attr, name):
+        names, setter, what = self._MODES[attr]
+        if name not in names:
+            raise FsError(FS_E_INVALID, f"unknown {what} {name!r} ({' | '.join(names)})")
+        self._check(getattr(self._L, setter)(self._h, names[name]))
+        setattr(self, attr, name)
 
     @contextlib.contextmanager
-    def _seed_order_for_call(self, order):
-        """seed_order= of one call: set for the call, the context's own setting restored afterwards"""
-        if order is None:
+    def _mode_for_call(self, attr, name):
+        """seed_order= / search= of one call: set for the call, the context's own setting restored afterwards"""
+        if name is None:
             yield
             return
-        prev = self._seed_order
-        self.set_frontier_seed_order(order)
+        prev = getattr(self, attr)
+        self._set_mode(attr, name)
         try:
             yield
         finally:
-            self.set_frontier_seed_order(prev)
+            self._set_mode(attr, prev)
 
     def search_frontiers(self, robot_xy, lethal_threshold=160, max_frontier_distance=50.0, min_frontier_cluster_size=1,
                          max_frontier_cluster_size=20, seeds=None, max_records=None, want_every=True, seed_order=None):
@@ -514,7 +524,7 @@ class FrontierScorer:
         (set_frontier_seed_order; seed_order= "nearest" / "reference" for this call only); else the cells (y * nx + x) that start
         one buildNewFrontier each, in order.  max_records None: every record (the buffers grow to what the search reports, at most
         the grid's cell count); else at most that many (last_search_counts has the full counts)."""
-        with self._seed_order_for_call(seed_order):
+        with self._mode_for_call("_seed_order", seed_order):
             return self._search_frontiers(robot_xy, lethal_threshold, max_frontier_distance, min_frontier_cluster_size,
                                           max_frontier_cluster_size, seeds, max_records, want_every)
 
@@ -548,7 +558,7 @@ class FrontierScorer:
         get_frontier_costs_planned returns).  blacklist_xy [k][2]: goal points to mark blacklisted (exact equality).
         max_records None: as many as the search finds (a longer list than the first round holds is searched again with exact
         sizes); else more records than that raise FsError.  seed_order: as search_frontiers'."""
-        with self._seed_order_for_call(seed_order):
+        with self._mode_for_call("_seed_order", seed_order):
             return self._get_frontier_costs_searched(robot_pose7, lethal_threshold, max_frontier_distance, min_frontier_cluster_size,
                                                      max_frontier_cluster_size, blacklist_xy, allow_unknown, with_fim, alpha, beta,
                                                      max_vx, max_wz, max_records)
@@ -591,7 +601,7 @@ class FrontierScorer:
         cap = min(nx * ny, self.SEARCH_FIRST_RECORDS) if max_records is None else int(max_records)
         pose = (C.c_double * 7)(*[float(v) for v in np.asarray(robot_pose7, dtype=np.float64).reshape(7)])
         bl = None if blacklist_xy is None else np.ascontiguousarray(np.asarray(blacklist_xy, dtype=np.float64).reshape(-1, 2))
-        with self._seed_order_for_call(seed_order), self._roadmap_search_for_call(search):
+        with self._mode_for_call("_seed_order", seed_order), self._mode_for_call("_roadmap_search", search):
             while True:
                 fr = np.zeros(max(cap, 0), dtype=FRONTIER_RECORD_DTYPE)
                 rec = np.zeros(max(cap, 0), dtype=RECORD_DTYPE)
@@ -974,23 +984,7 @@ class FrontierScorer:
         """How plan_paths, plan_paths_information, get_frontier_costs_planned and get_frontier_costs_searched plan on the grid
         (fs_set_grid_search): "converged" (a fresh context's: one converged field per robot cell) or "reference" (the reference's
         per-frontier A* wave, one per distinct goal cell, bit for bit)."""
-        if name not in GRID_SEARCHES:
-            raise FsError(FS_E_INVALID, f"unknown grid search {name!r} (converged | reference)")
-        self._check(self._L.fs_set_grid_search(self._h, GRID_SEARCHES[name]))
-        self._grid_search = name
-
-    @contextlib.contextmanager
-    def _grid_search_for_call(self, name):
-        """search= of one call: set for the call, the context's own setting restored afterwards"""
-        if name is None:
-            yield
-            return
-        prev = self._grid_search
-        self.set_grid_search(name)
-        try:
-            yield
-        finally:
-            self.set_grid_search(prev)
+        self._set_mode("_grid_search", name)
 
     def navfn_wave_potential(self, robot_pose7, goal_xyz, allow_unknown=False):
         """(field, limit): the field of ONE wave of the "reference" grid search, float32 [ny][nx] — the reference's potarr after
@@ -1021,7 +1015,7 @@ class FrontierScorer:
             raise ValueError(f"achievable_in has {ai.shape[0]} entries for {n} goals")
         pl, plm, ph = np.zeros(n), np.zeros(n), np.zeros(n)
         ach = np.zeros(n, dtype=np.uint8)
-        with self._grid_search_for_call(search):
+        with self._mode_for_call("_grid_search", search):
             self._check(self._L.fs_plan_paths(self._h, C.byref(pose), 1 if allow_unknown else 0, n, _p(goal), _p(ai), _p(pl), _p(plm), _p(ph), _p(ach)))
         return dict(path_length=pl, path_length_m=plm, path_heading=ph, achievable=ach)
 
@@ -1051,7 +1045,7 @@ class FrontierScorer:
             return self._L.fs_plan_paths_information(self._h, C.byref(pose), 1 if allow_unknown else 0, n, _p(goal), _p(ai), C.byref(prm),
                                                      _p(pl), _p(plm), _p(ph), _p(ach), _p(nwp), _p(mean), _p(mn), _p(unsafe), room,
                                                      total, _p(off), _p(poses), _p(info))
-        with self._grid_search_for_call(search):
+        with self._mode_for_call("_grid_search", search):
             return self._plan_paths_information_call(call, out, n, want_waypoints)
 
     def _plan_paths_information_call(self, call, out, n, want_waypoints):
@@ -1096,7 +1090,7 @@ class FrontierScorer:
         bl = None if blacklisted is None else np.ascontiguousarray(blacklisted, dtype=np.uint8)
         rec = np.zeros(n, dtype=RECORD_DTYPE)
         cost = np.zeros(n); au = np.zeros(n); du = np.zeros(n); order = np.zeros(n, dtype=np.int32); plm = np.zeros(n)
-        with self._grid_search_for_call(search):
+        with self._mode_for_call("_grid_search", search):
             self._check(self._L.fs_get_frontier_costs_planned(self._h, C.byref(pose), 1 if allow_unknown else 0, n, _p(goal), _p(fs), _p(bl),
                                                               alpha, beta, max_vx, max_wz, 1 if with_fim else 0, _p(rec), _p(cost), _p(au), _p(du),
                                                               _p(order), _p(plm)))
@@ -1171,23 +1165,7 @@ class FrontierScorer:
         """How roadmap_plan, get_frontier_costs_roadmap and roadmap_next_goal's pair lengths search the roadmap
         (fs_set_roadmap_search): "tree" (a fresh context's: one shortest-path tree per start node) or "reference" (the reference's
         per-goal A*, bit for bit)."""
-        if name not in ROADMAP_SEARCHES:
-            raise FsError(FS_E_INVALID, f"unknown roadmap search {name!r} (tree | reference)")
-        self._check(self._L.fs_set_roadmap_search(self._h, ROADMAP_SEARCHES[name]))
-        self._roadmap_search = name
-
-    @contextlib.contextmanager
-    def _roadmap_search_for_call(self, name):
-        """search= of one call: set for the call, the context's own setting restored afterwards"""
-        if name is None:
-            yield
-            return
-        prev = self._roadmap_search
-        self.set_roadmap_search(name)
-        try:
-            yield
-        finally:
-            self.set_roadmap_search(prev)
+        self._set_mode("_roadmap_search", name)
 
     def roadmap_plan(self, robot_pose7, goal_xyz, achievable_in=None, search=None):
         """setPlanForFrontierRoadmap for every goal, by the context's roadmap search (set_roadmap_search; search= "tree" /
@@ -1201,7 +1179,7 @@ class FrontierScorer:
             raise ValueError(f"achievable_in has {ai.shape[0]} entries for {n} goals")
         pl, plm, ph = np.zeros(n), np.zeros(n), np.zeros(n)
         ach = np.zeros(n, dtype=np.uint8)
-        with self._roadmap_search_for_call(search):
+        with self._mode_for_call("_roadmap_search", search):
             self._check(self._L.fs_roadmap_plan(self._h, C.byref(pose), n, _p(goal), _p(ai), _p(pl), _p(plm), _p(ph), _p(ach)))
         return dict(path_length=pl, path_length_m=plm, path_heading=ph, achievable=ach)
 
@@ -1225,7 +1203,7 @@ class FrontierScorer:
         n_routes, total, total_ref = C.c_int32(), C.c_int64(), C.c_int64()
         dump = want_nodes or want_legs
         room_r, room_n = max(n, 1), (64 * n + 64) if dump else 0
-        with self._roadmap_search_for_call(search):
+        with self._mode_for_call("_roadmap_search", search):
             for _ in range(2):
                 gn, nl = np.zeros(room_r, dtype=np.int32), np.zeros(room_r, dtype=np.int32)
                 comp = np.zeros(room_r, dtype=np.uint8)
@@ -1272,7 +1250,7 @@ class FrontierScorer:
         bl = None if blacklisted is None else np.ascontiguousarray(blacklisted, dtype=np.uint8)
         rec = np.zeros(n, dtype=RECORD_DTYPE)
         cost = np.zeros(n); au = np.zeros(n); du = np.zeros(n); order = np.zeros(n, dtype=np.int32); plm = np.zeros(n)
-        with self._roadmap_search_for_call(search):
+        with self._mode_for_call("_roadmap_search", search):
             self._check(self._L.fs_get_frontier_costs_roadmap(self._h, C.byref(pose), n, _p(goal), _p(fs), _p(bl), alpha, beta, max_vx,
                                                               max_wz, 1 if with_fim else 0, _p(rec), _p(cost), _p(au), _p(du), _p(order),
                                                               _p(plm)))
@@ -1335,7 +1313,7 @@ class FrontierScorer:
         cost = np.zeros((R, n)) if want_matrix else None
         plm = np.zeros((R, n)) if want_matrix else None
         ach = np.zeros((R, n), dtype=np.uint8) if want_matrix else None
-        with self._roadmap_search_for_call(search):
+        with self._mode_for_call("_roadmap_search", search):
             self._check(self._L.fs_fleet_allocate_roadmap(self._h, R, _p(poses), n, _p(goal), _p(fs), _p(bl), alpha, beta, max_vx, max_wz,
                                                           ALLOC_METHODS[method], _p(assignment), C.byref(total), _p(assigned), _p(rec),
                                                           _p(cost), _p(plm), _p(ach)))
@@ -1373,7 +1351,7 @@ class FrontierScorer:
         tour = np.zeros(max(nl, 0) + 1, dtype=np.int32)
         sel = np.zeros(n, dtype=np.uint8)
         mat = np.zeros(room * room) if want_matrix else None
-        with self._roadmap_search_for_call(search):
+        with self._mode_for_call("_roadmap_search", search):
             self._check(self._L.fs_roadmap_next_goal(self._h, C.byref(pose), n, _p(goal), _p(plm), _p(ach), _p(bl), circ.shape[0],
                                                      _p(circ) if circ.shape[0] else None, nl, float(local_radius), _p(fi),
                                                      float(fi_threshold), C.byref(nxt), C.byref(st), _p(tour), C.byref(tsz), C.byref(tl),
@@ -1392,23 +1370,7 @@ class FrontierScorer:
         """How refine_paths and refine_tour plan a leg (fs_set_refine_search): "field" (a fresh context's: a converged cost field per
         start cell, a descent, Theta*'s parent rule along it) or "reference" (the reference's own Theta* search, one wavefront per
         distinct leg: its status — 5 also where its loop drops the entry popped last —, vertices and poses bit for bit)."""
-        if name not in REFINE_SEARCHES:
-            raise FsError(FS_E_INVALID, f"unknown refine search {name!r} (field | reference)")
-        self._check(self._L.fs_set_refine_search(self._h, REFINE_SEARCHES[name]))
-        self._refine_search = name
-
-    @contextlib.contextmanager
-    def _refine_search_for_call(self, name):
-        """search= of one call: set for the call, the context's own setting restored afterwards"""
-        if name is None:
-            yield
-            return
-        prev = self._refine_search
-        self.set_refine_search(name)
-        try:
-            yield
-        finally:
-            self.set_refine_search(prev)
+        self._set_mode("_refine_search", name)
 
     def refine_paths(self, starts, goals, allow_unknown=True, w_euc=1.0, w_traversal=2.0, corners=8, search=None):
         """computePathBetweenPointsThetaStar for every leg starts[i] -> goals[i] ([n][2] world; extra columns ignored), by the
@@ -1427,7 +1389,7 @@ class FrontierScorer:
         st = np.zeros(n, dtype=np.int32); cost = np.zeros(n)
         nv = np.zeros(n, dtype=np.int32); npz = np.zeros(n, dtype=np.int32)
         args = (1 if allow_unknown else 0, float(w_euc), float(w_traversal), int(corners))
-        with self._refine_search_for_call(search):
+        with self._mode_for_call("_refine_search", search):
             # size first (the fields are cached, so the second call only repeats the legs; "reference" searches twice)
             self._check(self._L.fs_refine_paths(self._h, n, _p(s), _p(g), *args, _p(st), _p(cost), _p(nv), None, _p(npz), None))
             vert = np.zeros((int(nv.sum()), 2)); pose = np.zeros((int(npz.sum()), 2))

@@ -742,11 +742,18 @@ bool grid_world_to_map(const fs_ctx *c, double wx, double wy, int32_t &mx, int32
     return true;
 }
 
-// The device bound, a grid staged and that grid 2-D: what every planner stage needs (`what` names the stage in the error)
-int grid2d_check(fs_ctx *c, const char *what)
+// The device bound and a grid staged: what every call on the staged map needs first
+int grid_check(fs_ctx *c)
 {
     FS_HIP(c, hipSetDevice(c->device));
     if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    return FS_OK;
+}
+
+// ... and that grid 2-D: what every planner stage needs (`what` names the stage in the error)
+int grid2d_check(fs_ctx *c, const char *what)
+{
+    if (const int rc = grid_check(c)) return rc;
     if (c->nz != 1) return fail(c, FS_E_INVALID, "%s is defined on a 2-D costmap (nz == 1)", what);
     return FS_OK;
 }
@@ -970,6 +977,38 @@ void pose_to_rt(const double pose7[7], float Rt[12])
     Rt[9] = (float)pose7[0]; Rt[10] = (float)pose7[1]; Rt[11] = (float)pose7[2];
 }
 
+// The poses of a visibility call: pose7[n] into Rt[n][12].  False when a quaternion is off unit norm: chunk culling reasons in
+// world space and needs R orthonormal, so such a call (the reference would feed the quaternion to Eigen unnormalised) takes
+// the brute-force scan.
+bool poses_to_rt(const double *pose7, int32_t n, float *Rt)
+{
+    bool unit = true;
+    for (int32_t i = 0; i < n; ++i) {
+        const double *q = pose7 + 7 * (size_t)i + 3;
+        const double nq = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+        if (!(std::fabs(nq - 1.0) <= 1.0e-4)) unit = false;
+        pose_to_rt(pose7 + 7 * (size_t)i, Rt + 12 * (size_t)i);
+    }
+    return unit;
+}
+
+// Cells at the far end of a line-of-sight walk that are not tested, M = 1 + (unsigned)(margin / resolution); a walk has fewer than
+// 2^31 visits, so a larger quotient tests nothing either way
+uint32_t occlusion_margin(const fs_ctx *c, double end_margin_m)
+{
+    const double q = end_margin_m / c->res;
+    return 1u + (q < 2147483647.0 ? (uint32_t)q : 2147483647u);
+}
+
+// Landmark chunks per wave of a visibility scan over `items` poses: a single pose is the reference's real call, so fewer chunks
+// per wave until the launch fills the chip's wave slots
+int32_t chunks_per_wave(int64_t items, int32_t n_chunks)
+{
+    int32_t group = 64;
+    while (group > 4 && items * ((n_chunks + group - 1) / group) < 2048) group >>= 1;
+    return group;
+}
+
 // Which image of the grid the arrival fan walks.  The class walk spends ~1.3x the instructions per step and touches 4-8x fewer
 // cache lines (L2 -> L1 fill 4.4 GB -> 0.5 GB per C3 launch).  Measured (profiles/r03/ray_class_walk.json): on 3-D grids it wins
 // at every ray length (C3: 0.190 against 0.229 ms at 40 cells, 0.63 against 1.12 ms at 160); on a 2-D costmap a short fan lives
@@ -995,6 +1034,15 @@ FsGridDev grid_dev(const fs_ctx *c)
     const uint32_t bx = (uint32_t)(c->nx + 7) >> 3, by = (uint32_t)(c->ny + 7) >> 3, bz = (uint32_t)(c->nz + 7) >> 3;
     return FsGridDev{c->d_cells.p, c->nx, c->ny, c->nz, c->origin[0], c->origin[1], c->origin[2], c->res, c->d_counters.p + 29,
                      c->have_cls ? c->d_cls.p : nullptr, {512u - 8u, 512u * bx - 64u, 512u * bx * by - 512u}, 512u * bx * by * bz, nullptr};
+}
+
+// the ground-truth world, which is of the staged grid's shape and has no class image
+FsGridDev world_dev(const fs_ctx *c)
+{
+    FsGridDev w = grid_dev(c);
+    w.cells = c->d_world.p;
+    w.cls = nullptr;
+    return w;
 }
 
 // every upload path ends here: images derived from the grid are cut again on next use
@@ -1321,9 +1369,62 @@ int ko_after_snapshot(fs_ctx *c, int32_t nx, int32_t ny, int32_t nz, const doubl
     return FS_OK;
 }
 
-// fs_sense's and fs_drive's fan: `sensor`'s (validated and built by the same host code as fs_set_ray_params'; the table goes to the
-// device only when it is not the one already there) or, sensor == NULL, the context's
-int sense_fan_setup(fs_ctx *c, const fs_ray_params *sensor, FsSenseArgs &a)
+// The two steps of every route that writes cells of the staged map (last paragraph), enqueued after the write.  First the
+// keep-out layer, which runs last in the cycle: the stored zones are painted again over the window that changed.
+int ko_repaint_window(fs_ctx *c, int32_t x0, int32_t y0, int32_t sx, int32_t sy)
+{
+    if (!c->ko_zones.empty() && c->ko_mask_valid)
+        FS_HIP(c, fs_launch_keepout_apply(c->d_ko_mask.p, c->d_cells.p, c->nx, c->ny, x0, y0, sx, sy, nullptr, c->stream));
+    return FS_OK;
+}
+
+// Then the images cut from the cells: the class image is cut again for the bricks the box touches (none for an empty box; a
+// whole-map re-cut is a streaming pass over the grid — 1 GiB on C5 — for a box of a few thousand cells), the sparse image is dropped.
+int cells_changed_in_box(fs_ctx *c, int32_t x0, int32_t y0, int32_t z0, int32_t sx, int32_t sy, int32_t sz)
+{
+    if (c->have_cls && sx > 0 && sy > 0 && sz > 0) {
+        const int b0[3] = {x0 >> 3, y0 >> 3, z0 >> 3};
+        const int nb[3] = {((x0 + sx - 1) >> 3) - b0[0] + 1, ((y0 + sy - 1) >> 3) - b0[1] + 1, ((z0 + sz - 1) >> 3) - b0[2] + 1};
+        FS_HIP(c, fs_launch_classify_region(c->d_cells.p, c->d_cls.p, c->nx, c->ny, c->nz, c->cls_ranges[0], c->cls_ranges[1], c->cls_ranges[2],
+                                            c->cls_ranges[3], b0, nb, c->stream));
+    }
+    c->have_sparse = false;
+    return FS_OK;
+}
+
+// The window of fs_update_grid_region and fs_read_grid_region on the staged grid: refused, empty (nothing to move), or whole with
+// the strides' defaults filled in
+int window_check(fs_ctx *c, int32_t x0, int32_t y0, int32_t z0, int32_t sx, int32_t sy, int32_t sz, const uint8_t *cells,
+                 int64_t &row_stride, int64_t &slice_stride, bool &empty)
+{
+    empty = true;
+    if (sx < 0 || sy < 0 || sz < 0) return fail(c, FS_E_INVALID, "negative window size");
+    if (x0 < 0 || y0 < 0 || z0 < 0 || (int64_t)x0 + sx > c->nx || (int64_t)y0 + sy > c->ny || (int64_t)z0 + sz > c->nz)
+        return fail(c, FS_E_INVALID, "window [%d,%lld) x [%d,%lld) x [%d,%lld) leaves the %d x %d x %d grid", x0, (long long)x0 + sx, y0, (long long)y0 + sy,
+                    z0, (long long)z0 + sz, c->nx, c->ny, c->nz);
+    if (sx == 0 || sy == 0 || sz == 0) return FS_OK;
+    if (!cells) return FS_E_INVALID;
+    if (row_stride == 0) row_stride = sx;
+    if (slice_stride == 0) slice_stride = row_stride * (int64_t)sy;
+    if (row_stride < sx || slice_stride < row_stride * (int64_t)(sy - 1) + sx) return fail(c, FS_E_INVALID, "window strides smaller than the window");
+    empty = false;
+    return FS_OK;
+}
+
+// fs_sense's and fs_drive's prologue in three steps; a caller's own checks stand between them.  What a sweep needs staged:
+int sweep_state_check(fs_ctx *c, const fs_ray_params *sensor)
+{
+    if (const int rc = grid_check(c)) return rc;
+    if (!c->have_world) return fail(c, FS_E_STATE, "fs_upload_world has not been called");
+    if (!sensor && !c->have_ray) return fail(c, FS_E_STATE, "fs_set_ray_params has not been called and no sensor is given");
+    return FS_OK;
+}
+
+// The sweep's fan: `sensor`'s (validated and built by the same host code as fs_set_ray_params'; the table goes to the device only
+// when it is not the one already there) or, sensor == NULL, the context's.  Every one of the n_first first_ray lies inside it,
+// and the outputs are those of a sweep that reveals nothing.
+int sweep_fan_setup(fs_ctx *c, const fs_ray_params *sensor, const int32_t *first_ray, size_t n_first, FsSenseArgs &a, int64_t *n_seen,
+                    int64_t *n_revealed, int32_t window[6])
 {
     if (sensor) {
         std::vector<double> dir;
@@ -1343,26 +1444,29 @@ int sense_fan_setup(fs_ctx *c, const fs_ray_params *sensor, FsSenseArgs &a)
         a.dir = c->d_dir.p;
         a.n_yaw = c->n_yaw; a.n_elev = c->n_elev; a.window = c->window;
     }
+    if (first_ray)
+        for (size_t i = 0; i < n_first; ++i)
+            if (first_ray[i] < -1 || first_ray[i] > a.n_yaw - a.window)
+                return fail(c, FS_E_INVALID, "first_ray[%zu] = %d is outside [-1, %d]", i, first_ray[i], a.n_yaw - a.window);
+    if (n_seen) *n_seen = 0;
+    if (n_revealed) *n_revealed = 0;
+    if (window) std::fill(window, window + 6, 0);
     return FS_OK;
 }
 
-// the world, the staged grid, the walk's cap, the visitor's ranges and the clamp bounds of a sweep with ray parameters p
-void sense_world_setup(const fs_ctx *c, const fs_ray_params &p, FsSenseArgs &a)
+// For a sweep that has poses: the world, the staged grid, the walk's cap, the visitor's ranges and the clamp bounds of its ray
+// parameters, then the mark image
+int sweep_world_setup(fs_ctx *c, const fs_ray_params *sensor, FsSenseArgs &a)
 {
-    a.world = grid_dev(c);
-    a.world.cells = c->d_world.p;
-    a.world.cls = nullptr;
+    const fs_ray_params &p = sensor ? *sensor : c->rp;
+    a.world = world_dev(c);
     a.staged = c->d_cells.p;
     a.max_length = (unsigned int)(p.max_camera_depth / c->res);             // CostCalculator.cpp:28
     a.obst_min = p.obst_min; a.obst_max = p.obst_max; a.trace_min = p.trace_min; a.trace_max = p.trace_max;
     double b[6];
     ray_clamp_bounds(c, p, b);
     a.lo_x = b[0]; a.hi_x = b[1]; a.lo_y = b[2]; a.hi_y = b[3]; a.lo_z = b[4]; a.hi_z = b[5];
-}
-
-// the mark image: allocated and zeroed once per grid shape, all zero again after every merge
-int sense_mark_ready(fs_ctx *c)
-{
+    // the mark image: allocated and zeroed once per grid shape, all zero again after every merge
     const size_t total = (size_t)c->nx * (size_t)c->ny * (size_t)c->nz;
     const bool grown = c->d_sense_mark.cap < total;
     FS_HIP(c, c->d_sense_mark.ensure(total));
@@ -1378,6 +1482,41 @@ void drop_world(fs_ctx *c)
     c->d_sense_mark.release();
     c->have_world = false;
     c->sense_mark_clean = false;
+}
+
+// A snapshot's geometry (fs_upload_grid, fs_upload_grid_bricks), checked in two parts: the brick route's own check stands between
+int snapshot_geometry_check(fs_ctx *c, int32_t nx, int32_t ny, int32_t nz, const double origin_xyz[3], double resolution)
+{
+    if (nx <= 0 || ny <= 0 || nz <= 0 || !(resolution > 0.0) || !std::isfinite(resolution)) return fail(c, FS_E_INVALID, "bad grid shape or resolution");
+    // (worldToMap with a NaN origin is a float-to-integer conversion of NaN: undefined in the reference, refused here)
+    if (!std::isfinite(origin_xyz[0]) || !std::isfinite(origin_xyz[1]) || !std::isfinite(origin_xyz[2])) return fail(c, FS_E_INVALID, "grid origin must be finite");
+    return FS_OK;
+}
+
+int snapshot_size_check(fs_ctx *c, int32_t nx, int32_t ny, int32_t nz, uint64_t &total)
+{
+    total = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
+    // (cell offsets are 32-bit unsigned in the walks, one z step is a signed 32-bit stride; everything else indexes in 64 bits)
+    if (total >= (1ull << 32) || (uint64_t)nx * (uint64_t)ny >= (1ull << 31)) return fail(c, FS_E_INVALID, "dense grids are limited to 2^32 cells (and 2^31 per z slice)");
+    return FS_OK;
+}
+
+// ... and its tail, the new cells on their way into d_cells: the keep-out layer's cycle, the derived images, the wait, then the
+// context describes the new map
+int snapshot_done(fs_ctx *c, int32_t nx, int32_t ny, int32_t nz, const double origin_xyz[3], double resolution)
+{
+    if (!c->ko_zones.empty())
+        if (const int rc = ko_after_snapshot(c, nx, ny, nz, origin_xyz, resolution)) return rc;
+    if (const int rc = retile_grid(c, nx, ny, nz)) return rc;
+    FS_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->have_world && (nx != c->nx || ny != c->ny || nz != c->nz)) drop_world(c);   // (the world is of the staged grid's shape)
+    c->nx = nx; c->ny = ny; c->nz = nz;
+    c->origin[0] = origin_xyz[0]; c->origin[1] = origin_xyz[1]; c->origin[2] = origin_xyz[2];
+    c->res = resolution;
+    c->have_grid = true;
+    c->max_gt = 0.0; c->min_gt = 0.0;
+    ++c->epoch;
+    return FS_OK;
 }
 
 }  // namespace
@@ -1536,52 +1675,25 @@ int fs_upload_grid(fs_ctx *c, const uint8_t *cells, int32_t nx, int32_t ny, int3
 {
     if (!c || !cells || !origin_xyz) return FS_E_INVALID;
     FS_HIP(c, hipSetDevice(c->device));
-    if (nx <= 0 || ny <= 0 || nz <= 0 || !(resolution > 0.0) || !std::isfinite(resolution)) return fail(c, FS_E_INVALID, "bad grid shape or resolution");
-    // (worldToMap with a NaN origin is a float-to-integer conversion of NaN: undefined in the reference, refused here)
-    if (!std::isfinite(origin_xyz[0]) || !std::isfinite(origin_xyz[1]) || !std::isfinite(origin_xyz[2])) return fail(c, FS_E_INVALID, "grid origin must be finite");
-    const uint64_t total = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
-    // (cell offsets are 32-bit unsigned in the walks, one z step is a signed 32-bit stride; everything else indexes in 64 bits)
-    if (total >= (1ull << 32) || (uint64_t)nx * (uint64_t)ny >= (1ull << 31)) return fail(c, FS_E_INVALID, "dense grids are limited to 2^32 cells (and 2^31 per z slice)");
+    if (const int rc = snapshot_geometry_check(c, nx, ny, nz, origin_xyz, resolution)) return rc;
+    uint64_t total = 0;
+    if (const int rc = snapshot_size_check(c, nx, ny, nz, total)) return rc;
     ++c->grid_gen;
     FS_HIP(c, c->d_cells.ensure((size_t)total));
     FS_HIP(c, hipMemcpyAsync(c->d_cells.p, cells, (size_t)total, hipMemcpyHostToDevice, c->stream));
-    if (!c->ko_zones.empty()) {
-        const int rc = ko_after_snapshot(c, nx, ny, nz, origin_xyz, resolution);
-        if (rc) return rc;
-    }
-    {
-        const int rc = retile_grid(c, nx, ny, nz);
-        if (rc) return rc;
-    }
-    FS_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->have_world && (nx != c->nx || ny != c->ny || nz != c->nz)) drop_world(c);   // (the world is of the staged grid's shape)
-    c->nx = nx; c->ny = ny; c->nz = nz;
-    c->origin[0] = origin_xyz[0]; c->origin[1] = origin_xyz[1]; c->origin[2] = origin_xyz[2];
-    c->res = resolution;
-    c->have_grid = true;
-    c->max_gt = 0.0; c->min_gt = 0.0;
-    ++c->epoch;
-    return FS_OK;
+    return snapshot_done(c, nx, ny, nz, origin_xyz, resolution);
 }
 
 // Layer::updateCosts' window of the master grid (include/fitslam_frontier.h): packed on the host into page-locked memory, one
-// transfer, one scatter into the row-major image, and the class image re-cut for the bricks the window touches (a whole-map
-// re-cut is a streaming pass over the grid — 1 GiB on C5 — for a window of a few thousand cells).
+// transfer, one scatter into the row-major image, then what follows every write of cells (ko_repaint_window, cells_changed_in_box).
 int fs_update_grid_region(fs_ctx *c, int32_t x0, int32_t y0, int32_t z0, int32_t sx, int32_t sy, int32_t sz,
                           const uint8_t *cells, int64_t row_stride, int64_t slice_stride)
 {
     if (!c) return FS_E_INVALID;
-    FS_HIP(c, hipSetDevice(c->device));
-    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
-    if (sx < 0 || sy < 0 || sz < 0) return fail(c, FS_E_INVALID, "negative window size");
-    if (x0 < 0 || y0 < 0 || z0 < 0 || (int64_t)x0 + sx > c->nx || (int64_t)y0 + sy > c->ny || (int64_t)z0 + sz > c->nz)
-        return fail(c, FS_E_INVALID, "window [%d,%lld) x [%d,%lld) x [%d,%lld) leaves the %d x %d x %d grid", x0, (long long)x0 + sx, y0, (long long)y0 + sy,
-                    z0, (long long)z0 + sz, c->nx, c->ny, c->nz);
-    if (sx == 0 || sy == 0 || sz == 0) return FS_OK;
-    if (!cells) return FS_E_INVALID;
-    if (row_stride == 0) row_stride = sx;
-    if (slice_stride == 0) slice_stride = row_stride * (int64_t)sy;
-    if (row_stride < sx || slice_stride < row_stride * (int64_t)(sy - 1) + sx) return fail(c, FS_E_INVALID, "window strides smaller than the window");
+    if (const int rc = grid_check(c)) return rc;
+    bool empty = true;
+    if (const int rc = window_check(c, x0, y0, z0, sx, sy, sz, cells, row_stride, slice_stride, empty)) return rc;
+    if (empty) return FS_OK;
     const size_t total = (size_t)sx * (size_t)sy * (size_t)sz;
     ++c->grid_gen;
     FS_HIP(c, c->h_win.ensure(total));
@@ -1591,16 +1703,8 @@ int fs_update_grid_region(fs_ctx *c, int32_t x0, int32_t y0, int32_t z0, int32_t
             std::memcpy(c->h_win.p + ((size_t)z * sy + y) * sx, cells + (size_t)z * (size_t)slice_stride + (size_t)y * (size_t)row_stride, (size_t)sx);
     FS_HIP(c, hipMemcpyAsync(c->d_win.p, c->h_win.p, total, hipMemcpyHostToDevice, c->stream));
     FS_HIP(c, fs_launch_window_scatter(c->d_win.p, c->d_cells.p, c->nx, c->ny, x0, y0, z0, sx, sy, sz, c->stream));
-    // (the keep-out layer runs last in the cycle and paints its zones again: inside the window is all that changed)
-    if (!c->ko_zones.empty() && c->ko_mask_valid)
-        FS_HIP(c, fs_launch_keepout_apply(c->d_ko_mask.p, c->d_cells.p, c->nx, c->ny, x0, y0, sx, sy, nullptr, c->stream));
-    if (c->have_cls) {
-        const int b0[3] = {x0 >> 3, y0 >> 3, z0 >> 3};
-        const int nb[3] = {((x0 + sx - 1) >> 3) - b0[0] + 1, ((y0 + sy - 1) >> 3) - b0[1] + 1, ((z0 + sz - 1) >> 3) - b0[2] + 1};
-        FS_HIP(c, fs_launch_classify_region(c->d_cells.p, c->d_cls.p, c->nx, c->ny, c->nz, c->cls_ranges[0], c->cls_ranges[1], c->cls_ranges[2],
-                                            c->cls_ranges[3], b0, nb, c->stream));
-    }
-    c->have_sparse = false;
+    if (const int rc = ko_repaint_window(c, x0, y0, sx, sy)) return rc;       // (inside the window is all that changed)
+    if (const int rc = cells_changed_in_box(c, x0, y0, z0, sx, sy, sz)) return rc;
     FS_HIP(c, hipStreamSynchronize(c->stream));                  // (the page-locked window is the next call's again)
     if (c->h_win.cap > ((size_t)64 << 20)) { c->h_win.release(); c->d_win.release(); }   // (a window of map size: not worth keeping)
     ++c->epoch;
@@ -1612,13 +1716,10 @@ int fs_upload_grid_bricks(fs_ctx *c, int32_t nx, int32_t ny, int32_t nz, const d
 {
     if (!c || !origin_xyz || n_bricks < 0 || (n_bricks > 0 && (!brick_xyz || !brick_cells))) return FS_E_INVALID;
     FS_HIP(c, hipSetDevice(c->device));
-    if (nx <= 0 || ny <= 0 || nz <= 0 || !(resolution > 0.0) || !std::isfinite(resolution)) return fail(c, FS_E_INVALID, "bad grid shape or resolution");
-    // (worldToMap with a NaN origin is a float-to-integer conversion of NaN: undefined in the reference, refused here)
-    if (!std::isfinite(origin_xyz[0]) || !std::isfinite(origin_xyz[1]) || !std::isfinite(origin_xyz[2])) return fail(c, FS_E_INVALID, "grid origin must be finite");
+    if (const int rc = snapshot_geometry_check(c, nx, ny, nz, origin_xyz, resolution)) return rc;
     if ((nx & 7) || (ny & 7) || (nz & 7)) return fail(c, FS_E_INVALID, "brick upload needs dimensions that are multiples of 8");
-    const uint64_t total = (uint64_t)nx * (uint64_t)ny * (uint64_t)nz;
-    // (cell offsets are 32-bit unsigned in the walks, one z step is a signed 32-bit stride; everything else indexes in 64 bits)
-    if (total >= (1ull << 32) || (uint64_t)nx * (uint64_t)ny >= (1ull << 31)) return fail(c, FS_E_INVALID, "dense grids are limited to 2^32 cells (and 2^31 per z slice)");
+    uint64_t total = 0;
+    if (const int rc = snapshot_size_check(c, nx, ny, nz, total)) return rc;
     ++c->grid_gen;
     FS_HIP(c, c->d_cells.ensure((size_t)total));
     FS_HIP(c, hipMemsetAsync(c->d_cells.p, default_value, (size_t)total, c->stream));
@@ -1636,30 +1737,13 @@ int fs_upload_grid_bricks(fs_ctx *c, int32_t nx, int32_t ny, int32_t nz, const d
         if (d_bc.cap > ((size_t)64 << 20)) { d_bc.release(); d_xyz.release(); }   // a whole-map brick list (C5: 385 MB) is not worth keeping
         if (bad) { c->have_grid = false; return fail(c, FS_E_INVALID, "a brick lies outside the grid"); }
     }
-    if (!c->ko_zones.empty()) {
-        const int rc = ko_after_snapshot(c, nx, ny, nz, origin_xyz, resolution);
-        if (rc) return rc;
-    }
-    {
-        const int rc = retile_grid(c, nx, ny, nz);
-        if (rc) return rc;
-    }
-    FS_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->have_world && (nx != c->nx || ny != c->ny || nz != c->nz)) drop_world(c);   // (the world is of the staged grid's shape)
-    c->nx = nx; c->ny = ny; c->nz = nz;
-    c->origin[0] = origin_xyz[0]; c->origin[1] = origin_xyz[1]; c->origin[2] = origin_xyz[2];
-    c->res = resolution;
-    c->have_grid = true;
-    c->max_gt = 0.0; c->min_gt = 0.0;
-    ++c->epoch;
-    return FS_OK;
+    return snapshot_done(c, nx, ny, nz, origin_xyz, resolution);
 }
 
 int fs_frontier_cells(fs_ctx *c, int32_t lethal_threshold, uint8_t *mask, int64_t *count)
 {
     if (!c || !count) return FS_E_INVALID;
-    FS_HIP(c, hipSetDevice(c->device));
-    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (const int rc = grid_check(c)) return rc;
     const size_t total = (size_t)c->nx * c->ny * c->nz;
     DevBuf<uint8_t> &d_mask = c->d_mask;
     DevBuf<unsigned long long> &d_count = c->d_count;
@@ -1684,8 +1768,7 @@ int fs_frontier_cells(fs_ctx *c, int32_t lethal_threshold, uint8_t *mask, int64_
 int fs_upload_world(fs_ctx *c, const uint8_t *cells, int32_t nx, int32_t ny, int32_t nz)
 {
     if (!c) return FS_E_INVALID;
-    FS_HIP(c, hipSetDevice(c->device));
-    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (const int rc = grid_check(c)) return rc;
     if (!cells) {
         FS_HIP(c, hipStreamSynchronize(c->stream));
         drop_world(c);
@@ -1706,31 +1789,13 @@ int fs_sense(fs_ctx *c, int32_t n, const double *origin_xyz, const int32_t *firs
              int32_t *seen_unknown, int32_t *status, int64_t *n_seen, int64_t *n_revealed, int32_t window[6])
 {
     if (!c || n < 0 || (n > 0 && (!origin_xyz || !seen_unknown || !status))) return FS_E_INVALID;
-    FS_HIP(c, hipSetDevice(c->device));
-    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
-    if (!c->have_world) return fail(c, FS_E_STATE, "fs_upload_world has not been called");
-    if (!sensor && !c->have_ray) return fail(c, FS_E_STATE, "fs_set_ray_params has not been called and no sensor is given");
+    if (const int rc = sweep_state_check(c, sensor)) return rc;
     FsSenseArgs a{};
-    const fs_ray_params &p = sensor ? *sensor : c->rp;
-    {
-        const int rc = sense_fan_setup(c, sensor, a);
-        if (rc) return rc;
-    }
-    if (first_ray)
-        for (int32_t i = 0; i < n; ++i)
-            if (first_ray[i] < -1 || first_ray[i] > a.n_yaw - a.window)
-                return fail(c, FS_E_INVALID, "first_ray[%d] = %d is outside [-1, %d]", i, first_ray[i], a.n_yaw - a.window);
-    if (n_seen) *n_seen = 0;
-    if (n_revealed) *n_revealed = 0;
-    if (window) std::fill(window, window + 6, 0);
+    if (const int rc = sweep_fan_setup(c, sensor, first_ray, (size_t)n, a, n_seen, n_revealed, window)) return rc;
     if (n == 0) return FS_OK;
 
-    sense_world_setup(c, p, a);
+    if (const int rc = sweep_world_setup(c, sensor, a)) return rc;
     const size_t n_rays = (size_t)a.n_yaw * (size_t)a.n_elev;
-    {
-        const int rc = sense_mark_ready(c);
-        if (rc) return rc;
-    }
     const size_t un = (size_t)n;
     FS_HIP(c, c->d_sense_origin.ensure(3 * un)); FS_HIP(c, c->d_sense_out.ensure(6 + 2 * un)); FS_HIP(c, c->d_sense_counts.ensure(4));
     if (first_ray) FS_HIP(c, c->d_sense_first.ensure(un));
@@ -1761,19 +1826,11 @@ int fs_sense(fs_ctx *c, int32_t n, const double *origin_xyz, const int32_t *firs
     const int32_t x0 = out[0], y0 = out[1], z0 = out[2], sx = out[3] - out[0] + 1, sy = out[4] - out[1] + 1, sz = out[5] - out[2] + 1;
     if (x0 < 0 || y0 < 0 || z0 < 0 || sy < 1 || sz < 1 || out[3] >= c->nx || out[4] >= c->ny || out[5] >= c->nz)
         return fail(c, FS_E_HIP, "fs_sense: the seen cells' box [%d,%d] x [%d,%d] x [%d,%d] leaves the grid", out[0], out[3], out[1], out[4], out[2], out[5]);
-    // from here on: what fs_update_grid_region does for the window
     ++c->grid_gen;
     FS_HIP(c, hipMemsetAsync(c->d_sense_counts.p, 0, 2 * sizeof(unsigned long long), c->stream));
     FS_HIP(c, fs_launch_sense_merge(c->d_world.p, c->d_cells.p, c->d_sense_mark.p, c->nx, c->ny, x0, y0, z0, sx, sy, sz, c->d_sense_counts.p, c->stream));
-    if (!c->ko_zones.empty() && c->ko_mask_valid)
-        FS_HIP(c, fs_launch_keepout_apply(c->d_ko_mask.p, c->d_cells.p, c->nx, c->ny, x0, y0, sx, sy, nullptr, c->stream));
-    if (c->have_cls) {
-        const int b0[3] = {x0 >> 3, y0 >> 3, z0 >> 3};
-        const int nb[3] = {((x0 + sx - 1) >> 3) - b0[0] + 1, ((y0 + sy - 1) >> 3) - b0[1] + 1, ((z0 + sz - 1) >> 3) - b0[2] + 1};
-        FS_HIP(c, fs_launch_classify_region(c->d_cells.p, c->d_cls.p, c->nx, c->ny, c->nz, c->cls_ranges[0], c->cls_ranges[1], c->cls_ranges[2],
-                                            c->cls_ranges[3], b0, nb, c->stream));
-    }
-    c->have_sparse = false;
+    if (const int rc = ko_repaint_window(c, x0, y0, sx, sy)) return rc;
+    if (const int rc = cells_changed_in_box(c, x0, y0, z0, sx, sy, sz)) return rc;
     unsigned long long counts[2] = {0ull, 0ull};
     FS_HIP(c, hipMemcpyAsync(counts, c->d_sense_counts.p, sizeof counts, hipMemcpyDeviceToHost, c->stream));
     FS_HIP(c, hipStreamSynchronize(c->stream));                  // (the counts are the merge's)
@@ -1810,10 +1867,7 @@ int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32
 {
     if (!c || n_robots < 0 || (n_robots > 0 && (!station_xyz || !n_stations || !goal_xyz || !status || !reached || !station_status || !seen_unknown)))
         return FS_E_INVALID;
-    FS_HIP(c, hipSetDevice(c->device));
-    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
-    if (!c->have_world) return fail(c, FS_E_STATE, "fs_upload_world has not been called");
-    if (!sensor && !c->have_ray) return fail(c, FS_E_STATE, "fs_set_ray_params has not been called and no sensor is given");
+    if (const int rc = sweep_state_check(c, sensor)) return rc;
     if (c->nz != 1) return fail(c, FS_E_INVALID, "fs_drive is defined on a 2-D costmap (nz == 1)");
     if (n_robots > FS_DRIVE_MAX_ROBOTS) return fail(c, FS_E_INVALID, "%d robots, at most %d", n_robots, FS_DRIVE_MAX_ROBOTS);
     const size_t R = (size_t)n_robots;
@@ -1827,25 +1881,10 @@ int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32
     }
     const fs_drive_params dp = params ? *params : fs_drive_params{253, 254, 1};
     FsDriveArgs a{};
-    const fs_ray_params &p = sensor ? *sensor : c->rp;
-    {
-        const int rc = sense_fan_setup(c, sensor, a.sense);
-        if (rc) return rc;
-    }
-    if (first_ray)
-        for (size_t i = 0; i < T; ++i)
-            if (first_ray[i] < -1 || first_ray[i] > a.sense.n_yaw - a.sense.window)
-                return fail(c, FS_E_INVALID, "first_ray[%zu] = %d is outside [-1, %d]", i, first_ray[i], a.sense.n_yaw - a.sense.window);
-    if (n_seen) *n_seen = 0;
-    if (n_revealed) *n_revealed = 0;
-    if (window) std::fill(window, window + 6, 0);
+    if (const int rc = sweep_fan_setup(c, sensor, first_ray, T, a.sense, n_seen, n_revealed, window)) return rc;
     if (R == 0) return FS_OK;
 
-    sense_world_setup(c, p, a.sense);
-    {
-        const int rc = sense_mark_ready(c);
-        if (rc) return rc;
-    }
+    if (const int rc = sweep_world_setup(c, sensor, a.sense)) return rc;
     // what a station can touch: its cell +- the fan's reach (an end point lies within depth of the pose, so its cell within
     // max_length + 2 of the pose's), clipped; empty for a station off the map.  It sizes the merge launch and says where the
     // keep-out zones are painted again — over more cells than the sweep saw, which repeats what is already painted there.
@@ -1906,7 +1945,6 @@ int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32
     a.counts = c->d_sense_counts.p;
 
     ++c->grid_gen;
-    const bool paint = !c->ko_zones.empty() && c->ko_mask_valid;
     Win all{c->nx, c->ny, -1, -1};
     for (int32_t k = 0; k < K; ++k) {
         Win w{c->nx, c->ny, -1, -1};
@@ -1922,20 +1960,13 @@ int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32
         FS_HIP(c, fs_launch_drive_step(a, c->stream));
         if (w.x1 >= w.x0) {
             FS_HIP(c, fs_launch_drive_merge(a, (unsigned)((most + 255ull) / 256ull), c->stream));
-            if (paint)
-                FS_HIP(c, fs_launch_keepout_apply(c->d_ko_mask.p, c->d_cells.p, c->nx, c->ny, w.x0, w.y0, w.x1 - w.x0 + 1, w.y1 - w.y0 + 1, nullptr, c->stream));
+            if (const int rc = ko_repaint_window(c, w.x0, w.y0, w.x1 - w.x0 + 1, w.y1 - w.y0 + 1)) return rc;
             all = Win{std::min(all.x0, w.x0), std::min(all.y0, w.y0), std::max(all.x1, w.x1), std::max(all.y1, w.y1)};
         }
         if (dp.stop_when_mapped) FS_HIP(c, fs_launch_drive_goal(a, c->stream));
     }
-    // from here on: what fs_update_grid_region does, once, for everything the drive can have touched
-    if (c->have_cls && all.x1 >= all.x0) {
-        const int b0[3] = {all.x0 >> 3, all.y0 >> 3, 0};
-        const int nb[3] = {(all.x1 >> 3) - b0[0] + 1, (all.y1 >> 3) - b0[1] + 1, 1};
-        FS_HIP(c, fs_launch_classify_region(c->d_cells.p, c->d_cls.p, c->nx, c->ny, c->nz, c->cls_ranges[0], c->cls_ranges[1], c->cls_ranges[2],
-                                            c->cls_ranges[3], b0, nb, c->stream));
-    }
-    c->have_sparse = false;
+    // once, for everything the drive can have touched (an empty box where every station was off the map)
+    if (const int rc = cells_changed_in_box(c, all.x0, all.y0, 0, all.x1 - all.x0 + 1, all.y1 - all.y0 + 1, 1)) return rc;
     std::vector<int32_t> back(n_back);
     unsigned long long counts[2] = {0ull, 0ull};
     FS_HIP(c, hipMemcpyAsync(back.data(), d + o_state, n_back * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1960,8 +1991,7 @@ int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32
 int fs_grid_census(fs_ctx *c, int64_t counts[4])
 {
     if (!c || !counts) return FS_E_INVALID;
-    FS_HIP(c, hipSetDevice(c->device));
-    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (const int rc = grid_check(c)) return rc;
     unsigned long long v[4] = {0ull, 0ull, 0ull, 0ull};
     FS_HIP(c, c->d_sense_counts.ensure(4));
     FS_HIP(c, hipMemsetAsync(c->d_sense_counts.p, 0, sizeof v, c->stream));
@@ -2395,8 +2425,7 @@ int fs_trace_segments(fs_ctx *c, int32_t n, const double *start_xyz, const doubl
                       uint8_t *ok, int32_t *traced, uint8_t *hit, int32_t *unknown, int32_t *all)
 {
     if (!c) return FS_E_INVALID;
-    FS_HIP(c, hipSetDevice(c->device));
-    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (const int rc = grid_check(c)) return rc;
     if (n < 0 || (n > 0 && (!start_xyz || !end_xyz || !ok || !traced || !hit || !unknown || !all))) return fail(c, FS_E_INVALID, "null pointer");
     if (n == 0) return FS_OK;
     DevBuf<double> &d_s = c->d_seg_start, &d_e = c->d_seg_end;
@@ -2902,9 +2931,7 @@ static int occlusion_args(fs_ctx *c, FsFimArgs &a)
     if (!c->have_grid) return fail(c, FS_E_STATE, "occlusion is enabled (fs_set_occlusion) and fs_upload_grid has not been called");
     a.occ_grid = grid_dev(c);
     a.occ_min = c->occ.occ_min; a.occ_max = c->occ.occ_max;
-    // M = 1 + (unsigned)(end_margin_m / resolution); a walk has fewer than 2^31 visits, so a larger quotient tests nothing either way
-    const double q = c->occ.end_margin_m / c->res;
-    a.occ_margin = 1u + (q < 2147483647.0 ? (uint32_t)q : 2147483647u);
+    a.occ_margin = occlusion_margin(c, c->occ.end_margin_m);
     a.split_shift = 0; a.split_flags = nullptr; a.host_flag = nullptr;
     return FS_OK;
 }
@@ -2943,8 +2970,7 @@ int fs_get_occlusion(const fs_ctx *c, fs_occlusion_params *p)
 int fs_line_of_sight(fs_ctx *c, int32_t n, const double *from_xyz, const double *to_xyz, uint8_t *ok, uint8_t *blocked, int32_t *tested_cells)
 {
     if (!c) return FS_E_INVALID;
-    FS_HIP(c, hipSetDevice(c->device));
-    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
+    if (const int rc = grid_check(c)) return rc;
     if (n < 0 || (n > 0 && (!from_xyz || !to_xyz || !ok || !blocked))) return fail(c, FS_E_INVALID, "null pointer");
     if (n == 0) return FS_OK;
     // (the segment tracer's buffers: the same shapes, never in use at the same time)
@@ -3074,20 +3100,14 @@ int fs_score_fim_begin(fs_ctx *c, int32_t n, const double *pose7, float *info_re
     const size_t nn = (size_t)n;
     FS_HIP(c, c->h_in.ensure(nn * 12 * sizeof(float)));
     float *Rt = reinterpret_cast<float *>(c->h_in.p);
-    for (int32_t i = 0; i < n; ++i) pose_to_rt(pose7 + 7 * (size_t)i, Rt + 12 * (size_t)i);
+    const bool unit = poses_to_rt(pose7, n, Rt);
     FS_HIP(c, c->d_Rt.ensure(nn * 12));
     rc = ensure_candidate_scratch(c, n, fim21 != nullptr);
     if (rc) return rc;
     FsFimArgs a{};
     if (const int rc_args = fill_fim_args(c, a)) return rc_args;
     a.n = n; a.Rt = c->d_Rt.p;
-    // chunk culling reasons in world space and needs R orthonormal: a non-unit quaternion (which the
-    // reference would feed to Eigen unnormalised) switches this call to the brute-force scan
-    for (int32_t i = 0; i < n && a.cull; ++i) {
-        const double *q = pose7 + 7 * (size_t)i + 3;
-        const double nq = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-        if (!(std::fabs(nq - 1.0) <= 1.0e-4)) a.cull = 0;
-    }
+    if (!unit) a.cull = 0;
     a.fim21 = fim21 ? c->d_fim21.p : nullptr;
     // isPoseSafe reads the scalar alone (FIP/src/fisher_information/FisherInfoManager.cpp:83-100): a call that asks for nothing
     // but info_ref (and, at no cost, n_voxels) takes the worker without the 6x6 sums and with the exact table-box cull
@@ -3239,13 +3259,7 @@ int fs_landmarks_in_view(fs_ctx *c, int32_t n, const double *pose7, int64_t max_
     if (n == 0) { if (offsets) offsets[0] = 0; return FS_OK; }
     const size_t nn = (size_t)n;
     std::vector<float> Rt(nn * 12);
-    for (int32_t i = 0; i < n; ++i) pose_to_rt(pose7 + 7 * (size_t)i, &Rt[12 * (size_t)i]);
-    // (as fs_score_fim: the sphere cull needs R orthonormal — a non-unit quaternion switches the call to the brute-force scan)
-    for (int32_t i = 0; i < n && fa.cull; ++i) {
-        const double *q = pose7 + 7 * (size_t)i + 3;
-        const double nq = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-        if (!(std::fabs(nq - 1.0) <= 1.0e-4)) fa.cull = 0;
-    }
+    if (!poses_to_rt(pose7, n, Rt.data())) fa.cull = 0;
     const int32_t words = std::max(1, (c->m + 31) / 32);
     int64_t per_round = c->opt_view_round > 0 ? c->opt_view_round
                                               : std::max<int64_t>(1, std::min<int64_t>(FS_VIEW_MAX_ROUND, (int64_t)(FS_VIEW_MASK_BYTES / (sizeof(uint32_t) * (size_t)words))));
@@ -3259,9 +3273,7 @@ int fs_landmarks_in_view(fs_ctx *c, int32_t n, const double *pose7, int64_t max_
     a.perm = c->d_view_perm.p; a.inv = c->d_view_inv.p;
     a.Rt = c->d_view_Rt.p;
     a.words = words; a.mask = c->d_view_mask.p; a.counts = c->d_view_counts.p;
-    // a single pose is the reference's real call: fewer chunks per wave until the round fills the chip's wave slots
-    a.group = 64;
-    while (a.group > 4 && per_round * ((c->n_chunks + a.group - 1) / a.group) < 2048) a.group >>= 1;
+    a.group = chunks_per_wave(per_round, c->n_chunks);
     a.cull = fa.cull; a.max_dist_f = fa.max_dist_f;
     a.maxd2 = fa.maxd2; a.cos2 = fa.cos2; a.cone_mode = fa.cone_mode;
     a.table = fa.table; a.jx0 = fa.jx0; a.jy0 = fa.jy0; a.jz0 = fa.jz0; a.tx = fa.tx; a.ty = fa.ty; a.tz = fa.tz; a.inv_step = fa.inv_step;
@@ -3404,29 +3416,16 @@ int fs_sense_landmarks(fs_ctx *c, int32_t n, const double *pose7, const fs_landm
     float cos_a, sin_a;
     fim_volume(s.max_dist, s.max_angle, a.maxd2, a.max_dist_f, a.cos2, a.cone_mode, cos_a, sin_a);
     std::vector<float> Rt(nn * 12);
-    for (int32_t i = 0; i < n; ++i) pose_to_rt(pose7 + 7 * (size_t)i, &Rt[12 * (size_t)i]);
-    // (as fs_score_fim: the sphere cull needs R orthonormal — a non-unit quaternion switches the call to the brute-force scan)
-    a.cull = c->opt_cull ? 1 : 0;
-    for (int32_t i = 0; i < n && a.cull; ++i) {
-        const double *q = pose7 + 7 * (size_t)i + 3;
-        const double nq = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-        if (!(std::fabs(nq - 1.0) <= 1.0e-4)) a.cull = 0;
-    }
+    a.cull = (poses_to_rt(pose7, n, Rt.data()) && c->opt_cull) ? 1 : 0;
     a.lx = c->d_wl_lx.p; a.ly = c->d_wl_ly.p; a.lz = c->d_wl_lz.p; a.spheres = c->d_wl_spheres.p; a.perm = c->d_wl_perm.p;
     a.n_chunks = c->wl_chunks; a.m_world = c->wl_m;
     a.n = n;
-    // a single pose is the common call: fewer chunks per wave until the call fills the chip's wave slots (fs_landmarks_in_view's rule)
-    a.group = 64;
-    while (a.group > 4 && (int64_t)n * ((c->wl_chunks + a.group - 1) / a.group) < 2048) a.group >>= 1;
+    a.group = chunks_per_wave(n, c->wl_chunks);
     a.los = s.line_of_sight;
     if (a.los) {
-        a.world = grid_dev(c);
-        a.world.cells = c->d_world.p;
-        a.world.cls = nullptr;
+        a.world = world_dev(c);
         a.occ_min = s.occ_min; a.occ_max = s.occ_max;
-        // M = 1 + (unsigned)(end_margin_m / resolution), as occlusion_args
-        const double q = s.end_margin_m / c->res;
-        a.occ_margin = 1u + (q < 2147483647.0 ? (uint32_t)q : 2147483647u);
+        a.occ_margin = occlusion_margin(c, s.end_margin_m);
     }
     FS_HIP(c, c->d_wl_Rt.ensure(nn * 12)); FS_HIP(c, c->d_wl_out.ensure(3 + nn));
     a.Rt = c->d_wl_Rt.p; a.views = c->d_wl_views.p; a.n_in_view = c->d_wl_out.p + 3;
@@ -6865,13 +6864,7 @@ int ko_add(fs_ctx *c, int32_t kind, double wx, double wy, double yaw, double siz
         const int rc = c->ko_mask_valid ? ko_rasterise(c, id, g, box) : ko_rebuild(c, g, box);
         if (rc) { c->ko_zones.pop_back(); c->ko_mask_valid = false; return rc; }
         if (box[2] >= box[0]) {
-            if (c->have_cls) {
-                const int b0[3] = {box[0] >> 3, box[1] >> 3, 0};
-                const int nb[3] = {(box[2] >> 3) - b0[0] + 1, (box[3] >> 3) - b0[1] + 1, 1};
-                FS_HIP(c, fs_launch_classify_region(c->d_cells.p, c->d_cls.p, c->nx, c->ny, c->nz, c->cls_ranges[0], c->cls_ranges[1], c->cls_ranges[2],
-                                                    c->cls_ranges[3], b0, nb, c->stream));
-            }
-            c->have_sparse = false;
+            if (const int rc2 = cells_changed_in_box(c, box[0], box[1], 0, box[2] - box[0] + 1, box[3] - box[1] + 1, 1)) return rc2;
             ++c->grid_gen;
             ++c->epoch;
         }
@@ -6959,17 +6952,10 @@ int fs_read_grid_region(fs_ctx *c, int32_t x0, int32_t y0, int32_t z0, int32_t s
                         uint8_t *cells, int64_t row_stride, int64_t slice_stride)
 {
     if (!c) return FS_E_INVALID;
-    FS_HIP(c, hipSetDevice(c->device));
-    if (!c->have_grid) return fail(c, FS_E_STATE, "fs_upload_grid has not been called");
-    if (sx < 0 || sy < 0 || sz < 0) return fail(c, FS_E_INVALID, "negative window size");
-    if (x0 < 0 || y0 < 0 || z0 < 0 || (int64_t)x0 + sx > c->nx || (int64_t)y0 + sy > c->ny || (int64_t)z0 + sz > c->nz)
-        return fail(c, FS_E_INVALID, "window [%d,%lld) x [%d,%lld) x [%d,%lld) leaves the %d x %d x %d grid", x0, (long long)x0 + sx, y0, (long long)y0 + sy,
-                    z0, (long long)z0 + sz, c->nx, c->ny, c->nz);
-    if (sx == 0 || sy == 0 || sz == 0) return FS_OK;
-    if (!cells) return FS_E_INVALID;
-    if (row_stride == 0) row_stride = sx;
-    if (slice_stride == 0) slice_stride = row_stride * (int64_t)sy;
-    if (row_stride < sx || slice_stride < row_stride * (int64_t)(sy - 1) + sx) return fail(c, FS_E_INVALID, "window strides smaller than the window");
+    if (const int rc = grid_check(c)) return rc;
+    bool empty = true;
+    if (const int rc = window_check(c, x0, y0, z0, sx, sy, sz, cells, row_stride, slice_stride, empty)) return rc;
+    if (empty) return FS_OK;
     const size_t total = (size_t)sx * (size_t)sy * (size_t)sz;
     FS_HIP(c, c->h_win.ensure(total));
     FS_HIP(c, c->d_win.ensure(total));

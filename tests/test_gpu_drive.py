@@ -18,6 +18,11 @@ pytestmark = pytest.mark.gpu
 
 FS_E_INVALID, FS_E_STATE = -1, -4
 WORLD, STAGED = TR.WORLD, TR.STAGED
+# what a refused sweep says, word for word
+NO_GRID = "fs_upload_grid has not been called"
+NO_WORLD = "fs_upload_world has not been called"
+NO_SENSOR = "fs_set_ray_params has not been called and no sensor is given"
+NOT_2D = "fs_drive is defined on a 2-D costmap (nz == 1)"
 
 
 def _ctx(fs, staged, world, origin, res, params, zones=()):
@@ -213,16 +218,17 @@ def test_error_paths_leave_the_map_and_the_outputs_alone(fs):
     n_yaw, _, k = SR.fan_shape(EP.PARAMS)
     s = fs.FrontierScorer(device=0)
     try:
-        def refused(code, f, *args, **kw):
+        def refused(code, f, *args, text=None, **kw):
             with pytest.raises(fs.capi.FsError) as e:
                 f(*args, **kw)
             assert e.value.code == code
+            assert text is None or str(e.value) == f"fitslam_frontier error {code}: {text}"
         run = lambda **kw: s.drive(case["stations"], case["goals"], case["first_ray"], **kw)
-        refused(FS_E_STATE, run)                                         # no grid
+        refused(FS_E_STATE, run, text=NO_GRID)                           # no grid
         s.upload_grid(STAGED, EP.ORIGIN, EP.RES)
-        refused(FS_E_STATE, run)                                         # no world
+        refused(FS_E_STATE, run, text=NO_WORLD)                          # no world
         s.upload_world(WORLD)
-        refused(FS_E_STATE, run)                                         # no ray parameters and no sensor
+        refused(FS_E_STATE, run, text=NO_SENSOR)                         # no ray parameters and no sensor
         assert run(sensor=EP.PARAMS)["n_seen"] == TR.result("E")["n_seen"]
         s.upload_grid(STAGED, EP.ORIGIN, EP.RES)
         s.set_ray_params(robot_radius=0.15, **EP.PARAMS)
@@ -244,6 +250,7 @@ def test_error_paths_leave_the_map_and_the_outputs_alone(fs):
         for bad in (n_yaw - k + 1, -2):
             fr = first.copy(); fr[T - 2] = bad
             assert raw([9, 3], fr) == FS_E_INVALID
+            assert s._L.fs_last_error(s._h).decode() == f"first_ray[{T - 2}] = {bad} is outside [-1, {n_yaw - k}]"
         assert raw([12, 0], first) == FS_E_INVALID                       # a robot without a station
         assert raw([fs.capi.FS_DRIVE_MAX_STATIONS + 1, 3], first) == FS_E_INVALID    # (refused before a station is read)
         np.testing.assert_array_equal(s.read_grid_region(), STAGED)
@@ -255,7 +262,37 @@ def test_error_paths_leave_the_map_and_the_outputs_alone(fs):
         c1 = fs.synth.make_workload("C1", n_cand=4, n_landmarks=4)
         s.upload_grid(c1.cells, c1.origin, c1.resolution)
         s.upload_world(c1.cells)
-        refused(FS_E_INVALID, s.drive, [c1.goals[:2]], [c1.goals[0]])
+        refused(FS_E_INVALID, s.drive, [c1.goals[:2]], [c1.goals[0]], text=NOT_2D)
         np.testing.assert_array_equal(s.read_grid_region(), c1.cells)
+    finally:
+        s.close()
+
+
+def test_which_refusal_comes_first(fs):
+    """fs_sense and fs_drive check in the same order — the grid, the world, the fan's source, then the drive's own arguments,
+    then first_ray: a call that is wrong in two ways is refused with the text of the earlier check"""
+    def text(f, *args, **kw):
+        with pytest.raises(fs.capi.FsError) as e:
+            f(*args, **kw)
+        return str(e.value)
+    origin, res = (0.0, 0.0, 0.0), 0.1
+    flat = np.zeros((1, 16, 16), np.uint8)
+    pose = np.array([[0.85, 0.85, 0.0]])
+    s = fs.FrontierScorer(device=0)
+    try:
+        # neither grid nor world: the grid's text
+        assert text(s.sense, pose) == f"fitslam_frontier error {FS_E_STATE}: {NO_GRID}"
+        assert text(s.drive, [pose], pose) == f"fitslam_frontier error {FS_E_STATE}: {NO_GRID}"
+        # no ray parameters, no sensor and a first_ray out of range: the sensor's text
+        s.upload_grid(flat, origin, res)
+        s.upload_world(flat)
+        assert text(s.sense, pose, [10 ** 6]) == f"fitslam_frontier error {FS_E_STATE}: {NO_SENSOR}"
+        assert text(s.drive, [pose], pose, [[10 ** 6]]) == f"fitslam_frontier error {FS_E_STATE}: {NO_SENSOR}"
+        # a 3-D grid and more robots than a drive takes: the grid's shape is looked at first
+        vol = np.zeros((8, 16, 16), np.uint8)
+        s.upload_grid(vol, origin, res)
+        s.upload_world(vol)
+        for R in (65, fs.capi.FS_DRIVE_MAX_ROBOTS + 1):
+            assert text(s.drive, [pose] * R, np.repeat(pose, R, axis=0), sensor=EP.PARAMS) == f"fitslam_frontier error {FS_E_INVALID}: {NOT_2D}"
     finally:
         s.close()

@@ -98,20 +98,38 @@ def test_window_arguments(fs):
     w = fs.synth.make_small_2d(302, n=64, n_cand=24, n_landmarks=50)
     s = fs.FrontierScorer(device=0)
     try:
-        with pytest.raises(fs.capi.FsError) as e:
-            s.update_grid_region(0, 0, 0, np.zeros((4, 4), dtype=np.uint8))
-        assert e.value.code == FS_E_STATE
+        for call in (lambda: s.update_grid_region(0, 0, 0, np.zeros((4, 4), dtype=np.uint8)), lambda: s.read_grid_region(shape=(4, 4))):
+            with pytest.raises(fs.capi.FsError) as e:
+                call()
+            assert e.value.code == FS_E_STATE and str(e.value) == f"fitslam_frontier error {FS_E_STATE}: fs_upload_grid has not been called"
         s.set_ray_params(**_ray_kw(w))
         s.upload_grid(w.cells, w.origin, w.resolution)
         s.max_arrival()
         before = s.score_arrival(w.goals, w.frontier_size, w.blacklisted)
         for x0, y0, z0, shape in ((60, 0, 0, (1, 4, 8)), (0, 61, 0, (1, 4, 4)), (-1, 0, 0, (1, 2, 2)), (0, 0, 1, (1, 2, 2)), (0, 0, 0, (2, 2, 2)),
                                   (2 ** 31 - 4, 0, 0, (1, 1, 8))):
-            with pytest.raises(fs.capi.FsError) as e:
-                s.update_grid_region(x0, y0, z0, np.full(shape, 254, dtype=np.uint8))
-            assert e.value.code == FS_E_INVALID, (x0, y0, z0, shape)
+            sz, sy, sx = shape
+            text = f"window [{x0},{x0 + sx}) x [{y0},{y0 + sy}) x [{z0},{z0 + sz}) leaves the 64 x 64 x 1 grid"
+            out = np.full(shape, 77, dtype=np.uint8)
+            for call in (lambda: s.update_grid_region(x0, y0, z0, np.full(shape, 254, dtype=np.uint8)), lambda: s.read_grid_region(x0, y0, z0, out=out)):
+                with pytest.raises(fs.capi.FsError) as e:
+                    call()
+                assert e.value.code == FS_E_INVALID, (x0, y0, z0, shape)
+                assert str(e.value) == f"fitslam_frontier error {FS_E_INVALID}: {text}"
+            assert (out == 77).all()
+        # a negative size, strides smaller than the window, no cells: through the C ABI (numpy has no such array)
+        buf = np.full(64, 77, dtype=np.uint8)
+        for f in (s._L.fs_update_grid_region, s._L.fs_read_grid_region):
+            for args, text in (((0, 0, 0, -1, 2, 1, buf.ctypes.data, 0, 0), "negative window size"),
+                               ((0, 0, 0, 4, 2, 1, buf.ctypes.data, 3, 0), "window strides smaller than the window"),
+                               ((0, 0, 0, 4, 2, 1, buf.ctypes.data, 8, 11), "window strides smaller than the window")):
+                assert f(s._h, *args) == FS_E_INVALID and s._L.fs_last_error(s._h).decode() == text, args
+            assert f(s._h, 0, 0, 0, 4, 2, 1, None, 0, 0) == FS_E_INVALID
+            assert f(s._h, 5, 5, 0, 0, 7, 1, None, 0, 0) == 0                    # (an empty window needs no cells)
+        assert (buf == 77).all()
         s.update_grid_region(5, 5, 0, np.zeros((0, 7), dtype=np.uint8))         # empty: fine, nothing happens
         s.update_grid_region(64, 64, 0, np.zeros((0, 0), dtype=np.uint8))
+        assert s.read_grid_region(5, 5, 0, shape=(0, 7)).shape == (0, 7) and s.read_grid_region(64, 64, 0, shape=(0, 0)).size == 0
         _equal_arrival(s.score_arrival(w.goals, w.frontier_size, w.blacklisted), before)
         # the whole map as one window == a snapshot
         other = np.ascontiguousarray(np.rot90(w.cells[0]))
@@ -191,3 +209,32 @@ def test_map_windows_between_random_calls_equal_new_snapshots(fs, name, seed):
             _compare(fs, kind, _call(fs, win, kind, w, pick, poses, split, angle), _call(fs, snap, kind, w, pick, poses, split, angle), what)
     finally:
         snap.close(); win.close()
+
+
+def test_a_refused_call_costs_no_cache(fs):
+    """a window update, a sweep and a drive that are refused leave the map's generation alone: the NavFn field of the tick
+    before is still the one plan_paths reads (counter 1002 counts field builds)"""
+    w = fs.synth.make_small_2d(302, n=64, n_cand=24, n_landmarks=50)
+    pose = [float(w.goals[0][0]), float(w.goals[0][1]), 0.0, 0.0, 0.0, 0.0, 1.0]
+    s = fs.FrontierScorer(device=0)
+    try:
+        s.set_ray_params(**_ray_kw(w))
+        s.upload_grid(w.cells, w.origin, w.resolution)
+        s.upload_world(w.cells)
+        before = s.plan_paths(pose, w.goals, allow_unknown=True)
+        builds = s.get_counter(1002)
+        assert builds >= 1 and before["achievable"].any()
+        station = np.array([w.goals[1]], dtype=np.float64)
+        for call in (lambda: s.update_grid_region(60, 0, 0, np.full((4, 8), 254, dtype=np.uint8)),
+                     lambda: s.sense(w.goals[:3], [0, 10 ** 6, 0]),
+                     lambda: s.drive([station], station, [[10 ** 6]])):
+            with pytest.raises(fs.capi.FsError) as e:
+                call()
+            assert e.value.code == FS_E_INVALID
+        after = s.plan_paths(pose, w.goals, allow_unknown=True)
+        assert s.get_counter(1002) == builds
+        for k in before:
+            np.testing.assert_array_equal(after[k], before[k], err_msg=k)
+        np.testing.assert_array_equal(s.read_grid_region(), w.cells)
+    finally:
+        s.close()

@@ -400,6 +400,9 @@ def test_rules(fs):
             with pytest.raises(fs.capi.FsError) as e:
                 _add(s, bad)
             assert e.value.code == FS_E_INVALID, bad
+            text = ("the zone's size is 2^31 cells or more (the reference's conversion to unsigned int is undefined)" if bad[4] == RES * 2.0 ** 31
+                    else "a keep-out zone needs a finite position and yaw and a finite size >= 0")
+            assert str(e.value) == f"fitslam_frontier error {FS_E_INVALID}: {text}", bad
         assert s.keepout_get()[0].shape[0] == 1
         # a 3-D upload with zones stored is staged unmarked, and refuses a new zone; the zones are kept
         vol = np.random.default_rng(1).integers(0, 256, size=(3, 96, 96), dtype=np.uint8)
@@ -407,12 +410,13 @@ def test_rules(fs):
         np.testing.assert_array_equal(s.read_grid_region(), vol)
         spec, n_cells, mask = s.keepout_get()
         assert spec.shape[0] == 1 and n_cells[0] == 0 and mask.sum() == 0
+        not_2d = f"fitslam_frontier error {FS_E_INVALID}: keep-out zones are defined on a 2-D costmap (nz == 1)"
         with pytest.raises(fs.capi.FsError) as e:
             _add(s, (K.FOV, 1.0, 1.0, 0.0, 3.5))
-        assert e.value.code == FS_E_INVALID
+        assert e.value.code == FS_E_INVALID and str(e.value) == not_2d
         with pytest.raises(fs.capi.FsError) as e:
             s.mark_lethal_fov([1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0])
-        assert e.value.code == FS_E_INVALID
+        assert e.value.code == FS_E_INVALID and str(e.value) == not_2d
         assert s.keepout_get()[0].shape[0] == 1
         s.update_grid_region(0, 0, 1, np.zeros((1, 96, 96), np.uint8))          # (a window of a 3-D grid: no layer)
         assert s.read_grid_region(0, 0, 1, shape=(1, 96, 96)).sum() == 0
@@ -455,5 +459,96 @@ def test_zone_limit(fs):
         assert e.value.code == FS_E_INVALID
         assert s.keepout_get(want_mask=False)[0].shape[0] == limit
         np.testing.assert_array_equal(s.read_grid_region()[0], _painted(cells, want_mask))
+    finally:
+        s.close()
+
+
+def _snapshot(fs, s, route, cells, origin, res):
+    if route == "bricks":
+        xyz, bricks = fs.synth.dense_to_bricks(cells, 255)
+        s.upload_grid_bricks(cells.shape, origin, res, xyz, bricks, default_value=255)
+    else:
+        s.upload_grid(cells, origin, res)
+
+
+def test_the_two_snapshot_routes_are_one(fs):
+    """fs_upload_grid and fs_upload_grid_bricks differ in how the cells reach the device and in nothing after that: the map read
+    back, the arrival limits and the arrival records are equal, a stored zone is treated alike, a snapshot of the same shape keeps
+    the world and one of another shape drops it.  A brick snapshot has whole 8 x 8 x 8 bricks, so the pair is compared on
+    16 x 16 x 8; on 64 x 64 x 1 the brick route refuses the shape and changes nothing, and the dense route carries the zone."""
+    no_world = f"fitslam_frontier error {FS_E_STATE}: fs_upload_world has not been called"
+    w3 = fs.synth.make_workload("C1", n_cand=8, n_landmarks=8)
+    kw3 = dict(max_camera_depth=w3.max_camera_depth, delta_theta=w3.delta_theta, camera_fov=w3.camera_fov, robot_radius=w3.robot_radius,
+               n_rays=w3.n_yaw, elev=w3.elev, polygon=w3.polygon)
+    rng = np.random.default_rng(23)
+    res, origin = w3.resolution, (-1.0, -2.0, 0.5)
+    values = np.array([0, 0, 0, 0, 254, 255, 255, 253, 100], np.uint8)
+    vol, vol2, narrow = rng.choice(values, size=(8, 16, 16)), rng.choice(values, size=(8, 16, 16)), rng.choice(values, size=(8, 16, 8))
+    vol[:, 8:, 8:] = 255                                                         # (a brick the list leaves out: the default value)
+    goals = (rng.integers(0, (16, 16, 8), size=(12, 3)) + 0.5) * res + np.asarray(origin)
+    zone = (K.DISC, origin[0] + 8 * res, origin[1] + 8 * res, 0.0, 3 * res)
+    got = {}
+    for route in ("dense", "bricks"):
+        s = fs.FrontierScorer(device=0)
+        try:
+            s.set_ray_params(**kw3)
+            assert _add(s, zone) == (0, 0)                                       # stored; a 3-D snapshot is staged unmarked
+            _snapshot(fs, s, route, vol, origin, res)
+            s.upload_world(vol2)
+            spec, n_cells, mask = s.keepout_get()
+            assert spec.shape[0] == 1 and n_cells[0] == 0 and mask.sum() == 0
+            got[route] = dict(grid=s.read_grid_region(), limits=s.max_arrival(), arrival=s.score_arrival(goals))
+            _snapshot(fs, s, route, vol2, origin, res)                               # the same shape: the world stays
+            got[route]["sweep"] = s.sense(goals)
+            got[route]["grid2"] = s.read_grid_region()
+            _snapshot(fs, s, route, narrow, origin, res)                             # another shape: the world goes
+            with pytest.raises(fs.capi.FsError) as e:
+                s.sense(goals)
+            assert str(e.value) == no_world
+            np.testing.assert_array_equal(s.read_grid_region(), narrow)
+        finally:
+            s.close()
+    a, b = got["dense"], got["bricks"]
+    np.testing.assert_array_equal(a["grid"], vol)
+    np.testing.assert_array_equal(b["grid"], vol)
+    np.testing.assert_array_equal(a["grid2"], b["grid2"])
+    assert a["limits"] == b["limits"]
+    assert set(a["arrival"]) == set(b["arrival"])
+    for k in a["arrival"]:
+        np.testing.assert_array_equal(a["arrival"][k], b["arrival"][k], err_msg=k)
+    for k in ("status", "seen_unknown"):
+        np.testing.assert_array_equal(a["sweep"][k], b["sweep"][k], err_msg=k)
+    assert (a["sweep"]["n_seen"], a["sweep"]["n_revealed"], a["sweep"]["window"]) == (b["sweep"]["n_seen"], b["sweep"]["n_revealed"], b["sweep"]["window"])
+
+    w2 = fs.synth.make_small_2d(302, n=64, n_cand=12, n_landmarks=8)
+    kw2 = dict(max_camera_depth=w2.max_camera_depth, delta_theta=w2.delta_theta, camera_fov=w2.camera_fov, robot_radius=w2.robot_radius,
+               n_rays=w2.n_yaw, elev=w2.elev, polygon=w2.polygon)
+    flat = np.array(w2.cells, dtype=np.uint8, copy=True)
+    zone2 = (K.DISC, w2.origin[0] + 32 * w2.resolution, w2.origin[1] + 32 * w2.resolution, 0.0, 6 * w2.resolution)
+    marked = K.mark(flat[0], [zone2], w2.origin, w2.resolution)
+    assert (marked != flat[0]).any()
+    s = fs.FrontierScorer(device=0)
+    try:
+        s.set_ray_params(**kw2)
+        _add(s, zone2)
+        s.upload_grid(flat, w2.origin, w2.resolution)
+        s.upload_world(flat)
+        np.testing.assert_array_equal(s.read_grid_region()[0], marked)
+        limits, arrival = s.max_arrival(), s.score_arrival(w2.goals)
+        with pytest.raises(fs.capi.FsError) as e:
+            s.upload_grid_bricks(flat.shape, w2.origin, w2.resolution, np.zeros((0, 3), np.int32), np.zeros((0, 512), np.uint8))
+        assert str(e.value) == f"fitslam_frontier error {FS_E_INVALID}: brick upload needs dimensions that are multiples of 8"
+        np.testing.assert_array_equal(s.read_grid_region(shape=(64, 64)), marked)   # refused: the map, its limits and the world stay
+        assert s.max_arrival() == limits
+        again = s.score_arrival(w2.goals)
+        for k in arrival:
+            np.testing.assert_array_equal(again[k], arrival[k], err_msg=k)
+        s.upload_grid(flat, w2.origin, w2.resolution)                            # the same shape: the world stays, the zone marks again
+        np.testing.assert_array_equal(s.read_grid_region()[0], marked)
+        assert s.sense(w2.goals[:4])["status"].shape == (4,)
+        s.upload_grid(flat[:, :, :56], w2.origin, w2.resolution)                 # another shape: the world goes
+        with pytest.raises(fs.capi.FsError) as e:
+            s.sense(w2.goals[:4])
+        assert str(e.value) == no_world
     finally:
         s.close()

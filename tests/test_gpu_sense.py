@@ -13,6 +13,10 @@ pytestmark = pytest.mark.gpu
 
 FS_E_INVALID, FS_E_STATE = -1, -4
 N_POSES = 40
+# what a refused sweep says, word for word
+NO_GRID = "fs_upload_grid has not been called"
+NO_WORLD = "fs_upload_world has not been called"
+NO_SENSOR = "fs_set_ray_params has not been called and no sensor is given"
 
 
 def _params(w, **over):
@@ -201,16 +205,17 @@ def test_error_paths(fs):
     p = _params(w)
     s = fs.FrontierScorer(device=0)
     try:
-        def refused(code, f, *args, **kw):
+        def refused(code, f, *args, text=None, **kw):
             with pytest.raises(fs.capi.FsError) as e:
                 f(*args, **kw)
             assert e.value.code == code
-        refused(FS_E_STATE, s.upload_world, world)                              # no grid staged
+            assert text is None or str(e.value) == f"fitslam_frontier error {code}: {text}"
+        refused(FS_E_STATE, s.upload_world, world, text=NO_GRID)                # no grid staged
         s.set_ray_params(**p)
         s.upload_grid(staged, w.origin, w.resolution)
-        refused(FS_E_STATE, s.sense, poses, first)                              # no world
+        refused(FS_E_STATE, s.sense, poses, first, text=NO_WORLD)               # no world
         refused(FS_E_INVALID, s.upload_world, world[:, :60, :])                 # another shape: nothing changed
-        refused(FS_E_STATE, s.sense, poses, first)
+        refused(FS_E_STATE, s.sense, poses, first, text=NO_WORLD)
         s.upload_world(world)
         refused(FS_E_INVALID, s.upload_world, world[:, :, :60])                 # ... and the world staged before stays
         # first_ray out of range: nothing is written, the map stays
@@ -224,6 +229,7 @@ def test_error_paths(fs):
             rc = s._L.fs_sense(s._h, N_POSES, ptr(poses), ptr(fr), None, ptr(rays), ptr(seen), ptr(status), ctypes.byref(n_seen),
                                ctypes.byref(n_rev), ptr(win))
             assert rc == FS_E_INVALID
+            assert s._L.fs_last_error(s._h).decode() == f"first_ray[17] = {bad} is outside [-1, {n_yaw - k}]"
             assert (seen == 77).all() and (status == 77).all() and (win == 77).all() and (rays == 77).all()
             assert n_seen.value == 77 and n_rev.value == 77
         np.testing.assert_array_equal(s.read_grid_region(), staged)
@@ -236,16 +242,16 @@ def test_error_paths(fs):
         _equal_sweep(got, ref(fs, "61", "window", staged, world, p, poses, first), s.read_grid_region())
         # NULL releases it; a snapshot of another shape drops it
         s.upload_world(None)
-        refused(FS_E_STATE, s.sense, poses, first)
+        refused(FS_E_STATE, s.sense, poses, first, text=NO_WORLD)
         s.upload_world(world)
         s.upload_grid(staged[:, :60, :], w.origin, w.resolution)
-        refused(FS_E_STATE, s.sense, poses, first)
+        refused(FS_E_STATE, s.sense, poses, first, text=NO_WORLD)
         # a context without ray parameters needs a sensor
         t = fs.FrontierScorer(device=0)
         try:
             t.upload_grid(staged, w.origin, w.resolution)
             t.upload_world(world)
-            refused(FS_E_STATE, t.sense, poses, first)
+            refused(FS_E_STATE, t.sense, poses, first, text=NO_SENSOR)
             got = t.sense(poses, first, sensor=p, rays=True)
             _equal_sweep(got, _REFS[("61", "window")], t.read_grid_region())
         finally:

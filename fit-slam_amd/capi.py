@@ -57,9 +57,11 @@ EXPORTED_SYMBOLS = [
     "fs_landmarks_in_view",
     "fs_upload_world", "fs_sense", "fs_goals_mapped", "fs_grid_census", "fs_drive",
     "fs_upload_world_landmarks", "fs_sense_landmarks", "fs_world_landmarks_get", "fs_staged_cloud_get",
+    "fs_drive_slam",
 ]
 FS_KEEPOUT_MAX_ZONES = 1024
 FS_DRIVE_ARRIVED, FS_DRIVE_BLOCKED, FS_DRIVE_COLLIDED, FS_DRIVE_OFF_MAP, FS_DRIVE_MAPPED = 0, 1, 2, 3, 4
+FS_DRIVE_UNSAFE = 5
 FS_DRIVE_MAX_STATIONS, FS_DRIVE_MAX_ROBOTS = 2048, 4096
 KEEPOUT_FOV, KEEPOUT_DISC = 0, 1
 
@@ -126,6 +128,14 @@ class DriveParamsC(C.Structure):
 
 
 assert C.sizeof(DriveParamsC) == 12
+
+
+class DriveSlamParamsC(C.Structure):
+    _fields_ = [("block_min", C.c_int32), ("block_max", C.c_int32), ("stop_when_mapped", C.c_int32), ("gate", C.c_int32),
+                ("information_threshold", C.c_double), ("gate_first_station", C.c_int32)]
+
+
+assert C.sizeof(DriveSlamParamsC) == 32
 
 
 class ViewLandmarkC(C.Structure):
@@ -206,6 +216,8 @@ def load_library(build: bool = True, path: str | None = None):
     L.fs_drive.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(RayParamsC), C.POINTER(DriveParamsC), vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), vp]
     L.fs_upload_world_landmarks.argtypes = [vp, vp, i32, vp]
     L.fs_sense_landmarks.argtypes = [vp, i32, vp, C.POINTER(LandmarkSensorC), vp, C.POINTER(i32), C.POINTER(i32)]
+    L.fs_drive_slam.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(RayParamsC), C.POINTER(LandmarkSensorC), C.POINTER(DriveSlamParamsC),
+                                vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), vp, C.POINTER(i32), C.POINTER(i32)]
     L.fs_world_landmarks_get.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), vp, vp]
     L.fs_staged_cloud_get.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), vp, vp, vp]
     L.fs_information_frontier_pair.argtypes = [vp, i32, vp, vp, vp]
@@ -870,6 +882,47 @@ class FrontierScorer:
         buf = lm if m > 0 else np.zeros((1, 3), dtype=np.float32)        # (an empty world is xyz != NULL with m_world == 0)
         self._check(self._L.fs_upload_world_landmarks(self._h, _p(buf), m, _p(kn) if m > 0 else None))
 
+    def drive_slam(self, poses, goals, first_ray=None, sensor=None, lm_sensor=None, block=(253, 254), stop_when_mapped=True, threshold=550.0,
+                   gate=True, gate_first_station=1):
+        """fs_drive_slam: drive() whose stations are poses ([n_r][7], xyz + quaternion xyzw) and which, at every
+        station, sweeps the world landmarks (lm_sensor: as sense_landmarks()'s `sensor`) and scores the pose's Fisher information
+        against what has been discovered so far; with `gate`, a robot at a station >= gate_first_station whose information is not
+        above `threshold` stops there, FS_DRIVE_UNSAFE.  Returns drive()'s dict plus information, voxels and in_view (lists of
+        [n_r] arrays; 0, 0 and -1 for stations never reached), n_new and n_discovered."""
+        st = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 7) for a in poses]
+        R = len(st)
+        g = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
+        if g.shape[0] != R:
+            raise ValueError("goals must hold one entry per robot")
+        ns = np.array([a.shape[0] for a in st], dtype=np.int32)
+        T = int(ns.sum())
+        p7 = np.ascontiguousarray(np.concatenate(st, axis=0)) if R else np.zeros((0, 7))
+        fr = None
+        if first_ray is not None:
+            if len(first_ray) != R:
+                raise ValueError("first_ray must hold one array per robot")
+            parts = [np.asarray(f, dtype=np.int32).reshape(-1) for f in first_ray]
+            if any(f.shape[0] != n for f, n in zip(parts, ns)):
+                raise ValueError("first_ray must hold one entry per station")
+            fr = np.ascontiguousarray(np.concatenate(parts)) if R else np.zeros(0, dtype=np.int32)
+        sp = None if sensor is None else _ray_params_c(**sensor)
+        lp = _landmark_sensor_c(lm_sensor)
+        dp = DriveSlamParamsC(int(block[0]), int(block[1]), 1 if stop_when_mapped else 0, int(gate), float(threshold), int(gate_first_station))
+        status = np.zeros(R, dtype=np.int32); reached = np.zeros(R, dtype=np.int32)
+        sst = np.zeros(T, dtype=np.int32); seen = np.zeros(T, dtype=np.int32)
+        info = np.zeros(T, dtype=np.float32); vox = np.zeros(T, dtype=np.int32); inv = np.zeros(T, dtype=np.int32)
+        n_seen, n_rev = C.c_int64(), C.c_int64()
+        n_new, n_disc = C.c_int32(), C.c_int32()
+        win = np.zeros(6, dtype=np.int32)
+        self._check(self._L.fs_drive_slam(self._h, R, _p(p7), _p(ns), _p(fr), _p(g), None if sp is None else C.byref(sp),
+                                          None if lp is None else C.byref(lp), C.byref(dp), _p(status), _p(reached), _p(sst), _p(seen),
+                                          _p(info), _p(vox), _p(inv), C.byref(n_seen), C.byref(n_rev), _p(win), C.byref(n_new), C.byref(n_disc)))
+        cut = np.cumsum(ns)[:-1] if R else []
+        split = lambda a: np.split(a, cut) if R else []
+        return dict(status=status, reached=reached, station_status=split(sst), seen_unknown=split(seen), n_seen=n_seen.value,
+                    n_revealed=n_rev.value, window=tuple(int(v) for v in win), information=split(info), voxels=split(vox),
+                    in_view=split(inv), n_new=n_new.value, n_discovered=n_disc.value)
+
     def sense_landmarks(self, pose7, sensor=None):
         """fs_sense_landmarks: one sweep of the world cloud from each of pose7 [n][7]; what the poses see is counted, what reaches
         min_views sightings is discovered, and the staged cloud becomes the discovered set on the device.  sensor: None (the
@@ -877,11 +930,7 @@ class FrontierScorer:
         min_views (1), occ ((254, 254)), end_margin_m (0.3).  Returns a dict: n_in_view [n], n_new, n_discovered."""
         ps = np.ascontiguousarray(pose7, dtype=np.float64).reshape(-1, 7)
         n = ps.shape[0]
-        sp = None
-        if sensor is not None:
-            occ = sensor.get("occ", (254, 254))
-            sp = LandmarkSensorC(float(sensor["max_dist"]), float(sensor["max_angle"]), int(sensor.get("line_of_sight", 1)),
-                                 int(sensor.get("min_views", 1)), int(occ[0]), int(occ[1]), float(sensor.get("end_margin_m", 0.3)))
+        sp = _landmark_sensor_c(sensor)
         niv = np.zeros(n, dtype=np.int32)
         n_new, n_disc = C.c_int32(), C.c_int32()
         self._check(self._L.fs_sense_landmarks(self._h, n, _p(ps), None if sp is None else C.byref(sp), _p(niv), C.byref(n_new),
@@ -1460,6 +1509,15 @@ def fan_n_yaw(delta_theta, n_rays=0):
     return n
 
 
+def _landmark_sensor_c(sensor):
+    """a landmark sensor dict (sense_landmarks' `sensor`) as the C struct; None stays None: the context's defaults"""
+    if sensor is None:
+        return None
+    occ = sensor.get("occ", (254, 254))
+    return LandmarkSensorC(float(sensor["max_dist"]), float(sensor["max_angle"]), int(sensor.get("line_of_sight", 1)),
+                           int(sensor.get("min_views", 1)), int(occ[0]), int(occ[1]), float(sensor.get("end_margin_m", 0.3)))
+
+
 def first_ray_for_yaw(yaw, delta_theta, camera_fov, n_yaw):
     """The window start i in [0, n_yaw - window], window = (int)(camera_fov / delta_theta), whose pose yaw
     i * delta_theta + camera_fov / 2 (DEP/src/CostCalculator.cpp:119) is nearest to `yaw` (the first of equally near ones)."""
@@ -1507,6 +1565,29 @@ def stations_along(poses_xy, spacing_m, look=10, delta_theta=0.10, camera_fov=1.
     st[:, :2] = p[keep]
     st[:, 2] = z
     return st, first, np.asarray(keep, dtype=np.int64)
+
+
+def poses_along(poses_xy, index, look=10, z=0.0):
+    """Pose rows for FrontierScorer.drive_slam from a pose list [N][2] and stations_along's `index`: station j stands at pose
+    index[j] and looks — a rotation about Z, quaternion xyzw — at the pose `look` entries ahead, by stations_along's direction rule
+    (the last pose when there are fewer; a station with nothing ahead keeps the yaw of the station before it, a lone one looks
+    along +x).  Host only, numpy.  Returns [n][7]."""
+    import math
+    p = np.asarray(poses_xy, dtype=np.float64)
+    p = p.reshape(-1, p.shape[-1])[:, :2] if p.size else p.reshape(0, 2)
+    n = p.shape[0]
+    keep = np.asarray(index, dtype=np.int64).reshape(-1)
+    out = np.zeros((keep.shape[0], 7))
+    yaw = 0.0
+    for j, i in enumerate(keep):
+        a = min(int(i) + int(look), n - 1)
+        dx, dy = p[a, 0] - p[i, 0], p[a, 1] - p[i, 1]
+        if dx != 0.0 or dy != 0.0:
+            yaw = math.atan2(dy, dx)
+        out[j, :2] = p[i]
+        out[j, 2] = z
+        out[j, 5], out[j, 6] = math.sin(yaw / 2), math.cos(yaw / 2)
+    return out
 
 
 def shard_bounds(n: int, n_shards: int, shard: int):

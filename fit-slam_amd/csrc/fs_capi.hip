@@ -257,6 +257,12 @@ struct fs_ctx {
     DevBuf<int32_t> d_wl_perm, d_wl_inv, d_wl_out, d_wl_blocks;
     DevBuf<uint32_t> d_wl_views;
     DevBuf<uint8_t> d_wl_flag;
+    // the gated drive (fs_drive_slam.hip): d_ds_out = fallbacks [1] | in_view [T] | voxels [T] | information [T]
+    // (float bits), what comes back; the slabs' partial sums; counters 1047 .. 1049: host waits of the last call, voxels per pose
+    // the LDS tier takes at most, workgroups that took the fallback tier
+    DevBuf<int32_t> d_ds_out;
+    DevBuf<double> d_ds_partial;
+    int64_t ds_waits = 0, ds_capacity = (int64_t)FS_GATE_SLABS * FS_GATE_SLOTS, ds_fallbacks = 0;
 
     // landmarks
     bool have_lm = false;
@@ -1861,9 +1867,31 @@ int fs_goals_mapped(fs_ctx *c, int32_t n, const double *goal_xyz, uint8_t *mappe
 // the one wait at the end reads every output.  d_drive_i32, T = all stations: n_stations [R] | first station [R] | state [R][2] |
 // union box [4] | station_status [T] | seen_unknown [T] | station boxes [T][4] | first_ray [T]; the part from `state` up to the
 // boxes is what comes back.
-int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32_t *n_stations, const int32_t *first_ray, const double *goal_xyz,
-             const fs_ray_params *sensor, const fs_drive_params *params, int32_t *status, int32_t *reached, int32_t *station_status,
-             int32_t *seen_unknown, int64_t *n_seen, int64_t *n_revealed, int32_t window[6])
+//
+// fs_drive_slam is the same drive with stations of `stride` 7 doubles (a pose each; fs_drive: 3) and a DriveSlam:
+// its own refusals after fs_drive's and before anything is written, its launches after every step's merge — the gate launch in
+// place of the goal launch — and its results behind the same wait.  The slam_* pieces stand with the landmark sensor's host code.
+}  // extern "C"
+
+struct DriveSlam {
+    const fs_landmark_sensor *lm_sensor;      // the caller's, or nullptr
+    float *information;                       // the caller's outputs, each may be nullptr
+    int32_t *voxels, *in_view, *n_new, *n_discovered;
+    fs_landmark_sensor s;                     // resolved by slam_check
+    fs_drive_slam_params p;                   // the caller's, or the defaults
+    FsDriveSlamArgs a;                        // filled by slam_begin
+    std::vector<float> Rt;                    // the stations' pose records, the host's until the drive's wait
+    size_t T;
+};
+static int slam_check(fs_ctx *c, DriveSlam &g);
+static int slam_begin(fs_ctx *c, DriveSlam &g, const double *pose7, size_t T, const FsDriveArgs &d);
+static int slam_step(fs_ctx *c, DriveSlam &g, int32_t k);
+static int slam_copy_back(fs_ctx *c, DriveSlam &g, std::vector<int32_t> &back);
+static int slam_end(fs_ctx *c, DriveSlam &g, const std::vector<int32_t> &back, const int32_t *station_status);
+
+static int drive_run(fs_ctx *c, int32_t n_robots, const double *station_xyz, int stride, const int32_t *n_stations, const int32_t *first_ray,
+                     const double *goal_xyz, const fs_ray_params *sensor, const fs_drive_params *params, int32_t *status, int32_t *reached,
+                     int32_t *station_status, int32_t *seen_unknown, int64_t *n_seen, int64_t *n_revealed, int32_t window[6], DriveSlam *slam)
 {
     if (!c || n_robots < 0 || (n_robots > 0 && (!station_xyz || !n_stations || !goal_xyz || !status || !reached || !station_status || !seen_unknown)))
         return FS_E_INVALID;
@@ -1881,8 +1909,20 @@ int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32
     }
     const fs_drive_params dp = params ? *params : fs_drive_params{253, 254, 1};
     FsDriveArgs a{};
-    if (const int rc = sweep_fan_setup(c, sensor, first_ray, T, a.sense, n_seen, n_revealed, window)) return rc;
-    if (R == 0) return FS_OK;
+    const double *dir_was = c->sense_dir.data();
+    if (const int rc = sweep_fan_setup(c, sensor, first_ray, T, a.sense, nullptr, nullptr, nullptr)) return rc;
+    if (slam) {
+        if (const int rc = slam_check(c, *slam)) return rc;
+        c->ds_waits = c->sense_dir.data() != dir_was ? 1 : 0;    // (a sensor whose direction table was not the one on the device)
+    }
+    if (n_seen) *n_seen = 0;
+    if (n_revealed) *n_revealed = 0;
+    if (window) std::fill(window, window + 6, 0);
+    if (R == 0) {
+        if (slam && slam->n_new) *slam->n_new = 0;
+        if (slam && slam->n_discovered) *slam->n_discovered = c->wl_discovered;
+        return FS_OK;
+    }
 
     if (const int rc = sweep_world_setup(c, sensor, a.sense)) return rc;
     // what a station can touch: its cell +- the fan's reach (an end point lies within depth of the pose, so its cell within
@@ -1898,7 +1938,7 @@ int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32
             off[r] = (int32_t)t;
             for (int32_t k = 0; k < n_stations[r]; ++k, ++t) {
                 int32_t mx = 0, my = 0;
-                if (grid_world_to_map(c, station_xyz[3 * t], station_xyz[3 * t + 1], mx, my))
+                if (grid_world_to_map(c, station_xyz[(size_t)stride * t], station_xyz[(size_t)stride * t + 1], mx, my))
                     cons[t] = Win{std::max(mx - reach, 0), std::max(my - reach, 0), std::min(mx + reach, c->nx - 1), std::min(my + reach, c->ny - 1)};
                 else
                     cons[t] = Win{c->nx, c->ny, -1, -1};
@@ -1919,7 +1959,7 @@ int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32
     }
     if (first_ray) std::copy(first_ray, first_ray + T, h.begin() + (std::ptrdiff_t)o_first);
     std::vector<double> xyz(3 * (T + R));
-    std::copy(station_xyz, station_xyz + 3 * T, xyz.begin());
+    for (size_t t = 0; t < T; ++t) std::copy(station_xyz + (size_t)stride * t, station_xyz + (size_t)stride * t + 3, xyz.begin() + (std::ptrdiff_t)(3 * t));
     std::copy(goal_xyz, goal_xyz + 3 * R, xyz.begin() + (std::ptrdiff_t)(3 * T));
     FS_HIP(c, c->d_drive_xyz.ensure(xyz.size())); FS_HIP(c, c->d_drive_i32.ensure(n_i32)); FS_HIP(c, c->d_sense_counts.ensure(4));
     FS_HIP(c, hipMemcpyAsync(c->d_drive_xyz.p, xyz.data(), xyz.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -1943,6 +1983,8 @@ int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32
     a.move_max_length = (double)c->nx + (double)c->ny;
     a.state = d + o_state; a.station_box = d + o_box; a.union_box = d + o_union;
     a.counts = c->d_sense_counts.p;
+    if (slam)
+        if (const int rc = slam_begin(c, *slam, station_xyz, T, a)) return rc;
 
     ++c->grid_gen;
     Win all{c->nx, c->ny, -1, -1};
@@ -1963,7 +2005,8 @@ int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32
             if (const int rc = ko_repaint_window(c, w.x0, w.y0, w.x1 - w.x0 + 1, w.y1 - w.y0 + 1)) return rc;
             all = Win{std::min(all.x0, w.x0), std::min(all.y0, w.y0), std::max(all.x1, w.x1), std::max(all.y1, w.y1)};
         }
-        if (dp.stop_when_mapped) FS_HIP(c, fs_launch_drive_goal(a, c->stream));
+        if (slam) { if (const int rc = slam_step(c, *slam, k)) return rc; }
+        else if (dp.stop_when_mapped) FS_HIP(c, fs_launch_drive_goal(a, c->stream));
     }
     // once, for everything the drive can have touched (an empty box where every station was off the map)
     if (const int rc = cells_changed_in_box(c, all.x0, all.y0, 0, all.x1 - all.x0 + 1, all.y1 - all.y0 + 1, 1)) return rc;
@@ -1971,6 +2014,9 @@ int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32
     unsigned long long counts[2] = {0ull, 0ull};
     FS_HIP(c, hipMemcpyAsync(back.data(), d + o_state, n_back * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     FS_HIP(c, hipMemcpyAsync(counts, c->d_sense_counts.p, sizeof counts, hipMemcpyDeviceToHost, c->stream));
+    std::vector<int32_t> slam_back;
+    if (slam)
+        if (const int rc = slam_copy_back(c, *slam, slam_back)) return rc;
     FS_HIP(c, hipStreamSynchronize(c->stream));                  // (the one wait of the call)
     c->sense_mark_clean = true;
     ++c->epoch;
@@ -1985,7 +2031,17 @@ int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32
     if (n_seen) *n_seen = (int64_t)counts[0];
     if (n_revealed) *n_revealed = (int64_t)counts[1];
     if (window && ub[2] >= ub[0]) { window[0] = ub[0]; window[1] = ub[1]; window[2] = 0; window[3] = ub[2] - ub[0] + 1; window[4] = ub[3] - ub[1] + 1; window[5] = 1; }
-    return FS_OK;
+    return slam ? slam_end(c, *slam, slam_back, station_status) : FS_OK;
+}
+
+extern "C" {
+
+int fs_drive(fs_ctx *c, int32_t n_robots, const double *station_xyz, const int32_t *n_stations, const int32_t *first_ray, const double *goal_xyz,
+             const fs_ray_params *sensor, const fs_drive_params *params, int32_t *status, int32_t *reached, int32_t *station_status,
+             int32_t *seen_unknown, int64_t *n_seen, int64_t *n_revealed, int32_t window[6])
+{
+    return drive_run(c, n_robots, station_xyz, 3, n_stations, first_ray, goal_xyz, sensor, params, status, reached, station_status, seen_unknown,
+                     n_seen, n_revealed, window, nullptr);
 }
 
 int fs_grid_census(fs_ctx *c, int64_t counts[4])
@@ -2790,6 +2846,9 @@ int fs_get_counter(fs_ctx *c, int which, int64_t *value, int reset)
         // the REFERENCE refine search, of the last call under it: searches, slot batches, nodes popped, line-of-sight walks, largest heap
         {1042, &fs_ctx::rs_searches, false}, {1043, &fs_ctx::rs_batches, false}, {1044, &fs_ctx::rs_pops, false},
         {1045, &fs_ctx::rs_walks, false}, {1046, &fs_ctx::rs_max_heap, false},
+        // the gated drive (fs_drive_slam): host waits of the last call, occupied voxels per pose its LDS tier takes at most, workgroups
+        // that took the fallback tier
+        {1047, &fs_ctx::ds_waits, false}, {1048, &fs_ctx::ds_capacity, false}, {1049, &fs_ctx::ds_fallbacks, true},
     };
     // ... its waves, the waves that ended on the cycle budget, the waves that dropped a push at the cap and the chunks run again, of
     // the last call: they stay on the device until asked for
@@ -3348,6 +3407,136 @@ static int wl_restage(fs_ctx *c, int32_t n_disc, int32_t n_usable)
     return FS_OK;
 }
 
+// a landmark sensor as fs_sense_landmarks and fs_drive_slam take it: the caller's, or the context's defaults; refused with nothing written
+static int lm_sensor_resolve(fs_ctx *c, const fs_landmark_sensor *sensor, fs_landmark_sensor &s)
+{
+    if (sensor) s = *sensor;
+    else s = fs_landmark_sensor{c->fp.max_dist, c->fp.max_angle, c->have_world ? 1 : 0, 1, c->occ.occ_min, c->occ.occ_max, c->occ.end_margin_m};
+    if (!(s.max_dist > 0.0) || !(s.max_angle > 0.0)) return fail(c, FS_E_INVALID, "sensor: max_dist and max_angle must be positive");
+    if (!(s.max_dist < 1.0e9)) return fail(c, FS_E_INVALID, "sensor: max_dist must be below 1e9 m");
+    if (s.line_of_sight != 0 && s.line_of_sight != 1) return fail(c, FS_E_INVALID, "sensor: line_of_sight must be 0 or 1");
+    if (s.min_views < 1) return fail(c, FS_E_INVALID, "sensor: min_views must be at least 1");
+    if (s.occ_min < 0 || s.occ_max > 255 || s.occ_min > s.occ_max) return fail(c, FS_E_INVALID, "sensor: occ_min / occ_max must be costs 0..255 with occ_min <= occ_max");
+    if (!(s.end_margin_m >= 0.0) || !(s.end_margin_m < 1.0e6)) return fail(c, FS_E_INVALID, "sensor: end_margin_m must be finite, >= 0 and below 1e6 m");
+    return FS_OK;
+}
+
+// the world cloud, the sensor's volume and its line of sight through the WORLD grid, as the sweep kernels read them
+static void lm_sweep_args(fs_ctx *c, const fs_landmark_sensor &s, bool unit, int64_t poses, FsLandmarkSenseArgs &a)
+{
+    float cos_a, sin_a;
+    fim_volume(s.max_dist, s.max_angle, a.maxd2, a.max_dist_f, a.cos2, a.cone_mode, cos_a, sin_a);
+    a.cull = (unit && c->opt_cull) ? 1 : 0;
+    a.lx = c->d_wl_lx.p; a.ly = c->d_wl_ly.p; a.lz = c->d_wl_lz.p; a.spheres = c->d_wl_spheres.p; a.perm = c->d_wl_perm.p;
+    a.n_chunks = c->wl_chunks; a.m_world = c->wl_m;
+    a.group = chunks_per_wave(poses, c->wl_chunks);
+    a.los = s.line_of_sight;
+    if (a.los) {
+        a.world = world_dev(c);
+        a.occ_min = s.occ_min; a.occ_max = s.occ_max;
+        a.occ_margin = occlusion_margin(c, s.end_margin_m);
+    }
+    a.views = c->d_wl_views.p;
+}
+
+// ---- the gated drive's share of drive_run (fs_drive_slam)
+
+// its refusals, after fs_drive's and before anything is written
+static int slam_check(fs_ctx *c, DriveSlam &g)
+{
+    if (!c->have_wl) return fail(c, FS_E_STATE, "fs_upload_world_landmarks has not been called");
+    if (!c->have_table) return fail(c, FS_E_STATE, "no lookup table: call fs_lookup_generate / fs_lookup_load");
+    if (const int rc = lm_sensor_resolve(c, g.lm_sensor, g.s)) return rc;
+    if (g.p.gate != 0 && g.p.gate != 1) return fail(c, FS_E_INVALID, "gate must be 0 or 1");
+    if (g.p.gate_first_station < 0) return fail(c, FS_E_INVALID, "gate_first_station must not be negative");
+    if (!std::isfinite(g.p.information_threshold)) return fail(c, FS_E_INVALID, "information_threshold must be finite");
+    return FS_OK;
+}
+
+// the pose records of all stations (made once: every pose is known before the call), the sweep's and the gate's arguments, the
+// outputs' presets.  d: the drive's arguments, complete.
+static int slam_begin(fs_ctx *c, DriveSlam &g, const double *pose7, size_t T, const FsDriveArgs &d)
+{
+    const size_t R = (size_t)d.n_robots;
+    g.T = T;
+    g.Rt.resize(T * 12);
+    const bool unit = poses_to_rt(pose7, (int32_t)T, g.Rt.data());
+    FsDriveSlamArgs &a = g.a;
+    a = FsDriveSlamArgs{};
+    lm_sweep_args(c, g.s, unit, (int64_t)R, a.sweep);
+    FsFimArgs fa{};
+    if (const int rc = fill_fim_args(c, fa)) return rc;
+    const size_t n_blocks = ((size_t)std::max(c->wl_m, 1) + 255) / 256;
+    FS_HIP(c, c->d_wl_Rt.ensure(T * 12)); FS_HIP(c, c->d_wl_out.ensure(4)); FS_HIP(c, c->d_wl_blocks.ensure(4 * n_blocks));
+    FS_HIP(c, c->d_ds_out.ensure(1 + 3 * T)); FS_HIP(c, c->d_ds_partial.ensure(R * FS_GATE_SLABS * 2));
+    FS_HIP(c, hipMemcpyAsync(c->d_wl_Rt.p, g.Rt.data(), sizeof(float) * 12 * T, hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, hipMemsetAsync(c->d_ds_out.p, 0, sizeof(int32_t) * (1 + 3 * T), c->stream));
+    FS_HIP(c, hipMemsetAsync(c->d_wl_out.p, 0, sizeof(int32_t), c->stream));             // newly discovered: summed over the steps
+    int32_t *const o = c->d_ds_out.p;
+    a.sweep.Rt = c->d_wl_Rt.p; a.sweep.n = (int32_t)T; a.sweep.n_in_view = o + 1;
+    a.n_robots = d.n_robots; a.n_stations = d.n_stations; a.station_off = d.station_off; a.state = d.state; a.goal = d.goal;
+    a.staged = d.staged;
+    a.stop_when_mapped = g.p.stop_when_mapped;
+    a.flag = c->d_wl_flag.p;
+    a.cull = (unit && fa.cull) ? 1 : 0;
+    a.max_dist_f = fa.max_dist_f; a.maxd2 = fa.maxd2; a.cos2 = fa.cos2; a.cone_mode = fa.cone_mode;
+    a.table = fa.table; a.jx0 = fa.jx0; a.jy0 = fa.jy0; a.jz0 = fa.jz0; a.tx = fa.tx; a.ty = fa.ty; a.tz = fa.tz; a.inv_step = fa.inv_step;
+    a.table_full = fa.table_full; a.factor = fa.factor;
+    a.occluded = c->occ.enabled != 0 ? 1 : 0;
+    a.occ_min = c->occ.occ_min; a.occ_max = c->occ.occ_max; a.occ_margin = occlusion_margin(c, c->occ.end_margin_m);
+    a.partial = c->d_ds_partial.p;
+    a.voxels = o + 1 + T; a.information = reinterpret_cast<float *>(o + 1 + 2 * T); a.fallbacks = o;
+    a.threshold = g.p.information_threshold; a.gate = g.p.gate; a.gate_first = g.p.gate_first_station;
+    return FS_OK;
+}
+
+// steps 3b, 3c, 4 and 5 of step k, behind the step's merge
+static int slam_step(fs_ctx *c, DriveSlam &g, int32_t k)
+{
+    const size_t n_blocks = ((size_t)std::max(c->wl_m, 1) + 255) / 256;
+    g.a.step = k;
+    FS_HIP(c, fs_launch_drive_slam_sweep(g.a, c->stream));
+    FS_HIP(c, hipMemsetAsync(c->d_wl_out.p + 1, 0, 2 * sizeof(int32_t), c->stream));     // discovered, usable: the step's totals
+    FS_HIP(c, fs_launch_landmark_flags(c->d_wl_raw.p, c->d_wl_views.p, c->d_wl_flag.p, c->wl_m, (uint32_t)g.s.min_views, c->d_wl_blocks.p,
+                                       c->d_wl_blocks.p + 2 * n_blocks, c->d_wl_out.p, c->stream));
+    FS_HIP(c, fs_launch_drive_slam_info(g.a, c->stream));
+    FS_HIP(c, fs_launch_drive_slam_gate(g.a, c->stream));
+    return FS_OK;
+}
+
+// back = totals [3] | d_ds_out, on their way
+static int slam_copy_back(fs_ctx *c, DriveSlam &g, std::vector<int32_t> &back)
+{
+    back.assign(4 + 3 * g.T, 0);
+    FS_HIP(c, hipMemcpyAsync(back.data(), c->d_wl_out.p, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipMemcpyAsync(back.data() + 3, c->d_ds_out.p, (1 + 3 * g.T) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    return FS_OK;
+}
+
+// after the drive's wait: the staged cloud becomes the discovered set once, by fs_sense_landmarks' rule; then the outputs
+static int slam_end(fs_ctx *c, DriveSlam &g, const std::vector<int32_t> &back, const int32_t *station_status)
+{
+    const size_t T = g.T;
+    ++c->ds_waits;                                               // (the drive's own)
+    c->ds_fallbacks += back[3];
+    if (back[1] < 0 || back[1] > c->wl_m || back[2] < 0 || back[2] > back[1])
+        return fail(c, FS_E_HIP, "fs_drive_slam: %d discovered, %d usable of %d world landmarks", back[1], back[2], c->wl_m);
+    c->wl_discovered = back[1];
+    if (back[0] > 0 || !c->wl_staged) {
+        if (const int rc = wl_restage(c, back[1], back[2])) return rc;
+        ++c->ds_waits;                                           // (order_cloud_on_device's)
+    }
+    const int32_t *in_view = back.data() + 4, *voxels = in_view + T, *info = voxels + T;
+    for (size_t t = 0; t < T; ++t) {
+        if (g.in_view) g.in_view[t] = station_status[t] == -1 ? -1 : in_view[t];
+        if (g.voxels) g.voxels[t] = voxels[t];
+        if (g.information) std::memcpy(g.information + t, info + t, sizeof(float));
+    }
+    if (g.n_new) *g.n_new = back[0];
+    if (g.n_discovered) *g.n_discovered = back[1];
+    return FS_OK;
+}
+
 static void drop_world_landmarks(fs_ctx *c)
 {
     c->have_wl = false; c->wl_staged = false;
@@ -3394,14 +3583,7 @@ int fs_sense_landmarks(fs_ctx *c, int32_t n, const double *pose7, const fs_landm
 {
     if (!c || n < 0 || (n > 0 && !pose7)) return FS_E_INVALID;
     fs_landmark_sensor s;
-    if (sensor) s = *sensor;
-    else s = fs_landmark_sensor{c->fp.max_dist, c->fp.max_angle, c->have_world ? 1 : 0, 1, c->occ.occ_min, c->occ.occ_max, c->occ.end_margin_m};
-    if (!(s.max_dist > 0.0) || !(s.max_angle > 0.0)) return fail(c, FS_E_INVALID, "sensor: max_dist and max_angle must be positive");
-    if (!(s.max_dist < 1.0e9)) return fail(c, FS_E_INVALID, "sensor: max_dist must be below 1e9 m");
-    if (s.line_of_sight != 0 && s.line_of_sight != 1) return fail(c, FS_E_INVALID, "sensor: line_of_sight must be 0 or 1");
-    if (s.min_views < 1) return fail(c, FS_E_INVALID, "sensor: min_views must be at least 1");
-    if (s.occ_min < 0 || s.occ_max > 255 || s.occ_min > s.occ_max) return fail(c, FS_E_INVALID, "sensor: occ_min / occ_max must be costs 0..255 with occ_min <= occ_max");
-    if (!(s.end_margin_m >= 0.0) || !(s.end_margin_m < 1.0e6)) return fail(c, FS_E_INVALID, "sensor: end_margin_m must be finite, >= 0 and below 1e6 m");
+    if (const int rc = lm_sensor_resolve(c, sensor, s)) return rc;
     FS_HIP(c, hipSetDevice(c->device));
     if (!c->have_wl) return fail(c, FS_E_STATE, "fs_upload_world_landmarks has not been called");
     if (s.line_of_sight && (!c->have_grid || !c->have_world)) return fail(c, FS_E_STATE, "line_of_sight needs a world grid (fs_upload_world)");
@@ -3413,22 +3595,11 @@ int fs_sense_landmarks(fs_ctx *c, int32_t n, const double *pose7, const fs_landm
 
     const size_t nn = (size_t)n;
     FsLandmarkSenseArgs a{};
-    float cos_a, sin_a;
-    fim_volume(s.max_dist, s.max_angle, a.maxd2, a.max_dist_f, a.cos2, a.cone_mode, cos_a, sin_a);
     std::vector<float> Rt(nn * 12);
-    a.cull = (poses_to_rt(pose7, n, Rt.data()) && c->opt_cull) ? 1 : 0;
-    a.lx = c->d_wl_lx.p; a.ly = c->d_wl_ly.p; a.lz = c->d_wl_lz.p; a.spheres = c->d_wl_spheres.p; a.perm = c->d_wl_perm.p;
-    a.n_chunks = c->wl_chunks; a.m_world = c->wl_m;
+    lm_sweep_args(c, s, poses_to_rt(pose7, n, Rt.data()), n, a);
     a.n = n;
-    a.group = chunks_per_wave(n, c->wl_chunks);
-    a.los = s.line_of_sight;
-    if (a.los) {
-        a.world = world_dev(c);
-        a.occ_min = s.occ_min; a.occ_max = s.occ_max;
-        a.occ_margin = occlusion_margin(c, s.end_margin_m);
-    }
     FS_HIP(c, c->d_wl_Rt.ensure(nn * 12)); FS_HIP(c, c->d_wl_out.ensure(3 + nn));
-    a.Rt = c->d_wl_Rt.p; a.views = c->d_wl_views.p; a.n_in_view = c->d_wl_out.p + 3;
+    a.Rt = c->d_wl_Rt.p; a.n_in_view = c->d_wl_out.p + 3;
     FS_HIP(c, hipMemcpyAsync(c->d_wl_Rt.p, Rt.data(), sizeof(float) * 12 * nn, hipMemcpyHostToDevice, c->stream));
     FS_HIP(c, hipMemsetAsync(c->d_wl_out.p + 3, 0, sizeof(int32_t) * nn, c->stream));
     FS_HIP(c, fs_launch_sense_landmarks(a, c->stream));
@@ -3486,6 +3657,21 @@ int fs_staged_cloud_get(fs_ctx *c, int32_t *m, int32_t *n_chunks, float *soa, fl
     if (m) *m = c->m;
     if (n_chunks) *n_chunks = c->n_chunks;
     return FS_OK;
+}
+
+int fs_drive_slam(fs_ctx *c, int32_t n_robots, const double *station_pose7, const int32_t *n_stations, const int32_t *first_ray, const double *goal_xyz,
+                  const fs_ray_params *sensor, const fs_landmark_sensor *lm_sensor, const fs_drive_slam_params *params, int32_t *status,
+                  int32_t *reached, int32_t *station_status, int32_t *seen_unknown, float *station_information, int32_t *station_voxels,
+                  int32_t *station_in_view, int64_t *n_seen, int64_t *n_revealed, int32_t window[6], int32_t *n_new, int32_t *n_discovered)
+{
+    DriveSlam g{};
+    g.lm_sensor = lm_sensor;
+    g.p = params ? *params : fs_drive_slam_params{253, 254, 1, 1, 550.0, 1};
+    g.information = station_information; g.voxels = station_voxels; g.in_view = station_in_view;
+    g.n_new = n_new; g.n_discovered = n_discovered;
+    const fs_drive_params dp{g.p.block_min, g.p.block_max, g.p.stop_when_mapped};
+    return drive_run(c, n_robots, station_pose7, 7, n_stations, first_ray, goal_xyz, sensor, &dp, status, reached, station_status, seen_unknown,
+                     n_seen, n_revealed, window, &g);
 }
 
 int fs_information_frontier_pair(fs_ctx *c, int32_t n, const double *est_pose7, const double *triangle_xy, float *information)

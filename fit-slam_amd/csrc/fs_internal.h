@@ -816,6 +816,51 @@ hipError_t fs_launch_landmark_flags(const float *d_raw, const uint32_t *d_views,
 hipError_t fs_launch_landmark_scatter(const float *d_raw, const uint8_t *d_flag, int32_t m_world, const int32_t *d_block_off, int32_t n_disc,
                                       int32_t n_usable, float *d_raw_out, int32_t *d_usable_out, hipStream_t s);
 
+// ---- a drive gated on Fisher information (fs_drive_slam; fs_drive_slam.hip)
+// After fs_drive's step and merge launches of step k, for the robots that swept in it (still FS_DRIVE_DRIVING, with a station k):
+//   sweep — one wavefront per (robot, group of chunks): landmark_sweep_group from the robot's station-k pose record; the station's
+//           in_view += landmarks seen.  (fs_launch_landmark_flags follows, by the caller.)
+//   info  — FS_GATE_SLABS workgroups per robot: isPoseSafe's scalar of the station's pose straight from the WORLD cloud, counting
+//           only landmarks flagged discovered; workgroup w owns the voxels whose table x index is w modulo FS_GATE_SLABS, counts
+//           them in an LDS hash table of FS_GATE_SLOTS slots and, when that runs full, again in passes over ranges of its voxels'
+//           indices (fallbacks [0] += 1); partial [robot][slab][2] = information, occupied voxels.
+//   gate  — one lane per robot, in place of fs_drive's goal launch: the partial sums in slab order -> information / voxels of the
+//           station; then MAPPED (stop_when_mapped), else UNSAFE when gated and not information > threshold.
+#define FS_GATE_SLABS 8
+#define FS_GATE_SLOTS 2048
+struct FsDriveSlamArgs {
+    FsLandmarkSenseArgs sweep;     // the world cloud and the sensor's volume as fs_sense_landmarks fills them; Rt = [total][12] pose
+                                   // records of all stations, n_in_view [total] (zero-based sums); n is not used
+    int32_t n_robots, step;
+    const int32_t *n_stations;     // [R]
+    const int32_t *station_off;    // [R]
+    int32_t *state;                // [R][2], FsDriveArgs::state
+    const double *goal;            // [R][3]
+    FsGridDev staged;              // the staged grid: the goal test and, with occlusion, the gate's line of sight
+    int32_t stop_when_mapped;
+    // the gate's view: fs_set_fim_params' volume, the lookup table and fs_set_occlusion of the context (FsFimArgs' fields)
+    const uint8_t *flag;           // [m_world] discovered
+    int32_t cull;
+    float max_dist_f, maxd2, cos2;
+    int32_t cone_mode;
+    const float *table;
+    int32_t jx0, jy0, jz0, tx, ty, tz;
+    double inv_step;
+    int32_t table_full;
+    const float *factor;           // [FS_FACTOR_N]
+    int32_t occluded, occ_min, occ_max;
+    uint32_t occ_margin;
+    double *partial;               // [R][FS_GATE_SLABS][2]
+    float *information;            // [total]
+    int32_t *voxels;               // [total]
+    int32_t *fallbacks;            // [1]
+    double threshold;
+    int32_t gate, gate_first;
+};
+hipError_t fs_launch_drive_slam_sweep(const FsDriveSlamArgs &a, hipStream_t s);
+hipError_t fs_launch_drive_slam_info(const FsDriveSlamArgs &a, hipStream_t s);
+hipError_t fs_launch_drive_slam_gate(const FsDriveSlamArgs &a, hipStream_t s);
+
 // ---- FIM kernel arguments ---------------------------------------------------------------------
 struct FsFimArgs {
     // landmarks: SoA in k-d leaf order, n_chunks chunks of 64 (the tail padded with far-away sentinels),

@@ -2,7 +2,8 @@
 // 4.23).  This project's own extension, like fs_sense.hip: in the reference the map points come from the ORB-SLAM3 wrapper, which
 // is outside the vendored tree.  A WORLD cloud lives in HBM in a k-d leaf order of its own (fs_cloud.hip) beside one sighting
 // counter and one `discovered` flag per landmark; the staged cloud is the discovered part, put in order again on the device.
-//   sweep   — one wave per (pose, group of chunks), as fs_view_mark_kernel: the world cloud's spheres against the range sphere
+//   sweep   — one wave per (pose, group of chunks), as fs_view_mark_kernel (landmark_sweep_group, fs_sense_landmarks_dev.h): the
+//             world cloud's spheres against the range sphere
 //             (conservative), then the exact transform and predicate (fs_view.h) on the 64 landmarks of every accepted chunk and —
 //             with line_of_sight — the walk of fs_walk.h through the WORLD grid for the lanes the predicate accepts.  A seeing
 //             lane adds 1 to its landmark's counter; the wave adds popcount(ballot) to the pose's n_in_view once.  Integer sums
@@ -13,8 +14,7 @@
 //   scatter — one lane per world landmark again: a block prefix ranks every discovered landmark; its raw xyz goes to
 //             raw_out[rank] (ascending world index) and, when usable, its rank to usable_out — what the cloud ordering starts from.
 #include "fs_internal.h"
-#include "fs_walk.h"
-#include "fs_view.h"
+#include "fs_sense_landmarks_dev.h"   // one wave's share of a sweep, shared with fs_drive_slam.hip
 
 namespace {
 
@@ -26,45 +26,7 @@ void fs_sense_landmarks_kernel(const FsLandmarkSenseArgs a)
     const long long item = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
     if (item >= (long long)a.n * groups) return;
     const int pose = (int)(item / groups), grp = (int)(item % groups);
-    float Rt[12];
-    {
-        const float *src = a.Rt + 12 * (size_t)pose;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) Rt[k] = src[k];
-    }
-    // ---- cull: lane l < group holds chunk grp * group + l (fs_view_mark_kernel's test; an empty chunk's radius is -1e30)
-    bool accept = false;
-    {
-        const int j = grp * a.group + lane;
-        if (lane < a.group && j < a.n_chunks) {
-            if (!a.cull) accept = true;
-            else {
-                const float4 s = *reinterpret_cast<const float4 *>(a.spheres + 4 * (size_t)j);
-                const float dx = s.x - Rt[9], dy = s.y - Rt[10], dz = s.z - Rt[11];
-                const float d2 = dx * dx + dy * dy + dz * dz;
-                const float reach = a.max_dist_f + s.w;
-                accept = fminf(reach, reach * reach - d2) >= 0.0f;
-            }
-        }
-    }
-    unsigned long long todo = __ballot(accept);
-    const FsViewVis vis_p{a.maxd2, a.cos2, a.cone_mode};
-    int seen = 0;                                                    // (wave-uniform)
-    while (todo != 0ull) {
-        const int b = __builtin_ctzll(todo);
-        todo &= todo - 1ull;
-        const int slot = (grp * a.group + b) * FS_CHUNK + lane;      // < n_chunks * 64: the arrays are padded to whole chunks
-        const float wx = a.lx[slot], wy = a.ly[slot], wz = a.lz[slot];
-        float px, py, pz;
-        bool vis = fs_view_transform_visible(Rt, vis_p, wx, wy, wz, px, py, pz);
-        const int32_t i = a.perm[slot];
-        vis = vis && (uint32_t)i < (uint32_t)a.m_world;              // (a sentinel never passes the predicate; -1 names no landmark)
-        if (a.los && vis)
-            vis = !line_of_sight(a.world, (double)Rt[9], (double)Rt[10], (double)Rt[11], (double)wx, (double)wy, (double)wz,
-                                 a.occ_min, a.occ_max, a.occ_margin).blocked;
-        if (vis) atomicAdd(a.views + i, 1u);
-        seen += __popcll(__ballot(vis));
-    }
+    const int seen = landmark_sweep_group(a, a.Rt + 12 * (size_t)pose, grp, lane);
     if (lane == 0 && seen != 0) atomicAdd(a.n_in_view + pose, seen);
 }
 

@@ -31,6 +31,21 @@ __device__ __forceinline__ bool fs_view_transform_visible(const float *Rt, const
     return vis;
 }
 
+// The dense table's cell of a camera-frame point: round(x * (1 / step)) of getVoxelCoordinate (FisherInfoManager.hpp:119-121) in
+// fp64, as fs_lookup_query's host form — what the FIM worker's fp32 fast path (fs_fim.hip, voxel_key) is proven equal to; compared
+// as doubles, so no index leaves the range of an integer before it is known to be in the table.  A: any argument struct with
+// FsFimArgs' jx0 .. tz and inv_step.  False: the voxel lies outside the table's box.
+template <typename A>
+__device__ __forceinline__ bool fs_view_table_cell(const A &a, float px, float py, float pz, int &ix, int &iy, int &iz)
+{
+    const double rx = round((double)px * a.inv_step) - (double)a.jx0;
+    const double ry = round((double)py * a.inv_step) - (double)a.jy0;
+    const double rz = round((double)pz * a.inv_step) - (double)a.jz0;
+    if (!(rx >= 0.0 && rx < (double)a.tx && ry >= 0.0 && ry < (double)a.ty && rz >= 0.0 && rz < (double)a.tz)) return false;
+    ix = (int)rx; iy = (int)ry; iz = (int)rz;
+    return true;
+}
+
 }  // namespace
 
 #endif  // FS_VIEW_H_

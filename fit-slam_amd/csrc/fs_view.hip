@@ -176,13 +176,9 @@ void fs_view_emit_kernel(const FsViewArgs a)
                 float px, py, pz;
                 (void)fs_view_transform_visible(Rt, vis_p, a.lx[slot], a.ly[slot], a.lz[slot], px, py, pz);
                 e.p_camera[0] = px; e.p_camera[1] = py; e.p_camera[2] = pz;
-                // round(x * (1 / step)) of getVoxelCoordinate (FisherInfoManager.hpp:119-121) in fp64, as fs_lookup_query's host
-                // form; compared as doubles, so no index leaves the range of an integer before it is known to be in the table
-                const double rx = round((double)px * a.inv_step) - (double)a.jx0;
-                const double ry = round((double)py * a.inv_step) - (double)a.jy0;
-                const double rz = round((double)pz * a.inv_step) - (double)a.jz0;
-                if (rx >= 0.0 && rx < (double)a.tx && ry >= 0.0 && ry < (double)a.ty && rz >= 0.0 && rz < (double)a.tz)
-                    e.table_value = a.table[((size_t)(int)rx * (size_t)a.ty + (size_t)(int)ry) * (size_t)a.tz + (size_t)(int)rz];
+                int ix, iy, iz;
+                if (fs_view_table_cell(a, px, py, pz, ix, iy, iz))
+                    e.table_value = a.table[((size_t)ix * (size_t)a.ty + (size_t)iy) * (size_t)a.tz + (size_t)iz];
             }
             a.out[pos] = e;
             ++pos;

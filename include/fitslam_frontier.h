@@ -1001,7 +1001,7 @@ int fs_grid_census(fs_ctx *ctx, int64_t counts[4] /* known (!= 255), unknown (==
  * Decided before anything is written: no grid, no world, no ray parameters (and no sensor): FS_E_STATE; nz > 1, a first_ray
  * outside [-1, n_yaw - window], n_stations[r] < 1 or > FS_DRIVE_MAX_STATIONS, n_robots > FS_DRIVE_MAX_ROBOTS: FS_E_INVALID.
  * n_robots == 0: a no-op.  params == NULL: block 253..254 (isConnectable's visitor), stop_when_mapped 1.  Landmarks are not
- * sensed on the way: run fs_sense_landmarks on the reached stations afterwards. */
+ * sensed on the way: run fs_sense_landmarks on the reached stations afterwards, or drive with fs_drive_slam (below). */
 #define FS_DRIVE_ARRIVED  0   /* out of stations */
 #define FS_DRIVE_BLOCKED  1   /* the staged map shows something in the block range on the next segment */
 #define FS_DRIVE_COLLIDED 2   /* only the world does */
@@ -1091,6 +1091,58 @@ int fs_world_landmarks_get(fs_ctx *ctx, int32_t *m_world, int32_t *n_discovered,
  * fs_read_grid_region: what two routes that claim to stage the same cloud (fs_upload_landmarks with the device ordering,
  * fs_sense_landmarks) are held to, byte for byte — the Fisher float sums are not bit-stable from call to call even on one cloud.  No cloud staged: FS_E_STATE. */
 int fs_staged_cloud_get(fs_ctx *ctx, int32_t *m, int32_t *n_chunks, float *soa, float *spheres, int32_t *perm);
+
+/* ---------------------------------------------------------------- a drive gated on Fisher information (closed loop)
+ *
+ * THIS PROJECT'S OWN EXTENSION, fs_drive with the behaviour FIT-SLAM is named for: in the reference the robot evaluates isPoseSafe
+ * at its current pose on every behaviour-tree iteration while it is under way (EvaluateFisherInformation), and an unsafe pose ends
+ * the goal.  fs_drive_slam is fs_drive — same stations, moves, sweeps, merges, goal test, outputs and refusals — whose stations
+ * are POSES: station_pose7 [sum n_stations][7] = xyz + quaternion xyzw; the xyz part is fs_drive's station_xyz, the full pose
+ * (through getTransformFromPose, as fs_sense_landmarks and fs_score_fim convert it) is what the landmark sensor and the gate use.
+ * After fs_drive's steps 1 move, 2 sense and 3 merge of step k, for the robots that sensed in this step:
+ *   3b landmark sweep  exactly as ONE fs_sense_landmarks call with lm_sensor over those robots' station-k poses: +1 per sighting,
+ *                      station_in_view = that call's n_in_view, a landmark whose counter reaches min_views is discovered for
+ *                      good, line_of_sight walks the WORLD grid.  All robots' sightings of the step land before anybody is scored.
+ *   3c information     station_information / station_voxels = what fs_score_fim returns as info_ref / n_voxels for the pose on a
+ *                      context whose staged cloud is the set discovered after 3b, whose staged grid is this context's after step
+ *                      3's merge and whose fs_set_fim_params, lookup table and fs_set_occlusion are this context's (with
+ *                      occlusion enabled: the line-of-sight rule on the STAGED grid).  The integer is equal; the float agrees to
+ *                      rounding (fs_score_fim's own sums are not bit-stable from call to call).
+ *   4  goal            as fs_drive: FS_DRIVE_MAPPED.
+ *   5  gate            with gate != 0 and k >= gate_first_station, a robot still driving whose information is not
+ *                      > information_threshold (isPoseSafe's `total > threshold`, on the float reported) stops at station k,
+ *                      FS_DRIVE_UNSAFE.  MAPPED wins over UNSAFE in the same step.  Stations before gate_first_station are swept
+ *                      and reported but never stop the robot (the reference spins in place to initialise before it judges).
+ * After the last step the staged cloud becomes the discovered set ONCE, by fs_sense_landmarks' restaging rule (something was
+ * discovered, or the staged cloud is not currently that set); the steps themselves read the world cloud and its flags and never
+ * restage.  *n_new / *n_discovered are fs_sense_landmarks' figures for the whole call.  The host waits once for the drive and
+ * once more when it restages, however many stations and robots.
+ * station_information, station_voxels, station_in_view: one entry per station, 0, 0 and -1 for a station never reached; each may
+ * be NULL, and so may n_new and n_discovered.  Marking the zone lethal after an UNSAFE stop (fs_mark_lethal_fov) is the caller's step.
+ * params == NULL: fs_drive's defaults, threshold 550.0 (the value the reference's plugin constructor forces), gate 1,
+ * gate_first_station 1.  lm_sensor == NULL: fs_sense_landmarks' defaults.
+ * Refused before anything is written, counters included, in this order: fs_drive's refusals; no world cloud: FS_E_STATE; no lookup
+ * table: FS_E_STATE; an invalid lm_sensor (as fs_sense_landmarks refuses it), gate other than 0 / 1, gate_first_station < 0 or a
+ * non-finite threshold: FS_E_INVALID.  n_robots == 0: a no-op, *n_new = 0, *n_discovered = the total as it stands. */
+#define FS_DRIVE_UNSAFE   5   /* the pose's information is not above the threshold (fs_drive_slam) */
+
+typedef struct fs_drive_slam_params {
+    int32_t block_min, block_max;  /* fs_drive_params' fields */
+    int32_t stop_when_mapped;
+    int32_t gate;                  /* 0: sweep and report, never stop for information; 1: stop */
+    double  information_threshold;
+    int32_t gate_first_station;    /* stations with a smaller index never stop the robot */
+} fs_drive_slam_params;
+
+int fs_drive_slam(fs_ctx *ctx, int32_t n_robots, const double *station_pose7 /* [sum n_stations][7] */, const int32_t *n_stations /* [n_robots] */,
+                  const int32_t *first_ray /* [sum n_stations] or NULL */, const double *goal_xyz /* [n_robots][3] */,
+                  const fs_ray_params *sensor /* NULL: the context's ray parameters */, const fs_landmark_sensor *lm_sensor /* NULL: see above */,
+                  const fs_drive_slam_params *params /* NULL: the defaults */,
+                  int32_t *status /* [n_robots] */, int32_t *reached /* [n_robots] */, int32_t *station_status /* [sum n_stations] */,
+                  int32_t *seen_unknown /* [sum n_stations] */, float *station_information /* [sum n_stations] or NULL */,
+                  int32_t *station_voxels /* [sum n_stations] or NULL */, int32_t *station_in_view /* [sum n_stations] or NULL */,
+                  int64_t *n_seen, int64_t *n_revealed, int32_t window[6] /* x0 y0 z0 sx sy sz, may be NULL */,
+                  int32_t *n_new /* or NULL */, int32_t *n_discovered /* or NULL */);
 
 #ifdef __cplusplus
 }

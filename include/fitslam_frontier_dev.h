@@ -100,7 +100,10 @@ int  fs_set_option(fs_ctx *ctx, const char *key, double value);
  * 1042 .. 1046 = the REFERENCE refine search (fs_set_refine_search) in the last fs_refine_paths under it: 1042 = searches run (its
  * distinct (start cell, goal cell) pairs on the map), 1043 = slot batches, 1044 = nodes popped, summed over the searches, 1045 =
  * line-of-sight walks (one per expanded node), summed, 1046 = the largest heap of any search (all five 0 on a context that never
- * refined under FS_REFINE_SEARCH_REFERENCE). */
+ * refined under FS_REFINE_SEARCH_REFERENCE);
+ * 1047 .. 1049 = the gated drive (fs_drive_slam): 1047 = host waits of the last call (the drive's one, one more when the staged
+ * cloud was rebuilt at the end, one more when the call's sensor brought a direction table that was not on the device), 1048 = the
+ * occupied voxels per pose its LDS tier takes at most, 1049 = workgroups that took the fallback tier (cleared by `reset`). */
 int  fs_get_counter(fs_ctx *ctx, int which, int64_t *value, int reset);
 
 /* ---------------------------------------------------------------- self test */

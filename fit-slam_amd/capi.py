@@ -58,8 +58,10 @@ EXPORTED_SYMBOLS = [
     "fs_upload_world", "fs_sense", "fs_goals_mapped", "fs_grid_census", "fs_drive",
     "fs_upload_world_landmarks", "fs_sense_landmarks", "fs_world_landmarks_get", "fs_staged_cloud_get",
     "fs_drive_slam",
+    "fs_inflate", "fs_inflation_costs", "fs_multi_inflate",
 ]
 FS_KEEPOUT_MAX_ZONES = 1024
+FS_INFLATE_MAX_CELLS = 512
 FS_DRIVE_ARRIVED, FS_DRIVE_BLOCKED, FS_DRIVE_COLLIDED, FS_DRIVE_OFF_MAP, FS_DRIVE_MAPPED = 0, 1, 2, 3, 4
 FS_DRIVE_UNSAFE = 5
 FS_DRIVE_MAX_STATIONS, FS_DRIVE_MAX_ROBOTS = 2048, 4096
@@ -136,6 +138,14 @@ class DriveSlamParamsC(C.Structure):
 
 
 assert C.sizeof(DriveSlamParamsC) == 32
+
+
+class InflationParamsC(C.Structure):
+    _fields_ = [("inflation_radius", C.c_double), ("inscribed_radius", C.c_double), ("cost_scaling_factor", C.c_double),
+                ("inflate_unknown", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(InflationParamsC) == 32
 
 
 class ViewLandmarkC(C.Structure):
@@ -297,6 +307,9 @@ def load_library(build: bool = True, path: str | None = None):
     L.fs_multi_keepout_add_disc.argtypes = [vp, dbl, dbl, dbl, C.POINTER(i32), C.POINTER(i64)]
     L.fs_multi_keepout_clear.argtypes = [vp]
     L.fs_multi_mark_lethal_fov.argtypes = [vp, C.POINTER(dbl * 7), C.POINTER(dbl * 7), C.POINTER(i32), C.POINTER(i64)]
+    L.fs_inflate.argtypes = [vp, C.POINTER(InflationParamsC), i32, i32, i32, i32, C.POINTER(i64), C.POINTER(i64)]
+    L.fs_inflation_costs.argtypes = [vp, C.POINTER(InflationParamsC), C.POINTER(i32), vp]
+    L.fs_multi_inflate.argtypes = [vp, C.POINTER(InflationParamsC), i32, i32, i32, i32, C.POINTER(i64), C.POINTER(i64)]
     for name in EXPORTED_SYMBOLS:
         f = getattr(L, name)
         if name not in ("fs_ctx_destroy", "fs_last_error", "fs_multi_destroy", "fs_multi_last_error", "fs_multi_ctx"):
@@ -308,6 +321,10 @@ def load_library(build: bool = True, path: str | None = None):
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _inflation_params_c(inflation_radius, inscribed_radius, cost_scaling_factor, inflate_unknown):
+    return InflationParamsC(float(inflation_radius), float(inscribed_radius), float(cost_scaling_factor), 1 if inflate_unknown else 0, 0)
 
 
 def _window_args(window, view):
@@ -463,6 +480,27 @@ class FrontierScorer:
         zid, n = C.c_int32(), C.c_int64()
         self._check(self._L.fs_mark_lethal_fov(self._h, C.byref(pose), C.byref(black), C.byref(zid), C.byref(n)))
         return np.array(black[:], dtype=np.float64), zid.value, n.value
+
+    # -- inflation layer (nav2's InflationLayer on the exact distance to the nearest lethal cell)
+    def inflate(self, inflation_radius, inscribed_radius, cost_scaling_factor, window=None, inflate_unknown=False):
+        """fs_inflate: inflates the staged 2-D grid in place inside window = (x0, y0, sx, sy) (None: the whole map);
+        returns (seeds in the window grown by the radius, window cells whose byte changed)."""
+        if window is None:
+            nz, ny, nx = self._staged_shape()
+            window = (0, 0, nx, ny)
+        p = _inflation_params_c(inflation_radius, inscribed_radius, cost_scaling_factor, inflate_unknown)
+        seeds, changed = C.c_int64(), C.c_int64()
+        self._check(self._L.fs_inflate(self._h, C.byref(p), *[int(v) for v in window], C.byref(seeds), C.byref(changed)))
+        return seeds.value, changed.value
+
+    def inflation_costs(self, inflation_radius, inscribed_radius, cost_scaling_factor):
+        """fs_inflation_costs: (R = the radius in cells of the staged grid, cost_by_d2 [R * R + 1] = the table fs_inflate uses)."""
+        p = _inflation_params_c(inflation_radius, inscribed_radius, cost_scaling_factor, False)
+        r = C.c_int32()
+        self._check(self._L.fs_inflation_costs(self._h, C.byref(p), C.byref(r), None))
+        table = np.zeros(r.value * r.value + 1, dtype=np.uint8)
+        self._check(self._L.fs_inflation_costs(self._h, C.byref(p), C.byref(r), _p(table)))
+        return r.value, table
 
     def upload_grid_bricks(self, shape_zyx, origin, resolution, brick_xyz, brick_cells, default_value=255):
         nz, ny, nx = shape_zyx
@@ -1644,10 +1682,22 @@ class MultiScorer:
         nz, ny, nx = c.shape
         o = (C.c_double * 3)(*[float(v) for v in origin])
         self._check(self._L.fs_multi_upload_grid(self._h, _p(c), nx, ny, nz, C.byref(o), float(resolution)))
+        self._grid_shape = (nz, ny, nx)
 
     def update_grid_region(self, x0, y0, z0, window, view=False):
         ptr, sx, sy, sz, rs, ss, keep = _window_args(window, view)
         self._check(self._L.fs_multi_update_grid_region(self._h, int(x0), int(y0), int(z0), sx, sy, sz, ptr, rs, ss))
+
+    def inflate(self, inflation_radius, inscribed_radius, cost_scaling_factor, window=None, inflate_unknown=False):
+        """fs_multi_inflate: FrontierScorer.inflate on every member; the counts are member 0's."""
+        if window is None:
+            if getattr(self, "_grid_shape", None) is None:
+                raise FsError(FS_E_STATE, "no grid staged (upload_grid)")
+            window = (0, 0, self._grid_shape[2], self._grid_shape[1])
+        p = _inflation_params_c(inflation_radius, inscribed_radius, cost_scaling_factor, inflate_unknown)
+        seeds, changed = C.c_int64(), C.c_int64()
+        self._check(self._L.fs_multi_inflate(self._h, C.byref(p), *[int(v) for v in window], C.byref(seeds), C.byref(changed)))
+        return seeds.value, changed.value
 
     def keepout_add_fov(self, wx, wy, yaw, height_m=3.5):
         zid, n = C.c_int32(), C.c_int64()

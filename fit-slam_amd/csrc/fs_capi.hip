@@ -193,6 +193,14 @@ struct KoGeom {
     bool operator==(const KoGeom &o) const { return nx == o.nx && ny == o.ny && ox == o.ox && oy == o.oy && res == o.res; }
 };
 
+// One cost table of the inflation layer on the device: what it was computed from, its reach in cells, cost_by_d2 [R * R + 1]
+struct InflTable {
+    double inflation_radius, inscribed_radius, cost_scaling_factor, res;
+    int32_t R;
+    DevBuf<uint8_t> d_cost;
+};
+#define FS_INFL_TABLES 8
+
 }  // namespace
 
 struct fs_ctx {
@@ -230,6 +238,13 @@ struct fs_ctx {
     DevBuf<uint8_t> d_ko_mask, d_ko_scratch;
     DevBuf<int32_t> d_ko_rays;
     DevBuf<unsigned long long> d_ko_counts;
+
+    // the inflation layer (fs_inflate.hip): the cost tables of the parameter sets seen (the host fills one with
+    // its libm and uploads it once; the reference runs three sets, a handful is kept), the row distances of the call, its counters
+    std::vector<InflTable> infl_tables;
+    size_t infl_next = 0;                           // the slot a new set takes once all are used
+    DevBuf<uint16_t> d_infl_g;
+    DevBuf<unsigned long long> d_infl_counts;
 
     // the sensor sweep (fs_sense.hip): the ground-truth world, of the staged grid's shape; the mark image of seen
     // cells (all zero between calls — sense_mark_clean says it is known to be); the direction table of the last non-NULL `sensor`
@@ -7152,6 +7167,98 @@ int fs_read_grid_region(fs_ctx *c, int32_t x0, int32_t y0, int32_t z0, int32_t s
         for (int32_t y = 0; y < sy; ++y)
             std::memcpy(cells + (size_t)z * (size_t)slice_stride + (size_t)y * (size_t)row_stride, c->h_win.p + ((size_t)z * sy + y) * sx, (size_t)sx);
     if (c->h_win.cap > ((size_t)64 << 20)) { c->h_win.release(); c->d_win.release(); }   // (a window of map size: not worth keeping)
+    return FS_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ inflation layer (fs_inflate.hip)
+
+namespace {
+
+// What both entry points refuse about the parameters and the staged grid, in fs_inflate's order; R = the seeds' reach in cells
+int infl_check(fs_ctx *c, const fs_inflation_params *p, int32_t &R)
+{
+    if (const int rc = grid_check(c)) return rc;
+    if (c->nz != 1) return fail(c, FS_E_INVALID, "the inflation layer is defined on a 2-D costmap (nz == 1)");
+    if (!std::isfinite(p->inflation_radius) || !std::isfinite(p->inscribed_radius) || !std::isfinite(p->cost_scaling_factor) ||
+        !(p->inflation_radius >= 0.0) || !(p->inscribed_radius >= 0.0) || !(p->cost_scaling_factor >= 0.0))
+        return fail(c, FS_E_INVALID, "the inflation layer needs finite radii and a finite scaling factor, all >= 0");
+    R = fs_inflation_cell_radius(p->inflation_radius, c->res);
+    if (R < 0) return fail(c, FS_E_INVALID, "an inflation radius of more than %d cells", FS_INFLATE_MAX_CELLS);
+    return FS_OK;
+}
+
+// The cost table of (p, the staged resolution) on the device: one of those kept, or filled on the host and uploaded into a free
+// slot — the oldest one's once all are used
+int infl_table(fs_ctx *c, const fs_inflation_params *p, int32_t R, const uint8_t *&d_cost)
+{
+    for (const InflTable &t : c->infl_tables)
+        if (t.inflation_radius == p->inflation_radius && t.inscribed_radius == p->inscribed_radius &&
+            t.cost_scaling_factor == p->cost_scaling_factor && t.res == c->res) { d_cost = t.d_cost.p; return FS_OK; }
+    size_t slot = c->infl_tables.size();
+    if (slot < (size_t)FS_INFL_TABLES) c->infl_tables.emplace_back();
+    else slot = c->infl_next++ % FS_INFL_TABLES;
+    InflTable &t = c->infl_tables[slot];
+    t.res = 0.0;                                                  // (no key matches it until it is whole)
+    const size_t n = (size_t)R * (size_t)R + 1;
+    std::vector<uint8_t> cost(n);
+    fs_inflation_cost_table(*p, c->res, R, cost.data());
+    FS_HIP(c, t.d_cost.ensure(n));
+    FS_HIP(c, hipMemcpyAsync(t.d_cost.p, cost.data(), n, hipMemcpyHostToDevice, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));                  // (the host copy is this function's)
+    t.inflation_radius = p->inflation_radius; t.inscribed_radius = p->inscribed_radius; t.cost_scaling_factor = p->cost_scaling_factor;
+    t.R = R; t.res = c->res;
+    d_cost = t.d_cost.p;
+    return FS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fs_inflation_costs(const fs_ctx *ctx, const fs_inflation_params *p, int32_t *cell_radius, uint8_t *cost_by_d2)
+{
+    fs_ctx *c = const_cast<fs_ctx *>(ctx);                        // (the error text is the context's)
+    if (!c || !p || !cell_radius) return FS_E_INVALID;
+    int32_t R = 0;
+    if (const int rc = infl_check(c, p, R)) return rc;
+    *cell_radius = R;
+    if (cost_by_d2) fs_inflation_cost_table(*p, c->res, R, cost_by_d2);
+    return FS_OK;
+}
+
+// The rows pass, the columns pass and what follows every write of cells (cells_changed_in_box; the keep-out zones need no
+// repaint: max(253, cost) is 253) on the stream back to back, one wait at the end for the two counters
+int fs_inflate(fs_ctx *c, const fs_inflation_params *p, int32_t x0, int32_t y0, int32_t sx, int32_t sy, int64_t *n_seeds, int64_t *n_changed)
+{
+    if (!c || !p) return FS_E_INVALID;
+    int32_t R = 0;
+    if (const int rc = infl_check(c, p, R)) return rc;
+    if (sx < 0 || sy < 0) return fail(c, FS_E_INVALID, "negative window size");
+    if (x0 < 0 || y0 < 0 || (int64_t)x0 + sx > c->nx || (int64_t)y0 + sy > c->ny)
+        return fail(c, FS_E_INVALID, "window [%d,%lld) x [%d,%lld) leaves the %d x %d grid", x0, (long long)x0 + sx, y0, (long long)y0 + sy, c->nx, c->ny);
+    if (n_seeds) *n_seeds = 0;
+    if (n_changed) *n_changed = 0;
+    if (sx == 0 || sy == 0 || R == 0) return FS_OK;
+    const uint8_t *d_cost = nullptr;
+    if (const int rc = infl_table(c, p, R, d_cost)) return rc;
+    const FsInflateBox b = fs_inflate_box(c->nx, c->ny, x0, y0, sx, sy, R);
+    FS_HIP(c, c->d_infl_g.ensure((size_t)b.gh * (size_t)sx));
+    FS_HIP(c, c->d_infl_counts.ensure(2));
+    ++c->grid_gen;
+    FS_HIP(c, hipMemsetAsync(c->d_infl_counts.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    FS_HIP(c, fs_launch_inflate_rows(c->d_cells.p, c->nx, c->ny, x0, y0, sx, sy, R, c->d_infl_g.p, c->d_infl_counts.p, c->stream));
+    FS_HIP(c, fs_launch_inflate_cols(c->d_infl_g.p, d_cost, c->d_cells.p, c->nx, c->ny, x0, y0, sx, sy, R, p->inflate_unknown != 0,
+                                     c->d_infl_counts.p + 1, c->stream));
+    if (const int rc = cells_changed_in_box(c, x0, y0, 0, sx, sy, 1)) return rc;
+    unsigned long long counts[2] = {0ull, 0ull};
+    FS_HIP(c, hipMemcpyAsync(counts, c->d_infl_counts.p, sizeof counts, hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(c, hipStreamSynchronize(c->stream));                  // (the counts are the two passes')
+    if (c->d_infl_g.cap * sizeof(uint16_t) > ((size_t)64 << 20)) c->d_infl_g.release();   // (row distances of a map-sized window: not worth keeping)
+    ++c->epoch;
+    if (n_seeds) *n_seeds = (int64_t)counts[0];
+    if (n_changed) *n_changed = (int64_t)counts[1];
     return FS_OK;
 }
 

@@ -69,6 +69,28 @@ hipError_t fs_launch_keepout_apply(const uint8_t *d_mask, uint8_t *d_cells, int 
 hipError_t fs_launch_keepout_fold(uint8_t *d_src, uint8_t *d_mask, uint8_t *d_cells, int nx, int ny, int x0, int y0, int sx, int sy,
                                   unsigned long long *d_count, hipStream_t s);
 
+// the inflation layer (fs_inflate.hip) on the window [x0, x0+sx) x [y0, y0+sy) of a 2-D grid, R = the seeds' reach in
+// cells (1 .. FS_INFLATE_MAX_CELLS).  The box: that window grown by R on every side and clipped to the map — where seeds are looked
+// for and counted.  cell_radius: Costmap2D::cellDistance, -1 beyond the limit.  cost_table: InflationLayer::computeCost for every
+// d2 = dx^2 + dy^2 in 0 .. R^2, on the host (libm's exp and sqrt).  rows: d_g [gh][sx] = distance along the row to the nearest
+// seed (cell == 254) within R, 0xFFFF for none; *d_n_seeds += seeds in the box.  cols: every window cell whose nearest seed has
+// d2 <= R^2 takes d_cost_by_d2[d2] under the layer's write rule; *d_n_changed += cells whose byte changed.
+struct FsInflateBox {
+    int32_t gx0, gy0, gw, gh;
+};
+inline FsInflateBox fs_inflate_box(int nx, int ny, int x0, int y0, int sx, int sy, int R)
+{
+    const int gx0 = x0 - R > 0 ? x0 - R : 0, gy0 = y0 - R > 0 ? y0 - R : 0;
+    const long long gx1 = (long long)x0 + sx + R < nx ? (long long)x0 + sx + R : nx, gy1 = (long long)y0 + sy + R < ny ? (long long)y0 + sy + R : ny;
+    return FsInflateBox{gx0, gy0, (int32_t)(gx1 - gx0), (int32_t)(gy1 - gy0)};
+}
+int fs_inflation_cell_radius(double inflation_radius, double res);
+void fs_inflation_cost_table(const fs_inflation_params &p, double res, int R, uint8_t *cost_by_d2);
+hipError_t fs_launch_inflate_rows(const uint8_t *d_cells, int nx, int ny, int x0, int y0, int sx, int sy, int R, uint16_t *d_g,
+                                  unsigned long long *d_n_seeds, hipStream_t s);
+hipError_t fs_launch_inflate_cols(const uint16_t *d_g, const uint8_t *d_cost_by_d2, uint8_t *d_cells, int nx, int ny, int x0, int y0,
+                                  int sx, int sy, int R, int inflate_unknown, unsigned long long *d_n_changed, hipStream_t s);
+
 struct FsRayArgs {
     FsGridDev grid;
     // fan geometry, precomputed on the host in double with libm (ray directions are

@@ -235,6 +235,14 @@ int fs_multi_keepout_add_disc(fs_multi *m, double wx, double wy, double radius_m
     });
 }
 
+int fs_multi_inflate(fs_multi *m, const fs_inflation_params *p, int32_t x0, int32_t y0, int32_t sx, int32_t sy, int64_t *n_seeds, int64_t *n_changed)
+{
+    return for_all_parallel(m, "fs_inflate", [&](fs_ctx *c) {
+        const bool first = c == m->ctx[0];
+        return fs_inflate(c, p, x0, y0, sx, sy, first ? n_seeds : nullptr, first ? n_changed : nullptr);
+    });
+}
+
 int fs_multi_keepout_clear(fs_multi *m)
 {
     return for_all_parallel(m, "fs_keepout_clear", [&](fs_ctx *c) { return fs_keepout_clear(c); });

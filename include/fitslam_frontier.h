@@ -192,6 +192,49 @@ int fs_keepout_get(fs_ctx *ctx, int32_t *n_zones, double *spec, int64_t *n_cells
  * yaw, z = 0, orientation yaw + pi about Z.  Publishing it is the caller's job. */
 int fs_mark_lethal_fov(fs_ctx *ctx, const double robot_pose7[7], double blacklist_pose7[7], int32_t *zone_id, int64_t *n_cells);
 
+/* ---------------------------------------------------------------- inflation layer (nav2_costmap_2d::InflationLayer)
+ *
+ * The costmap layer every planner of the reference reads through: its global costmap stacks static_layer, inflation_layer
+ * (inflation_radius 5.0, cost_scaling_factor 0.6), lethal_marker_global_costmap and lethal_inflation_layer (radius 0.3) at
+ * resolution 0.05 with robot_radius 0.05 (fit_slam2/params/active_slam_nav2_params.yaml:153-170).  nav2's InflationLayer is
+ * third-party and not under the reference tree, so the behaviour is stated here, after ROS 2 Humble's
+ * InflationLayer::computeCost and the write rule of InflationLayer::updateCosts.  fs_inflate inflates the staged 2-D grid
+ * (nz == 1) IN PLACE inside the window [x0, x0+sx) x [y0, y0+sy):
+ *   R     = (int)max(0.0, ceil(inflation_radius / resolution))                       (Costmap2D::cellDistance)
+ *   seeds = the cells equal to 254 (LETHAL_OBSTACLE) of the window grown by R on every side and clipped to the map; unknown
+ *           cells (255) are never seeds (inflate_around_unknown is not built)
+ *   d2    = for a cell of the window, the smallest dx^2 + dy^2 to a seed, in integers; no seed with d2 <= R^2: untouched
+ *   cost  = 254 for d2 == 0; else with d = sqrt((double)d2) * resolution: 253 where d <= inscribed_radius, else
+ *           (unsigned char)(252 * exp(-1.0 * cost_scaling_factor * (d - inscribed_radius)))       (computeCost, in double)
+ *   write = old == 255 and (inflate_unknown ? cost > 0 : cost >= 253): the cost; every other cell: max(old, cost)
+ * The costs are a table indexed by d2 that the HOST fills with its own libm (fs_inflation_costs returns it) and uploads once per
+ * distinct (parameters, resolution); the device works in integers only.
+ * ONE deliberate deviation: Humble propagates with a distance-ordered brushfire over 4-neighbours that carries each cell's
+ * source seed, so a cell whose nearest seed cannot reach it through a 4-connected chain of cells that adopted that same seed
+ * gets the distance to another seed.  Here every cell gets its EXACT nearest seed — independent of order, the same for a window
+ * as for the whole map, and never a cost below the brushfire's (DESIGN.md 4.26 has the measured count of cells that differ).
+ *   - idempotent: costs are <= 253 and never become seeds
+ *   - it cannot LOWER a cost: a wall that vanished keeps its band until its cells are rewritten — stage the raw map again
+ *     (the limit of fs_keepout_clear); keep-out cells stay 253 by the write rule; two calls with different radii compose by max,
+ *     as the reference's two inflation layers do
+ *   - cells outside the window are never written (Humble restricts its writes to the cycle's bounds in the same way)
+ *   - refused with FS_E_INVALID, nothing written: non-finite or negative radii or scaling factor, R > FS_INFLATE_MAX_CELLS, a
+ *     window that leaves the grid, a 3-D grid staged; no grid staged: FS_E_STATE
+ *   - an empty window or R == 0 is a no-op that reports zeros
+ * n_seeds (seeds in the grown, clipped window) and n_changed (window cells whose byte changed) may be NULL.  Images derived from
+ * the grid follow as after fs_update_grid_region, cached arrival limits stay: scoring, planning and searching afterwards equal
+ * the same calls after fs_upload_grid of the inflated map, bit for bit. */
+#define FS_INFLATE_MAX_CELLS 512
+typedef struct fs_inflation_params {
+    double inflation_radius, inscribed_radius, cost_scaling_factor;   /* [m], [m], [1/m] */
+    int32_t inflate_unknown, reserved;
+} fs_inflation_params;
+int fs_inflate(fs_ctx *ctx, const fs_inflation_params *p, int32_t x0, int32_t y0, int32_t sx, int32_t sy,
+               int64_t *n_seeds, int64_t *n_changed);
+/* *cell_radius = R and cost_by_d2 [R * R + 1] (may be NULL: ask for R first) = the cost table fs_inflate would use on the grid
+ * staged now; the refusals of fs_inflate that concern the parameters and the grid. */
+int fs_inflation_costs(const fs_ctx *ctx, const fs_inflation_params *p, int32_t *cell_radius, uint8_t *cost_by_d2);
+
 /* Frontier-cell predicate of FrontierSearch::isNewFrontierCell (DEP/src/FrontierSearch.cpp:218-249; isFree / isLethal /
  * isUnknown: DEP/include/.../FrontierSearch.hpp:129-142; frontierSearch/lethal_threshold 160) evaluated for every cell
  * of the staged grid, slice by slice: unknown cell, no lethal in-plane 4-neighbour, at least one free one.
@@ -470,6 +513,9 @@ int  fs_multi_keepout_add_fov(fs_multi *m, double wx, double wy, double yaw, dou
 int  fs_multi_keepout_add_disc(fs_multi *m, double wx, double wy, double radius_m, int32_t *zone_id, int64_t *n_cells);
 int  fs_multi_keepout_clear(fs_multi *m);
 int  fs_multi_mark_lethal_fov(fs_multi *m, const double robot_pose7[7], double blacklist_pose7[7], int32_t *zone_id, int64_t *n_cells);
+/* fs_inflate on every member (the same map on each, so the same cells); the counts are member 0's */
+int  fs_multi_inflate(fs_multi *m, const fs_inflation_params *p, int32_t x0, int32_t y0, int32_t sx, int32_t sy,
+                      int64_t *n_seeds, int64_t *n_changed);
 int  fs_multi_upload_landmarks(fs_multi *m, const float *xyz, int32_t n_landmarks);
 int  fs_multi_lookup_generate(fs_multi *m, const float bounds[6]);
 int  fs_multi_lookup_load(fs_multi *m, const char *path);

@@ -12,7 +12,7 @@ import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["fs_raymarch.hip", "fs_fim.hip", "fs_rank.hip", "fs_sort.hip", "fs_gridops.hip", "fs_keepout.hip", "fs_inflate.hip", "fs_cloud.hip", "fs_view.hip", "fs_sense.hip", "fs_drive.hip", "fs_sense_landmarks.hip", "fs_drive_slam.hip", "fs_frontier.hip", "fs_keyframes.hip", "fs_navfn.hip", "fs_pathinfo.hip", "fs_roadmap.hip", "fs_roadmap_kf.hip", "fs_roadmap_update.hip", "fs_refine.hip", "fs_search.hip", "fs_allocate.hip", "fs_multi.hip", "fs_capi.hip"]
+SOURCES = ["fs_raymarch.hip", "fs_fim.hip", "fs_rank.hip", "fs_sort.hip", "fs_gridops.hip", "fs_keepout.hip", "fs_inflate.hip", "fs_infolayer.hip", "fs_cloud.hip", "fs_view.hip", "fs_sense.hip", "fs_drive.hip", "fs_sense_landmarks.hip", "fs_drive_slam.hip", "fs_frontier.hip", "fs_keyframes.hip", "fs_navfn.hip", "fs_pathinfo.hip", "fs_roadmap.hip", "fs_roadmap_kf.hip", "fs_roadmap_update.hip", "fs_refine.hip", "fs_search.hip", "fs_allocate.hip", "fs_multi.hip", "fs_capi.hip"]
 HEADERS = ["fs_internal.h", "fs_keepout.h", "fs_median_sort.h", "fs_navfn_wave.h", "fs_roadmap_astar.h", "fs_roadmap_update.h", "fs_sense_dev.h", "fs_sense_landmarks_dev.h", "fs_thetastar.h", "fs_view.h", "fs_walk.h", os.path.join("..", "..", "include", "fitslam_frontier.h"), os.path.join("..", "..", "include", "fitslam_frontier_dev.h")]
 
 # -ffp-contract=off: the ray set-up (fp64) and the landmark transform (fp32) must round exactly like

@@ -59,9 +59,13 @@ EXPORTED_SYMBOLS = [
     "fs_upload_world_landmarks", "fs_sense_landmarks", "fs_world_landmarks_get", "fs_staged_cloud_get",
     "fs_drive_slam",
     "fs_inflate", "fs_inflation_costs", "fs_multi_inflate",
+    "fs_information_layer", "fs_multi_information_layer",
 ]
 FS_KEEPOUT_MAX_ZONES = 1024
 FS_INFLATE_MAX_CELLS = 512
+FS_INFO_LAYER_MAX_STRIDE, FS_INFO_LAYER_MAX_YAW = 32, 64
+FS_INFO_REDUCE_MIN, FS_INFO_REDUCE_MEAN, FS_INFO_REDUCE_MAX = 0, 1, 2
+INFO_REDUCE = {"min": FS_INFO_REDUCE_MIN, "mean": FS_INFO_REDUCE_MEAN, "max": FS_INFO_REDUCE_MAX}
 FS_DRIVE_ARRIVED, FS_DRIVE_BLOCKED, FS_DRIVE_COLLIDED, FS_DRIVE_OFF_MAP, FS_DRIVE_MAPPED = 0, 1, 2, 3, 4
 FS_DRIVE_UNSAFE = 5
 FS_DRIVE_MAX_STATIONS, FS_DRIVE_MAX_ROBOTS = 2048, 4096
@@ -146,6 +150,14 @@ class InflationParamsC(C.Structure):
 
 
 assert C.sizeof(InflationParamsC) == 32
+
+
+class InfoLayerParamsC(C.Structure):
+    _fields_ = [("stride_cells", C.c_int32), ("n_yaw", C.c_int32), ("yaw0", C.c_double), ("pose_z", C.c_double),
+                ("reduce", C.c_int32), ("info_lo", C.c_double), ("info_hi", C.c_double), ("max_cost", C.c_int32), ("write", C.c_int32)]
+
+
+assert C.sizeof(InfoLayerParamsC) == 56
 
 
 class ViewLandmarkC(C.Structure):
@@ -310,6 +322,8 @@ def load_library(build: bool = True, path: str | None = None):
     L.fs_inflate.argtypes = [vp, C.POINTER(InflationParamsC), i32, i32, i32, i32, C.POINTER(i64), C.POINTER(i64)]
     L.fs_inflation_costs.argtypes = [vp, C.POINTER(InflationParamsC), C.POINTER(i32), vp]
     L.fs_multi_inflate.argtypes = [vp, C.POINTER(InflationParamsC), i32, i32, i32, i32, C.POINTER(i64), C.POINTER(i64)]
+    for f in (L.fs_information_layer, L.fs_multi_information_layer):
+        f.argtypes = [vp, C.POINTER(InfoLayerParamsC), i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
     for name in EXPORTED_SYMBOLS:
         f = getattr(L, name)
         if name not in ("fs_ctx_destroy", "fs_last_error", "fs_multi_destroy", "fs_multi_last_error", "fs_multi_ctx"):
@@ -325,6 +339,46 @@ def _p(a):
 
 def _inflation_params_c(inflation_radius, inscribed_radius, cost_scaling_factor, inflate_unknown):
     return InflationParamsC(float(inflation_radius), float(inscribed_radius), float(cost_scaling_factor), 1 if inflate_unknown else 0, 0)
+
+
+class InformationLayerResult:
+    """What fs_information_layer returns: info [nby][nbx] (NaN: unscored block), anchor_cell [nby][nbx] (y * nx + x, or -1),
+    info_per_yaw [K][nby][nbx] or None, quat_zw [K][2], pose7 [n_scored * K][7] (scored blocks in block order, headings in
+    order — rebuilt on the host from the anchors and quat_zw: the poses that were scored), n_scored, n_changed."""
+
+    def __init__(self, info, anchor_cell, info_per_yaw, quat_zw, pose7, n_scored, n_changed):
+        self.info, self.anchor_cell, self.info_per_yaw, self.quat_zw = info, anchor_cell, info_per_yaw, quat_zw
+        self.pose7, self.n_scored, self.n_changed = pose7, n_scored, n_changed
+
+
+def _information_layer(call, handle, check, grid_shape, grid_geom, stride_cells, n_yaw, yaw0, pose_z, reduce, info_lo, info_hi, max_cost,
+                       window, write, want_per_yaw):
+    """The body of FrontierScorer.information_layer and MultiScorer.information_layer."""
+    nz, ny, nx = grid_shape
+    x0, y0, sx, sy = (0, 0, nx, ny) if window is None else [int(v) for v in window]
+    if reduce not in INFO_REDUCE:
+        raise FsError(FS_E_INVALID, "reduce must be one of %s" % sorted(INFO_REDUCE))
+    p = InfoLayerParamsC(int(stride_cells), int(n_yaw), float(yaw0), float(pose_z), INFO_REDUCE[reduce], float(info_lo), float(info_hi),
+                         int(max_cost), 1 if write else 0)
+    s, K = max(1, p.stride_cells), max(0, p.n_yaw)           # (room for the outputs; the call refuses what is out of range)
+    nbx, nby = max(0, -(-sx // s)), max(0, -(-sy // s))
+    info = np.full((nby, nbx), np.nan, dtype=np.float32)
+    anchor = np.full((nby, nbx), -1, dtype=np.int32)
+    per_yaw = np.full((K, nby, nbx), np.nan, dtype=np.float32) if want_per_yaw else None
+    quat = np.zeros((max(K, FS_INFO_LAYER_MAX_YAW), 2), dtype=np.float64)
+    n_scored, n_changed = C.c_int64(), C.c_int64()
+    check(call(handle, C.byref(p), x0, y0, sx, sy, _p(info), _p(anchor), _p(per_yaw), _p(quat), C.byref(n_scored), C.byref(n_changed)))
+    quat = quat[:K].copy()
+    cells = anchor.reshape(-1)
+    cells = cells[cells >= 0].astype(np.int64)
+    (ox, oy, _oz), res = grid_geom
+    pose7 = np.zeros((cells.size, K, 7), dtype=np.float64)
+    pose7[:, :, 0] = (ox + ((cells % nx).astype(np.float64) + 0.5) * res)[:, None]
+    pose7[:, :, 1] = (oy + ((cells // nx).astype(np.float64) + 0.5) * res)[:, None]
+    pose7[:, :, 2] = float(pose_z)
+    pose7[:, :, 5] = quat[None, :, 0]
+    pose7[:, :, 6] = quat[None, :, 1]
+    return InformationLayerResult(info, anchor, per_yaw, quat, pose7.reshape(-1, 7), n_scored.value, n_changed.value)
 
 
 def _window_args(window, view):
@@ -423,6 +477,7 @@ class FrontierScorer:
         self._grid_shape = None
         self._check(self._L.fs_upload_grid(self._h, _p(c), nx, ny, nz, C.byref(o), float(resolution)))
         self._grid_shape = (nz, ny, nx)
+        self._grid_geom = (tuple(float(v) for v in origin), float(resolution))
 
     def update_grid_region(self, x0, y0, z0, window, view=False):
         """fs_update_grid_region: `window` [sz][sy][sx] (or [sy][sx]) replaces the cells from (x0, y0, z0) on; view=True passes a
@@ -493,6 +548,17 @@ class FrontierScorer:
         self._check(self._L.fs_inflate(self._h, C.byref(p), *[int(v) for v in window], C.byref(seeds), C.byref(changed)))
         return seeds.value, changed.value
 
+    def information_layer(self, stride_cells=5, n_yaw=8, yaw0=0.0, pose_z=0.0, reduce="mean", info_lo=550.0, info_hi=1100.0, max_cost=252,
+                          window=None, write=True, want_per_yaw=False):
+        """fs_information_layer — this project's own extension, the reference has no such layer: the Fisher information of a
+        lattice of poses (one per block of stride_cells x stride_cells cells, n_yaw headings each, reduced by "min" | "mean" | "max")
+        as costs of the staged 2-D grid inside window = (x0, y0, sx, sy) (None: the whole map): cost max_cost at info_lo and below,
+        0 at info_hi and above, linear between, stored by max into the writable cells (write=False: the field only).
+        info_lo = 550 is the reference's isPoseSafe threshold (FisherInfoBTPlugin.cpp:20); info_hi = 2 * info_lo is a default
+        nobody has measured.  Call it after staging and inflate, before planning.  Returns an InformationLayerResult."""
+        return _information_layer(self._L.fs_information_layer, self._h, self._check, self._staged_shape(), self._grid_geom, stride_cells,
+                                  n_yaw, yaw0, pose_z, reduce, info_lo, info_hi, max_cost, window, write, want_per_yaw)
+
     def inflation_costs(self, inflation_radius, inscribed_radius, cost_scaling_factor):
         """fs_inflation_costs: (R = the radius in cells of the staged grid, cost_by_d2 [R * R + 1] = the table fs_inflate uses)."""
         p = _inflation_params_c(inflation_radius, inscribed_radius, cost_scaling_factor, False)
@@ -511,6 +577,7 @@ class FrontierScorer:
         self._check(self._L.fs_upload_grid_bricks(self._h, nx, ny, nz, C.byref(o), float(resolution), int(default_value),
                                                   xyz.shape[0], _p(xyz), _p(cells)))
         self._grid_shape = (int(nz), int(ny), int(nx))
+        self._grid_geom = (tuple(float(v) for v in origin), float(resolution))
 
     def frontier_cells(self, shape_zyx, lethal_threshold=160, want_mask=True):
         mask = np.zeros(shape_zyx, dtype=np.uint8) if want_mask else None
@@ -1683,6 +1750,7 @@ class MultiScorer:
         o = (C.c_double * 3)(*[float(v) for v in origin])
         self._check(self._L.fs_multi_upload_grid(self._h, _p(c), nx, ny, nz, C.byref(o), float(resolution)))
         self._grid_shape = (nz, ny, nx)
+        self._grid_geom = (tuple(float(v) for v in origin), float(resolution))
 
     def update_grid_region(self, x0, y0, z0, window, view=False):
         ptr, sx, sy, sz, rs, ss, keep = _window_args(window, view)
@@ -1698,6 +1766,14 @@ class MultiScorer:
         seeds, changed = C.c_int64(), C.c_int64()
         self._check(self._L.fs_multi_inflate(self._h, C.byref(p), *[int(v) for v in window], C.byref(seeds), C.byref(changed)))
         return seeds.value, changed.value
+
+    def information_layer(self, stride_cells=5, n_yaw=8, yaw0=0.0, pose_z=0.0, reduce="mean", info_lo=550.0, info_hi=1100.0, max_cost=252,
+                          window=None, write=True, want_per_yaw=False):
+        """fs_multi_information_layer: FrontierScorer.information_layer on every member; the result is member 0's."""
+        if getattr(self, "_grid_shape", None) is None:
+            raise FsError(FS_E_STATE, "no grid staged (upload_grid)")
+        return _information_layer(self._L.fs_multi_information_layer, self._h, self._check, self._grid_shape, self._grid_geom, stride_cells,
+                                  n_yaw, yaw0, pose_z, reduce, info_lo, info_hi, max_cost, window, write, want_per_yaw)
 
     def keepout_add_fov(self, wx, wy, yaw, height_m=3.5):
         zid, n = C.c_int32(), C.c_int64()

@@ -246,6 +246,17 @@ struct fs_ctx {
     DevBuf<uint16_t> d_infl_g;
     DevBuf<unsigned long long> d_infl_counts;
 
+    // the information layer (fs_infolayer.hip): anchor | flag [nb + 1] | rank [nb + 1] | list; the heading pairs
+    // (il_quat: their host copy, alive until the call's last wait); the pose records of a batch; the worker's values
+    // [scored][K]; info [nb] | per_yaw [K][nb]; rocPRIM's scratch; n_changed
+    int64_t opt_il_batch = 65536;                   // "infolayer.batch": poses per scoring launch
+    DevBuf<int32_t> d_il_idx;
+    DevBuf<double> d_il_quat;
+    std::vector<double> il_quat;
+    DevBuf<float> d_il_rt, d_il_val, d_il_out;
+    DevBuf<char> d_il_temp;
+    DevBuf<unsigned long long> d_il_count;
+
     // the sensor sweep (fs_sense.hip): the ground-truth world, of the staged grid's shape; the mark image of seen
     // cells (all zero between calls — sense_mark_clean says it is known to be); the direction table of the last non-NULL `sensor`
     // (sense_dir: its host copy, what a new one is compared with); the call's inputs and results (d_sense_out: box [6] | status [n]
@@ -2811,6 +2822,7 @@ int fs_set_option(fs_ctx *c, const char *key, double value)
     if (std::strcmp(key, "refine.search_bytes") == 0 && value >= 1 && value <= 1099511627776.0) { c->rs_opt_bytes = (int64_t)value; return FS_OK; }
     if (std::strcmp(key, "view.round_poses") == 0 && value >= 0 && value <= FS_VIEW_MAX_ROUND) { c->opt_view_round = (int32_t)value; return FS_OK; }
     if (std::strcmp(key, "pathinfo.dedup") == 0) { c->opt_pi_dedup = value != 0.0; return FS_OK; }
+    if (std::strcmp(key, "infolayer.batch") == 0 && value >= 1 && value <= (double)(1 << 24)) { c->opt_il_batch = (int64_t)value; return FS_OK; }
     if (std::strcmp(key, "routes.dedup") == 0) { c->opt_rt_dedup = value != 0.0; return FS_OK; }
     if (std::strcmp(key, "routes.pool_nodes") == 0 && value >= 1 && value <= (double)(1 << 30)) { c->rt_pool_cap = (int64_t)value; return FS_OK; }
     if (std::strcmp(key, "refine.max_fields") == 0 && value >= 1 && value <= RF_MAX_FIELDS) {
@@ -4634,23 +4646,26 @@ int pathinfo_prepare(fs_ctx *c, FsPathInfoArgs &a, int64_t bound, bool dump, con
     return FS_OK;
 }
 
-// ... and their information (distinct > 0, known after the caller's synchronisation): fs_score_fim's launch sequence on the records;
-// a.info is where the finish kernel finds it.  What decides the size of the per-item scratch (maybe_split) comes before any pointer
-// into it.  A refused scratch returns as it is; every later failure goes through the caller's `stop`.
+// fs_score_fim's launch sequence on n > 0 pose records that lie on the device (rt [n][12]); *info is the worker's info_ref column.
+// `split`: a call of few poses may spread each over several workgroups (maybe_split), which changes the order of a pose's
+// partial sums with n — a caller whose values must not depend on how its poses are batched passes false.  What decides the size of
+// the per-item scratch comes before any pointer into it.  A refused scratch returns as it is; every later failure goes through
+// the caller's `stop`.
 template <class Stop>
-int pathinfo_score(fs_ctx *c, FsPathInfoArgs &a, int64_t distinct, Stop stop)
+int score_records(fs_ctx *c, const float *rt, int64_t n, bool split, Stop stop, const float **info)
 {
-    int rc = ensure_candidate_scratch(c, (size_t)distinct, false);
+    int rc = ensure_candidate_scratch(c, (size_t)n, false);
     if (rc) return rc;
     FsFimArgs fa{};
     if (const int rc_args = fill_fim_args(c, fa)) return rc_args;
-    fa.n = (int32_t)distinct;
+    fa.n = (int32_t)n;
     fa.info_only = c->opt_special ? 1 : 0;
     if (fa.info_only && fa.skip32 < 20) fa.skip32 = 20;        // (as fs_score_fim_begin)
     const bool occluded = c->occ.enabled != 0;
-    rc = occluded ? occlusion_args(c, fa) : maybe_split(c, fa, (size_t)distinct, false);
+    if (occluded) rc = occlusion_args(c, fa);
+    else if (split) rc = maybe_split(c, fa, (size_t)n, false);
     if (rc) return stop(rc);
-    fa.Rt = c->d_pi_rt.p;
+    fa.Rt = rt;
     bind_fim_outputs(c, fa);
     if (occluded) rc = run_fim_occluded(c, fa);
     else {
@@ -4659,8 +4674,16 @@ int pathinfo_score(fs_ctx *c, FsPathInfoArgs &a, int64_t distinct, Stop stop)
         rc = run_fim_rest(c, fa);
     }
     if (rc) return stop(rc);
-    a.info = fa.info_ref;
+    *info = fa.info_ref;
     return FS_OK;
+}
+
+// ... and the information of the pose records of pathinfo_prepare (distinct > 0, known after the caller's synchronisation); a.info
+// is where the finish kernel finds it.
+template <class Stop>
+int pathinfo_score(fs_ctx *c, FsPathInfoArgs &a, int64_t distinct, Stop stop)
+{
+    return score_records(c, c->d_pi_rt.p, distinct, true, stop, &a.info);
 }
 
 }  // namespace
@@ -7259,6 +7282,113 @@ int fs_inflate(fs_ctx *c, const fs_inflation_params *p, int32_t x0, int32_t y0, 
     ++c->epoch;
     if (n_seeds) *n_seeds = (int64_t)counts[0];
     if (n_changed) *n_changed = (int64_t)counts[1];
+    return FS_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ information layer (fs_infolayer.hip)
+
+extern "C" {
+
+// Anchors, compaction, THE mid-call synchronisation for n_scored (it sizes the scoring launches), then per batch of poses the
+// records, fs_score_fim's launch sequence and the values' copy, then reduce / cost / store and what follows every write of cells
+// (cells_changed_in_box; keep-out cells are not writable, so no repaint), one wait at the end: two synchronisations.
+int fs_information_layer(fs_ctx *c, const fs_info_layer_params *p, int32_t x0, int32_t y0, int32_t sx, int32_t sy, float *info,
+                         int32_t *anchor_cell, float *info_per_yaw, double *quat_zw, int64_t *n_scored, int64_t *n_changed)
+{
+    if (!c || !p) return FS_E_INVALID;
+    int rc = grid2d_check(c, "the information layer");
+    if (rc) return rc;
+    if (p->stride_cells < 1 || p->stride_cells > FS_INFO_LAYER_MAX_STRIDE) return fail(c, FS_E_INVALID, "stride_cells must be 1 .. %d", FS_INFO_LAYER_MAX_STRIDE);
+    if (p->n_yaw < 1 || p->n_yaw > FS_INFO_LAYER_MAX_YAW) return fail(c, FS_E_INVALID, "n_yaw must be 1 .. %d", FS_INFO_LAYER_MAX_YAW);
+    if (!std::isfinite(p->yaw0) || !std::isfinite(p->pose_z)) return fail(c, FS_E_INVALID, "yaw0 and pose_z must be finite");
+    if (p->reduce != FS_INFO_REDUCE_MIN && p->reduce != FS_INFO_REDUCE_MEAN && p->reduce != FS_INFO_REDUCE_MAX) return fail(c, FS_E_INVALID, "unknown reduction %d", p->reduce);
+    if (!std::isfinite(p->info_lo) || !std::isfinite(p->info_hi) || !(p->info_hi > p->info_lo) || !std::isfinite(p->info_hi - p->info_lo))
+        return fail(c, FS_E_INVALID, "info_lo and info_hi must be finite with info_hi > info_lo");
+    if (p->max_cost < 1 || p->max_cost > 252) return fail(c, FS_E_INVALID, "max_cost must be 1 .. 252");
+    if (sx < 0 || sy < 0) return fail(c, FS_E_INVALID, "negative window size");
+    if (x0 < 0 || y0 < 0 || (int64_t)x0 + sx > c->nx || (int64_t)y0 + sy > c->ny)
+        return fail(c, FS_E_INVALID, "window [%d,%lld) x [%d,%lld) leaves the %d x %d grid", x0, (long long)x0 + sx, y0, (long long)y0 + sy, c->nx, c->ny);
+    rc = check_scoring_state(c, false, true);
+    if (rc) return rc;
+    if (n_scored) *n_scored = 0;
+    if (n_changed) *n_changed = 0;
+    const int K = p->n_yaw;
+    c->il_quat.resize(2 * (size_t)K);
+    for (int k = 0; k < K; ++k) {
+        const double psi = p->yaw0 + (double)k * (2.0 * M_PI / (double)K);
+        c->il_quat[2 * k] = std::sin(psi / 2.0); c->il_quat[2 * k + 1] = std::cos(psi / 2.0);
+    }
+    if (quat_zw) std::memcpy(quat_zw, c->il_quat.data(), sizeof(double) * 2 * (size_t)K);
+    if (sx == 0 || sy == 0) return FS_OK;
+    const int s = p->stride_cells;
+    const int32_t nbx = (sx + s - 1) / s, nby = (sy + s - 1) / s;
+    const size_t nb = (size_t)nbx * (size_t)nby;
+    const bool want_yaw = info_per_yaw != nullptr;
+    const size_t temp_bytes = fs_infolayer_temp_bytes((int64_t)nb, c->stream);
+    if (temp_bytes == 0) return fail(c, FS_E_HIP, "rocPRIM refused the size query");
+    FS_HIP(c, c->d_il_temp.ensure(temp_bytes));
+    FS_HIP(c, c->d_il_idx.ensure(4 * nb + 2));
+    FS_HIP(c, c->d_il_quat.ensure(2 * (size_t)FS_INFO_LAYER_MAX_YAW));
+    FS_HIP(c, c->d_il_out.ensure(nb * (want_yaw ? (size_t)K + 1 : 1)));
+    FS_HIP(c, c->d_il_count.ensure(1));
+    FsInfoLayerArgs a{};
+    a.cells = c->d_cells.p; a.nx = c->nx; a.ny = c->ny;
+    a.ox = c->origin[0]; a.oy = c->origin[1]; a.res = c->res;
+    a.x0 = x0; a.y0 = y0; a.sx = sx; a.sy = sy; a.s = s; a.nbx = nbx; a.nby = nby;
+    a.K = K; a.reduce = p->reduce; a.max_cost = p->max_cost; a.write = p->write != 0;
+    a.pose_z = p->pose_z; a.info_lo = p->info_lo; a.info_hi = p->info_hi;
+    a.quat_zw = c->d_il_quat.p;
+    a.anchor = c->d_il_idx.p; a.flag = a.anchor + nb; a.rank = a.flag + nb + 1; a.list = a.rank + nb + 1;
+    a.info = c->d_il_out.p; a.per_yaw = want_yaw ? c->d_il_out.p + nb : nullptr;
+    a.n_changed = c->d_il_count.p;
+    a.temp = c->d_il_temp.p; a.temp_bytes = c->d_il_temp.cap;
+    // (an error after the first launch waits for the stream: the next call may grow what the launches still use)
+    const auto stop = [&](int code) { (void)hipStreamSynchronize(c->stream); return code; };
+#define IL_HIP(call)                                                                                                  \
+    do {                                                                                                              \
+        const hipError_t e__ = (call);                                                                                \
+        if (e__ != hipSuccess) return stop(fail(c, FS_E_HIP, "%s: %s", #call, hipGetErrorString(e__)));               \
+    } while (0)
+    IL_HIP(hipMemcpyAsync(c->d_il_quat.p, c->il_quat.data(), sizeof(double) * 2 * (size_t)K, hipMemcpyHostToDevice, c->stream));
+    if (fs_launch_infolayer_anchors(a, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "information layer anchors: launch failed"));
+    int32_t scored32 = 0;
+    IL_HIP(hipMemcpyAsync(&scored32, a.rank + nb, sizeof scored32, hipMemcpyDeviceToHost, c->stream));
+    IL_HIP(hipStreamSynchronize(c->stream));                  // THE mid-call synchronisation: n_scored sizes the scoring launches
+    const int64_t total = (int64_t)scored32 * K;
+    if (total > 0) {
+        const int64_t batch = std::min<int64_t>(c->opt_il_batch, total);
+        IL_HIP(c->d_il_val.ensure((size_t)total));
+        IL_HIP(c->d_il_rt.ensure(12 * (size_t)batch));
+        a.val = c->d_il_val.p;
+        for (int64_t p0 = 0; p0 < total; p0 += batch) {
+            const int64_t n = std::min(batch, total - p0);
+            if (fs_launch_infolayer_records(a, p0, n, c->d_il_rt.p, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "information layer records: launch failed"));
+            const float *values = nullptr;
+            rc = score_records(c, c->d_il_rt.p, n, false, stop, &values);
+            if (rc) return stop(rc);
+            IL_HIP(hipMemcpyAsync(a.val + p0, values, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+        }
+    }
+    const bool writes = a.write && total > 0;
+    if (writes) ++c->grid_gen;
+    IL_HIP(hipMemsetAsync(c->d_il_count.p, 0, sizeof(unsigned long long), c->stream));
+    if (fs_launch_infolayer_store(a, c->stream) != hipSuccess) return stop(fail(c, FS_E_HIP, "information layer store: launch failed"));
+    if (writes && (rc = cells_changed_in_box(c, x0, y0, 0, sx, sy, 1))) return stop(rc);
+    unsigned long long changed = 0ull;
+    IL_HIP(hipMemcpyAsync(&changed, c->d_il_count.p, sizeof changed, hipMemcpyDeviceToHost, c->stream));
+    if (info) IL_HIP(hipMemcpyAsync(info, a.info, sizeof(float) * nb, hipMemcpyDeviceToHost, c->stream));
+    if (anchor_cell) IL_HIP(hipMemcpyAsync(anchor_cell, a.anchor, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, c->stream));
+    if (want_yaw) IL_HIP(hipMemcpyAsync(info_per_yaw, a.per_yaw, sizeof(float) * nb * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    IL_HIP(hipStreamSynchronize(c->stream));
+#undef IL_HIP
+    // (the values of a map-sized lattice at stride 1: not worth keeping)
+    if (c->d_il_val.cap * sizeof(float) > ((size_t)64 << 20)) c->d_il_val.release();
+    if (c->d_il_out.cap * sizeof(float) > ((size_t)64 << 20)) c->d_il_out.release();
+    if (writes) ++c->epoch;
+    if (n_scored) *n_scored = scored32;
+    if (n_changed) *n_changed = (int64_t)changed;
     return FS_OK;
 }
 

@@ -691,6 +691,32 @@ hipError_t fs_launch_pathinfo_offsets(const FsPathInfoArgs &a, hipStream_t s);  
 hipError_t fs_launch_pathinfo_prepare(const FsPathInfoArgs &a, hipStream_t s);            // keys ... records, hdr
 hipError_t fs_launch_pathinfo_finish(const FsPathInfoArgs &a, hipStream_t s);             // the per-frontier columns
 
+// ---- the information layer (fs_infolayer.hip): Fisher information of a pose lattice on the staged 2-D grid as costs.
+// Blocks of s x s cells tile the window [x0, x0+sx) x [y0, y0+sy) (nbx x nby of them, row-major); pose p = scored block (p / K) in
+// block order, heading p % K.
+struct FsInfoLayerArgs {
+    uint8_t *cells;                   // the staged grid [ny][nx]
+    int32_t nx, ny;
+    double ox, oy, res;
+    int32_t x0, y0, sx, sy, s, nbx, nby;
+    int32_t K, reduce, max_cost, write;
+    double pose_z, info_lo, info_hi;
+    const double *quat_zw;            // [K][2] sin, cos of half the heading: the host's libm
+    int32_t *anchor;                  // [nb] anchor cell y * nx + x, or -1
+    int32_t *flag, *rank;             // [nb + 1] scored?; scored blocks before this one (rank[nb] = n_scored)
+    int32_t *list;                    // [n_scored] the scored blocks in block order
+    float *val;                       // [n_scored][K] the worker's info_ref per pose
+    float *info;                      // [nb] the reduced value, NaN where unscored
+    float *per_yaw;                   // [K][nb] or nullptr
+    unsigned long long *n_changed;    // [1]
+    void *temp;                       // rocPRIM's scratch
+    size_t temp_bytes;
+};
+size_t fs_infolayer_temp_bytes(int64_t nb, hipStream_t s);                                 // rocPRIM's scratch for nb blocks; 0: it refused
+hipError_t fs_launch_infolayer_anchors(const FsInfoLayerArgs &a, hipStream_t s);           // anchor, flag, rank, list
+hipError_t fs_launch_infolayer_records(const FsInfoLayerArgs &a, int64_t p0, int64_t n, float *rt, hipStream_t s);   // rt [n][12] of poses [p0, p0 + n)
+hipError_t fs_launch_infolayer_store(const FsInfoLayerArgs &a, hipStream_t s);             // info, per_yaw, the cells, n_changed
+
 // ---- landmark staging (fs_capi.hip), split so that fs_multi orders a cloud once for all its devices
 struct FsStagedCloud {
     int32_t m = 0, n_chunks = 0;

@@ -243,6 +243,16 @@ int fs_multi_inflate(fs_multi *m, const fs_inflation_params *p, int32_t x0, int3
     });
 }
 
+int fs_multi_information_layer(fs_multi *m, const fs_info_layer_params *p, int32_t x0, int32_t y0, int32_t sx, int32_t sy, float *info,
+                               int32_t *anchor_cell, float *info_per_yaw, double *quat_zw, int64_t *n_scored, int64_t *n_changed)
+{
+    return for_all_parallel(m, "fs_information_layer", [&](fs_ctx *c) {
+        const bool first = c == m->ctx[0];
+        return fs_information_layer(c, p, x0, y0, sx, sy, first ? info : nullptr, first ? anchor_cell : nullptr, first ? info_per_yaw : nullptr,
+                                    first ? quat_zw : nullptr, first ? n_scored : nullptr, first ? n_changed : nullptr);
+    });
+}
+
 int fs_multi_keepout_clear(fs_multi *m)
 {
     return for_all_parallel(m, "fs_keepout_clear", [&](fs_ctx *c) { return fs_keepout_clear(c); });

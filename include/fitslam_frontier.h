@@ -235,6 +235,65 @@ int fs_inflate(fs_ctx *ctx, const fs_inflation_params *p, int32_t x0, int32_t y0
  * staged now; the refusals of fs_inflate that concern the parameters and the grid. */
 int fs_inflation_costs(const fs_ctx *ctx, const fs_inflation_params *p, int32_t *cell_radius, uint8_t *cost_by_d2);
 
+/* ---------------------------------------------------------------- information layer (this project's own extension)
+ *
+ * Traversability costs that know where SLAM keeps tracking: the Fisher information of a lattice of poses, as costs of the
+ * staged 2-D grid, BEFORE the plan.  The reference has no such layer — its answer to a path that drops below isPoseSafe's
+ * threshold is to blacklist the goal and paint a keep-out zone afterwards (MarkLethalFOV) — so the rule is stated here and is
+ * normative.  On the staged 2-D grid (nz == 1), inside the window [x0, x0+sx) x [y0, y0+sy):
+ *   1 blocks  with s = stride_cells, block (i, j) covers the cells x in [x0 + i*s, min(x0 + (i+1)*s, x0 + sx)), y likewise; the
+ *             field has nbx = ceil(sx / s) by nby = ceil(sy / s) blocks; the centre cell is cx = min(x0 + i*s + s/2, x0 + sx - 1)
+ *             in integers, cy likewise
+ *   2 anchor  a cell is WRITABLE when its cost is <= 252 (known, neither inscribed nor lethal); the anchor of a block is its
+ *             writable cell with the smallest dx^2 + dy^2 to the centre cell, ties to the smaller y, then the smaller x; a block
+ *             without a writable cell is not scored: its info is NaN, its anchor -1, nothing in it is written
+ *   3 poses   for every scored block and every k < K = n_yaw: position = the anchor's cell centre, origin + (cell + 0.5) * res in
+ *             double, at height pose_z; orientation (0, 0, sin(psi_k / 2), cos(psi_k / 2)), psi_k = yaw0 + k * (2 pi / K)
+ *             evaluated on the HOST in double with its libm (quat_zw returns the K pairs; the device calls no trigonometric
+ *             function); the pose record is made as fs_score_fim makes it of that pose7
+ *   4 value   fs_score_fim's info_ref at that pose under the context's cloud, table and fs_set_fim_params, through the info-only
+ *             worker; with fs_set_occlusion enabled through the occluded worker, as fs_plan_paths_information chooses — its launch
+ *             sequence WITHOUT the pose split (a pose is never spread over several workgroups: the split's slab count follows the
+ *             number of poses in a launch, and a value must not depend on the batch it fell into)
+ *   5 reduce  per block over k in order: FS_INFO_REDUCE_MIN / _MAX the float minimum / maximum; _MEAN the fp64 sum in k order,
+ *             divided by K, rounded once to float
+ *   6 cost    t = (info_hi - (double)v) / (info_hi - info_lo); if !(t > 0) t = 0; if t > 1 t = 1;
+ *             cost = (unsigned char)(max_cost * t) — one multiply in double, then truncation; correctly rounded fp64 operations,
+ *             no fused multiply-add: the same expression on the host from the returned float gives the same byte
+ *   7 store   (write != 0) every writable cell of a scored block becomes max(old, cost); nothing else is written — not unknown
+ *             cells, not cells at 253 and above, not cells outside the window, not cells of unscored blocks
+ * Like fs_inflate the layer cannot LOWER a cost: stage the raw map again to remove it.  Applied after fs_inflate it composes by
+ * max, as nav2's updateWithMax layers do.  After a write the images derived from the grid follow as after fs_update_grid_region;
+ * cached arrival limits stay.
+ * Outputs, each may be NULL: info [nby][nbx] (NaN: unscored), anchor_cell [nby][nbx] (y * nx + x, or -1), info_per_yaw
+ * [K][nby][nbx] (NaN: unscored), quat_zw [K][2] (the uploaded sin, cos pairs), n_scored (scored blocks), n_changed (cells whose
+ * byte changed).
+ *   - FS_E_INVALID, nothing written: a parameter outside the ranges below or not finite, info_hi <= info_lo, a window that
+ *     leaves the grid or has a negative size, a 3-D grid staged; FS_E_STATE: no grid staged; then what fs_score_fim refuses
+ *     (no cloud, no table), with its codes
+ *   - an empty window, or one without a writable cell, reports zeros (info NaN, anchors -1) and launches no scorer
+ *   - poses are scored in batches of fs_set_option("infolayer.batch", n) (default 65536) so the per-pose scratch stays bounded;
+ *     no pose's launch sequence depends on the batch size (poses are never split over workgroups here); what remains is the FIM
+ *     worker's own call-to-call variation in the last bits of its float sums, here as in two fs_score_fim calls
+ *   - TWO synchronisations: one to learn n_scored (it sizes the scoring launches), one at the end */
+#define FS_INFO_LAYER_MAX_STRIDE 32
+#define FS_INFO_LAYER_MAX_YAW 64
+#define FS_INFO_REDUCE_MIN 0
+#define FS_INFO_REDUCE_MEAN 1
+#define FS_INFO_REDUCE_MAX 2
+typedef struct fs_info_layer_params {
+    int32_t stride_cells;       /* 1 .. FS_INFO_LAYER_MAX_STRIDE */
+    int32_t n_yaw;              /* K, 1 .. FS_INFO_LAYER_MAX_YAW */
+    double  yaw0;               /* heading k is yaw0 + k * (2*pi / K), evaluated on the host in double */
+    double  pose_z;             /* camera height of every pose */
+    int32_t reduce;             /* FS_INFO_REDUCE_MIN | _MEAN | _MAX over the K headings */
+    double  info_lo, info_hi;   /* finite, info_hi > info_lo */
+    int32_t max_cost;           /* 1 .. 252 */
+    int32_t write;              /* 0: compute and return the field only, the grid is not touched */
+} fs_info_layer_params;
+int fs_information_layer(fs_ctx *ctx, const fs_info_layer_params *p, int32_t x0, int32_t y0, int32_t sx, int32_t sy,
+                         float *info, int32_t *anchor_cell, float *info_per_yaw, double *quat_zw, int64_t *n_scored, int64_t *n_changed);
+
 /* Frontier-cell predicate of FrontierSearch::isNewFrontierCell (DEP/src/FrontierSearch.cpp:218-249; isFree / isLethal /
  * isUnknown: DEP/include/.../FrontierSearch.hpp:129-142; frontierSearch/lethal_threshold 160) evaluated for every cell
  * of the staged grid, slice by slice: unknown cell, no lethal in-plane 4-neighbour, at least one free one.
@@ -516,6 +575,10 @@ int  fs_multi_mark_lethal_fov(fs_multi *m, const double robot_pose7[7], double b
 /* fs_inflate on every member (the same map on each, so the same cells); the counts are member 0's */
 int  fs_multi_inflate(fs_multi *m, const fs_inflation_params *p, int32_t x0, int32_t y0, int32_t sx, int32_t sy,
                       int64_t *n_seeds, int64_t *n_changed);
+/* fs_information_layer on every member (the same map, cloud and table on each, so the same cells); the outputs are member 0's */
+int  fs_multi_information_layer(fs_multi *m, const fs_info_layer_params *p, int32_t x0, int32_t y0, int32_t sx, int32_t sy,
+                                float *info, int32_t *anchor_cell, float *info_per_yaw, double *quat_zw, int64_t *n_scored,
+                                int64_t *n_changed);
 int  fs_multi_upload_landmarks(fs_multi *m, const float *xyz, int32_t n_landmarks);
 int  fs_multi_lookup_generate(fs_multi *m, const float bounds[6]);
 int  fs_multi_lookup_load(fs_multi *m, const char *path);
